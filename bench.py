@@ -8,7 +8,18 @@ fusion) followed by BPR scoring of B = 4096 (u, i+, i-) triples.  Inputs (x, wei
 resident in HBM when the timed region starts.  value = messages reduced per step (sum over metapaths/steps of
 E + N self loops) / step time, whole job.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--preset ml25m_shaped] [--kind gat]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--preset ml25m_shaped] [--kind gat] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (metric, value, unit, ms_per_step, ...).
+--dump-outputs DIR: after the timed steps, what the last one computed goes to DIR/*.npy (float32 / float64): `loss` (the BPR
+loss, float64, shape [1]) and, when this process holds the whole table, `cached_repr` (the fused [N, repr_dim] table; above
+48 MB a fixed seeded sample of its rows, whose ids are in `cached_repr_rows`).  Inputs are seeded: the same arguments give the
+same inputs on every run.
+--full adds everything else the benchmark measures or checks: the HIP-event pass behind `roofline` and `kernels_ms_per_step`,
+the training leg (`training_step`, gradient check), the eval variant, the CPU baseline with the full-size parity check, and
+on the headline workload the 13-metapath and the full-size stress (`hbm_resident`) legs.  The --no-* options and
+--train-steps / --grad-check-triples / --cpu-samples / --hbm-scale shape those legs; an explicit --train-steps N also runs
+the training leg without --full (no HIP-event pass, no gradient check there).
 
 With --gpus N > 1 and no WORLD_SIZE in the environment the script launches its own N ranks (one process per GPU,
 127.0.0.1 rendezvous) BEFORE anything touches a GPU; under an external launcher (torch.distributed.run) it is one
@@ -66,14 +77,20 @@ def parse(argv=None):
                     '(PEAEngine.forward_graphed; for launch-bound presets such as ml_small)')
     ap.add_argument('--train-steps', type=int, default=-1, help='also time this many full training steps '
                     '(zero_grad, loss, backward, Adam step: reference solvers.py:213-216) -> `training_step`; default: 6 on '
-                    'one GPU, 0 on a sharded run (give a count to time the sharded training step too)')
+                    'one GPU with --full, 0 otherwise (give a count to time the sharded training step too)')
     ap.add_argument('--grad-check-triples', type=int, default=48, help='training leg: full-size gradient check of a sub-batch '
                     'of this many triples against float64 autograd on its 2-hop neighbourhood (oracle/grad64.py); 0 = skip')
     ap.add_argument('--emulate-world', type=int, default=0, help='single process: time ONE rank (rank 0) of a sharded run of\n'
                     'this many ranks with the collectives skipped (results are wrong, timings are per-rank compute + host work)')
+    ap.add_argument('--full', action='store_true', help='also run the roofline pass, the training leg, the eval variant, the CPU '
+                    'baseline and parity checks and the 13-metapath / full-size stress legs (see the module docstring)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write what the last timed step computed to DIR/*.npy')
     ap.add_argument('--backend', default='nccl', help="torch.distributed backend for N > 1 ('nccl' = RCCL; 'gloo' "
                     'only to rehearse several ranks on one GPU)')
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
+    return args
 
 
 def launch_ranks(cmds_envs, poll_s=0.05, grace_s=5.0):
@@ -398,7 +415,9 @@ def main():
         loss = step()
     torch.cuda.synchronize()
     lib = _lib.load()
-    profile = not args.no_profile
+    profile = args.full and not args.no_profile
+    cpu_checks = args.full and not args.no_cpu_baseline
+    extras = args.full and not args.no_extras
 
     from graph_recsys_benchmark_amd import engine as _eng
 
@@ -425,9 +444,11 @@ def main():
             elapsed = float(t.item())
         return elapsed, out
 
-    # the timed region proper (K steps, nothing but the work), then the same K steps again with a pair of HIP events
-    # around every kernel launch (on the launch stream) for the per-kernel roofline
+    # the timed region proper (K steps, nothing but the work), then (--full) the same K steps again with a pair of HIP
+    # events around every kernel launch (on the launch stream) for the per-kernel roofline
     dt, loss = timed_region(step, args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, loss)
     prof, dt_prof = {}, None
     comm_ms = None
     if profile:
@@ -497,12 +518,12 @@ def main():
             out['emulated'] = ('ONE rank (rank 0) of %d on one GPU, collectives skipped: ms_per_step = that rank\'s kernels + host '
                                'work; value is NOT a job throughput' % args.emulate_world)
     single = world == 1 and args.emulate_world <= 1
-    train_steps = args.train_steps if args.train_steps >= 0 else (6 if single else 0)
+    train_steps = args.train_steps if args.train_steps >= 0 else (6 if single and args.full else 0)
     if train_steps > 0:          # sharded too: every rank steps its replica with the all-reduced gradients
         snapshot = {k: v.detach().clone() for k, v in model.state_dict().items()}
         try:
             out['training_step'] = training_leg(dataset, model, batch, args, timed_region, train_steps, world, profile,
-                                                rank == 0 and single and not args.no_cpu_baseline)
+                                                rank == 0 and single and cpu_checks)
         except torch.cuda.OutOfMemoryError as e:
             # the training buffers (per level: T, O and their gradients for every channel) of the largest presets do not fit
             # beside the inference schedule's (stress_10m at full size: 4 x 82 GB): reported, not fatal -- unless sharded,
@@ -518,23 +539,23 @@ def main():
             for k, v in model.state_dict().items():   # forward steps above ran on, not the ones Adam has stepped
                 v.copy_(snapshot[k])
         del snapshot
-    if single and not args.no_extras:
+    if single and extras:
         out['eval_variant'] = eval_variant(dataset, model, args, timed_region)
-    if rank == 0 and single and not args.no_cpu_baseline:
+    if rank == 0 and single and cpu_checks:
         base, want = cpu_baseline(dataset, model, args.kind, args.cpu_samples)
         out['cpu_baseline'] = base
         with torch.no_grad():                                 # same weights as the oracle run (Adam may have stepped above)
             got = model.forward().cpu().numpy()               # full-size parity of the fused table against the oracle
         out['parity_vs_cpu_oracle'] = {'max_abs_err': float(np.abs(got - want).max()),
                                        'max_abs_value': float(np.abs(want).max()), 'rows': int(want.shape[0])}
-    if rank == 0 and single and args.preset == 'stress_10m' and args.kind in ('gat', 'sage'):
+    if rank == 0 and single and args.full and args.preset == 'stress_10m' and args.kind in ('gat', 'sage'):
         # the CPU oracle is out of reach at this size (pass --no-cpu-baseline): sampled rows in float64 instead
         out['parity_vs_float64_sampled_rows'] = sampled_rows_check(dataset, model, args.kind, device)
-    if single and not args.no_extras and args.preset == 'ml25m_shaped' and not args.metapaths and args.scale == 1.0:
+    if single and extras and args.preset == 'ml25m_shaped' and not args.metapaths and args.scale == 1.0:
         del model
         torch.cuda.empty_cache()
         out['metapaths_13'] = thirteen_metapaths(dataset, args, device, batch, timed_region, not args.no_cpu_baseline)
-    if single and not args.no_extras and args.preset == 'ml25m_shaped' and not args.metapaths and args.scale == 1.0:
+    if single and extras and args.preset == 'ml25m_shaped' and not args.metapaths and args.scale == 1.0:
         # BASELINE configs[4] at FULL size (10 M nodes, 200 M edges, 16 metapaths, emb 128: 240 of the 288 GB of HBM, ~100 s of
         # the run, most of it generating the graph on the host); should the card not have that much free, at 30 %
         try:
@@ -549,6 +570,26 @@ def main():
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_BYTES = 48 << 20     # the fused table is written whole up to this size, as a seeded row sample above it
+
+
+def dump_outputs(path, model, loss):
+    """--dump-outputs: what the last timed step handed its caller (the loss) and the fused table it computed on the way
+    (model.cached_repr), copied to the host right after the timed region.  A sharded rank holds only its own rows of
+    the table, so there only the loss is written."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, 'loss.npy'), np.array([float(loss)], dtype=np.float64))
+    if getattr(model, '_repr_partial', False):
+        return
+    table = model.cached_repr.detach()
+    row_bytes = table.shape[1] * 4
+    if table.shape[0] * row_bytes > DUMP_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(table.shape[0], DUMP_BYTES // row_bytes, replace=False))
+        np.save(os.path.join(path, 'cached_repr_rows.npy'), rows.astype(np.float64))
+        table = table[torch.from_numpy(rows).to(table.device)]
+    np.save(os.path.join(path, 'cached_repr.npy'), table.float().cpu().numpy())
 
 
 # xGMI model of the exchanges (NOT measured: no multi-GPU lease was available to this build).  MI355X: 7 links per GPU, 153.6 GB/s

@@ -240,6 +240,51 @@ def make_checkpoint_manifest():
     print('checkpoint_manifest.json', {k: len(v['keys']) for k, v in man.items()})
 
 
+class _LegacyNumpyPickler(__import__('pickle').Pickler):
+    """Writes numpy globals under the numpy 1.x module name (numpy.core.multiarray), as the shipped checkpoints carry
+    them, so a fixture is read back with the same weights_only allowlist as the originals.  torch.save pickles with
+    protocol 2, where a global is a text line: the rename is a byte substitution on whole GLOBAL opcodes."""
+
+    def __init__(self, f, protocol=None):
+        import io
+        self._dest, self._buf = f, io.BytesIO()
+        super().__init__(self._buf, protocol)
+
+    def dump(self, obj):
+        super().dump(obj)
+        self._dest.write(self._buf.getvalue().replace(b'cnumpy._core.multiarray\n', b'cnumpy.core.multiarray\n'))
+
+
+def make_checkpoint_fixtures():
+    """tests/golden/checkpoints/<model>_ea<0|1>.pt: the six shipped checkpoints without their optimizer state and without
+    the [2933, 64] node embedding table x (750 KB of each file's 1-1.2 MB; its key, shape and checksums are in
+    checkpoint_manifest.json): epoch, every other tensor of model_states.model and the numpy rec_metrics as shipped,
+    about 210-410 KB each."""
+    root = os.path.join(REF, 'experiments', 'checkpoint', 'weights', 'Movielenslatest-small')
+    import numpy._core.multiarray as ncm
+    allow = [(ncm._reconstruct, 'numpy.core.multiarray._reconstruct'),
+             (ncm.scalar, 'numpy.core.multiarray.scalar'),
+             np.ndarray, np.dtype, type(np.dtype(np.float64))]
+    out = os.path.join(OUT, 'checkpoints')
+    os.makedirs(out, exist_ok=True)
+    pickle_module = types.SimpleNamespace(__name__='pickle', Pickler=_LegacyNumpyPickler)
+    for model in ('PEAGAT', 'PEAGCN', 'PEASage'):
+        base = os.path.join(root, model, 'BPR')
+        for d in sorted(os.listdir(base)):
+            with torch.serialization.safe_globals(allow):
+                ck = torch.load(os.path.join(base, d, 'run_1', 'latest.pkl'), map_location='cpu', weights_only=True)
+            ea = int("'entity_aware': True" in d)
+            path = os.path.join(out, '%s_ea%d.pt' % (model, ea))
+            sd = {k: v for k, v in ck['model_states']['model'].items() if k != 'x'}
+            torch.save({'epoch': ck['epoch'], 'model_states': {'model': sd}, 'rec_metrics': ck['rec_metrics']}, path,
+                       pickle_module=pickle_module)
+            with torch.serialization.safe_globals(allow):
+                back = torch.load(path, map_location='cpu', weights_only=True)
+            assert back['model_states']['model'].keys() == sd.keys()
+            assert all(torch.equal(back['model_states']['model'][k], v) for k, v in sd.items())
+            print(os.path.basename(path), os.path.getsize(path))
+
+
 class _FakeDataset:
     """The attributes the reference's sampling / evaluation code reads from a dataset object
     (datasets/movielens.py:879-997, solvers.py:21-31,50-54), filled from a tiny synthetic HIN."""
@@ -478,6 +523,7 @@ if __name__ == '__main__':
     make_rec_utils(mods)
     make_rng_streams()
     make_checkpoint_manifest()
+    make_checkpoint_fixtures()
     make_sampling_and_metrics(mods)
     make_entity_rows(mods)
     make_nn_convs()

@@ -44,3 +44,32 @@ def test_metric_string_follows_the_workload():
     b = bench.parse(['--preset', 'yelp_shaped', '--kind', 'sage'])
     assert 'yelp_shaped' in bench.metric_name(b) and 'PEASAGE' in bench.metric_name(b)
     assert bench.metric_name(b) != bench.metric_name(a)
+
+
+def test_plain_run_leaves_the_extra_legs_to_full():
+    a = bench.parse(['--steps', '7', '--warmup', '2'])
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    b = bench.parse(['--full', '--dump-outputs', 'out'])
+    assert b.full and b.dump_outputs == 'out'
+
+
+def test_dump_outputs_writes_float_arrays(tmp_path, monkeypatch):
+    import types
+    import numpy as np
+    import torch
+    table = torch.arange(64 * 16, dtype=torch.float32).reshape(64, 16)
+    bench.dump_outputs(str(tmp_path / 'whole'), types.SimpleNamespace(cached_repr=table, _repr_partial=False), torch.tensor(1.25))
+    assert sorted(os.listdir(tmp_path / 'whole')) == ['cached_repr.npy', 'loss.npy']
+    loss = np.load(tmp_path / 'whole' / 'loss.npy')
+    assert loss.dtype == np.float64 and loss.tolist() == [1.25]
+    got = np.load(tmp_path / 'whole' / 'cached_repr.npy')
+    assert got.dtype == np.float32 and np.array_equal(got, table.numpy())
+    monkeypatch.setattr(bench, 'DUMP_BYTES', 16 * 4 * 10)          # above the cap: a fixed sample of 10 rows, and their ids
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), types.SimpleNamespace(cached_repr=table, _repr_partial=False), torch.tensor(1.25))
+    rows = np.load(tmp_path / 'a' / 'cached_repr_rows.npy')
+    assert rows.dtype == np.float64 and rows.size == 10
+    assert np.array_equal(np.load(tmp_path / 'a' / 'cached_repr.npy'), table.numpy()[rows.astype(np.int64)])
+    assert np.array_equal(rows, np.load(tmp_path / 'b' / 'cached_repr_rows.npy'))
+    bench.dump_outputs(str(tmp_path / 'rank'), types.SimpleNamespace(cached_repr=table, _repr_partial=True), torch.tensor(1.25))
+    assert os.listdir(tmp_path / 'rank') == ['loss.npy']         # a sharded rank holds only its own rows

@@ -222,12 +222,14 @@ def test_rccl_backend_single_rank_smoke():
 
 def test_bench_self_launches_its_ranks():
     """`python bench.py --gpus 2` with no launcher in the environment: the script starts its own two ranks before
-    anything touches a GPU and rank 0 prints the one JSON line (here over gloo, both ranks on the box's one GPU)."""
+    anything touches a GPU and rank 0 prints the one JSON line (here over gloo, both ranks on one GPU; --full for the
+    collective timings of the HIP-event pass)."""
     import json
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT')}
     p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--backend', 'gloo', '--preset', 'ml_small',
-                        '--steps', '3', '--warmup', '1', '--train-steps', '2'], capture_output=True, text=True, env=env, timeout=600)
+                        '--steps', '3', '--warmup', '1', '--train-steps', '2', '--full'], capture_output=True, text=True, env=env,
+                       timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{"metric"')]
     assert len(lines) == 1, p.stdout[-2000:]
