@@ -14,6 +14,7 @@ KIND_GAT, KIND_GCN, KIND_SAGE = 0, 1, 2
 PLAN_SELF_LOOPS = 1
 PLAN_EDGE_IDS = 2
 FUSE_ATT, FUSE_MEAN = 0, 1
+KG_KGAT, KG_KGCN = 0, 1     # include/peahip.h PEA_KG_*
 
 _ERR_NAMES = {-1: 'bad argument', -2: 'id out of range', -3: 'HIP runtime error', -4: 'workspace too small',
               -5: 'no gfx950 device'}
@@ -115,6 +116,12 @@ SIGNATURES = {
     'pea_sage_conv': (_int, [_vp, _int, _int, _int, _vp, _i64, _vp, _vp, _vp, _int, _vp, _i64, _vp, _sz, _vp]),
     'pea_weighted_aggregate_workspace_bytes': (_sz, [_vp, _int, _int]),
     'pea_weighted_aggregate': (_int, [_vp, _int, _int, _vp, _i64, _vp, _vp, _i64, _vp, _sz, _vp]),
+    'pea_edge_softmax_workspace_bytes': (_sz, [_vp, _int]),
+    'pea_edge_softmax': (_int, [_vp, _int, _vp, _vp, _vp, _sz, _vp]),
+    'pea_edge_softmax_backward': (_int, [_vp, _int, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'pea_kg_edge_types': (_int, [_vp, _int, _vp, _i64, _int, _vp, _vp]),
+    'pea_kg_attention_workspace_bytes': (_sz, [_vp, _int, _int, _int]),
+    'pea_kg_attention': (_int, [_vp, _int, _int, _int, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'pea_grad_weight_workspace_bytes': (_sz, []),
     'pea_grad_weight': (_int, [_i64, _int, C.POINTER(GwJob), _vp, _sz, _vp]),
     'pea_dense_batch': (_int, [_i64, _int, C.POINTER(DenseJob), _vp]),

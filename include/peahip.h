@@ -33,6 +33,8 @@
  *   pea_model_forward_train / _backward_level, pea_grad_weight, pea_dense_batch
  *                       solvers.py:213-216 (loss.backward() through the convs: sparse half / dense half)
  *   pea_weighted_aggregate   nn/kgat_conv.py:36-44, nn/kgcn_conv.py:32-37, nn/ngcf_conv.py:42-45 (message + scatter)
+ *   pea_edge_softmax[_backward], pea_kg_edge_types, pea_kg_attention
+ *                            experiments/kgat_solver_bpr.py:313-320, kgcn_solver_bpr.py:313-319 (att_map + PyG softmax)
  *   pea_sample_negatives     datasets/movielens.py:920-940 (an on-GPU sampler NEXT TO the bit-exact host mirror)
  *   pea_entity_reg           models/base.py:50-73 (entity-aware regulariser of the loss, value + gradient rows)
  *   pea_bpr_train            models/base.py:193-214 + 46-48 under autograd (fusion + scorer + BPR loss, forward + backward)
@@ -388,6 +390,42 @@ size_t pea_weighted_aggregate_workspace_bytes(const pea_plan *plan, int relation
 int pea_weighted_aggregate(const pea_plan *plan, int relation, int width, const float *x, int64_t ldx,
                            const float *edge_weight, float *out, int64_t ldo, void *workspace,
                            size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Edge softmax and the attention maps of the reference's KG baselines (csrc/kg_attention.hip):
+ *   pea_edge_softmax            torch_geometric.utils.softmax (PyG 1.5.0) of a 1-D src:
+ *                               out_e = exp(src_e - max_{e' -> i} src_e') / (sum_{e' -> i} exp(src_e' - max) + 1e-16)
+ *   pea_edge_softmax_backward   grad_src_e = y_e (grad_e - sum_{e' -> i} y_e' grad_e')   (y = the forward output)
+ *   pea_kg_attention            experiments/kgat_solver_bpr.py:313-320 (PEA_KG_KGAT) and kgcn_solver_bpr.py:313-319
+ *                               (PEA_KG_KGCN): per edge e = (j -> i) of type t, s = -1 where t < 0 else +1 (so a
+ *                               reversed type-0 edge keeps +r[0]), rho = r[|t|]:
+ *                                 KGAT  alpha_e = sum_d xp[i,d] tanh(xp[j,d] + s rho[d]),  xp = x @ proj  ([emb, emb])
+ *                                 KGCN  alpha_e = sum_d x[i,d] s rho[d]                     (proj = NULL)
+ *                               then att_map = the edge softmax of alpha.  Nothing of width emb is stored per edge.
+ *   pea_kg_edge_types           the relation's edge types (int64, edge_type[e * stride]: edge_attr[:, 0]) permuted once
+ *                               into CSR slot order as int32 (kept next to the plan by the caller, read by every
+ *                               pea_kg_attention call); synchronises once to report |t| >= num_types as PEA_ERR_RANGE.
+ *                               r must then have num_types rows.
+ * Every per-edge array is in the caller's COO order (one value per column of edge_index).  Self loops and multi-edges take
+ * part as given; rows without in-edges contribute nothing.  The plan must carry PEA_PLAN_EDGE_IDS and not
+ * PEA_PLAN_SELF_LOOPS; pass gather_row_bytes = 4 * emb for the KG maps.  x [N, emb] with row stride ldx; emb a multiple
+ * of 4, <= 256.  Workspace: pea_edge_softmax_workspace_bytes (forward and backward) / pea_kg_attention_workspace_bytes.
+ * Fixed reduction order, no float atomics: bitwise reproducible run to run.  Only these calls' workspace and outputs
+ * are written; nothing synchronises except pea_kg_edge_types.
+ * ---------------------------------------------------------------------------------------------- */
+#define PEA_KG_KGAT 0
+#define PEA_KG_KGCN 1
+size_t pea_edge_softmax_workspace_bytes(const pea_plan *plan, int relation);
+int pea_edge_softmax(const pea_plan *plan, int relation, const float *src, float *out, void *workspace,
+                     size_t workspace_bytes, void *stream);
+int pea_edge_softmax_backward(const pea_plan *plan, int relation, const float *y, const float *grad, float *grad_src,
+                              void *workspace, size_t workspace_bytes, void *stream);
+int pea_kg_edge_types(const pea_plan *plan, int relation, const int64_t *edge_type, int64_t stride, int num_types,
+                      int32_t *types_slot, void *stream);
+size_t pea_kg_attention_workspace_bytes(const pea_plan *plan, int relation, int mode, int emb);
+int pea_kg_attention(const pea_plan *plan, int relation, int mode, int emb, const float *x, int64_t ldx,
+                     const float *proj, const float *r, const int32_t *types_slot, float *att_map, void *workspace,
+                     size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Fusion of the channel stack (models/base.py:196-203).
