@@ -22,6 +22,7 @@ import torch
 from torch.nn import Linear, Parameter
 
 from .. import _lib
+from ..autograd import _view, backward_conv_stack, layout_of, param_grads, save_params, saved_params
 from ..engine import GraphPlan
 from .inits import glorot, zeros
 
@@ -64,30 +65,22 @@ class _ConvFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, engine, x, width, *params):
-        from ..autograd import _Layout, _view
-        lay = getattr(engine, '_layout', None)
-        if lay is None:
-            lay = engine._layout = _Layout(engine)
+        lay = layout_of(engine)
         engine.forward([tuple(params)], x, att=None, train=True, out=engine._scratch_out)
         out = _view(engine._wsf, lay.off_x, engine.plan.num_nodes, lay.ld_x)[:, :width].clone()
         ctx.engine, ctx.width = engine, width
-        ctx.save_for_backward(x, *[t for t in params if t is not None])
-        ctx.present = [t is not None for t in params]
+        save_params(ctx, x, params)
         return out
 
     @staticmethod
     def backward(ctx, d_out):
-        from ..autograd import backward_conv_stack
-        saved = list(ctx.saved_tensors)
-        x, it = saved[0], iter(saved[1:])
-        params = tuple(next(it) if p else None for p in ctx.present)
-        n = x.shape[0]
+        x, params = saved_params(ctx)
+        layer_params = [tuple(params)]
         with torch.no_grad():
             # the forward's statistics live in the engine's workspace: one backward per forward, in order (a module
             # called twice before backward -- weight sharing across calls -- would need a second workspace)
-            dx, grads = backward_conv_stack(ctx.engine, d_out.contiguous().view(n, 1, ctx.width), x, [params])
-        out = [None if t is None else g.reshape(t.shape) for t, g in zip(params, grads[0])]
-        return (None, dx, None, *out)
+            dx, grads = backward_conv_stack(ctx.engine, d_out.contiguous().view(x.shape[0], 1, ctx.width), x, layer_params)
+        return (None, dx, None, *param_grads(layer_params, grads))
 
 
 def _train_engine(module, kind, plan, in_channels, out_channels, heads, **kw):

@@ -189,13 +189,8 @@ def test_two_step_training_schedule_matches_float64_and_the_levelwise_schedule(k
             assert err <= 2e-4 * np.abs(w).max() + 1e-6 * g_max, 'schedule %s, %s: max err %.3e vs scale %.3e' % (mode, name, err, np.abs(w).max())
 
 
-@pytest.mark.parametrize('kind', ['gat', 'gcn', 'sage'])
-def test_sparse_backward_equals_the_dense_one_over_several_steps(kind, monkeypatch):
-    """The training backward walks the gradient's support (rows with a non-zero dT_1 -- SAGE: or in the batch --, compacted on
-    the device: csrc/rows.hip) and keeps dA_0 (SAGE: dM_0 and the root blocks) zero outside it from step to step.  Three steps
-    with DIFFERENT batches on one model (so rows enter and leave the support) against the same steps with PEA_SPARSE_BWD=0:
-    the skipped rows contribute exact zeros, so every gradient agrees to fp32 summation order (1e-5 of the tensor's scale;
-    gradients that vanish analytically: of the largest gradient)."""
+def _support_case(kind):
+    """A model of 2-step channels on the two-step schedule and three DIFFERENT batches (rows enter and leave the support)."""
     n, blocks, rel = random_hin(53, n_user=1600, n_item=420, n_attr=30, e_u2i=12000, e_attr=900)
     u2i, a2i = rel['u2i'], rel['a2i']
     flip = lambda e: np.ascontiguousarray(e[::-1])
@@ -203,26 +198,73 @@ def test_sparse_backward_equals_the_dense_one_over_several_steps(kind, monkeypat
     rng = np.random.default_rng(11)
     batches = [torch.from_numpy(np.stack([rng.integers(*blocks['u'], size=24), rng.integers(*blocks['i'], size=24),
                                           rng.integers(*blocks['i'], size=24)], axis=1).astype(np.int64)).cuda() for _ in range(3)]
-    out = {}
-    for mode in ('1', '0'):
-        monkeypatch.setenv('PEA_SPARSE_BWD', mode)
+
+    def new_model():
         model = build_model(kind, n, edges, [2, 2, 2], 64, 64, 16)
         model.load_state_dict(random_state_dict(model, 21, scale=0.2))
         model.train()
-        steps = []
-        for bt in batches:
-            model.zero_grad()
-            loss = model.loss(bt)
-            loss.backward()
-            steps.append((float(loss), {k: p.grad.detach().clone() for k, p in model.named_parameters()}))
-        out[mode] = steps
+        return model
+    return n, new_model, batches
+
+
+def _train_step(model, bt):
+    model.zero_grad()
+    loss = model.loss(bt)
+    loss.backward()
+    return float(loss), {k: p.grad.detach().clone() for k, p in model.named_parameters()}
+
+
+def _assert_sparse_equals_dense(l1, g1, l0, g0):
+    """The skipped rows contribute exact zeros, so every gradient agrees to fp32 summation order (1e-5 of the tensor's
+    scale; gradients that vanish analytically: of the largest gradient)."""
+    assert l1 == l0
+    g_max = max(float(v.abs().max()) for v in g0.values())
+    for k in g0:
+        scale = float(g0[k].abs().max())
+        assert float((g1[k] - g0[k]).abs().max()) <= 1e-5 * scale + 1e-7 * g_max + 1e-12, k
+
+
+@pytest.mark.parametrize('kind', ['gat', 'gcn', 'sage'])
+def test_sparse_backward_equals_the_dense_one_over_several_steps(kind, monkeypatch):
+    """The training backward walks the gradient's support (rows with a non-zero dT_1 -- SAGE: or in the batch --, compacted on
+    the device: csrc/rows.hip) and keeps dA_0 (SAGE: dM_0 and the root blocks) zero outside it from step to step.  Three steps
+    with DIFFERENT batches on one model (so rows enter and leave the support) against the same steps with PEA_SPARSE_BWD=0."""
+    n, new_model, batches = _support_case(kind)
+    out = {}
+    for mode in ('1', '0'):
+        monkeypatch.setenv('PEA_SPARSE_BWD', mode)
+        model = new_model()
+        out[mode] = [_train_step(model, bt) for bt in batches]
         if mode == '1':
             live = model._train_engine._live_rows
             torch.cuda.synchronize()
             assert 0 < int(live.count.item()) < n           # the support is a proper subset of the nodes here
     for (l1, g1), (l0, g0) in zip(out['1'], out['0']):
-        assert l1 == l0
-        g_max = max(float(v.abs().max()) for v in g0.values())
-        for k in g0:
-            scale = float(g0[k].abs().max())
-            assert float((g1[k] - g0[k]).abs().max()) <= 1e-5 * scale + 1e-7 * g_max + 1e-12, k
+        _assert_sparse_equals_dense(l1, g1, l0, g0)
+
+
+@pytest.mark.parametrize('kind', ['gat', 'gcn', 'sage'])
+def test_sparse_backward_recovers_from_an_aborted_backward(kind, monkeypatch):
+    """A backward that raises after level 1 collected the gradient support and before level 0 re-zeroed the rows the previous
+    step left in dA_0 (SAGE: dM_0 and the root blocks) -- a host-side exception here, standing in for an OOM, a PeaError or a
+    KeyboardInterrupt -- must not leave stale rows there: the next step equals the dense backward's."""
+    from graph_recsys_benchmark_amd import autograd
+    _, new_model, batches = _support_case(kind)
+    monkeypatch.setenv('PEA_SPARSE_BWD', '1')
+    model = new_model()
+    _train_step(model, batches[0])
+    grad_weight, aborted = autograd.grad_weight, []
+
+    def abort_once(pairs, **kw):             # the first weight-gradient call over the support: level 1, after collecting it
+        if kw.get('rows') is not None and not aborted:
+            aborted.append(True)
+            raise RuntimeError('backward aborted')
+        return grad_weight(pairs, **kw)
+    monkeypatch.setattr(autograd, 'grad_weight', abort_once)
+    with pytest.raises(RuntimeError, match='backward aborted'):
+        _train_step(model, batches[1])
+    monkeypatch.setattr(autograd, 'grad_weight', grad_weight)
+    l1, g1 = _train_step(model, batches[2])
+    monkeypatch.setenv('PEA_SPARSE_BWD', '0')
+    l0, g0 = _train_step(new_model(), batches[2])
+    _assert_sparse_equals_dense(l1, g1, l0, g0)
