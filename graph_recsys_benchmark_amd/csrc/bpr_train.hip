@@ -264,6 +264,9 @@ __global__ __launch_bounds__(256) void bpr_train_final_kernel(int n_blocks, cons
 // no atomics.  ids < 0 sort to the end and are skipped.
 constexpr int kSortThreads = 1024;
 constexpr int kSortMax = 16384;
+// widest batch row pea_rows_scatter_sum moves (one wave per node, 4 float4 columns per lane): P * R floats.  The
+// training head is offered only where its gradient rows can go back that way (pea_bpr_train_supported)
+constexpr int kScatterMaxCols = 1024;
 constexpr int kBuckets = 2048;
 
 // Groups the batch's (id, position) keys: bucket = id % 2048 (LDS histogram + prefix sum; integer atomics only decide
@@ -385,7 +388,7 @@ extern "C" int pea_rows_scatter_sum(int64_t n, const int64_t *ids, const float *
     hipStream_t stream = (hipStream_t)stream_;
     PEA_REQUIRE(n >= 0 && n <= kSortMax, PEA_ERR_ARG, "rows_scatter_sum: %lld positions (the batch is sorted in LDS: <= %d)",
                 (long long)n, kSortMax);
-    PEA_REQUIRE(P > 0 && P <= kMaxChannels && R > 0 && R % 4 == 0 && P * R <= 1024, PEA_ERR_ARG,
+    PEA_REQUIRE(P > 0 && P <= kMaxChannels && R > 0 && R % 4 == 0 && P * R <= kScatterMaxCols, PEA_ERR_ARG,
                 "rows_scatter_sum: P=%d R=%d (R a multiple of 4, P * R <= 1024)", P, R);
     PEA_REQUIRE(ids && src && dst && col_of_channel_host && ld_src >= (int64_t)P * R && ld_src % 4 == 0 && ld_dst % 4 == 0 &&
                     num_rows >= 0 && num_rows < ((int64_t)1 << 31),
@@ -423,7 +426,7 @@ extern "C" size_t pea_bpr_train_workspace_bytes(int64_t B) {
 
 extern "C" int pea_bpr_train_supported(int P, int R) {
     const int r4 = R / 4;
-    return P > 0 && P <= kMaxChannels && R > 0 && R % 4 == 0 && r4 <= 8 ? 1 : 0;
+    return P > 0 && P <= kMaxChannels && R > 0 && R % 4 == 0 && r4 <= 8 && P * R <= kScatterMaxCols ? 1 : 0;
 }
 
 extern "C" int pea_bpr_train(int64_t B, int P, int R, const float *rows, int64_t ld_rows, const float *att,
@@ -432,7 +435,7 @@ extern "C" int pea_bpr_train(int64_t B, int P, int R, const float *rows, int64_t
                              size_t workspace_bytes, void *stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     PEA_REQUIRE(B >= 0 && pea_bpr_train_supported(P, R), PEA_ERR_ARG,
-                "bpr_train: B=%lld P=%d R=%d (repr_dim a multiple of 4, <= 32)", (long long)B, P, R);
+                "bpr_train: B=%lld P=%d R=%d (repr_dim a multiple of 4, <= 32, P * repr_dim <= 1024)", (long long)B, P, R);
     PEA_REQUIRE(rows && fc1_w && fc1_b && fc2_w && fc2_b && out_loss && grad_rows && dhx && zx && workspace, PEA_ERR_ARG,
                 "bpr_train: null pointer");
     PEA_REQUIRE(att == nullptr || dsc != nullptr, PEA_ERR_ARG, "bpr_train: 'att' fusion needs the dsc buffer");

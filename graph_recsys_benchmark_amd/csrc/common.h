@@ -355,7 +355,9 @@ int launch_pack(const PackJob *jobs_host, int n_jobs, hipStream_t stream);
 // ---------------------------------------------------------------- two-step inference schedule, dense half (mlp2.hip)
 // T_1[n, c] = relu(in_c(n) . W0_c + b0_c) . W1_c for every 2-step channel c, in_c(n) = the first layer's aggregate of x
 // (A_0) or, for rows without incoming edges there, x[n] itself: both transforms of a channel chained in one kernel.
-constexpr int kMaxMlp2Chan = 32;   // the launch descriptor travels as a kernel argument (4 KB limit)
+// the launch descriptor travels by value as a kernel argument: sizeof(Mlp2Launch) = 5136 bytes, channels 25 .. 31 lie (partly)
+// past byte 4096 and arrive intact (tests/test_gpu_two_step_matrix.py runs 32 channels on the fused path)
+constexpr int kMaxMlp2Chan = 32;
 struct Mlp2Chan {
     const float *w0, *b0, *w1;            // first-layer weight / bias, second-layer weight (raw parameter tensors)
     const float *att_src0, *att_dst0;     // GAT first layer: att_j, att_i [hid]

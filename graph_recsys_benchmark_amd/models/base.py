@@ -253,7 +253,7 @@ class PEABaseRecsysModel(GraphRecsysModel):
                                          self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias, *flat)
             self.cached_repr, self._repr_partial = opts.fused, eng.sharded
             return loss
-        stack = PEAStackFunction.apply(eng, self.x, eng.slots, opts, *flat)      # repr_dim > 32 or > 5461 triples: torch ops
+        stack = PEAStackFunction.apply(eng, self.x, eng.slots, opts, *flat)      # repr_dim > 32, P * repr_dim > 1024 or > 5461 triples: torch ops
         self.cached_repr, self._repr_partial = opts.fused, eng.sharded
         b = t.shape[0]
         if eng.sharded:

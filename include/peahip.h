@@ -490,7 +490,8 @@ int pea_entity_reg(int64_t B, int emb_dim, int64_t num_nodes, const float *x, in
  *   dhx [2B, R+4], zx [2B, 3R+4]:  G = dhx^T zx  ->  d fc1.weight = G[0:R, 0:2R], d fc1.bias = G[0:R, 3R],
  *                                                     d fc2.weight = G[R, 2R:3R],  d fc2.bias = G[R, 3R]
  *   dsc [3B, P4] (P4 = P rounded up to 4; 'att' only):  d att[p, :] = (dsc^T rows)[p, p*R:(p+1)*R]
- * repr_dim R: a multiple of 4, <= 32 (pea_bpr_train_supported).  No atomics, fixed reduction order.
+ * repr_dim R: a multiple of 4, <= 32, and P*R <= 1024: the batch's gradient rows go back into the stack through
+ * pea_rows_scatter_sum (pea_bpr_train_supported).  No atomics, fixed reduction order.
  * pea_rows_scatter_sum: dst[id, col_of_channel[p] + c] = sum over the positions k with ids[k] == id of src[k, p*R + c],
  * added in increasing k (the index backward of rows = stack[ids]: the batch's gradient rows into the node-indexed
  * output-gradient buffer: the batch's (id, position) keys are sorted in LDS by one workgroup, then one wave per node adds

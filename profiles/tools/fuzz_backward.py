@@ -1,6 +1,9 @@
 """Randomised gradient sweep (GPU box): loss.backward() of the HIP path (conv stack forward + backward in HIP, batch-row
 fusion / scorer) against float64 torch autograd of the restated model, on random graphs (hubs, empty relations, forced
-source slicing), widths, heads and step counts.  python profiles/tools/fuzz_backward.py [N] [seed]"""
+source slicing), widths, heads and step counts.  python profiles/tools/fuzz_backward.py [N] [seed]
+FUZZ_TWOSTEP=1: only configurations the two-step training schedule takes (every channel 2 steps, one head, emb == hidden
+64 or 128, repr <= 32 -- <= 16 for SAGE, GCN on either degree side): csrc/mlp2.hip TRAIN and csrc/mlp2_bwd.hip, asserted
+to have run."""
 import os
 import sys
 import traceback
@@ -20,6 +23,12 @@ def one(rng, i):
     heads = int(rng.choice([1, 1, 2])) if kind == 'gat' else 1
     n = int(rng.integers(30, 1500))
     emb, hidden, repr_dim = 4 * int(rng.integers(1, 17)), 4 * int(rng.integers(1, 17)), 4 * int(rng.integers(1, 5))
+    twostep = os.environ.get('FUZZ_TWOSTEP') == '1'
+    deg = 'row'
+    if twostep:
+        heads, emb = 1, int(rng.choice([64, 128]))
+        hidden, repr_dim = emb, 4 * int(rng.integers(1, 5 if kind == 'sage' else 9))
+        deg = str(rng.choice(['row', 'col'])) if kind == 'gcn' else 'row'
     rels = []
     for _ in range(int(rng.integers(1, 4))):
         e = int(rng.choice([0, 30, 800, 12000]))
@@ -29,7 +38,7 @@ def one(rng, i):
         rels.append(np.stack([rng.integers(0, n, e), dst]).astype(np.int64))
     steps, edges = [], []
     for _ in range(int(rng.integers(1, 5))):
-        s = int(rng.integers(1, 4))
+        s = 2 if twostep else int(rng.integers(1, 4))
         if kind == 'gat' and heads > 1 and s == 1:
             s = 2
         steps.append(s)
@@ -41,10 +50,12 @@ def one(rng, i):
         os.environ['PEA_SLICE_MIN_EDGES'], os.environ['PEA_SLICE_BYTES'] = '500', str(int(rng.choice([512, 4096])))
     else:
         os.environ.pop('PEA_SLICE_MIN_EDGES', None), os.environ.pop('PEA_SLICE_BYTES', None)
-    desc = '%d: %s heads %d n %d emb %d hid %d repr %d steps %s aggr %s sliced %s edges %s' % (
-        i, kind, heads, n, emb, hidden, repr_dim, steps, aggr, sliced, [r.shape[1] for r in rels])
+    desc = '%d: %s heads %d n %d emb %d hid %d repr %d steps %s aggr %s sliced %s edges %s%s' % (
+        i, kind, heads, n, emb, hidden, repr_dim, steps, aggr, sliced, [r.shape[1] for r in rels],
+        ' deg ' + deg if twostep and kind == 'gcn' else '')
     try:
-        model = build_model(kind, n, edges, steps, emb, hidden, repr_dim, heads=heads, channel_aggr=aggr)
+        kw = {'gcn_deg_from': deg} if twostep else {}     # the plain sweep calls the helpers exactly as before
+        model = build_model(kind, n, edges, steps, emb, hidden, repr_dim, heads=heads, channel_aggr=aggr, **kw)
         model.load_state_dict(random_state_dict(model, int(rng.integers(0, 1000)), scale=0.25))
         b = int(rng.integers(1, 300))
         batch = np.stack([rng.integers(0, n, b), rng.integers(0, n, b), rng.integers(0, n, b)], axis=1).astype(np.int64)
@@ -52,8 +63,11 @@ def one(rng, i):
         model.zero_grad()
         loss = model.loss(torch.from_numpy(batch).cuda())
         loss.backward()
+        if twostep:
+            from graph_recsys_benchmark_amd.autograd import _Layout
+            assert _Layout(model._train_engine).two_step_train, 'not on the two-step schedule'
         sd = {k: v.detach().cpu().numpy() for k, v in model.state_dict().items()}
-        want_loss, want = f64_loss_and_grads(kind, sd, edges, steps, heads, aggr, batch)
+        want_loss, want = f64_loss_and_grads(kind, sd, edges, steps, heads, aggr, batch, **kw)
         assert abs(float(loss) - want_loss) <= 5e-5 * max(abs(want_loss), 1.0), 'loss %r vs %r' % (float(loss), want_loss)
         top0 = max(float(np.abs(w).max()) for w in want.values())
         worst = max(float(np.abs(p.grad.detach().cpu().numpy().astype(np.float64) - want[n_]).max()) /

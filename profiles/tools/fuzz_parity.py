@@ -2,7 +2,8 @@
 random widths / heads / step counts, optionally with the source-sliced layout forced on small graphs, HIP path against
 the CPU oracle (and float64 where fp32 orders legitimately differ).  python profiles/tools/fuzz_parity.py [N] [seed]
 FUZZ_TWOSTEP=1: only configurations the two-step inference schedule takes (every channel 2 steps, one head, emb / hidden
-64 or 128, repr <= 32 -- <= 16 for SAGE): csrc/mlp2.hip and the first-layer aggregation of x."""
+64 or 128, repr <= 32 -- <= 16 for SAGE, GCN on either degree side): csrc/mlp2.hip and the first-layer aggregation of x,
+asserted to have run."""
 import os
 import sys
 import traceback
@@ -27,6 +28,7 @@ def one(rng, i):
         heads, emb, hidden = 1, int(rng.choice([64, 128])), int(rng.choice([64, 128]))
         repr_dim = 4 * int(rng.integers(1, 5 if kind == 'sage' else 9))
         n_ch = int(rng.integers(1, 12))
+    deg = str(rng.choice(['row', 'col'])) if twostep and kind == 'gcn' else 'row'
     rels = []
     for _ in range(int(rng.integers(1, 4))):
         e = int(rng.choice([0, 5, 200, 3000, 30000]))
@@ -49,11 +51,16 @@ def one(rng, i):
         os.environ['PEA_SLICE_MIN_EDGES'], os.environ['PEA_SLICE_BYTES'] = '500', str(int(rng.choice([512, 4096, 20000])))
     else:
         os.environ.pop('PEA_SLICE_MIN_EDGES', None), os.environ.pop('PEA_SLICE_BYTES', None)
-    from test_gpu_edge_cases import _check
-    desc = '%d: %s heads %d n %d emb %d hid %d repr %d steps %s aggr %s sliced %s edges %s' % (
-        i, kind, heads, n, emb, hidden, repr_dim, steps, aggr, sliced, [r.shape[1] for r in rels])
+    from test_gpu_edge_cases import _check, _kernel_names_of_one_forward
+    desc = '%d: %s heads %d n %d emb %d hid %d repr %d steps %s aggr %s sliced %s edges %s%s' % (
+        i, kind, heads, n, emb, hidden, repr_dim, steps, aggr, sliced, [r.shape[1] for r in rels],
+        ' deg ' + deg if twostep and kind == 'gcn' else '')
     try:
-        _check(kind, n, edges, steps, emb, hidden * 1, repr_dim, heads=heads, aggr=aggr, seed=int(rng.integers(0, 1000)))
+        kw = {'gcn_deg_from': deg} if twostep else {}     # (error_symmetry.py / debug_case.py stand in for _check otherwise)
+        model = _check(kind, n, edges, steps, emb, hidden * 1, repr_dim, heads=heads, aggr=aggr, seed=int(rng.integers(0, 1000)),
+                       **kw)
+        if twostep:
+            assert 'mlp2_fused' in _kernel_names_of_one_forward(model), 'not on the two-step schedule'
         return True, desc
     except Exception:
         return False, desc + '\n' + traceback.format_exc(limit=3)

@@ -10,7 +10,7 @@ from helpers import build_model, random_hin, random_state_dict
 pytestmark = pytest.mark.gpu
 
 
-def f64_loss_and_grads(kind, sd, edges, steps, heads, aggr, batch):
+def f64_loss_and_grads(kind, sd, edges, steps, heads, aggr, batch, gcn_deg_from='row'):
     from oracle import pyg_restatement as R
     params = {k: torch.from_numpy(v).double().requires_grad_(True) for k, v in sd.items()}
     x = params['x']
@@ -30,7 +30,7 @@ def f64_loss_and_grads(kind, sd, edges, steps, heads, aggr, batch):
                 conv.lin.weight = params[pre + 'lin.weight']
                 conv.att_i, conv.att_j, conv.bias = params[pre + 'att_i'], params[pre + 'att_j'], params[pre + 'bias']
             elif kind == 'gcn':
-                conv = R.GCNConv(h.shape[1], sd[pre + 'weight'].shape[1]).double()
+                conv = R.GCNConv(h.shape[1], sd[pre + 'weight'].shape[1], gcn_deg_from=gcn_deg_from).double()
                 del conv._parameters['weight'], conv._parameters['bias']
                 conv.weight, conv.bias = params[pre + 'weight'], params[pre + 'bias']
             else:

@@ -77,14 +77,25 @@ def test_dense_half_rejects_bad_arguments():
     assert grad_weight([]) == []
 
 
-@pytest.mark.parametrize('emb,hid,out', [(64, 64, 16), (128, 128, 16), (64, 64, 8)])
-@pytest.mark.parametrize('form', ['gat', 'gcn', 'sage'])
-def test_fused_dense_backward_matches_float64(form, emb, hid, out):
-    """csrc/mlp2_bwd.hip on its own: dZ = (dT_1 W_1 [+ dR_1 W_1root]) gated by H > 0, dA = dZ W_0 [, dXr = dZ W_0root] for three
-    channels laid out side by side like the training workspace, all rows and a listed subset (rows outside the list untouched)."""
+# (form, emb, hid, out, rows, channels).  Besides the first nine: all four (emb, hid) pairs the ABI takes, product 1's NQ =
+# ceil(k / 8) = 1 .. 4 for both forms (k = out, SAGE 2 x out), channel counts that need several LDS passes (64/64: 4 images per
+# pass, SAGE 2), and row counts 1, 31, 33 (a partial 32-row tile, one full tile and one row more)
+_FUSED_BWD = [pytest.param(f, e, h, o, 3001, 3, id='%s-%d-%d-%d' % (f, e, h, o))
+              for e, h, o in [(64, 64, 16), (128, 128, 16), (64, 64, 8)] for f in ('gat', 'gcn', 'sage')]
+_FUSED_BWD += [pytest.param(*c, id='%s-%d-%d-%d-n%d-p%d' % c) for c in [
+    ('gat', 64, 64, 4, 33, 5), ('gcn', 64, 64, 28, 3001, 5), ('gcn', 64, 128, 20, 31, 3), ('gat', 64, 128, 12, 3001, 3),
+    ('gat', 128, 64, 32, 3001, 2), ('gcn', 128, 64, 4, 3001, 3), ('gcn', 128, 128, 12, 1, 2), ('gat', 128, 128, 20, 33, 2),
+    ('sage', 64, 64, 8, 33, 5), ('sage', 64, 64, 12, 3001, 3), ('sage', 64, 128, 4, 3001, 2), ('sage', 64, 128, 16, 3001, 3),
+    ('sage', 128, 64, 12, 31, 2), ('sage', 128, 64, 4, 3001, 2), ('sage', 128, 128, 16, 1, 2)]]
+
+
+@pytest.mark.parametrize('form,emb,hid,out,n,p', _FUSED_BWD)
+def test_fused_dense_backward_matches_float64(form, emb, hid, out, n, p):
+    """csrc/mlp2_bwd.hip on its own: dZ = (dT_1 W_1 [+ dR_1 W_1root]) gated by H > 0, dA = dZ W_0 [, dXr = dZ W_0root] for p
+    channels laid out side by side like the training workspace, all rows, a listed subset (rows outside the list untouched)
+    and an empty list (nothing written)."""
     from graph_recsys_benchmark_amd.engine import RowSet, mlp2_backward_data, mlp2_backward_data_sage
     g = torch.Generator(device='cuda').manual_seed(emb + out)
-    n, p = 3001, 3
     dt1 = torch.randn(n, p * out + 4, generator=g, device='cuda')
     dr1 = torch.randn(n, p * out, generator=g, device='cuda')
     h = torch.randn(n, p * hid, generator=g, device='cuda')          # about half of the gates closed
@@ -93,9 +104,11 @@ def test_fused_dense_backward_matches_float64(form, emb, hid, out):
     w1 = [torch.randn(out, hid, generator=g, device='cuda') * 0.1 for _ in range(p)]
     w1r = [torch.randn(out, hid, generator=g, device='cuda') * 0.1 for _ in range(p)]
     mark = torch.zeros(n, 4, device='cuda')
-    mark[torch.randperm(n, generator=torch.Generator().manual_seed(1))[:700].cuda(), 2] = 1.0
+    mark[torch.randperm(n, generator=torch.Generator().manual_seed(1))[:min(700, (n + 1) // 2)].cuda(), 2] = 1.0
     live = RowSet(n, torch.device('cuda')).fill_from(mark, 4)
-    for rows in (None, live):
+    none = RowSet(n, torch.device('cuda')).fill_from(torch.zeros(n, 4, device='cuda'), 4)
+    assert int(none.count.item()) == 0
+    for rows in (None, live, none):
         dz = torch.full((n, p * hid), float('nan'), device='cuda')
         da = torch.full((n, p * emb), float('nan'), device='cuda')
         dx = torch.full((n, p * emb), float('nan'), device='cuda')
@@ -107,6 +120,9 @@ def test_fused_dense_backward_matches_float64(form, emb, hid, out):
             chans = [((w0[c].t().contiguous() if gcn else w0[c]), (w1[c].t().contiguous() if gcn else w1[c]),
                       c * out, c * hid, c * hid, c * emb) for c in range(p)]
             mlp2_backward_data(chans, emb, hid, out, dt1, h, dz, da, rows=rows, weights_in_out=gcn)
+        if rows is none:
+            assert torch.isnan(dz).all() and torch.isnan(da).all() and torch.isnan(dx).all()
+            continue
         sel = torch.arange(n, device='cuda') if rows is None else torch.nonzero(mark[:, 2]).flatten()
         rest = torch.ones(n, dtype=torch.bool, device='cuda')
         rest[sel] = False
@@ -120,6 +136,7 @@ def test_fused_dense_backward_matches_float64(form, emb, hid, out):
             if form == 'sage':
                 _close(dx[sel, c * emb:(c + 1) * emb], z @ w0r[c].double())
         assert torch.isnan(dz[rest]).all() and torch.isnan(da[rest]).all()      # listed rows only
+        assert torch.isnan(dx[rest]).all() if form == 'sage' else torch.isnan(dx).all()
 
 
 def test_row_sets_and_masked_weight_gradient():

@@ -15,8 +15,8 @@ def _np(t):
     return t.detach().cpu().numpy()
 
 
-def _check(kind, n, edges, steps, emb, hidden, repr_dim, heads=1, aggr='att', seed=3):
-    model = build_model(kind, n, edges, steps, emb, hidden, repr_dim, heads=heads, channel_aggr=aggr)
+def _check(kind, n, edges, steps, emb, hidden, repr_dim, heads=1, aggr='att', seed=3, gcn_deg_from='row'):
+    model = build_model(kind, n, edges, steps, emb, hidden, repr_dim, heads=heads, channel_aggr=aggr, gcn_deg_from=gcn_deg_from)
     model.load_state_dict(random_state_dict(model, seed))
     model.eval()
     with torch.no_grad():
@@ -27,8 +27,9 @@ def _check(kind, n, edges, steps, emb, hidden, repr_dim, heads=1, aggr='att', se
         cps.append([{k[len('pea_channels.%d.gnn_layers.%d.' % (p, s)):]: v for k, v in sd.items()
                      if k.startswith('pea_channels.%d.gnn_layers.%d.' % (p, s))} for s in range(S)])
         hls.append([1] * S if kind != 'gat' else ([heads] * (S - 1) + [1] if S > 1 else [heads]))
-    want, wstack = orc.pea_forward(kind, sd['x'], edges, cps, hls, att=sd.get('att'), channel_aggr=aggr, return_stack=True)
-    t_fused, t_stack = f64_forward(kind, sd, edges, steps, heads, aggr)
+    want, wstack = orc.pea_forward(kind, sd['x'], edges, cps, hls, att=sd.get('att'), channel_aggr=aggr,
+                                   gcn_deg_from=gcn_deg_from, return_stack=True)
+    t_fused, t_stack = f64_forward(kind, sd, edges, steps, heads, aggr, gcn_deg_from=gcn_deg_from)
     assert_fp32_close(_np(stack), wstack, t_stack, what='stack')
     assert_fused_close(_np(fused), _np(stack), want, t_fused, sd.get('att'), aggr, truth_stack=t_stack)
     return model

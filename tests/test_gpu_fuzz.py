@@ -32,6 +32,13 @@ def test_forward_sweep():
     _sweep('fuzz_parity', 40, 101)
 
 
+def test_two_step_forward_sweep(monkeypatch):
+    """Configurations the two-step inference schedule takes (csrc/mlp2.hip): every channel 2 steps, one head, emb / hidden
+    64 or 128, up to 11 channels, GCN on either degree side."""
+    monkeypatch.setenv('FUZZ_TWOSTEP', '1')
+    _sweep('fuzz_parity', 30, 107)
+
+
 def test_hip_is_not_the_looser_side(capsys):
     """The per-row fallback of helpers.assert_fp32_close carries 16 fp32 ulps of the row's magnitude because the ratio of
     two independent fp32 realisations' row maxima exceeds 2 by chance, on either side.  That reading only holds while the
@@ -65,6 +72,13 @@ def test_scoring_sweep():
 
 def test_gradient_sweep():
     _sweep('fuzz_backward', 15, 104)
+
+
+def test_two_step_gradient_sweep(monkeypatch):
+    """Training steps on the two-step schedule (mlp2 TRAIN + csrc/mlp2_bwd.hip): emb == hidden in {64, 128}, every channel
+    2 steps, one head, GCN on either degree side."""
+    monkeypatch.setenv('FUZZ_TWOSTEP', '1')
+    _sweep('fuzz_backward', 10, 108)
 
 
 def test_sharded_sweep_world2():
