@@ -162,6 +162,11 @@ SIGNATURES = {
     'pea_rows_unpack_batch': (_int, [_int, C.POINTER(XchgJob), _vp, _i64, _vp]),
     'pea_rows_select_owned': (_int, [_vp, _i64, _int, _i64, _vp, _i64, _i64, _int, _int, _int, _vp, _vp, _vp]),
     'pea_rank_eval': (_int, [_i64, _int, _int, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'pea_topk_workspace_bytes': (_sz, [_i64, _i64, _int, _int]),
+    'pea_recommend_topk': (_int, [_i64, _int, _int, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                  _sz, _vp]),
+    'pea_rank_full': (_int, [_i64, _int, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                             _sz, _vp]),
 }
 
 _lib = None

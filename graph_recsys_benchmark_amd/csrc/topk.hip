@@ -1,0 +1,489 @@
+// Full-catalogue scoring for gfx950: top-K recommendation lists and the all-item rank of a held-out positive.
+//   predict      graph_recsys_benchmark/models/base.py:208-214   fc2(relu(fc1([repr[u] || repr[i]])))
+//   rank / auc   solvers.py:85-96, utils/rec_utils.py:7-30       over EVERY eligible item instead of 99 sampled ones
+// fc1 splits by columns, so the user half A[u] = fc1_b + W_u repr[u] and the item half B[i] = W_i repr[i] are computed
+// once per requested user / catalogue item (topk_prep) and a pair costs R x (add, max, fma):
+//   s(u, i) = (fma chain over k of max(A[u,k] + B[i,k], 0) * fc2_w[k], from 0) + fc2_b            (pair_score)
+// Every score of this file goes through pair_score on rows written by topk_prep, so a pair has the same bits wherever
+// it is computed (top-K scan, rank scan, the exclusion walk of rank_full, any U / K / item split).  No float atomics.
+#include <algorithm>
+
+#include "common.h"
+
+namespace pea {
+namespace {
+
+constexpr int kTileFloats = 2048;   // LDS tile of item rows: 8 KB = 128 rows at R = 16
+constexpr int kMaxMerge = 2048;     // partial entries of one user (splits * K) the merge kernel folds
+constexpr int kMaxSplits = 64;
+constexpr int kEmpty = 0x7fffffff;  // item slot of a list entry that holds nothing
+
+__device__ __forceinline__ float4 ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
+
+// rows are padded to RP in {16, 32, 64} columns with zeros (A, B and fc2_w alike): a padded column adds
+// fma(max(0 + 0, 0), 0, o) = o, so the padding changes no bit of the score
+int padded_r(int R) { return R <= 16 ? 16 : (R <= 32 ? 32 : 64); }
+
+struct Layout {
+    int RP = 16, NT = 128, S = 1;
+    int64_t span = 0;
+    size_t off_w2 = 0, off_a = 0, off_p = 0, off_b = 0, off_part = 0, bytes = 0;
+};
+
+size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// How a call is cut: NT users per workgroup (one per lane), the catalogue in S item ranges of `span` items so that few
+// users still fill the machine.  Depends on (U, n_items, K, R) only, so the workspace query and the call agree.
+Layout make_layout(int64_t U, int64_t n_items, int K, int R) {
+    Layout L;
+    L.RP = padded_r(R);
+    L.NT = K <= 32 ? 128 : 64;      // a lane's K-entry list is an LDS column of 8 K bytes
+    const int tile_items = kTileFloats / L.RP;
+    const int64_t user_blocks = std::max<int64_t>((U + L.NT - 1) / L.NT, 1);
+    int64_t s = (1024 + user_blocks - 1) / user_blocks;                       // ~4 workgroups per CU
+    s = std::min<int64_t>(s, std::max<int64_t>(n_items / 512, 1));           // an item range is worth >= 512 items
+    s = std::min<int64_t>(s, std::min<int64_t>(kMaxSplits, kMaxMerge / std::max(K, 1)));
+    s = std::max<int64_t>(s, 1);
+    int64_t span = (std::max<int64_t>(n_items, 1) + s - 1) / s;
+    span = (span + tile_items - 1) / tile_items * tile_items;
+    L.span = span;
+    L.S = (int)std::max<int64_t>((n_items + span - 1) / span, 1);
+    size_t o = 256;                                                           // error flag
+    L.off_w2 = o; o = align256(o + (size_t)L.RP * 4);
+    L.off_a = o;  o = align256(o + (size_t)std::max<int64_t>(U, 1) * L.RP * 4);
+    L.off_p = o;  o = align256(o + (size_t)std::max<int64_t>(U, 1) * L.RP * 4);
+    L.off_b = o;  o = align256(o + (size_t)std::max<int64_t>(n_items, 1) * L.RP * 4);
+    L.off_part = o;
+    o = align256(o + (size_t)L.S * std::max(K, 1) * std::max<int64_t>(U, 1) * 8);
+    L.bytes = o;
+    return L;
+}
+
+// ---------------------------------------------------------------------------------------------- prep
+// One thread per (row, column): rows [0, U) the user halves A, [U, U + U_pos) the positives' item halves (rank_full),
+// the rest the catalogue's item halves B.  Fixed summation order: c ascending, bias last.
+__global__ __launch_bounds__(256) void topk_prep_kernel(int64_t U, int64_t U_pos, int64_t n_items, int R, int RP, int64_t N,
+                                                        const float *__restrict__ repr, const int64_t *__restrict__ unids,
+                                                        const int64_t *__restrict__ pos_items, int64_t item_lo,
+                                                        const float *__restrict__ fc1_w, const float *__restrict__ fc1_b,
+                                                        const float *__restrict__ fc2_w, float *__restrict__ A,
+                                                        float *__restrict__ P, float *__restrict__ B,
+                                                        float *__restrict__ w2p, int *err) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t < RP) w2p[t] = t < R ? fc2_w[t] : 0.f;
+    const int64_t row = t / RP;
+    const int k = (int)(t % RP);
+    if (row >= U + U_pos + n_items) return;
+    int64_t node;
+    float *dst;
+    bool user_half = false;
+    if (row < U) {
+        node = unids[row];
+        dst = A + row * RP;
+        user_half = true;
+    } else if (row < U + U_pos) {
+        node = pos_items[row - U];
+        dst = P + (row - U) * RP;
+    } else {
+        node = item_lo + (row - U - U_pos);
+        dst = B + (row - U - U_pos) * RP;
+    }
+    if (node < 0 || node >= N) {
+        if (k == 0) atomicOr(err, 1);
+        dst[k] = 0.f;
+        return;
+    }
+    if (k >= R) {
+        dst[k] = 0.f;
+        return;
+    }
+    const float *w = fc1_w + (int64_t)k * 2 * R + (user_half ? 0 : R);
+    const float *x = repr + node * R;
+    float acc = 0.f;
+    for (int c = 0; c < R; ++c) acc += w[c] * x[c];
+    dst[k] = user_half ? acc + fc1_b[k] : acc;
+}
+
+// the one place a pair is scored: a = the user's half (registers), b = the item's half (LDS tile or global row)
+template <int RP>
+__device__ __forceinline__ float pair_score(const float (&a)[RP], const float *b, const float *__restrict__ w2, float b2) {
+    float o = 0.f;
+#pragma unroll
+    for (int k = 0; k < RP; k += 4) {
+        const float4 v = ld4(b + k);
+        o = fmaf(fmaxf(a[k] + v.x, 0.f), w2[k], o);
+        o = fmaf(fmaxf(a[k + 1] + v.y, 0.f), w2[k + 1], o);
+        o = fmaf(fmaxf(a[k + 2] + v.z, 0.f), w2[k + 2], o);
+        o = fmaf(fmaxf(a[k + 3] + v.w, 0.f), w2[k + 3], o);
+    }
+    return o + b2;
+}
+
+// pair_score of four consecutive item rows, the four chains advanced side by side: per item the very same operations in
+// the very same order as pair_score, so the same bits
+template <int RP>
+__device__ __forceinline__ void pair_score4(const float (&a)[RP], const float *b, const float *__restrict__ w2, float b2,
+                                            float (&out)[4]) {
+    float o[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < RP; k += 4) {
+        float4 v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = ld4(b + j * RP + k);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = fmaf(fmaxf(a[k] + v[j].x, 0.f), w2[k], o[j]);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = fmaf(fmaxf(a[k + 1] + v[j].y, 0.f), w2[k + 1], o[j]);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = fmaf(fmaxf(a[k + 2] + v[j].z, 0.f), w2[k + 2], o[j]);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = fmaf(fmaxf(a[k + 3] + v[j].w, 0.f), w2[k + 3], o[j]);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) out[j] = o[j] + b2;
+}
+
+template <int RP>
+__device__ __forceinline__ void load_half(const float *p, float (&a)[RP]) {
+#pragma unroll
+    for (int k = 0; k < RP; k += 4) {
+        const float4 v = ld4(p + k);
+        a[k] = v.x; a[k + 1] = v.y; a[k + 2] = v.z; a[k + 3] = v.w;
+    }
+}
+
+// is `node` in the strictly ascending list ex[lo, hi)?
+__device__ __forceinline__ bool in_sorted(const int64_t *__restrict__ ex, int64_t lo, int64_t hi, int64_t node) {
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        const int64_t v = ex[mid];
+        if (v == node) return true;
+        if (v < node) lo = mid + 1; else hi = mid;
+    }
+    return false;
+}
+
+struct ScanArgs {
+    int64_t U, n_items, item_lo, span;
+    int K;
+    const float *A, *B, *P, *w2, *fc2_b;
+    const int64_t *excl_rowptr, *excl_items;
+    float *part_s;   // top-K: [S, K, U] scores          rank: unused
+    int *part_i;     // top-K: [S, K, U] catalogue index  rank: [S, 2, U] counts of (s > pos), (s < pos)
+};
+
+extern __shared__ float topk_smem[];
+
+// A lane owns one user (its half A[q] in RP registers); the workgroup streams its item range through an LDS tile and all
+// lanes read the same item row at once (identical addresses: broadcast).
+//   RANK = false: the lane keeps its K best (score, index) as a column of LDS, unordered, and knows the worst of them
+//     (lowest score, highest index among equals).  Items arrive in ascending id, so only a strictly higher score can
+//     displace the worst; only such a score is looked up in the exclusion list, replaces the worst entry, and the column
+//     is rescanned for the new worst.  The (user, range) column goes to the workspace for topk_merge.
+//   RANK = true: two counters, s > pos and s < pos, over every item of the range (exclusions are taken out afterwards by
+//     rank_full_kernel, exact because a pair's score has the same bits there).
+template <int RP, bool RANK, int NT>
+__global__ __launch_bounds__(NT) void topk_scan_kernel(const ScanArgs g) {
+    constexpr int TI = kTileFloats / RP;
+    float *tile = topk_smem;
+    float *ls = topk_smem + kTileFloats;                      // [K][NT]
+    int *li = reinterpret_cast<int *>(ls + (RANK ? 0 : g.K * NT));
+    const int tid = threadIdx.x;
+    const int64_t q = (int64_t)blockIdx.x * NT + tid;
+    const bool valid = q < g.U;
+    const int64_t qr = valid ? q : g.U - 1;
+    float a[RP];
+    load_half<RP>(g.A + qr * RP, a);
+    const float b2 = g.fc2_b[0];
+    const int K = g.K;
+    float pos = 0.f, thr = -INFINITY;
+    int hi = 0, lo = 0, wslot = 0;
+    int64_t ex_lo = 0, ex_hi = 0;
+    if (RANK) {
+        pos = pair_score<RP>(a, g.P + qr * RP, g.w2, b2);
+    } else {
+        for (int j = 0; j < K; ++j) {
+            ls[j * NT + tid] = -INFINITY;
+            li[j * NT + tid] = kEmpty;
+        }
+        if (g.excl_rowptr) {
+            ex_lo = g.excl_rowptr[qr];
+            ex_hi = g.excl_rowptr[qr + 1];
+        }
+    }
+    const int64_t i0 = (int64_t)blockIdx.y * g.span;
+    const int64_t i1 = i0 + g.span < g.n_items ? i0 + g.span : g.n_items;
+    for (int64_t t0 = i0; t0 < i1; t0 += TI) {
+        const int nt = (int)(i1 - t0 < TI ? i1 - t0 : TI);
+        __syncthreads();
+        for (int x = tid; x < nt * (RP / 4); x += NT)
+            reinterpret_cast<float4 *>(tile)[x] = ld4(g.B + t0 * RP + (int64_t)x * 4);
+        __syncthreads();
+        // four items at a time: their fma chains are independent, so the scheduler interleaves them (one chain alone
+        // waits on itself).  Rows past nt inside the tile are scored from stale LDS and ignored.
+        for (int j0 = 0; j0 < nt; j0 += 4) {
+            float s4[4];
+            pair_score4<RP>(a, tile + j0 * RP, g.w2, b2, s4);
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj) {
+                const float s = s4[jj];
+                if (j0 + jj >= nt) break;
+                if (RANK) {
+                    hi += s > pos ? 1 : 0;
+                    lo += s < pos ? 1 : 0;
+                } else if (s > thr) {
+                    const int idx = (int)(t0 + j0 + jj);
+                    if (ex_lo < ex_hi && in_sorted(g.excl_items, ex_lo, ex_hi, g.item_lo + idx)) continue;
+                    ls[wslot * NT + tid] = s;
+                    li[wslot * NT + tid] = idx;
+                    float w = ls[tid];
+                    int wi = li[tid];
+                    wslot = 0;
+                    for (int m = 1; m < K; ++m) {
+                        const float sc = ls[m * NT + tid];
+                        const int id = li[m * NT + tid];
+                        if (sc < w || (sc == w && id > wi)) {
+                            w = sc;
+                            wi = id;
+                            wslot = m;
+                        }
+                    }
+                    thr = w;
+                }
+            }
+        }
+    }
+    if (!valid) return;
+    if (RANK) {
+        g.part_i[((int64_t)blockIdx.y * 2) * g.U + q] = hi;
+        g.part_i[((int64_t)blockIdx.y * 2 + 1) * g.U + q] = lo;
+    } else {
+        for (int j = 0; j < K; ++j) {
+            const int64_t o = ((int64_t)blockIdx.y * K + j) * g.U + q;
+            g.part_s[o] = ls[j * NT + tid];
+            g.part_i[o] = li[j * NT + tid];
+        }
+    }
+}
+
+// One workgroup per user: the S unordered K-entry columns (padded with empty entries to a power of two) are put in
+// (score descending, index ascending) order by a bitonic network in LDS and the first K written.  Catalogue indices are
+// unique, so the order is total over the real entries; empty entries (-inf, kEmpty) compare equal to each other only and
+// end up last, where they become the (-1, -inf) tail of a user with fewer than K eligible items.
+__global__ __launch_bounds__(256) void topk_merge_kernel(int64_t U, int K, int S, int P2, int64_t item_lo,
+                                                         const float *__restrict__ part_s, const int *__restrict__ part_i,
+                                                         int64_t *__restrict__ out_items, float *__restrict__ out_scores) {
+    __shared__ float cs[kMaxMerge];
+    __shared__ int ci[kMaxMerge];
+    const int64_t q = blockIdx.x;
+    const int M = S * K;
+    for (int m = threadIdx.x; m < P2; m += blockDim.x) {
+        cs[m] = m < M ? part_s[(int64_t)m * U + q] : -INFINITY;
+        ci[m] = m < M ? part_i[(int64_t)m * U + q] : kEmpty;
+    }
+    __syncthreads();
+    for (int k = 2; k <= P2; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = threadIdx.x; i < P2; i += blockDim.x) {
+                const int l = i ^ j;
+                if (l > i) {
+                    const float si = cs[i], sl = cs[l];
+                    const int ii = ci[i], il = ci[l];
+                    const bool l_first = sl > si || (sl == si && il < ii);   // entry l belongs ahead of entry i
+                    const bool i_first = si > sl || (si == sl && ii < il);
+                    if ((i & k) == 0 ? l_first : i_first) {
+                        cs[i] = sl; ci[i] = il;
+                        cs[l] = si; ci[l] = ii;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    }
+    for (int j = threadIdx.x; j < K; j += blockDim.x) {
+        const bool real = j < P2 && ci[j] != kEmpty;
+        out_items[q * K + j] = real ? item_lo + ci[j] : -1;
+        out_scores[q * K + j] = real ? cs[j] : -INFINITY;
+    }
+}
+
+// One thread per user: sums the ranges' counters, then walks the user's exclusion list once and takes out what those
+// items contributed (same pair_score on the same rows: the same bits the scan compared).
+template <int RP>
+__global__ __launch_bounds__(64) void rank_full_kernel(int64_t U, int S, int64_t n_items, int64_t item_lo,
+                                                       const float *__restrict__ A, const float *__restrict__ B,
+                                                       const float *__restrict__ P, const float *__restrict__ w2,
+                                                       const float *__restrict__ fc2_b, const int64_t *__restrict__ pos_items,
+                                                       const int64_t *__restrict__ excl_rowptr,
+                                                       const int64_t *__restrict__ excl_items, const int *__restrict__ part,
+                                                       int32_t *rank, float *auc, float *pos_score) {
+    const int64_t q = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (q >= U) return;
+    float a[RP];
+    load_half<RP>(A + q * RP, a);
+    const float b2 = fc2_b[0];
+    const float pos = pair_score<RP>(a, P + q * RP, w2, b2);
+    int64_t hi = 0, lo = 0;
+    for (int s = 0; s < S; ++s) {
+        hi += part[((int64_t)s * 2) * U + q];
+        lo += part[((int64_t)s * 2 + 1) * U + q];
+    }
+    const int64_t pn = pos_items[q];
+    int64_t others = n_items - ((pn >= item_lo && pn < item_lo + n_items) ? 1 : 0);
+    if (excl_rowptr) {
+        for (int64_t e = excl_rowptr[q]; e < excl_rowptr[q + 1]; ++e) {
+            const int64_t node = excl_items[e];
+            if (node < item_lo || node >= item_lo + n_items || node == pn) continue;
+            const float s = pair_score<RP>(a, B + (node - item_lo) * RP, w2, b2);
+            hi -= s > pos ? 1 : 0;
+            lo -= s < pos ? 1 : 0;
+            --others;
+        }
+    }
+    if (rank) rank[q] = (int32_t)hi;
+    if (auc) auc[q] = others > 0 ? (float)lo / (float)others : 0.f;
+    if (pos_score) pos_score[q] = pos;
+}
+
+int read_err(int *err_dev, hipStream_t stream, const char *what) {
+    int h = 0;
+    PEA_HIP(hipMemcpyAsync(&h, err_dev, sizeof(int), hipMemcpyDeviceToHost, stream));
+    PEA_HIP(hipStreamSynchronize(stream));
+    PEA_REQUIRE(h == 0, PEA_ERR_RANGE, "%s: node id outside [0, num_nodes)", what);
+    return PEA_OK;
+}
+
+template <int RP, bool RANK, int NT>
+int launch_scan_nt(const Layout &L, const ScanArgs &g, hipStream_t stream) {
+    const size_t lds = (size_t)kTileFloats * 4 + (RANK ? 0 : (size_t)g.K * NT * 8);
+    if (lds > 64 * 1024)
+        PEA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&topk_scan_kernel<RP, RANK, NT>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const dim3 grid((unsigned)((g.U + NT - 1) / NT), (unsigned)L.S);
+    PEA_LAUNCH((topk_scan_kernel<RP, RANK, NT>), grid, dim3(NT), lds, stream, g);
+    PEA_HIP(hipGetLastError());
+    return PEA_OK;
+}
+
+template <bool RANK>
+int launch_scan(const Layout &L, const ScanArgs &g, hipStream_t stream) {
+    if (RANK || L.NT == 128) {
+        if (L.RP == 16) return launch_scan_nt<16, RANK, 128>(L, g, stream);
+        if (L.RP == 32) return launch_scan_nt<32, RANK, 128>(L, g, stream);
+        return launch_scan_nt<64, RANK, 128>(L, g, stream);
+    }
+    if (L.RP == 16) return launch_scan_nt<16, false, 64>(L, g, stream);
+    if (L.RP == 32) return launch_scan_nt<32, false, 64>(L, g, stream);
+    return launch_scan_nt<64, false, 64>(L, g, stream);
+}
+
+int check_common(const char *what, int64_t U, int R, int64_t num_nodes, int64_t item_lo, int64_t n_items) {
+    PEA_REQUIRE(R > 0 && R % 4 == 0 && R <= 64, PEA_ERR_ARG, "%s: repr_dim %d must be a multiple of 4, <= 64", what, R);
+    PEA_REQUIRE(U >= 0 && num_nodes > 0 && n_items >= 0 && n_items < ((int64_t)1 << 31) - 1, PEA_ERR_ARG,
+                "%s: U=%lld n_items=%lld", what, (long long)U, (long long)n_items);
+    PEA_REQUIRE(item_lo >= 0 && item_lo + n_items <= num_nodes, PEA_ERR_RANGE,
+                "%s: catalogue [%lld, %lld) outside [0, num_nodes = %lld)", what, (long long)item_lo,
+                (long long)(item_lo + n_items), (long long)num_nodes);
+    return PEA_OK;
+}
+
+int launch_prep(const Layout &L, int64_t U, int64_t U_pos, int64_t n_items, int R, int64_t N, const float *repr,
+                const int64_t *unids, const int64_t *pos_items, int64_t item_lo, const float *fc1_w, const float *fc1_b,
+                const float *fc2_w, char *ws, hipStream_t stream) {
+    ProfScope ps("topk_prep", stream, 4.0 * (double)(U + U_pos + n_items) * (R + L.RP));
+    const int64_t threads = std::max<int64_t>((U + U_pos + n_items) * L.RP, L.RP);
+    PEA_LAUNCH(topk_prep_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, U, U_pos, n_items, R, L.RP, N,
+               repr, unids, pos_items, item_lo, fc1_w, fc1_b, fc2_w, (float *)(ws + L.off_a), (float *)(ws + L.off_p),
+               (float *)(ws + L.off_b), (float *)(ws + L.off_w2), (int *)ws);
+    PEA_HIP(hipGetLastError());
+    return PEA_OK;
+}
+
+}  // namespace
+}  // namespace pea
+
+// ---------------------------------------------------------------------------------------------- C ABI
+extern "C" size_t pea_topk_workspace_bytes(int64_t U, int64_t n_items, int K, int R) {
+    if (U < 0 || n_items < 0 || K < 1 || K > 128 || R <= 0 || R > 64) return 0;
+    return pea::make_layout(U, n_items, K, R).bytes;
+}
+
+extern "C" int pea_recommend_topk(int64_t U, int K, int R, int64_t num_nodes, const float *repr, const int64_t *unids,
+                                  int64_t item_lo, int64_t n_items, const int64_t *excl_rowptr,
+                                  const int64_t *excl_items, const float *fc1_w, const float *fc1_b, const float *fc2_w,
+                                  const float *fc2_b, int64_t *out_items, float *out_scores, void *workspace,
+                                  size_t workspace_bytes, void *stream_) {
+    using namespace pea;
+    hipStream_t stream = (hipStream_t)stream_;
+    PEA_REQUIRE(K >= 1 && K <= 128, PEA_ERR_ARG, "recommend_topk: K=%d (1..128)", K);
+    PEA_TRY(check_common("recommend_topk", U, R, num_nodes, item_lo, n_items));
+    PEA_REQUIRE(repr && unids && fc1_w && fc1_b && fc2_w && fc2_b && out_items && out_scores && workspace, PEA_ERR_ARG,
+                "recommend_topk: null pointer");
+    PEA_REQUIRE(!excl_rowptr || excl_items, PEA_ERR_ARG, "recommend_topk: excl_rowptr without excl_items");
+    const Layout L = make_layout(U, n_items, K, R);
+    PEA_REQUIRE(workspace_bytes >= L.bytes, PEA_ERR_NOMEM, "recommend_topk: workspace too small (%zu < %zu)", workspace_bytes,
+                L.bytes);
+    if (U == 0) return PEA_OK;
+    char *ws = (char *)workspace;
+    PEA_MEMSET_ASYNC((int *)ws, 0, sizeof(int), stream);
+    PEA_TRY(launch_prep(L, U, 0, n_items, R, num_nodes, repr, unids, nullptr, item_lo, fc1_w, fc1_b, fc2_w, ws, stream));
+    ScanArgs g;
+    g.U = U; g.n_items = n_items; g.item_lo = item_lo; g.span = L.span; g.K = K;
+    g.A = (const float *)(ws + L.off_a); g.B = (const float *)(ws + L.off_b); g.P = nullptr;
+    g.w2 = (const float *)(ws + L.off_w2); g.fc2_b = fc2_b;
+    g.excl_rowptr = excl_rowptr; g.excl_items = excl_items;
+    g.part_s = (float *)(ws + L.off_part);
+    g.part_i = (int *)(ws + L.off_part + (size_t)L.S * K * U * 4);
+    {
+        ProfScope ps("topk_scan", stream, (double)U * (double)n_items * 3.0 * R);
+        PEA_TRY(launch_scan<false>(L, g, stream));
+    }
+    {
+        ProfScope ps("topk_merge", stream, 8.0 * (double)U * K * (L.S + 1.5));
+        int p2 = 2;
+        while (p2 < L.S * K) p2 <<= 1;      // <= kMaxMerge: make_layout keeps S K <= 2048
+        PEA_LAUNCH(topk_merge_kernel, dim3((unsigned)U), dim3(p2 <= 128 ? 64 : 256), 0, stream, U, K, L.S, p2, item_lo,
+                   (const float *)g.part_s, (const int *)g.part_i, out_items, out_scores);
+        PEA_HIP(hipGetLastError());
+    }
+    return read_err((int *)ws, stream, "recommend_topk");
+}
+
+extern "C" int pea_rank_full(int64_t U, int R, int64_t num_nodes, const float *repr, const int64_t *unids,
+                             const int64_t *pos_items, int64_t item_lo, int64_t n_items, const int64_t *excl_rowptr,
+                             const int64_t *excl_items, const float *fc1_w, const float *fc1_b, const float *fc2_w,
+                             const float *fc2_b, int32_t *rank, float *auc, float *pos_score, void *workspace,
+                             size_t workspace_bytes, void *stream_) {
+    using namespace pea;
+    hipStream_t stream = (hipStream_t)stream_;
+    PEA_TRY(check_common("rank_full", U, R, num_nodes, item_lo, n_items));
+    PEA_REQUIRE(repr && unids && pos_items && fc1_w && fc1_b && fc2_w && fc2_b && workspace, PEA_ERR_ARG,
+                "rank_full: null pointer");
+    PEA_REQUIRE(!excl_rowptr || excl_items, PEA_ERR_ARG, "rank_full: excl_rowptr without excl_items");
+    const Layout L = make_layout(U, n_items, 1, R);
+    PEA_REQUIRE(workspace_bytes >= L.bytes, PEA_ERR_NOMEM, "rank_full: workspace too small (%zu < %zu)", workspace_bytes, L.bytes);
+    if (U == 0) return PEA_OK;
+    char *ws = (char *)workspace;
+    PEA_MEMSET_ASYNC((int *)ws, 0, sizeof(int), stream);
+    PEA_TRY(launch_prep(L, U, U, n_items, R, num_nodes, repr, unids, pos_items, item_lo, fc1_w, fc1_b, fc2_w, ws, stream));
+    ScanArgs g;
+    g.U = U; g.n_items = n_items; g.item_lo = item_lo; g.span = L.span; g.K = 0;
+    g.A = (const float *)(ws + L.off_a); g.B = (const float *)(ws + L.off_b); g.P = (const float *)(ws + L.off_p);
+    g.w2 = (const float *)(ws + L.off_w2); g.fc2_b = fc2_b;
+    g.excl_rowptr = nullptr; g.excl_items = nullptr;
+    g.part_s = nullptr;
+    g.part_i = (int *)(ws + L.off_part);
+    {
+        ProfScope ps("rank_full", stream, (double)U * (double)n_items * 3.0 * R);
+        PEA_TRY(launch_scan<true>(L, g, stream));
+#define PEA_RANK_FINISH(rp)                                                                                              \
+    PEA_LAUNCH(rank_full_kernel<rp>, dim3((unsigned)((U + 63) / 64)), dim3(64), 0, stream, U, L.S, n_items, item_lo, g.A, \
+               g.B, g.P, g.w2, fc2_b, pos_items, excl_rowptr, excl_items, (const int *)g.part_i, rank, auc, pos_score)
+        if (L.RP == 16) PEA_RANK_FINISH(16);
+        else if (L.RP == 32) PEA_RANK_FINISH(32);
+        else PEA_RANK_FINISH(64);
+#undef PEA_RANK_FINISH
+        PEA_HIP(hipGetLastError());
+    }
+    return read_err((int *)ws, stream, "rank_full");
+}

@@ -826,6 +826,82 @@ def rank_eval(repr_, unids, cand, fc1_w, fc1_b, fc2_w, fc2_b):
     return scores, rank, auc, loss
 
 
+def _catalogue_args(repr_, unids, item_range, exclude):
+    unids = unids.to(torch.int64).contiguous()
+    if unids.dim() != 1:
+        raise ValueError('unids must be 1-d')
+    item_lo, item_hi = int(item_range[0]), int(item_range[1])
+    if item_hi < item_lo:
+        raise ValueError('item_range is (first item node id, one past the last)')
+    rowptr = items = None
+    if exclude is not None:
+        rowptr, items = exclude
+        if rowptr.dtype != torch.int64 or items.dtype != torch.int64 or rowptr.numel() != unids.numel() + 1:
+            raise ValueError('exclude is (rowptr int64 [U + 1], items int64) -- see utils.interactions.seen_items_csr')
+        if rowptr.device != repr_.device or items.device != repr_.device:
+            raise ValueError('the exclusion lists must live on the device of the table')
+        rowptr, items = rowptr.contiguous(), items.contiguous()
+        if items.numel() == 0:                  # a valid pointer for the C side even when nobody has seen anything
+            items = torch.zeros(1, dtype=torch.int64, device=repr_.device)
+    return unids, item_lo, item_hi - item_lo, rowptr, items
+
+
+def recommend_topk(repr_, unids, k, item_range, fc1_w, fc1_b, fc2_w, fc2_b, exclude=None):
+    """The k best items of the catalogue item_range = (lo, hi) (node ids [lo, hi)) for every user of `unids`, scored
+    like predict (reference models/base.py:208-214) and ordered by (score descending, node id ascending); `exclude`
+    = (rowptr [U + 1], items) names per requested user the items to leave out (utils.interactions.seen_items_csr).
+    Returns (items int64 [U, k], scores float32 [U, k]); a user with fewer than k eligible items gets (-1, -inf) in the
+    tail.  One pass over the catalogue on the device (include/peahip.h, pea_recommend_topk); the [U, items] score matrix
+    is never written."""
+    lib = _lib.require_device()
+    check_pending_errors()
+    unids, item_lo, n_items, rowptr, items = _catalogue_args(repr_, unids, item_range, exclude)
+    u, k, r = unids.shape[0], int(k), repr_.shape[1]
+    dev = repr_.device
+    out_items = torch.empty((u, max(k, 0)), dtype=torch.int64, device=dev)
+    out_scores = torch.empty((u, max(k, 0)), dtype=torch.float32, device=dev)
+    ws_bytes = int(lib.pea_topk_workspace_bytes(u, n_items, k, r))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    args = [t.detach().contiguous() for t in (repr_, fc1_w, fc1_b, fc2_w, fc2_b)]
+    rc = lib.pea_recommend_topk(u, k, r, repr_.shape[0], _lib.ptr(args[0]), _lib.ptr(unids), item_lo, n_items,
+                                _lib.ptr(rowptr), _lib.ptr(items), _lib.ptr(args[1]), _lib.ptr(args[2]), _lib.ptr(args[3]),
+                                _lib.ptr(args[4]), _lib.ptr(out_items), _lib.ptr(out_scores), _lib.ptr(ws), ws_bytes,
+                                _lib.current_stream())
+    if rc == -2:
+        raise IndexError(_lib.last_error())
+    _lib.check(rc)
+    return out_items, out_scores
+
+
+def rank_full(repr_, unids, pos_items, item_range, fc1_w, fc1_b, fc2_w, fc2_b, exclude=None):
+    """All-item evaluation (the protocol of reference solvers.py:56-96 with EVERY eligible item as a negative instead of
+    99 sampled ones): per user the rank of the held-out positive = number of eligible other items scoring strictly
+    higher, auc = share of them scoring strictly lower, and the positive's score.  Returns (rank int32 [U], auc [U],
+    pos_score [U]).  include/peahip.h, pea_rank_full."""
+    lib = _lib.require_device()
+    check_pending_errors()
+    unids, item_lo, n_items, rowptr, items = _catalogue_args(repr_, unids, item_range, exclude)
+    pos_items = pos_items.to(torch.int64).contiguous()
+    if pos_items.shape != unids.shape:
+        raise ValueError('one positive per requested user')
+    u, r = unids.shape[0], repr_.shape[1]
+    dev = repr_.device
+    rank = torch.empty(u, dtype=torch.int32, device=dev)
+    auc = torch.empty(u, dtype=torch.float32, device=dev)
+    pos_score = torch.empty(u, dtype=torch.float32, device=dev)
+    ws_bytes = int(lib.pea_topk_workspace_bytes(u, n_items, 1, r))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    args = [t.detach().contiguous() for t in (repr_, fc1_w, fc1_b, fc2_w, fc2_b)]
+    rc = lib.pea_rank_full(u, r, repr_.shape[0], _lib.ptr(args[0]), _lib.ptr(unids), _lib.ptr(pos_items), item_lo, n_items,
+                           _lib.ptr(rowptr), _lib.ptr(items), _lib.ptr(args[1]), _lib.ptr(args[2]), _lib.ptr(args[3]),
+                           _lib.ptr(args[4]), _lib.ptr(rank), _lib.ptr(auc), _lib.ptr(pos_score), _lib.ptr(ws), ws_bytes,
+                           _lib.current_stream())
+    if rc == -2:
+        raise IndexError(_lib.last_error())
+    _lib.check(rc)
+    return rank, auc, pos_score
+
+
 def bpr_train_raw(picked, att, fc1_w, fc1_b, fc2_w, fc2_b):
     """One launch of csrc/bpr_train.hip + the two fixed-order reductions (pea_grad_weight): returns
     (loss, grad_rows [3B, P*R], (d_att | None, d_fc1_w, d_fc1_b, d_fc2_w, d_fc2_b)) for picked [3B, P, R]."""

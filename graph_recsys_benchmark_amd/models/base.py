@@ -70,6 +70,17 @@ class GraphRecsysModel(torch.nn.Module):
                 self.cached_repr = self.forward()
         return self
 
+    def recommend(self, unids, k, item_range, exclude=None):
+        """The k best items of the catalogue item_range = (first item node id, one past the last) for every user of
+        `unids`, from the eval-mode cache: call model.eval() first.  exclude = (rowptr, items) leaves out per requested
+        user the items named there (utils.interactions.seen_items_csr).  Returns (items int64 [U, k], scores [U, k]),
+        ordered by (score descending, node id ascending) -- engine.recommend_topk."""
+        cached = getattr(self, 'cached_repr', None)
+        if cached is None or self.training or getattr(self, '_repr_partial', False) or cached.requires_grad:
+            raise RuntimeError('recommend() reads the eval-mode table: call model.eval() first')
+        return _engine.recommend_topk(cached, unids, k, item_range, self.fc1.weight, self.fc1.bias, self.fc2.weight,
+                                      self.fc2.bias, exclude=exclude)
+
 
 class _ShardedRows(torch.autograd.Function):
     """rows = table[ids] of a row-sharded [N, W] table: forward = the rows each rank owns summed over the ranks

@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from . import engine
+from .utils.interactions import seen_items_csr
 from .utils.sampling import generate_candidates
 
 NUM_RECS_RANGE = 20   # utils/rec_utils.py:4
@@ -46,3 +47,39 @@ def metrics(model, dataset, num_neg_candidates=99):
                                                model.fc2.weight, model.fc2.bias)
     hr, ndcg = metrics_from_ranks(rank.cpu().numpy())
     return hr.mean(axis=0), ndcg.mean(axis=0), np.array([auc.double().mean().item()]), np.array([loss.double().mean().item()])
+
+
+def metrics_full_from_ranks(rank, auc):
+    """(HR[16], NDCG[16], AUC[1]) means over the users from per-user all-item ranks and aucs."""
+    hr, ndcg = metrics_from_ranks(rank)
+    return hr.mean(axis=0), ndcg.mean(axis=0), np.array([np.asarray(auc, dtype=np.float64).mean()])
+
+
+def metrics_full(model, u_nids, pos_items, item_range, exclude=None):
+    """Unsampled evaluation: every item of the catalogue item_range that is not in the user's exclusion row is a negative
+    (the reference's neg_unid_inid_map[u] in full, where solvers.py:21-31 draws 99 of it).  Returns (HR[16], NDCG[16],
+    AUC[1]) means through the same metrics_from_ranks as `metrics`; no eval loss at full catalogue.  `model` must be
+    in eval() mode; exclude = (rowptr, items) on the model's device (utils.interactions.seen_items_csr)."""
+    dev = model.cached_repr.device
+    rank, auc, _ = engine.rank_full(model.cached_repr, torch.as_tensor(np.asarray(u_nids, dtype=np.int64), device=dev),
+                                    torch.as_tensor(np.asarray(pos_items, dtype=np.int64), device=dev), item_range,
+                                    model.fc1.weight, model.fc1.bias, model.fc2.weight, model.fc2.bias, exclude=exclude)
+    return metrics_full_from_ranks(rank.cpu().numpy(), auc.double().cpu().numpy())
+
+
+def metrics_full_from_dataset(model, dataset):
+    """metrics_full with users and positives from dataset.test_pos_unid_inid_map (one positive per user, as `metrics`
+    insists), the item block from dataset.type_accs / num_iids and the exclusion from dataset.edge_index_nps['user2item']."""
+    u_nids = list(dataset.test_pos_unid_inid_map.keys())
+    pos = []
+    for u_nid in u_nids:
+        p = dataset.test_pos_unid_inid_map[u_nid]
+        if len(p) != 1:
+            raise NotImplementedError('the batched evaluator expects the leave-one-out protocol (one positive per user, '
+                                      'datasets/movielens.py:304-308)')
+        pos.append(p[0])
+    item_range = (dataset.type_accs['iid'], dataset.type_accs['iid'] + dataset.num_iids)
+    dev = model.cached_repr.device
+    u_t = torch.as_tensor(np.asarray(u_nids, dtype=np.int64), device=dev)
+    exclude = seen_items_csr(dataset.edge_index_nps['user2item'], u_t, item_range)
+    return metrics_full(model, u_nids, pos, item_range, exclude)

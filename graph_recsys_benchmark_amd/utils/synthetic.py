@@ -186,6 +186,30 @@ class SyntheticHIN:
             self.neg_unid_inid_map[u0 + k] = [int(v) for v in np.delete(unseen, j)]
         return self.test_pos_unid_inid_map, self.neg_unid_inid_map
 
+    def eval_holdout(self, num_users=None, seed=2021):
+        """(u_nids [U], pos_items [U]) int64: per user one item drawn uniformly from those the user has NOT interacted
+        with -- the held-out positive of the all-item protocol (solvers.metrics_full), vectorised: the j-th unseen item
+        of a user with sorted seen offsets s_0 < s_1 < ... is j + #{m : s_m - m <= j}.  Works at 25m size, where
+        eval_split's per-user lists do not."""
+        rng = np.random.default_rng(seed)
+        u2i = self.edge_index_nps['user2item'].astype(np.int64)
+        u0, i0, ni = self.type_accs['uid'], self.type_accs['iid'], self.num_iids
+        nu = self.num_uids if num_users is None else min(int(num_users), self.num_uids)
+        keys = np.unique((u2i[0] - u0) * ni + (u2i[1] - i0))           # sorted by (user, item offset)
+        keys = keys[keys < nu * ni]
+        ku, ki = keys // ni, keys % ni
+        starts = np.searchsorted(ku, np.arange(nu + 1))
+        deg = np.diff(starts)
+        if (deg >= ni).any():
+            raise ValueError('a user has interacted with every item: nothing to hold out')
+        j = np.floor(rng.random(nu) * (ni - deg)).astype(np.int64)    # index among the user's unseen items
+        j = np.minimum(j, ni - deg - 1)
+        shifted = ki - (np.arange(keys.size) - starts[ku])            # s_m - m, non-decreasing inside a user
+        # count per user the shifted values <= j: a search inside each user's segment, done on one global sorted key
+        seg = ku * (ni + 1) + shifted
+        cnt = np.searchsorted(seg, np.arange(nu) * (ni + 1) + j, side='right') - starts[:-1]
+        return np.arange(u0, u0 + nu, dtype=np.int64), (i0 + j + cnt).astype(np.int64)
+
     def eval_candidates(self, num_users=None, num_neg=99, seed=2021):
         """(u_nids [U], cand [U, 1 + num_neg]) int64 for the batched evaluator: column 0 the held-out positive, the rest
         negatives drawn WITH replacement (solvers.py:29), all uniform over the item block -- the vectorised stand-in for

@@ -38,6 +38,8 @@
  *   pea_sample_negatives     datasets/movielens.py:920-940 (an on-GPU sampler NEXT TO the bit-exact host mirror)
  *   pea_entity_reg           models/base.py:50-73 (entity-aware regulariser of the loss, value + gradient rows)
  *   pea_bpr_train            models/base.py:193-214 + 46-48 under autograd (fusion + scorer + BPR loss, forward + backward)
+ *   pea_recommend_topk, pea_rank_full   models/base.py:208-214 over the WHOLE item catalogue: the K best unseen items per
+ *                            user, and solvers.py:85-96 with every unseen item as a negative instead of 99 sampled ones
  *   pea_model_forward_stage[_train], pea_model_backward_level (phases), pea_rows_pack / _unpack / _select_owned,
  *   pea_grad_weight_sharded, pea_dense_batch_rows
  *                       no counterpart in the reference (its step is single-process): one rank's share of a step
@@ -467,6 +469,43 @@ int pea_rank_eval(int64_t U, int C, int R, int64_t num_nodes, const float *repr,
                   const int64_t *cand /*[U, C]*/, const float *fc1_w, const float *fc1_b,
                   const float *fc2_w, const float *fc2_b, float *scores, int32_t *rank, float *auc,
                   float *loss, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Full-catalogue scoring (csrc/topk.hip).  The catalogue is the node-id block [item_lo, item_lo + n_items); user row q
+ * (unids[q]; users may repeat and come in any order) is eligible for the catalogue minus
+ * excl_items[excl_rowptr[q] : excl_rowptr[q + 1]] -- node ids in strictly ascending order, entries outside the
+ * catalogue allowed and ignored; excl_rowptr == NULL excludes nothing.  fc1 splits by columns, so with
+ *   A[q, k] = (sum_c fc1_w[k, c] repr[u, c]) + fc1_b[k]        B[i, k] = sum_c fc1_w[k, R + c] repr[i, c]    (c ascending)
+ * the score of a pair is  s(u, i) = fma-chain_k(max(A[q, k] + B[i, k], 0) * fc2_w[k]) + fc2_b  (k ascending, from 0): the
+ * predict of models/base.py:208-214 in another order of operations, so it equals pea_predict to fp32 rounding, not
+ * bitwise.  SAME PAIR, SAME BITS: s(u, i) does not depend on U, K, the place of u in unids, the exclusion lists, how
+ * the library cuts the catalogue, or which of the two entry points computed it; identical calls give identical bytes.
+ * No float atomics.
+ *
+ * pea_recommend_topk: out_items[q, :] = the K eligible items of highest score ordered by (score descending, node id
+ *   ascending) -- the same rule decides who of a tie group at the K-th place gets in -- and out_scores[q, :] their
+ *   scores.  Fewer than K eligible items: the tail is item -1, score -inf.  An item whose score is NaN is never
+ *   returned (nor is one whose score is -inf: it cannot be told from the padding).  K in 1..128.
+ * pea_rank_full: for the held-out positive pos_items[q] (any node id; it is scored whether or not it is in the catalogue
+ *   or in the user's own exclusion list, and never counted among the others): rank[q] = number of eligible OTHER items
+ *   scoring strictly higher, auc[q] = share of the eligible others scoring strictly lower (0 when there are none),
+ *   pos_score[q] its score; each output may be NULL.  (pea_rank_eval's tie rule and gt / (C - 1).)  No eval loss.
+ * R: a multiple of 4, <= 64.  n_items < 2^31 - 1.  workspace: pea_topk_workspace_bytes(U, n_items, K, R) bytes
+ * (pea_rank_full: K = 1); 0 = bad arguments.  Bad K / R / null pointers -> PEA_ERR_ARG, a short workspace ->
+ * PEA_ERR_NOMEM, a catalogue block outside [0, num_nodes) -> PEA_ERR_RANGE, all before anything is launched; a user or
+ * positive id outside [0, num_nodes) -> PEA_ERR_RANGE after ONE stream synchronisation (as pea_predict does).
+ * ---------------------------------------------------------------------------------------------- */
+size_t pea_topk_workspace_bytes(int64_t U, int64_t n_items, int K, int R);
+int pea_recommend_topk(int64_t U, int K, int R, int64_t num_nodes, const float *repr, const int64_t *unids,
+                       int64_t item_lo, int64_t n_items, const int64_t *excl_rowptr /* [U+1] or NULL */,
+                       const int64_t *excl_items, const float *fc1_w, const float *fc1_b, const float *fc2_w,
+                       const float *fc2_b, int64_t *out_items /* [U, K] */, float *out_scores /* [U, K] */,
+                       void *workspace, size_t workspace_bytes, void *stream);
+int pea_rank_full(int64_t U, int R, int64_t num_nodes, const float *repr, const int64_t *unids,
+                  const int64_t *pos_items /* [U] */, int64_t item_lo, int64_t n_items, const int64_t *excl_rowptr,
+                  const int64_t *excl_items, const float *fc1_w, const float *fc1_b, const float *fc2_w,
+                  const float *fc2_b, int32_t *rank, float *auc, float *pos_score, void *workspace,
+                  size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Entity-aware regulariser of the loss (models/base.py:50-73, only with --entity_aware=true):
