@@ -329,6 +329,13 @@ struct GemmJob {
     // pick its kernel from properties that do not depend on how jobs were cut: the first-layer (shared-input) jobs are
     // merged per relation when sharded and all together on one GPU, and both must give the same bits.
     int no_narrow;
+    // Columns of B, counted from the job's own B pointer, that the float4 loaders of the B images may read: [c, c + 4) only
+    // where c < b_cols.  Filled in by launch_gemm_batch (callers leave it alone): n_out rounded up to 4, and never more than
+    // what is left of the k row (ldb, or ldb - c0 for the column chunk [c0, c1) of an oversize job, whose B pointer is
+    // already c0 columns into the row).  The images are padded to 32 columns; bounding the loads by ldb instead read the
+    // pad columns from the next k row and, on the last row of a chunk or of a block that sits at a column offset inside a
+    // wider buffer, from behind the weight buffer.
+    int b_cols;
 };
 int launch_gemm(const GemmJob &job, const int *rows, int64_t n_rows, hipStream_t stream);
 int launch_gemm_batch(const GemmJob *jobs, int n_jobs, const int *rows, int64_t n_rows, hipStream_t stream);

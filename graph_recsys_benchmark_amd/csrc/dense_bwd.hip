@@ -566,6 +566,11 @@ extern "C" int pea_dense_batch_rows(int64_t n_rows, const int32_t *rows, int n_j
         PEA_REQUIRE(S.a && S.w && S.out && S.k > 0 && S.n_out > 0 && S.k % 4 == 0 && S.n_out % 4 == 0 && S.lda % 4 == 0 &&
                         S.ldw >= S.n_out && S.ldo >= S.n_out && S.lda >= S.k,
                     PEA_ERR_ARG, "dense_batch: job %d malformed (widths and the input stride must be multiples of 4)", q);
+        // the B images are filled with float4 loads at column offsets that are multiples of 4: with any other row stride a
+        // load would straddle two k rows and the last one run past the buffer; the block itself starts on a 16-byte boundary
+        PEA_REQUIRE(S.ldw % 4 == 0, PEA_ERR_ARG, "dense_batch: job %d: the weight row stride %lld must be a multiple of 4 floats", q,
+                    (long long)S.ldw);
+        PEA_REQUIRE(reinterpret_cast<uintptr_t>(S.w) % 16 == 0, PEA_ERR_ARG, "dense_batch: job %d: the weight block must be 16-byte aligned", q);
         GemmJob J{};
         J.A1 = S.a;
         J.lda1 = (int)S.lda;

@@ -175,7 +175,7 @@ __global__ __launch_bounds__(256) void gemm_mfma_kernel(const GemmBatch Bt, cons
         for (int i = 0; i < NLD; ++i) {
             const int idx = tid + i * 256;
             const int k = kc + idx / 8, c = col0 + (idx & 7) * 4;
-            pre[i] = (k < K && c < J.ldb) ? ld4(J.B + (size_t)k * J.ldb + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+            pre[i] = (k < K && c < J.b_cols) ? ld4(J.B + (size_t)k * J.ldb + c) : make_float4(0.f, 0.f, 0.f, 0.f);
         }
     };
     auto stash = [&](int buf) {
@@ -242,7 +242,7 @@ __global__ __launch_bounds__(256) void gemm_deep_kernel(const GemmBatch Bt, cons
         for (int i = 0; i < NLD; ++i) {
             const int idx = tid + i * 256;
             const int k = kc * 2 * KH + idx / (W / 4), c = (idx % (W / 4)) * 4;
-            pre[i] = (k < K && c < J.ldb) ? ld4(J.B + (size_t)k * J.ldb + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+            pre[i] = (k < K && c < J.b_cols) ? ld4(J.B + (size_t)k * J.ldb + c) : make_float4(0.f, 0.f, 0.f, 0.f);
         }
     };
     auto stash = [&](int buf) {
@@ -290,8 +290,9 @@ __global__ __launch_bounds__(256) void gemm_deep_kernel(const GemmBatch Bt, cons
 
 // Deep k with a B that fits the LDS whole (K x 32 NCT floats <= 150 KB: the 25m model's dx = dT_0 W_cat is 576 x 64 =
 // 147 KB): every workgroup copies B once, then its 16 waves walk 32-row tiles with NO barrier, like the persistent kernel
-// below, but over k chunks of 64.  Same k order
-// per output as gemm_deep_kernel.
+// below, but over k chunks of 64.  NOT the k order of gemm_deep_kernel: one MFMA step here takes k and k + 4 (the lane
+// halves interleave by float4, as in the persistent kernel), there k and k + 64, so the two round differently and a
+// product is bit-identical only against the same kernel (which one runs follows from the batch's largest k and n_out).
 // lean A fragment load for jobs with one input block and no edge-less-row substitution (the backward's products): no
 // temporaries beyond the fragment itself
 template <int KH>
@@ -324,7 +325,7 @@ __global__ __launch_bounds__(1024) void gemm_deep_resident_kernel(const GemmBatc
     const int nkc = (K + 2 * KH - 1) / (2 * KH);
     for (int idx = tid; idx < K * (W / 4); idx += 1024) {   // the whole k-major B: K rows (a partial last chunk re-reads row K - 1
         const int k = idx / (W / 4), c = (idx % (W / 4)) * 4;   // against A values that are zero there)
-        *reinterpret_cast<float4 *>(g_lds + (size_t)k * W + c) = c < J.ldb ? ld4(J.B + (size_t)k * J.ldb + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+        *reinterpret_cast<float4 *>(g_lds + (size_t)k * W + c) = c < J.b_cols ? ld4(J.B + (size_t)k * J.ldb + c) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
     __syncthreads();
     const int64_t n_tiles = (n_rows + 31) / 32;
@@ -408,7 +409,7 @@ __global__ __launch_bounds__(KH > 32 ? 512 : 1024) void gemm_persist_kernel(cons
             for (int u = 0; u < U; ++u) {
                 const int idx = base + u * NT + tid;
                 const int k = (int)(((float)idx + 0.5f) * inv_q4), c = (idx - k * q4) * 4;
-                v[u] = (idx < total && k < K && c < J.ldb) ? ld4(J.B + (size_t)k * J.ldb + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+                v[u] = (idx < total && k < K && c < J.b_cols) ? ld4(J.B + (size_t)k * J.ldb + c) : make_float4(0.f, 0.f, 0.f, 0.f);
             }
 #pragma unroll
             for (int u = 0; u < U; ++u) {
@@ -925,6 +926,7 @@ int launch_gemm_batch(const GemmJob *jobs_in, int n_jobs_in, const int *rows, in
         const int max_cols = (int)(kLdsBudget / sizeof(float) / (size_t)(2 * KH + 1)) / 32 * 32;
         if (K > 128 || J.n_out <= max_cols) {
             jobs.push_back(J);
+            jobs.back().b_cols = std::min(J.ldb, (J.n_out + 3) / 4 * 4);   // the job's own columns: see GemmJob::b_cols
             continue;
         }
         for (int c0 = 0; c0 < J.n_out; c0 += max_cols) {  // column chunks of an oversize job
@@ -932,6 +934,7 @@ int launch_gemm_batch(const GemmJob *jobs_in, int n_jobs_in, const int *rows, in
             const int c1 = std::min(J.n_out, c0 + max_cols);
             C.B = J.B + c0;
             C.n_out = c1 - c0;
+            C.b_cols = std::min(J.ldb - c0, (C.n_out + 3) / 4 * 4);   // the chunk's own columns; the image's pad past c1 is not loaded
             C.bias = J.bias ? J.bias + c0 : nullptr;
             C.n_seg = 0;
             for (int sg = 0; sg < J.n_seg; ++sg) {

@@ -583,9 +583,10 @@ def grad_weight(pairs, shard=None, rows=None):
 
 def dense_batch(triples_, rows=None):
     """out_q = a_q @ w_q for (a_q [N, k], w_q [k, n_out], out_q [N, n_out] view) in triples_: one launch (the input
-    gradients dIn = dT W of one level); k, n_out and a's row stride must be multiples of 4.  rows (int32 device tensor):
-    only those rows are computed (the rows a rank owns in a sharded training step).  A fourth element gate_q [N, n_out]
-    (k <= 128) zeroes the outputs where gate_q <= 0: the relu mask of the layer below, applied in the epilogue."""
+    gradients dIn = dT W of one level); k, n_out and a's row stride must be multiples of 4 (a w whose row stride is not,
+    or that does not start on a 16-byte boundary, is copied first).  rows (int32 device tensor): only those rows are
+    computed (the rows a rank owns in a sharded training step).  A fourth element gate_q [N, n_out] (k <= 128) zeroes the
+    outputs where gate_q <= 0: the relu mask of the layer below, applied in the epilogue."""
     lib = _lib.require_device()
     if not triples_:
         return
@@ -596,7 +597,9 @@ def dense_batch(triples_, rows=None):
         a, w, out = item[:3]
         gate = item[3] if len(item) > 3 else None
         a, out = _rows2d(a), _rows2d(out)
-        w = _rows2d(w if w.stride(1) == 1 else w.contiguous())
+        # the library reads w with 16-byte loads: unit column stride, row stride a multiple of 4 floats, 16-byte aligned
+        ok = w.stride(1) == 1 and w.stride(0) % 4 == 0 and w.data_ptr() % 16 == 0
+        w = _rows2d(w if ok else w.clone(memory_format=torch.contiguous_format))
         keep.append(w)
         if a.shape != (n, w.shape[0]) or out.shape != (n, w.shape[1]):
             raise ValueError('dense_batch: shapes %s @ %s -> %s' % (tuple(a.shape), tuple(w.shape), tuple(out.shape)))

@@ -176,7 +176,10 @@ int pea_model_set_active_rows(pea_model *model, const unsigned char *row_active)
  *                   jobs over the same n_rows: the weight gradients dW = dT^T In (GAT lin, SAGE lin_rel / lin_root) or
  *                   In^T dT (GCN).  Row parts are reduced in a fixed order: bitwise reproducible, no atomics.
  * pea_dense_batch:  out[n][c] = sum_k a[n*lda + k] * w[k*ldw + c]   (k and n_out multiples of 4): the input gradients
- *                   dIn = dT W of one level, all channels in one launch.
+ *                   dIn = dT W of one level, all channels in one launch.  a and w are read with 16-byte loads: lda and
+ *                   ldw must be multiples of 4 floats and w must start on a 16-byte boundary (so w may be a column block
+ *                   of a wider buffer, ldw > n_out, at a column offset that is a multiple of 4), else PEA_ERR_ARG; the
+ *                   caller keeps a's blocks on 16-byte boundaries as well (not checked).  ldo and ld_gate are free.
  * pea_model_backward_level: phase | PEA_BWD_PREMASKED = the level's output gradients already carry the relu mask (its
  *                   producer was a gated pea_dense_batch): the level's own relu-mask pass is skipped.                 */
 #define PEA_BWD_PREMASKED 0x100
