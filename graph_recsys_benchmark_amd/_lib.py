@@ -56,6 +56,12 @@ class DenseJob(C.Structure):
                 ('n_out', C.c_int), ('out', C.c_void_p), ('ldo', C.c_int64), ('gate', C.c_void_p), ('ld_gate', C.c_int64)]
 
 
+class DenseRouteEntry(C.Structure):      # family: include/peahip.h PEA_ROUTE_*
+    _fields_ = [('name', C.c_char * 32), ('family', C.c_int), ('variant', C.c_int), ('listed', C.c_int), ('col_group', C.c_int),
+                ('lds_bytes', C.c_int64), ('n_jobs', C.c_int), ('job', C.c_int * 12), ('col0', C.c_int * 12),
+                ('n_out', C.c_int * 12), ('gate_col0', C.c_int * 12)]
+
+
 class Mlp2BwdChan(C.Structure):
     _fields_ = [('w0', C.c_void_p), ('w1', C.c_void_p), ('dt1_col', C.c_int), ('h_col', C.c_int), ('dz_col', C.c_int),
                 ('da_col', C.c_int)]
@@ -140,6 +146,7 @@ SIGNATURES = {
     'pea_block_sum': (_int, [_i64, _int, _int, _vp, _i64, _vp, _i64, _vp]),
     'pea_grad_weight_sharded': (_int, [_i64, _int, _int, _int, _int, C.POINTER(GwJob), _vp, _sz, _vp]),
     'pea_dense_batch_rows': (_int, [_i64, _vp, _int, C.POINTER(DenseJob), _vp]),
+    'pea_dense_route': (_int, [_i64, _int, _int, C.POINTER(DenseJob), _int, C.POINTER(DenseRouteEntry), C.POINTER(_int)]),
     'pea_sample_negatives': (_int, [_i64, _int, _vp, _vp, _i64, _i64, _vp, _i64, C.c_uint64, C.c_uint32, _vp, _i64, _vp, _vp]),
     'pea_fuse': (_int, [_i64, _int, _int, _vp, _i64, C.POINTER(_int), _vp, _int, _int, _vp, _vp]),
     'pea_bpr_workspace_bytes': (_sz, [_i64]),
@@ -195,6 +202,17 @@ def last_error():
 def check(rc):
     if rc != PEA_OK:
         raise PeaError(rc, last_error())
+
+
+def dense_route(n_rows, rows_given, jobs):
+    """The launches pea_dense_batch (rows_given false) / pea_dense_batch_rows would issue for a ctypes array of DenseJob, as
+    DenseRouteEntry records in issue order (pea_dense_route: needs no device, reads through none of the pointers)."""
+    lib = load()
+    cnt = C.c_int()
+    check(lib.pea_dense_route(n_rows, int(rows_given), len(jobs), jobs, 0, None, C.byref(cnt)))
+    out = (DenseRouteEntry * max(cnt.value, 1))()
+    check(lib.pea_dense_route(n_rows, int(rows_given), len(jobs), jobs, cnt.value, out, C.byref(cnt)))
+    return list(out[:cnt.value])
 
 
 def require_device():

@@ -16,6 +16,19 @@ void set_error(const char *fmt, ...) {
 
 const char *get_error() { return g_err; }
 
+int device_cu_count(int *n_cu) {
+    static int cached = 0;
+    if (!cached) {
+        hipDeviceProp_t prop;
+        int dev = 0;
+        PEA_HIP(hipGetDevice(&dev));
+        PEA_HIP(hipGetDeviceProperties(&prop, dev));
+        cached = prop.multiProcessorCount;
+    }
+    *n_cu = cached;
+    return PEA_OK;
+}
+
 }  // namespace pea
 
 extern "C" const char *pea_version(void) { return "peahip 0.1.0 (gfx950)"; }

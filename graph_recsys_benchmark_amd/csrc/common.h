@@ -76,6 +76,9 @@ inline void launch_rec(F f, hipStream_t stream) {
 #define PEA_MEMSET_ASYNC(ptr, value, bytes, stream) \
     pea::launch_rec([=](hipStream_t s_) { (void)hipMemsetAsync(ptr, value, bytes, s_); }, stream)
 
+// compute units of the current device, queried once per process (capi.hip)
+int device_cu_count(int *n_cu);
+
 constexpr int kWave = 64;          // gfx950 wavefront
 constexpr int kShortDeg = 32;      // rows with <= this many kept edges go to the row-per-subgroup kernel
 constexpr int kChunk = 512;        // hub rows are cut into chunks of at most this many edges
@@ -330,7 +333,7 @@ struct GemmJob {
     // merged per relation when sharded and all together on one GPU, and both must give the same bits.
     int no_narrow;
     // Columns of B, counted from the job's own B pointer, that the float4 loaders of the B images may read: [c, c + 4) only
-    // where c < b_cols.  Filled in by launch_gemm_batch (callers leave it alone): n_out rounded up to 4, and never more than
+    // where c < b_cols.  Filled in by launch_gemm_batch's planner (callers leave it alone): n_out rounded up to 4, and never more than
     // what is left of the k row (ldb, or ldb - c0 for the column chunk [c0, c1) of an oversize job, whose B pointer is
     // already c0 columns into the row).  The images are padded to 32 columns; bounding the loads by ldb instead read the
     // pad columns from the next k row and, on the last row of a chunk or of a block that sits at a column offset inside a
@@ -339,6 +342,9 @@ struct GemmJob {
 };
 int launch_gemm(const GemmJob &job, const int *rows, int64_t n_rows, hipStream_t stream);
 int launch_gemm_batch(const GemmJob *jobs, int n_jobs, const int *rows, int64_t n_rows, hipStream_t stream);
+// what launch_gemm_batch would issue for these jobs, without a device (pea_dense_route); *count = all launches, the first
+// `cap` of them described in entries
+int gemm_route(const GemmJob *jobs, int n_jobs, bool rows_given, int64_t n_rows, int cap, pea_dense_route_entry *entries, int *count);
 
 // weight packing: produces the k-major extended weight blocks the GEMM consumes
 struct PackJob {

@@ -349,13 +349,8 @@ __global__ __launch_bounds__(256) void gw_stage2(const GwBatch Jb, const float *
 // +-15 % (2.7-3.9 TB/s of operand bytes: 256-byte pieces of 2304-byte rows), while stage 2 grows with the part count.
 // PEA_GW_PARTS overrides (experiments).
 int gw_parts(int n_jobs, int64_t n_rows, bool lds_kernel) {
-    static int n_cu = 0;
-    if (!n_cu) {
-        hipDeviceProp_t prop;
-        int dev = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n_cu = prop.multiProcessorCount;
-        if (n_cu <= 0) n_cu = 256;
-    }
+    static int n_cu = 0;   // the fallback is kept too: a failed query is not repeated
+    if (!n_cu && (device_cu_count(&n_cu) != PEA_OK || n_cu <= 0)) n_cu = 256;
     const char *env = getenv("PEA_GW_PARTS");
     int parts;
     if (env && atoi(env) > 0) {
@@ -549,18 +544,15 @@ static int grad_weight_impl(const pea::RowMap &rowmap, int64_t n_rows, int n_job
     return PEA_OK;
 }
 
-extern "C" int pea_dense_batch_rows(int64_t n_rows, const int32_t *rows, int n_jobs, const pea_dense_job *jobs_host,
-                                    void *stream);
-
 extern "C" int pea_dense_batch(int64_t n_rows, int n_jobs, const pea_dense_job *jobs_host, void *stream) {
     return pea_dense_batch_rows(n_rows, nullptr, n_jobs, jobs_host, stream);
 }
 
-// rows != null: only the listed rows (device int32 [n_rows], e.g. the rows a rank owns) of every operand are read / written
-extern "C" int pea_dense_batch_rows(int64_t n_rows, const int32_t *rows, int n_jobs, const pea_dense_job *jobs_host,
-                                    void *stream) {
+// the argument checks of pea_dense_batch[_rows] / pea_dense_route and the jobs as the transform kernels take them
+static int dense_jobs(int64_t n_rows, int n_jobs, const pea_dense_job *jobs_host, std::vector<GemmJob> *out) {
     PEA_REQUIRE(n_rows >= 0 && n_jobs >= 0 && (jobs_host || n_jobs == 0), PEA_ERR_ARG, "dense_batch: bad arguments");
-    std::vector<GemmJob> jobs((size_t)n_jobs);
+    std::vector<GemmJob> &jobs = *out;
+    jobs.resize((size_t)n_jobs);
     for (int q = 0; q < n_jobs; ++q) {
         const pea_dense_job &S = jobs_host[q];
         PEA_REQUIRE(S.a && S.w && S.out && S.k > 0 && S.n_out > 0 && S.k % 4 == 0 && S.n_out % 4 == 0 && S.lda % 4 == 0 &&
@@ -590,7 +582,23 @@ extern "C" int pea_dense_batch_rows(int64_t n_rows, const int32_t *rows, int n_j
         J.seg[0].ld_gate = (int)S.ld_gate;
         jobs[(size_t)q] = J;
     }
+    return PEA_OK;
+}
+
+// rows != null: only the listed rows (device int32 [n_rows], e.g. the rows a rank owns) of every operand are read / written
+extern "C" int pea_dense_batch_rows(int64_t n_rows, const int32_t *rows, int n_jobs, const pea_dense_job *jobs_host,
+                                    void *stream) {
+    std::vector<GemmJob> jobs;
+    PEA_TRY(dense_jobs(n_rows, n_jobs, jobs_host, &jobs));
     return launch_gemm_batch(jobs.data(), n_jobs, rows, n_rows, (hipStream_t)stream);
+}
+
+extern "C" int pea_dense_route(int64_t n_rows, int rows_given, int n_jobs, const pea_dense_job *jobs_host, int cap,
+                               pea_dense_route_entry *entries_out, int *count_out) {
+    PEA_REQUIRE(count_out && cap >= 0 && (entries_out || cap == 0), PEA_ERR_ARG, "dense_route: bad arguments");
+    std::vector<GemmJob> jobs;
+    PEA_TRY(dense_jobs(n_rows, n_jobs, jobs_host, &jobs));
+    return gemm_route(jobs.data(), n_jobs, rows_given != 0, n_rows, cap, entries_out, count_out);
 }
 
 

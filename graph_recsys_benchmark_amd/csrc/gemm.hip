@@ -697,65 +697,6 @@ __global__ __launch_bounds__(512) void gemm_skinny_kernel(const GemmBatch Bt, co
     }
 }
 
-// a job qualifies when its output is at most 16 columns wide, k fits 128 and every segment can take float4 stores
-static bool skinny_ok(const GemmJob &J) {
-    if (J.no_narrow || J.seg[0].gate || J.n_out > 16 || J.K1 + J.K2 > 128 || J.ldb < J.n_out) return false;
-    for (int sg = 0; sg < J.n_seg; ++sg) {
-        const GemmSegment &S = J.seg[sg];
-        if (S.c0 % 4 || S.c1 % 4 || S.ld % 4 || (reinterpret_cast<uintptr_t>(S.dst) & 15)) return false;
-    }
-    return true;
-}
-
-template <int KQ, bool LISTED>
-static int launch_skinny_v(const GemmBatch &Bt, const SkinnyArgs &Sa, size_t lds, int grid, const int *rows, int64_t n_rows,
-                           double bytes, hipStream_t stream) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        PEA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_skinny_kernel<KQ, LISTED>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
-        attr_set = true;
-    }
-    ProfScope ps("gemm_mfma_narrow", stream, bytes);
-    PEA_LAUNCH((gemm_skinny_kernel<KQ, LISTED>), dim3((unsigned)grid), dim3(512), lds, stream, Bt, Sa, rows, n_rows);
-    PEA_HIP(hipGetLastError());
-    return PEA_OK;
-}
-
-template <int KQ>
-static int launch_skinny(const GemmBatch &Bt, const int *rows, int64_t n_rows, double bytes, hipStream_t stream) {
-    SkinnyArgs Sa;
-    int off = 0, items = 0;
-    bool listed = rows != nullptr;
-    for (int j = 0; j < Bt.n; ++j) {
-        listed = listed || Bt.j[j].rows != nullptr;
-        Sa.lds_off[j] = off;
-        off += (16 * KQ + 1) * 16;
-        Sa.item_start[j] = items;
-        items += (int)(((Bt.j[j].rows ? Bt.j[j].n_rows : n_rows) + 63) / 64);
-    }
-    Sa.item_start[Bt.n] = items;
-    Sa.n_items = items;
-    Sa.tiles_per_job = 0;
-    {
-        bool same = Bt.n > 1;
-        for (int j = 1; j < Bt.n; ++j) same = same && (Sa.item_start[j + 1] - Sa.item_start[j]) == Sa.item_start[1];
-        const char *env = getenv("PEA_SKINNY_JOBMAJOR");
-        if (same && !(env && atoi(env) != 0)) Sa.tiles_per_job = Sa.item_start[1];
-    }
-    static int n_cu = 0;
-    if (!n_cu) {
-        hipDeviceProp_t prop;
-        int dev = 0;
-        PEA_HIP(hipGetDevice(&dev));
-        PEA_HIP(hipGetDeviceProperties(&prop, dev));
-        n_cu = prop.multiProcessorCount;
-    }
-    const int grid = std::min(n_cu * 2, (items + 7) / 8);
-    const size_t lds = (size_t)off * sizeof(float);
-    return listed ? launch_skinny_v<KQ, true>(Bt, Sa, lds, grid, rows, n_rows, bytes, stream)
-                  : launch_skinny_v<KQ, false>(Bt, Sa, lds, grid, rows, n_rows, bytes, stream);
-}
 
 struct PackLaunch {
     int n;
@@ -810,6 +751,45 @@ __global__ __launch_bounds__(256) void pack_kernel(const PackLaunch L) {
 
 }  // namespace
 
+// ---------------------------------------------------------------- host side: plan, then launch
+// plan_gemm_launches decides what launch_gemm_batch issues, with no device and no environment (pea_dense_route shows the same
+// decision where no GPU is).  The kernels differ in k summation order, so the rules are bit-relevant; DESIGN.md section 4 has
+// them as a table.  In this order: the gate check; narrow jobs (skinny_ok) to the skinny kernel, one launch per k class (k <=
+// 32 / 64 / 128: KH = 16 / 32 / 64, KQ = KH / 8); of the others, those with k <= 128 to the persistent kernel per k class,
+// cut into column chunks where the B image exceeds the LDS budget, a launch closing when the next image would not fit; then
+// k > 128, the deep kernel chosen per launch (close_deep).  At most kMaxBatch jobs per launch; jobs are checked (check_job) as
+// they are reached and dropped when they have no rows.
+constexpr size_t kLdsBudget = 160 * 1024 - 1024;  // dynamic LDS a workgroup may claim (one workgroup per CU)
+static_assert(kMaxBatch == PEA_ROUTE_MAX_JOBS, "pea_dense_route_entry holds one index per batch entry");
+
+struct GemmEnv {   // the A/B switches, read once per call by the caller of the planner
+    bool deep_staged;      // PEA_DEEP_STAGED=1: every deep launch on the per-column-tile staged kernel
+    bool skinny_jobmajor;  // PEA_SKINNY_JOBMAJOR=1: the skinny kernel's old job-major item order
+};
+static GemmEnv gemm_env() {
+    const char *deep = getenv("PEA_DEEP_STAGED"), *major = getenv("PEA_SKINNY_JOBMAJOR");
+    return GemmEnv{deep && atoi(deep) != 0, major && atoi(major) != 0};
+}
+
+struct GemmLaunch {
+    GemmLaunch() {}        // filled in place by the planner: nothing of its ~4 KB is cleared first
+    int family, variant;   // PEA_ROUTE_*; KQ (skinny), KH (persist), NCT (deep resident / chunk), 64 (staged)
+    bool listed;           // some job reads a row list
+    GemmBatch Bt;          // chunk rewrites and b_cols applied
+    int src[kMaxBatch];    // index of each batch entry's job in the caller's list
+    PersistArgs Pa;        // PEA_ROUTE_PERSIST
+    SkinnyArgs Sa;         // PEA_ROUTE_SKINNY
+    size_t lds;            // dynamic LDS bytes
+    const char *name;      // profile name
+    double bytes;          // attributed to the launch
+    int per_cu;            // grid = (per_cu ? min(per_cu * CUs, blocks) : blocks, deep kernels: one grid row per job)
+    int64_t blocks;
+};
+struct GemmPiece {   // columns [c0, c1) of job src (all of them unless the job was cut), on their way into a launch
+    int src, c0, c1;
+    int family, KH;  // PEA_ROUTE_SKINNY, _PERSIST or _DEEP_STAGED (k > 128: the launch picks the deep kernel); k class
+};
+
 static int check_job(const GemmJob &job) {
     PEA_REQUIRE(job.K1 > 0 && job.K1 % 4 == 0 && job.K2 % 4 == 0, PEA_ERR_ARG,
                 "gemm: input widths (%d, %d) must be multiples of 4", job.K1, job.K2);
@@ -820,36 +800,49 @@ static int check_job(const GemmJob &job) {
     return PEA_OK;
 }
 
-constexpr size_t kLdsBudget = 160 * 1024 - 1024;  // dynamic LDS a workgroup may claim (one workgroup per CU)
-
-template <int KH, bool LISTED>
-int launch_persist_v(const GemmBatch &Bt, const PersistArgs &Pa, size_t lds, int grid, const int *rows, int64_t n_rows,
-                     double bytes, hipStream_t stream) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        PEA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_persist_kernel<KH, LISTED>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget));
-        attr_set = true;
+// a job qualifies when its output is at most 16 columns wide, k fits 128 and every segment can take float4 stores
+static bool skinny_ok(const GemmJob &J) {
+    if (J.no_narrow || J.seg[0].gate || J.n_out > 16 || J.K1 + J.K2 > 128 || J.ldb < J.n_out) return false;
+    for (int sg = 0; sg < J.n_seg; ++sg) {
+        const GemmSegment &S = J.seg[sg];
+        if (S.c0 % 4 || S.c1 % 4 || S.ld % 4 || (reinterpret_cast<uintptr_t>(S.dst) & 15)) return false;
     }
-    constexpr int NT = KH > 32 ? 512 : 1024;
-    ProfScope ps(Bt.n == 1 ? "gemm_mfma_shared" : "gemm_mfma_batch", stream, bytes);
-    PEA_LAUNCH((gemm_persist_kernel<KH, LISTED>), dim3((unsigned)grid), dim3(NT), lds, stream, Bt, Pa, rows, n_rows);
-    PEA_HIP(hipGetLastError());
-    return PEA_OK;
+    return true;
 }
 
-template <int KH>
-int launch_persist(const GemmBatch &Bt, const int *rows, int64_t n_rows, double bytes, hipStream_t stream) {
-    PersistArgs Pa;
-    Pa.col_group = kColGroup;
-    for (int j = 0; j < Bt.n; ++j)
-        if (Bt.j[j].seg[0].gate) Pa.col_group = 2;   // gated epilogues hold the gate values of two column tiles
+static int k_class(int K) { return K <= 32 ? 16 : K <= 64 ? 32 : 64; }   // KH of the persistent kernel; KQ = KH / 8
+
+static void close_skinny(GemmLaunch &L, int KQ, int64_t n_rows, const GemmEnv &env) {
+    SkinnyArgs &Sa = L.Sa;
     int off = 0, items = 0;
-    bool listed = rows != nullptr;
-    for (int j = 0; j < Bt.n; ++j) {
-        const int nct = (Bt.j[j].n_out + 31) / 32;
-        const int n_tiles = (int)(((Bt.j[j].rows ? Bt.j[j].n_rows : n_rows) + 31) / 32);
-        listed = listed || Bt.j[j].rows != nullptr;
+    for (int j = 0; j < L.Bt.n; ++j) {
+        Sa.lds_off[j] = off;
+        off += (16 * KQ + 1) * 16;
+        Sa.item_start[j] = items;
+        items += (int)(((L.Bt.j[j].rows ? L.Bt.j[j].n_rows : n_rows) + 63) / 64);
+    }
+    Sa.item_start[L.Bt.n] = items;
+    Sa.n_items = items;
+    bool same = L.Bt.n > 1;
+    for (int j = 1; j < L.Bt.n; ++j) same = same && (Sa.item_start[j + 1] - Sa.item_start[j]) == Sa.item_start[1];
+    Sa.tiles_per_job = same && !env.skinny_jobmajor ? Sa.item_start[1] : 0;
+    L.family = PEA_ROUTE_SKINNY;
+    L.variant = KQ;
+    L.name = "gemm_mfma_narrow";
+    L.lds = (size_t)off * sizeof(float);
+    L.per_cu = 2;
+    L.blocks = (items + 7) / 8;
+}
+
+static void close_persist(GemmLaunch &L, int KH, int64_t n_rows) {
+    PersistArgs &Pa = L.Pa;
+    Pa.col_group = kColGroup;
+    for (int j = 0; j < L.Bt.n; ++j)
+        if (L.Bt.j[j].seg[0].gate) Pa.col_group = 2;   // gated epilogues hold the gate values of two column tiles
+    int off = 0, items = 0;
+    for (int j = 0; j < L.Bt.n; ++j) {
+        const int nct = (L.Bt.j[j].n_out + 31) / 32;
+        const int n_tiles = (int)(((L.Bt.j[j].rows ? L.Bt.j[j].n_rows : n_rows) + 31) / 32);
         Pa.n_tiles[j] = n_tiles;
         Pa.lds_ld[j] = nct * 32;
         Pa.lds_off[j] = off;
@@ -857,29 +850,90 @@ int launch_persist(const GemmBatch &Bt, const int *rows, int64_t n_rows, double 
         Pa.item_start[j] = items;
         items += n_tiles * ((nct + Pa.col_group - 1) / Pa.col_group);
     }
-    Pa.item_start[Bt.n] = items;
+    Pa.item_start[L.Bt.n] = items;
     Pa.n_items = items;
-    const size_t lds = (size_t)off * sizeof(float);
-    static int n_cu = 0;
-    if (!n_cu) {
-        hipDeviceProp_t prop;
-        int dev = 0;
-        PEA_HIP(hipGetDevice(&dev));
-        PEA_HIP(hipGetDeviceProperties(&prop, dev));
-        n_cu = prop.multiProcessorCount;
-    }
-    const int per_cu = lds * 2 <= kLdsBudget ? 2 : 1;  // two workgroups share a CU when their B images both fit
-    constexpr int NT = KH > 32 ? 512 : 1024;
-    const int grid = std::min(n_cu * per_cu, (items + NT / 64 - 1) / (NT / 64));
-    return listed ? launch_persist_v<KH, true>(Bt, Pa, lds, grid, rows, n_rows, bytes, stream)
-                  : launch_persist_v<KH, false>(Bt, Pa, lds, grid, rows, n_rows, bytes, stream);
+    const int waves = (KH > 32 ? 512 : 1024) / 64;
+    L.family = PEA_ROUTE_PERSIST;
+    L.variant = KH;
+    L.name = L.Bt.n == 1 ? "gemm_mfma_shared" : "gemm_mfma_batch";
+    L.lds = (size_t)off * sizeof(float);
+    L.per_cu = L.lds * 2 <= kLdsBudget ? 2 : 1;  // two workgroups share a CU when their B images both fit
+    L.blocks = (items + waves - 1) / waves;
 }
 
-// Jobs of one call share the row set; jobs with the same k-depth class go out as one launch.  A job whose B does
-// not fit the LDS budget is cut into column chunks; k deeper than 128 falls back to the staged kernel.
-int launch_gemm_batch(const GemmJob *jobs_in, int n_jobs_in, const int *rows, int64_t n_rows, hipStream_t stream) {
-    if (n_jobs_in <= 0) return PEA_OK;
-    std::vector<GemmJob> jobs;
+static void close_deep(GemmLaunch &L, int64_t n_rows, const GemmEnv &env) {
+    int64_t max_rows = n_rows;
+    int max_out = 0, max_k = 0;
+    bool plain = true;   // one input block, no edge-less-row substitution: what the resident kernel's loader takes
+    for (int q = 0; q < L.Bt.n; ++q) {
+        const GemmJob &J = L.Bt.j[q];
+        max_rows = std::max<int64_t>(max_rows, J.rows ? J.n_rows : 0);
+        max_out = std::max(max_out, J.n_out);
+        max_k = std::max(max_k, J.K1 + J.K2);
+        plain = plain && J.K2 == 0 && J.a1_mask == nullptr;
+    }
+    const int nct = max_out <= 32 ? 1 : max_out <= 64 ? 2 : 4;
+    const size_t lds_res = (size_t)max_k * 32 * nct * sizeof(float);
+    L.name = "gemm_mfma_deep";
+    L.variant = nct;
+    L.per_cu = 0;
+    L.blocks = (max_rows + 127) / 128;
+    if (plain && max_out <= 64 && lds_res <= kLdsBudget && !env.deep_staged) {   // (4 column tiles would spill)
+        L.family = PEA_ROUTE_DEEP_RESIDENT;   // B resident in LDS, no barriers: persistent workgroups
+        L.lds = lds_res;
+        L.per_cu = 1;
+        L.blocks = std::max<int64_t>(1, ((max_rows + 31) / 32 + 15) / 16);
+    } else if (max_out <= 128 && !env.deep_staged) {
+        L.family = PEA_ROUTE_DEEP_CHUNK;
+        L.lds = (size_t)2 * 128 * 32 * nct * sizeof(float);
+    } else {
+        L.family = PEA_ROUTE_DEEP_STAGED;
+        L.variant = 64;
+        L.lds = 0;
+    }
+}
+
+// The batch entry of a piece: the job itself (b_cols filled in, except for the skinny kernel, which does not read it), or its
+// column chunk: B, bias, the segments and their gates move with the columns.
+static void place_piece(GemmJob &C, const GemmJob &J, const GemmPiece &P) {
+    C = J;
+    if (P.family == PEA_ROUTE_SKINNY) return;
+    C.b_cols = std::min(J.ldb - P.c0, (P.c1 - P.c0 + 3) / 4 * 4);   // the piece's own columns (GemmJob::b_cols); the image's pad past c1 is not loaded
+    if (P.c1 - P.c0 == J.n_out) return;
+    C.B = J.B + P.c0;
+    C.n_out = P.c1 - P.c0;
+    C.bias = J.bias ? J.bias + P.c0 : nullptr;
+    C.n_seg = 0;
+    for (int sg = 0; sg < J.n_seg; ++sg) {
+        const int a0 = std::max(J.seg[sg].c0, P.c0), a1 = std::min(J.seg[sg].c1, P.c1);
+        if (a1 <= a0) continue;
+        GemmSegment S = J.seg[sg];
+        S.dst = J.seg[sg].dst + (a0 - J.seg[sg].c0);
+        if (S.gate) S.gate = J.seg[sg].gate + (a0 - J.seg[sg].c0);
+        S.c0 = a0 - P.c0;
+        S.c1 = a1 - P.c0;
+        C.seg[C.n_seg++] = S;
+    }
+}
+
+// what the batch in L.Bt needs beside its jobs
+static void close_launch(GemmLaunch &L, int family, int KH, bool rows_given, int64_t n_rows, const GemmEnv &env) {
+    L.listed = rows_given;
+    L.bytes = 0.0;
+    for (int q = 0; q < L.Bt.n; ++q) {
+        const GemmJob &J = L.Bt.j[q];
+        L.listed = L.listed || J.rows != nullptr;
+        L.bytes += 4.0 * (double)(J.rows ? J.n_rows : n_rows) * (J.K1 + J.K2 + J.n_out);
+    }
+    if (family == PEA_ROUTE_SKINNY) close_skinny(L, KH / 8, n_rows, env);
+    else if (family == PEA_ROUTE_PERSIST) close_persist(L, KH, n_rows);
+    else close_deep(L, n_rows, env);
+}
+
+// The launches of one launch_gemm_batch call, in issue order.  Pure: no HIP call, no getenv, and of the pointers inside the
+// jobs only the segments' dst addresses are looked at (their alignment, skinny_ok); none is dereferenced.
+static int plan_gemm_launches(const GemmJob *jobs_in, int n_jobs_in, bool rows_given, int64_t n_rows, const GemmEnv &env,
+                              std::vector<GemmLaunch> *out) {
     for (int i = 0; i < n_jobs_in; ++i) {   // a gated epilogue exists in the persistent kernel only (k <= 128)
         bool any = false, all = true;
         for (int sg = 0; sg < jobs_in[i].n_seg; ++sg) {
@@ -889,157 +943,153 @@ int launch_gemm_batch(const GemmJob *jobs_in, int n_jobs_in, const int *rows, in
         PEA_REQUIRE(!any || (all && jobs_in[i].K1 + jobs_in[i].K2 <= 128), PEA_ERR_ARG,
                     "gemm: a gated job needs the gate on every segment and k <= 128");
     }
-    // narrow outputs first: one launch per k class
-    for (int kq : {2, 4, 8}) {
-        GemmBatch Bt;
-        Bt.n = 0;
-        double bytes = 0.0;
-        auto flush = [&]() -> int {
-            if (Bt.n == 0) return PEA_OK;
-            int rc = kq == 2 ? launch_skinny<2>(Bt, rows, n_rows, bytes, stream)
-                     : kq == 4 ? launch_skinny<4>(Bt, rows, n_rows, bytes, stream)
-                               : launch_skinny<8>(Bt, rows, n_rows, bytes, stream);
-            Bt.n = 0;
-            bytes = 0.0;
-            return rc;
-        };
+    std::vector<GemmPiece> pieces;
+    pieces.reserve((size_t)n_jobs_in);
+    for (int KH : {16, 32, 64})   // narrow outputs first, by k class
         for (int i = 0; i < n_jobs_in; ++i) {
             const GemmJob &J = jobs_in[i];
-            const int K = J.K1 + J.K2;
-            if (!skinny_ok(J) || (K <= 32 ? 2 : K <= 64 ? 4 : 8) != kq) continue;
+            if (!skinny_ok(J) || k_class(J.K1 + J.K2) != KH) continue;
             PEA_TRY(check_job(J));
-            const int64_t nr = J.rows ? J.n_rows : n_rows;
-            if (nr <= 0) continue;
-            Bt.j[Bt.n++] = J;
-            bytes += 4.0 * (double)nr * (K + J.n_out);
-            if (Bt.n == kMaxBatch) PEA_TRY(flush());
+            if ((J.rows ? J.n_rows : n_rows) > 0) pieces.push_back({i, 0, J.n_out, PEA_ROUTE_SKINNY, KH});
         }
-        PEA_TRY(flush());
-    }
     for (int i = 0; i < n_jobs_in; ++i) {
         if (skinny_ok(jobs_in[i])) continue;
         PEA_TRY(check_job(jobs_in[i]));
         const GemmJob &J = jobs_in[i];
         if ((J.rows ? J.n_rows : n_rows) <= 0) continue;
-        const int K = J.K1 + J.K2;
-        const int KH = K <= 32 ? 16 : K <= 64 ? 32 : 64;
+        const int K = J.K1 + J.K2, KH = k_class(K);
         const int max_cols = (int)(kLdsBudget / sizeof(float) / (size_t)(2 * KH + 1)) / 32 * 32;
         if (K > 128 || J.n_out <= max_cols) {
-            jobs.push_back(J);
-            jobs.back().b_cols = std::min(J.ldb, (J.n_out + 3) / 4 * 4);   // the job's own columns: see GemmJob::b_cols
+            pieces.push_back({i, 0, J.n_out, K > 128 ? PEA_ROUTE_DEEP_STAGED : PEA_ROUTE_PERSIST, KH});
             continue;
         }
-        for (int c0 = 0; c0 < J.n_out; c0 += max_cols) {  // column chunks of an oversize job
-            GemmJob C = J;
+        for (int c0 = 0; c0 < J.n_out; c0 += max_cols) {  // column chunks of an oversize job; one that no segment stores is dropped
             const int c1 = std::min(J.n_out, c0 + max_cols);
-            C.B = J.B + c0;
-            C.n_out = c1 - c0;
-            C.b_cols = std::min(J.ldb - c0, (C.n_out + 3) / 4 * 4);   // the chunk's own columns; the image's pad past c1 is not loaded
-            C.bias = J.bias ? J.bias + c0 : nullptr;
-            C.n_seg = 0;
-            for (int sg = 0; sg < J.n_seg; ++sg) {
-                const int a0 = std::max(J.seg[sg].c0, c0), a1 = std::min(J.seg[sg].c1, c1);
-                if (a1 <= a0) continue;
-                GemmSegment S = J.seg[sg];
-                S.dst = J.seg[sg].dst + (a0 - J.seg[sg].c0);
-                if (S.gate) S.gate = J.seg[sg].gate + (a0 - J.seg[sg].c0);
-                S.c0 = a0 - c0;
-                S.c1 = a1 - c0;
-                C.seg[C.n_seg++] = S;
-            }
-            if (C.n_seg) jobs.push_back(C);
+            bool stored = false;
+            for (int sg = 0; sg < J.n_seg; ++sg) stored = stored || std::min(J.seg[sg].c1, c1) > std::max(J.seg[sg].c0, c0);
+            if (stored) pieces.push_back({i, c0, c1, PEA_ROUTE_PERSIST, KH});
         }
     }
-    const int n_jobs = (int)jobs.size();
-    const int classes[3] = {16, 32, 64};
-    for (int ci = 0; ci < 3; ++ci) {
-        for (int deep = 0; deep < 2; ++deep) {  // deep: K > 2*KH, staged kernel
-            GemmBatch Bt;
-            Bt.n = 0;
-            double bytes = 0.0;
+    out->reserve(pieces.size());   // no launch record is ever moved
+    for (int family : {PEA_ROUTE_SKINNY, PEA_ROUTE_PERSIST, PEA_ROUTE_DEEP_STAGED})
+        for (int KH : {16, 32, 64}) {
+            GemmLaunch *L = nullptr;   // the open launch of this pass
             size_t lds = 0;
-            auto flush = [&]() -> int {
-                if (Bt.n == 0) return PEA_OK;
-                int rc = PEA_OK;
-                if (!deep) {
-                    switch (classes[ci]) {
-                        case 16: rc = launch_persist<16>(Bt, rows, n_rows, bytes, stream); break;
-                        case 32: rc = launch_persist<32>(Bt, rows, n_rows, bytes, stream); break;
-                        default: rc = launch_persist<64>(Bt, rows, n_rows, bytes, stream); break;
-                    }
-                } else {
-                    int64_t max_rows = n_rows;
-                    for (int q = 0; q < Bt.n; ++q) max_rows = std::max<int64_t>(max_rows, Bt.j[q].rows ? Bt.j[q].n_rows : 0);
-                    dim3 grid((unsigned)((max_rows + 127) / 128), (unsigned)Bt.n);
-                    ProfScope ps("gemm_mfma_deep", stream, bytes);
-                    int max_out = 0;
-                    for (int q = 0; q < Bt.n; ++q) max_out = std::max(max_out, Bt.j[q].n_out);
-                    const char *env = getenv("PEA_DEEP_STAGED");   // A/B switch: the per-column-tile staged kernel
-                    int max_k = 0;
-                    for (int q = 0; q < Bt.n; ++q) max_k = std::max(max_k, Bt.j[q].K1 + Bt.j[q].K2);
-                    const int nct_r = max_out <= 32 ? 1 : max_out <= 64 ? 2 : 4;
-                    const size_t lds_res = (size_t)max_k * 32 * nct_r * sizeof(float);
-                    bool plain = true;   // one input block, no edge-less-row substitution: what the resident kernel's loader takes
-                    for (int q = 0; q < Bt.n; ++q) plain = plain && Bt.j[q].K2 == 0 && Bt.j[q].a1_mask == nullptr;
-                    if (plain && max_out <= 64 && lds_res <= kLdsBudget && !(env && atoi(env) != 0)) {   // (4 column tiles would spill)
-                        // B resident in LDS, no barriers: persistent workgroups of 8 waves
-                        static bool attr_res = false;
-                        if (!attr_res) {
-                            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_deep_resident_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget);
-                            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_deep_resident_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget);
-                            attr_res = true;
-                        }
-                        hipDeviceProp_t prop;
-                        int dev = 0;
-                        static int n_cu_deep = 0;
-                        if (!n_cu_deep && hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n_cu_deep = prop.multiProcessorCount;
-                        const int64_t tiles = (max_rows + 31) / 32;
-                        dim3 grid_r((unsigned)std::max<int64_t>(1, std::min<int64_t>(n_cu_deep > 0 ? n_cu_deep : 256, (tiles + 15) / 16)), (unsigned)Bt.n);
-                        if (nct_r == 1) PEA_LAUNCH(gemm_deep_resident_kernel<1>, grid_r, dim3(1024), lds_res, stream, Bt, rows, n_rows);
-                        else PEA_LAUNCH(gemm_deep_resident_kernel<2>, grid_r, dim3(1024), lds_res, stream, Bt, rows, n_rows);
-                    } else if (max_out <= 128 && !(env && atoi(env) != 0)) {
-                        const int nct = max_out <= 32 ? 1 : max_out <= 64 ? 2 : 4;
-                        const size_t lds_deep = (size_t)2 * 128 * 32 * nct * sizeof(float);
-                        static bool attr_set = false;
-                        if (!attr_set) {
-                            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_deep_kernel<2>),
-                                                      hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 128 * 64 * 4);
-                            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_deep_kernel<4>),
-                                                      hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 128 * 128 * 4);
-                            attr_set = true;
-                        }
-                        if (nct == 1) PEA_LAUNCH(gemm_deep_kernel<1>, grid, dim3(256), lds_deep, stream, Bt, rows, n_rows);
-                        else if (nct == 2) PEA_LAUNCH(gemm_deep_kernel<2>, grid, dim3(256), lds_deep, stream, Bt, rows, n_rows);
-                        else PEA_LAUNCH(gemm_deep_kernel<4>, grid, dim3(256), lds_deep, stream, Bt, rows, n_rows);
-                    } else {
-                        PEA_LAUNCH(gemm_mfma_kernel<64>, grid, dim3(256), 0, stream, Bt, rows, n_rows);
-                    }
-                    if (hipGetLastError() != hipSuccess) rc = PEA_ERR_HIP;
+            for (const GemmPiece &P : pieces) {
+                if (P.family != family || P.KH != KH) continue;
+                const size_t need =   // the piece's B image in the persistent kernel's LDS
+                    family != PEA_ROUTE_PERSIST ? 0 : (size_t)(2 * KH + 1) * ((P.c1 - P.c0 + 31) / 32 * 32) * sizeof(float);
+                if (L && (L->Bt.n == kMaxBatch || lds + need > kLdsBudget)) {
+                    close_launch(*L, family, KH, rows_given, n_rows, env);
+                    L = nullptr;
                 }
-                Bt.n = 0;
-                bytes = 0.0;
-                lds = 0;
-                return rc;
-            };
-            for (int i = 0; i < n_jobs; ++i) {
-                const int K = jobs[i].K1 + jobs[i].K2;
-                const int cls = K <= 32 ? 16 : K <= 64 ? 32 : 64;
-                if (cls != classes[ci] || (K > 128) != (deep == 1)) continue;
-                const size_t need = (size_t)(2 * cls + 1) * ((jobs[i].n_out + 31) / 32 * 32) * sizeof(float);
-                if (!deep && Bt.n > 0 && lds + need > kLdsBudget) PEA_TRY(flush());
-                Bt.j[Bt.n++] = jobs[i];
+                if (!L) {
+                    out->emplace_back();
+                    L = &out->back();
+                    L->Bt.n = 0;
+                    lds = 0;
+                }
+                L->src[L->Bt.n] = P.src;
+                place_piece(L->Bt.j[L->Bt.n++], jobs_in[P.src], P);
                 lds += need;
-                bytes += 4.0 * (double)(jobs[i].rows ? jobs[i].n_rows : n_rows) * (K + jobs[i].n_out);
-                if (Bt.n == kMaxBatch) PEA_TRY(flush());
             }
-            PEA_TRY(flush());
+            if (L) close_launch(*L, family, KH, rows_given, n_rows, env);
         }
+    return PEA_OK;
+}
+
+// Raises a kernel's dynamic-LDS limit, once per kernel.
+template <auto Kernel>
+static int max_dynamic_lds(int bytes) {
+    static bool done = false;
+    if (!done) {
+        PEA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+        done = true;
     }
+    return PEA_OK;
+}
+
+// tables: the PersistArgs / SkinnyArgs of the launch.  PEA_LAUNCH captures the batch and the tables by value (tape replay).
+template <auto Kernel, class... Tables>
+static int issue(const GemmLaunch &L, dim3 grid, int threads, int lds_limit, const int *rows, int64_t n_rows, hipStream_t stream,
+                 const Tables &...tables) {
+    if (lds_limit) PEA_TRY(max_dynamic_lds<Kernel>(lds_limit));
+    const GemmBatch &Bt = L.Bt;
+    const size_t lds = L.lds;
+    ProfScope ps(L.name, stream, L.bytes);
+    PEA_LAUNCH(Kernel, grid, dim3(threads), lds, stream, Bt, tables..., rows, n_rows);
+    PEA_HIP(hipGetLastError());
+    return PEA_OK;
+}
+
+constexpr int route_key(int family, int variant, bool listed) { return family * 1000 + variant * 2 + (listed ? 1 : 0); }
+
+static int issue_gemm(const GemmLaunch &L, const int *rows, int64_t n_rows, hipStream_t stream) {
+    int n_cu = 0;
+    if (L.per_cu) PEA_TRY(device_cu_count(&n_cu));
+    const dim3 grid((unsigned)(L.per_cu ? std::min<int64_t>((int64_t)L.per_cu * n_cu, L.blocks) : L.blocks),
+                    (unsigned)(L.family >= PEA_ROUTE_DEEP_RESIDENT ? L.Bt.n : 1));
+    constexpr int kAll = (int)kLdsBudget;
+    const int own = (int)L.lds;   // the 128-chunk kernels: 64 KiB (NCT = 2) and 128 KiB (NCT = 4); NCT = 1 fits the default limit
+    // only the skinny and the persistent kernel have a variant for row lists
+    switch (route_key(L.family, L.variant, L.listed && L.family <= PEA_ROUTE_PERSIST)) {
+        case route_key(PEA_ROUTE_SKINNY, 2, true): return issue<gemm_skinny_kernel<2, true>>(L, grid, 512, kAll, rows, n_rows, stream, L.Sa);
+        case route_key(PEA_ROUTE_SKINNY, 2, false): return issue<gemm_skinny_kernel<2, false>>(L, grid, 512, kAll, rows, n_rows, stream, L.Sa);
+        case route_key(PEA_ROUTE_SKINNY, 4, true): return issue<gemm_skinny_kernel<4, true>>(L, grid, 512, kAll, rows, n_rows, stream, L.Sa);
+        case route_key(PEA_ROUTE_SKINNY, 4, false): return issue<gemm_skinny_kernel<4, false>>(L, grid, 512, kAll, rows, n_rows, stream, L.Sa);
+        case route_key(PEA_ROUTE_SKINNY, 8, true): return issue<gemm_skinny_kernel<8, true>>(L, grid, 512, kAll, rows, n_rows, stream, L.Sa);
+        case route_key(PEA_ROUTE_SKINNY, 8, false): return issue<gemm_skinny_kernel<8, false>>(L, grid, 512, kAll, rows, n_rows, stream, L.Sa);
+        case route_key(PEA_ROUTE_PERSIST, 16, true): return issue<gemm_persist_kernel<16, true>>(L, grid, 1024, kAll, rows, n_rows, stream, L.Pa);
+        case route_key(PEA_ROUTE_PERSIST, 16, false): return issue<gemm_persist_kernel<16, false>>(L, grid, 1024, kAll, rows, n_rows, stream, L.Pa);
+        case route_key(PEA_ROUTE_PERSIST, 32, true): return issue<gemm_persist_kernel<32, true>>(L, grid, 1024, kAll, rows, n_rows, stream, L.Pa);
+        case route_key(PEA_ROUTE_PERSIST, 32, false): return issue<gemm_persist_kernel<32, false>>(L, grid, 1024, kAll, rows, n_rows, stream, L.Pa);
+        case route_key(PEA_ROUTE_PERSIST, 64, true): return issue<gemm_persist_kernel<64, true>>(L, grid, 512, kAll, rows, n_rows, stream, L.Pa);
+        case route_key(PEA_ROUTE_PERSIST, 64, false): return issue<gemm_persist_kernel<64, false>>(L, grid, 512, kAll, rows, n_rows, stream, L.Pa);
+        case route_key(PEA_ROUTE_DEEP_RESIDENT, 1, false): return issue<gemm_deep_resident_kernel<1>>(L, grid, 1024, kAll, rows, n_rows, stream);
+        case route_key(PEA_ROUTE_DEEP_RESIDENT, 2, false): return issue<gemm_deep_resident_kernel<2>>(L, grid, 1024, kAll, rows, n_rows, stream);
+        case route_key(PEA_ROUTE_DEEP_CHUNK, 2, false): return issue<gemm_deep_kernel<2>>(L, grid, 256, own, rows, n_rows, stream);
+        case route_key(PEA_ROUTE_DEEP_CHUNK, 4, false): return issue<gemm_deep_kernel<4>>(L, grid, 256, own, rows, n_rows, stream);
+        case route_key(PEA_ROUTE_DEEP_CHUNK, 1, false): return issue<gemm_deep_kernel<1>>(L, grid, 256, 0, rows, n_rows, stream);
+        case route_key(PEA_ROUTE_DEEP_STAGED, 64, false): return issue<gemm_mfma_kernel<64>>(L, grid, 256, 0, rows, n_rows, stream);
+    }
+    set_error("gemm: no kernel for route (%d, %d)", L.family, L.variant);
+    return PEA_ERR_ARG;
+}
+
+int launch_gemm_batch(const GemmJob *jobs, int n_jobs, const int *rows, int64_t n_rows, hipStream_t stream) {
+    std::vector<GemmLaunch> plan;
+    PEA_TRY(plan_gemm_launches(jobs, n_jobs, rows != nullptr, n_rows, gemm_env(), &plan));
+    for (const GemmLaunch &L : plan) PEA_TRY(issue_gemm(L, rows, n_rows, stream));
     return PEA_OK;
 }
 
 int launch_gemm(const GemmJob &job, const int *rows, int64_t n_rows, hipStream_t stream) {
     return launch_gemm_batch(&job, 1, rows, n_rows, stream);
+}
+
+int gemm_route(const GemmJob *jobs, int n_jobs, bool rows_given, int64_t n_rows, int cap, pea_dense_route_entry *entries, int *count) {
+    std::vector<GemmLaunch> plan;
+    PEA_TRY(plan_gemm_launches(jobs, n_jobs, rows_given, n_rows, gemm_env(), &plan));
+    *count = (int)plan.size();
+    for (int i = 0; i < *count && i < cap; ++i) {
+        const GemmLaunch &L = plan[(size_t)i];
+        pea_dense_route_entry &E = entries[i];
+        snprintf(E.name, sizeof(E.name), "%s", L.name);
+        E.family = L.family;
+        E.variant = L.variant;
+        E.listed = L.listed ? 1 : 0;
+        E.col_group = L.family == PEA_ROUTE_PERSIST ? L.Pa.col_group : 0;
+        E.lds_bytes = (int64_t)L.lds;
+        E.n_jobs = L.Bt.n;
+        for (int q = 0; q < L.Bt.n; ++q) {   // differences of addresses only: nothing is read through them
+            const GemmJob &C = L.Bt.j[q], &J = jobs[L.src[q]];
+            E.job[q] = L.src[q];
+            E.col0[q] = (int)(C.B - J.B);
+            E.n_out[q] = C.n_out;
+            E.gate_col0[q] = C.seg[0].gate ? (int)(C.seg[0].gate - J.seg[0].gate) : -1;
+        }
+    }
+    return PEA_OK;
 }
 
 int launch_pack(const PackJob *jobs, int n_jobs, hipStream_t stream) {

@@ -403,14 +403,8 @@ static int launch_mlp2_v(Mlp2Launch L, const int *rows, int64_t n_rows, hipStrea
         PEA_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         lds_set = lds;
     }
-    static int n_cu = 0;
-    if (!n_cu) {
-        hipDeviceProp_t prop;
-        int dev = 0;
-        PEA_HIP(hipGetDevice(&dev));
-        PEA_HIP(hipGetDeviceProperties(&prop, dev));
-        n_cu = prop.multiProcessorCount;
-    }
+    int n_cu = 0;
+    PEA_TRY(device_cu_count(&n_cu));
     const int64_t n_tiles = (n_rows + 31) / 32;
     constexpr int kMlp2Threads = SAGE ? 512 : Mlp2Cfg<ET, HT>::kThreads;
     constexpr int WPB = kMlp2Threads / 64;

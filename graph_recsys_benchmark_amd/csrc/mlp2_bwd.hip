@@ -237,14 +237,8 @@ int launch_bwd_v(Mlp2BwdLaunch L, int64_t n_rows, hipStream_t stream) {
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         lds_set = lds;
     }
-    static int n_cu = 0;
-    if (!n_cu) {
-        hipDeviceProp_t prop;
-        int dev = 0;
-        PEA_HIP(hipGetDevice(&dev));
-        PEA_HIP(hipGetDeviceProperties(&prop, dev));
-        n_cu = prop.multiProcessorCount;
-    }
+    int n_cu = 0;
+    PEA_TRY(device_cu_count(&n_cu));
     const int64_t n_tiles = (n_rows + 31) / 32;
     constexpr int WPB = 512 / 64;
     L.n_groups = passes;

@@ -581,12 +581,14 @@ def grad_weight(pairs, shard=None, rows=None):
     return outs
 
 
-def dense_batch(triples_, rows=None):
+def dense_batch(triples_, rows=None, route=None):
     """out_q = a_q @ w_q for (a_q [N, k], w_q [k, n_out], out_q [N, n_out] view) in triples_: one launch (the input
     gradients dIn = dT W of one level); k, n_out and a's row stride must be multiples of 4 (a w whose row stride is not,
     or that does not start on a 16-byte boundary, is copied first).  rows (int32 device tensor): only those rows are
     computed (the rows a rank owns in a sharded training step).  A fourth element gate_q [N, n_out] (k <= 128) zeroes the
-    outputs where gate_q <= 0: the relu mask of the layer below, applied in the epilogue."""
+    outputs where gate_q <= 0: the relu mask of the layer below, applied in the epilogue.  route: diagnostic only -- a list
+    that receives the library's account of the launches this call makes (_lib.dense_route of the very job structs); the
+    tests of the dispatch use it, nothing in the product does."""
     lib = _lib.require_device()
     if not triples_:
         return
@@ -611,6 +613,8 @@ def dense_batch(triples_, rows=None):
             g_ptr, g_ld = gate.data_ptr(), gate.stride(0)
         jobs[q] = _lib.DenseJob(a.data_ptr(), a.stride(0), w.shape[0], w.data_ptr(), w.stride(0), w.shape[1],
                                 out.data_ptr(), out.stride(0), g_ptr, g_ld)
+    if route is not None:
+        route += _lib.dense_route(n if rows is None else rows.numel(), rows is not None, jobs)
     if rows is not None:
         _lib.check(lib.pea_dense_batch_rows(rows.numel(), _lib.ptr(rows), len(triples_), jobs, _lib.current_stream()))
     else:

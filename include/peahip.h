@@ -268,6 +268,34 @@ int pea_block_sum(int64_t n_rows, int n_blocks, int width, const float *src, int
 int pea_grad_weight_sharded(int64_t n_rows, int shard_tile, int shard_world, int shard_rank, int n_jobs,
                             const pea_gw_job *jobs_host, void *workspace, size_t workspace_bytes, void *stream);
 int pea_dense_batch_rows(int64_t n_rows, const int32_t *rows, int n_jobs, const pea_dense_job *jobs_host, void *stream);
+/* The launches pea_dense_batch (rows_given = 0) / pea_dense_batch_rows (rows_given = 1) would issue for these jobs, in issue
+ * order, decided by the same code and after the same argument checks -- but nothing is launched and no pointer is read
+ * through, so the call needs no device (the addresses may be made up; only their alignment matters).  *count_out = the
+ * number of launches; the first `cap` of them are described in entries_out (may be NULL when cap = 0).  The kernels differ
+ * in k summation order, so the route of a shape is part of what a result's bits depend on.  Like the launching calls, this
+ * one reads the environment switches PEA_DEEP_STAGED and PEA_SKINNY_JOBMAJOR when it is called: the answer is the route under
+ * their values at that moment.
+ *   family / variant: SKINNY: float4 k chunks per lane, 2 / 4 / 8 (k <= 32 / 64 / 128);  PERSIST: k rows per image half,
+ *   16 / 32 / 64;  DEEP_RESIDENT: 32-column tiles, 1 / 2;  DEEP_CHUNK: 1 / 2 / 4;  DEEP_STAGED: 64.
+ *   job[q]: index in jobs_host of batch entry q; an oversize job appears once per column chunk, entry q then covering its
+ *   columns [col0[q], col0[q] + n_out[q]) with the gate read from column gate_col0[q] on (-1: no gate).                   */
+#define PEA_ROUTE_SKINNY 0
+#define PEA_ROUTE_PERSIST 1
+#define PEA_ROUTE_DEEP_RESIDENT 2
+#define PEA_ROUTE_DEEP_CHUNK 3
+#define PEA_ROUTE_DEEP_STAGED 4
+#define PEA_ROUTE_MAX_JOBS 12
+typedef struct pea_dense_route_entry {
+    char name[32];          /* the launch's name in the profile log (pea_profile_read) */
+    int family, variant;    /* PEA_ROUTE_*, and the kernel's template variant */
+    int listed;             /* some job reads a row list */
+    int col_group;          /* PERSIST: 32-column tiles per work item (2 when a job of the launch is gated), else 0 */
+    int64_t lds_bytes;      /* dynamic LDS of the launch */
+    int n_jobs;
+    int job[PEA_ROUTE_MAX_JOBS], col0[PEA_ROUTE_MAX_JOBS], n_out[PEA_ROUTE_MAX_JOBS], gate_col0[PEA_ROUTE_MAX_JOBS];
+} pea_dense_route_entry;
+int pea_dense_route(int64_t n_rows, int rows_given, int n_jobs, const pea_dense_job *jobs_host, int cap,
+                    pea_dense_route_entry *entries_out, int *count_out);
 
 /* ---- device-side BPR negative sampler (an addition next to the bit-exact host mirror of the reference's
  * datasets/movielens.py:920-940 in graph_recsys_benchmark_amd/utils/sampling.py) -----------------------------------

@@ -273,3 +273,61 @@ def assert_fused_close(got_fused, got_stack, want_fused, truth_fused, att, chann
             k = int(np.flatnonzero(bad)[0])
             raise AssertionError('%s (and against float64: row %d off by %.3e, bound %.3e = stack error %.3e x condition %.1f)'
                                  % (first, k, err[k], bound[k], err_stack[k], cond[k]))
+
+
+# ------------------------------------------------------------------------------------------------------------
+# the dense products' dispatch (csrc/gemm.hip), written down by hand: tests/test_dense_route_cpu.py asks the library's planner
+# (pea_dense_route) about every row without a GPU, tests/test_gpu_dense_matrix.py also runs every row
+# ------------------------------------------------------------------------------------------------------------
+DENSE_NS = (1, 31, 32, 33, 4099)      # a partial tile, a full tile, one row more, many tiles
+
+# (k values, n_out values, kernel, profile name, launches, row counts, output column offset in floats)
+DENSE_ROUTES = [
+    ((16, 32), (4, 16), 'skinny<2>', 'gemm_mfma_narrow', 1, DENSE_NS, 4),
+    ((36, 64), (12, 16), 'skinny<4>', 'gemm_mfma_narrow', 1, DENSE_NS, 4),
+    ((68, 128), (8, 16), 'skinny<8>', 'gemm_mfma_narrow', 1, DENSE_NS, 4),
+    ((16,), (16,), 'persist<16>', 'gemm_mfma_shared', 1, DENSE_NS, 2),     # out not 16-byte aligned: no float4 stores, not skinny
+    ((16, 32), (20, 64), 'persist<16>', 'gemm_mfma_shared', 1, DENSE_NS, 4),
+    ((36, 64), (36, 100), 'persist<32>', 'gemm_mfma_shared', 1, DENSE_NS, 4),
+    ((68, 128), (64, 288), 'persist<64>', 'gemm_mfma_shared', 1, DENSE_NS, 4),     # 288: the last unchunked width
+    ((128,), (292,), 'persist<64>', 'gemm_mfma_shared', 2, DENSE_NS, 4),
+    ((128,), (580,), 'persist<64>', 'gemm_mfma_shared', 3, DENSE_NS, 4),
+    ((64,), (612,), 'persist<32>', 'gemm_mfma_shared', 2, DENSE_NS, 4),
+    ((32,), (1220,), 'persist<16>', 'gemm_mfma_shared', 2, (33, 515), 4),
+    ((132, 1272), (4, 32), 'resident<1>', 'gemm_mfma_deep', 1, DENSE_NS, 4),      # 1272 x 32 floats: exactly the LDS budget
+    ((1276,), (32,), 'staged<1>', 'gemm_mfma_deep', 1, (33, 515), 4),
+    ((636,), (64,), 'resident<2>', 'gemm_mfma_deep', 1, DENSE_NS, 4),
+    ((640, 700), (36, 64), 'staged<2>', 'gemm_mfma_deep', 1, DENSE_NS, 4),        # 700: a partial last 128-chunk
+    ((136,), (68, 128), 'staged<4>', 'gemm_mfma_deep', 1, DENSE_NS, 4),
+    ((132, 260), (132, 160), 'fallback', 'gemm_mfma_deep', 1, DENSE_NS, 4),
+]
+DENSE_ROUTE_CASES = [(k, c, kern, name, cnt, n, off) for ks, cs, kern, name, cnt, ns, off in DENSE_ROUTES for k in ks for c in cs for n in ns]
+DENSE_ROUTE_IDS = ['%s-k%d-c%d%s-n%d' % (kern, k, c, '-off2' if off == 2 else '', n) for k, c, kern, name, cnt, n, off in DENSE_ROUTE_CASES]
+DENSE_DEEP_CASES = [(k, c, n) for ks, cs, kern, name, cnt, ns, off in DENSE_ROUTES if name == 'gemm_mfma_deep' for k in ks for c in cs
+                    for n in (33, 515)]
+DENSE_DEEP_IDS = ['k%d-c%d-n%d' % kcn for kcn in DENSE_DEEP_CASES]
+
+# (k, n_out, gated): every class in one call; with the first 9 + n_deep jobs the deep group runs on DENSE_MIXED_DEEP[n_deep]
+DENSE_MIXED = [(16, 16, False), (64, 16, False), (128, 16, False),          # skinny, one per k class
+               (16, 64, False), (64, 100, False), (128, 64, False),         # persistent, one per k class
+               (128, 292, False),                                           # two column chunks
+               (16, 64, True), (128, 36, True),                             # gated
+               (160, 32, False), (576, 64, False), (136, 128, False), (132, 132, False)]   # deep
+DENSE_MIXED_DEEP = {4: 'fallback', 3: 'staged<4>', 2: 'resident<2>'}
+DENSE_MIXED_PLAN = [        # (profile name, kernel, source jobs) in launch order; the deep launch follows
+    ('gemm_mfma_narrow', 'skinny<2>', [0]), ('gemm_mfma_narrow', 'skinny<4>', [1]), ('gemm_mfma_narrow', 'skinny<8>', [2]),
+    ('gemm_mfma_batch', 'persist<16>', [3, 7]),       # k = 16 ungated + gated
+    ('gemm_mfma_shared', 'persist<32>', [4]),
+    ('gemm_mfma_shared', 'persist<64>', [5]),         # k = 128 x 64; the 288-column chunk does not fit beside it
+    ('gemm_mfma_shared', 'persist<64>', [6]),         # the 288-column chunk
+    ('gemm_mfma_batch', 'persist<64>', [6, 8])]       # the 4-column chunk + the gated k = 128 job
+
+# the table's kernel names by pea_dense_route family (include/peahip.h PEA_ROUTE_*): 'staged<NCT>' is the 128-chunk deep
+# kernel, 'fallback' the per-column-tile staged kernel gemm_mfma_kernel<64>
+_DENSE_KERNELS = ('skinny<%d>', 'persist<%d>', 'resident<%d>', 'staged<%d>', 'fallback')
+
+
+def dense_route_rows(entries):
+    """[(profile name, kernel as the tables above spell it, [source job of each batch entry])] of _lib.dense_route's records"""
+    return [(e.name.decode(), _DENSE_KERNELS[e.family] % e.variant if e.family < 4 else 'fallback', list(e.job[:e.n_jobs]))
+            for e in entries]

@@ -1,6 +1,6 @@
 """The dense products (csrc/gemm.hip through pea_dense_batch[_rows], csrc/dense_bwd.hip through pea_grad_weight[_rows]) on every
 route their dispatch can take, each against a float64 torch product of the same operands, with the route read back from the
-library's launch log.
+library: its plan for the call and its launch log.
 
 Two bounds per product, neither tuned on the kernels:
   1. elementwise |got - want| <= (k + 4) 2^-24 (|a| |w|) + 1e-30: the forward bound of an fp32 dot product of length k in any
@@ -9,92 +9,24 @@ Two bounds per product, neither tuned on the kernels:
      for grad_weight.
 Outputs are column blocks of NaN-filled buffers: whatever lies outside a job's rows x columns must still be NaN afterwards.
 
-What the launch log can tell: the profile names separate the narrow kernel (gemm_mfma_narrow), the persistent kernel with one
-job (gemm_mfma_shared) or several (gemm_mfma_batch) and the deep-k launches (gemm_mfma_deep), and their count gives the column
-chunks and the batch splits.  It cannot tell the template variants apart: skinny<2/4/8>, persist<16/32/64> and the deep
-resident / 128-chunk / fallback kernels share their names.  For those the variant comes from _plan(), a restatement of
-launch_gemm_batch kept in this file and asserted against the hand-written route table; a dispatch change that moved a shape
-between variants of one name shows here only if _plan() is kept in step with the code."""
+Two accounts of the route, both from the library.  The launch log (pea_profile_read) names what was actually launched: the
+profile names separate the narrow kernel (gemm_mfma_narrow), the persistent kernel with one job (gemm_mfma_shared) or several
+(gemm_mfma_batch) and the deep-k launches (gemm_mfma_deep), and their count gives the column chunks and the batch splits.  It
+cannot tell the template variants apart: skinny<2/4/8>, persist<16/32/64> and the deep resident / 128-chunk / fallback kernels
+share their names.  Those come from pea_dense_route, the planner launch_gemm_batch itself executes, asked about the very job
+structs of each call (engine.dense_batch(route=...)): every call asserts that its log matches the plan's names, and the
+hand-written tables (tests/helpers.py: DENSE_ROUTES, DENSE_MIXED_PLAN) are asserted against the plan's kernels, variants and
+batch composition.  The same tables are put to the planner without a GPU in tests/test_dense_route_cpu.py."""
 import contextlib
 import ctypes as C
 
 import pytest
 import torch
 
+from helpers import (DENSE_DEEP_CASES, DENSE_DEEP_IDS, DENSE_MIXED, DENSE_MIXED_DEEP, DENSE_MIXED_PLAN, DENSE_ROUTE_CASES,
+                     DENSE_ROUTE_IDS, dense_route_rows)
+
 pytestmark = pytest.mark.gpu
-
-# ------------------------------------------------------------------------------------------------ the dispatch, restated
-_BUDGET = 160 * 1024 - 1024      # kLdsBudget
-_MAX_BATCH = 12                  # kMaxBatch
-
-
-def _kh(k):
-    return 16 if k <= 32 else 32 if k <= 64 else 64
-
-
-def _max_cols(k):
-    return _BUDGET // 4 // (2 * _kh(k) + 1) // 32 * 32
-
-
-def _ceil32(c):
-    return (c + 31) // 32 * 32
-
-
-def _plan(specs, n_rows, staged_env=False):
-    """launch_gemm_batch restated for jobs of pea_dense_batch.  specs: (k, n_out, gated, out_takes_float4) per job; returns
-    [(profile name, kernel, [job index, ...])] in launch order."""
-    if n_rows <= 0:
-        return []
-    skinny = [not g and n <= 16 and k <= 128 and al for k, n, g, al in specs]
-    out = []
-    for kq, lo, hi in ((2, 0, 32), (4, 32, 64), (8, 64, 128)):
-        grp = [i for i, (k, _, _, _) in enumerate(specs) if skinny[i] and lo < k <= hi]
-        out += [('gemm_mfma_narrow', 'skinny<%d>' % kq, grp[b:b + _MAX_BATCH]) for b in range(0, len(grp), _MAX_BATCH)]
-    pieces = []
-    for i, (k, n, _, _) in enumerate(specs):
-        if skinny[i]:
-            continue
-        mc = _max_cols(k)
-        if k > 128 or n <= mc:
-            pieces.append((i, k, n))
-        else:
-            pieces += [(i, k, min(mc, n - c0)) for c0 in range(0, n, mc)]
-    for cls in (16, 32, 64):
-        for deep in (False, True):
-            batch, lds = [], 0
-
-            def flush():
-                if not batch:
-                    return
-                idx = [p[0] for p in batch]
-                if not deep:
-                    out.append(('gemm_mfma_shared' if len(batch) == 1 else 'gemm_mfma_batch', 'persist<%d>' % cls, idx))
-                else:
-                    max_out, max_k = max(p[2] for p in batch), max(p[1] for p in batch)
-                    nct = 1 if max_out <= 32 else 2 if max_out <= 64 else 4
-                    if not staged_env and max_out <= 64 and max_k * 32 * nct * 4 <= _BUDGET:
-                        kern = 'resident<%d>' % nct
-                    elif not staged_env and max_out <= 128:
-                        kern = 'staged<%d>' % nct
-                    else:
-                        kern = 'fallback'
-                    out.append(('gemm_mfma_deep', kern, idx))
-                del batch[:]
-
-            for p in pieces:
-                if _kh(p[1]) != cls or (p[1] > 128) != deep:
-                    continue
-                need = (2 * cls + 1) * _ceil32(p[2]) * 4
-                if not deep and batch and lds + need > _BUDGET:
-                    flush()
-                    lds = 0
-                batch.append(p)
-                lds += need
-                if len(batch) == _MAX_BATCH:
-                    flush()
-                    lds = 0
-            flush()
-    return out
 
 
 # ------------------------------------------------------------------------------------------------ helpers
@@ -154,9 +86,6 @@ class _Job:
         if gated:
             self.want = torch.where(gate > 0, self.want, torch.zeros_like(self.want))
 
-    def spec(self):
-        return (self.k, self.n_out, self.gate is not None, self.out.data_ptr() % 16 == 0 and self.out.stride(0) % 4 == 0)
-
     def item(self):
         return (self.a, self.w, self.out) if self.gate is None else (self.a, self.w, self.out, self.gate)
 
@@ -186,10 +115,16 @@ class _Job:
 
 
 def _run(jobs, rows=None):
+    """One dense_batch call: the names in its launch log, which must be the names of the library's plan for the very job
+    structs of the call, and that plan as (profile name, kernel, [source job, ...]) rows."""
     from graph_recsys_benchmark_amd import engine
+    route = []
     with _launch_log() as names:
-        engine.dense_batch([j.item() for j in jobs], rows=rows)
-    return names
+        engine.dense_batch([j.item() for j in jobs], rows=rows, route=route)
+    plan = dense_route_rows(route)
+    assert names == [p[0] for p in plan], 'the launch log and the plan differ'
+    assert all(e.listed == (rows is not None) for e in route)
+    return names, plan
 
 
 def _rows3(n):
@@ -197,65 +132,37 @@ def _rows3(n):
 
 
 _EMPTY = dict(dtype=torch.int32, device='cuda')
-_NS = (1, 31, 32, 33, 4099)      # a partial tile, a full tile, one row more, many tiles
 
-# (k values, n_out values, kernel, profile name, launches, row counts, output column offset in floats)
-_ROUTES = [
-    ((16, 32), (4, 16), 'skinny<2>', 'gemm_mfma_narrow', 1, _NS, 4),
-    ((36, 64), (12, 16), 'skinny<4>', 'gemm_mfma_narrow', 1, _NS, 4),
-    ((68, 128), (8, 16), 'skinny<8>', 'gemm_mfma_narrow', 1, _NS, 4),
-    ((16,), (16,), 'persist<16>', 'gemm_mfma_shared', 1, _NS, 2),     # out not 16-byte aligned: no float4 stores, not skinny
-    ((16, 32), (20, 64), 'persist<16>', 'gemm_mfma_shared', 1, _NS, 4),
-    ((36, 64), (36, 100), 'persist<32>', 'gemm_mfma_shared', 1, _NS, 4),
-    ((68, 128), (64, 288), 'persist<64>', 'gemm_mfma_shared', 1, _NS, 4),     # 288: the last unchunked width
-    ((128,), (292,), 'persist<64>', 'gemm_mfma_shared', 2, _NS, 4),
-    ((128,), (580,), 'persist<64>', 'gemm_mfma_shared', 3, _NS, 4),
-    ((64,), (612,), 'persist<32>', 'gemm_mfma_shared', 2, _NS, 4),
-    ((32,), (1220,), 'persist<16>', 'gemm_mfma_shared', 2, (33, 515), 4),
-    ((132, 1272), (4, 32), 'resident<1>', 'gemm_mfma_deep', 1, _NS, 4),      # 1272 x 32 floats: exactly the LDS budget
-    ((1276,), (32,), 'staged<1>', 'gemm_mfma_deep', 1, (33, 515), 4),
-    ((636,), (64,), 'resident<2>', 'gemm_mfma_deep', 1, _NS, 4),
-    ((640, 700), (36, 64), 'staged<2>', 'gemm_mfma_deep', 1, _NS, 4),        # 700: a partial last 128-chunk
-    ((136,), (68, 128), 'staged<4>', 'gemm_mfma_deep', 1, _NS, 4),
-    ((132, 260), (132, 160), 'fallback', 'gemm_mfma_deep', 1, _NS, 4),
-]
-_ROUTE_CASES = [pytest.param(k, c, kern, name, cnt, n, off, id='%s-k%d-c%d%s-n%d' % (kern, k, c, '-off2' if off == 2 else '', n))
-                for ks, cs, kern, name, cnt, ns, off in _ROUTES for k in ks for c in cs for n in ns]
-_DEEP_CASES = [pytest.param(k, c, n, id='k%d-c%d-n%d' % (k, c, n))
-               for ks, cs, kern, name, cnt, ns, off in _ROUTES if name == 'gemm_mfma_deep' for k in ks for c in cs for n in (33, 515)]
-
-
-def _one_route(k, n_out, kernel, name, count, n, off, staged_env=False):
+def _one_route(k, n_out, kernel, name, count, n, off):
     g = torch.Generator().manual_seed(1000 * k + 7 * n_out + n)
     job = _Job(n, k, n_out, g, out_off=off)
-    plan = _plan([job.spec()], n, staged_env)
-    assert [p[1] for p in plan] == [kernel] * count and [p[0] for p in plan] == [name] * count     # the table vs the restated rules
-    assert _run([job]) == [name] * count                                                         # ... and vs the library
+    want = [(name, kernel, [0])] * count        # the table: against the library's plan and (the names) against its launch log
+    assert _run([job]) == ([name] * count, want)
     job.check()
     first = job.out.clone()
-    assert _run([job.reset()]) == [name] * count
+    assert _run([job.reset()]) == ([name] * count, want)
     assert _same_bits(job.out, first), 'two identical calls differ'
     rows = _rows3(n)
-    assert _run([job.reset()], rows=rows) == [name] * count
+    assert _run([job.reset()], rows=rows) == ([name] * count, want)
     job.check(rows)
     assert _same_bits(job.out[rows.long()], first[rows.long()]), 'a listed row differs from the same row of the unlisted call'
-    assert _run([job.reset()], rows=torch.empty(0, **_EMPTY)) == []
+    assert _run([job.reset()], rows=torch.empty(0, **_EMPTY)) == ([], [])
     assert bool(torch.isnan(job.buf).all()), 'an empty row list wrote something'
 
 
 # ------------------------------------------------------------------------------------------------ 1. one case per route
-@pytest.mark.parametrize('k,n_out,kernel,name,count,n,off', _ROUTE_CASES)
+@pytest.mark.parametrize('k,n_out,kernel,name,count,n,off', DENSE_ROUTE_CASES, ids=DENSE_ROUTE_IDS)
 def test_every_route_matches_float64(k, n_out, kernel, name, count, n, off):
     """Unlisted, rows 0, 3, 6, ... listed, and an empty list; two calls bit-identical, listed rows bit-identical to unlisted."""
     _one_route(k, n_out, kernel, name, count, n, off)
 
 
-@pytest.mark.parametrize('k,n_out,n', _DEEP_CASES)
+@pytest.mark.parametrize('k,n_out,n', DENSE_DEEP_CASES, ids=DENSE_DEEP_IDS)
 def test_deep_shapes_on_the_fallback_kernel(k, n_out, n, monkeypatch):
     """PEA_DEEP_STAGED=1 (read per call) sends every deep job to gemm_mfma_kernel<64>: the shapes the resident and the
     128-chunk kernels normally take, on the kernel that otherwise only sees n_out > 128."""
     monkeypatch.setenv('PEA_DEEP_STAGED', '1')
-    _one_route(k, n_out, 'fallback', 'gemm_mfma_deep', 1, n, 4, staged_env=True)
+    _one_route(k, n_out, 'fallback', 'gemm_mfma_deep', 1, n, 4)
 
 
 # ------------------------------------------------------------------------------------------------ 2. batches
@@ -284,10 +191,9 @@ def test_batches_split_at_twelve_jobs(n_jobs, k, n_out, names, listed):
     n = 1030
     g = torch.Generator().manual_seed(n_jobs + k)
     jobs = [_Job(n, k, n_out, g) for _ in range(n_jobs)]
-    plan = _plan([j.spec() for j in jobs], n)
-    assert [p[0] for p in plan] == names and [len(p[2]) for p in plan] == [12] * (len(names) - 1) + [n_jobs - 12 * (len(names) - 1)]
     rows = _rows3(n) if listed else None
-    assert _run(jobs, rows=rows) == names
+    got, plan = _run(jobs, rows=rows)
+    assert got == names and [p[2] for p in plan] == [list(range(b, min(b + 12, n_jobs))) for b in range(0, n_jobs, 12)]
     for j in jobs:
         j.check(rows)
     for j in (jobs[0], jobs[11], jobs[12], jobs[-1]):       # either side of the split
@@ -300,12 +206,12 @@ def test_skinny_item_orders_give_the_same_bits(n, monkeypatch):
     restores the job-major order.  Which wave computes a tile must not change a bit."""
     g = torch.Generator().manual_seed(n)
     jobs = [_Job(n, k, c, g) for k, c in ((64, 16), (36, 12), (64, 4), (40, 16), (64, 8))]
-    assert _run(jobs) == ['gemm_mfma_narrow']
+    assert _run(jobs)[0] == ['gemm_mfma_narrow']
     for j in jobs:
         j.check()
     tile_major = [j.out.clone() for j in jobs]
     monkeypatch.setenv('PEA_SKINNY_JOBMAJOR', '1')
-    assert _run([j.reset() for j in jobs]) == ['gemm_mfma_narrow']
+    assert _run([j.reset() for j in jobs])[0] == ['gemm_mfma_narrow']
     for j, t in zip(jobs, tile_major):
         j.check()
         assert _same_bits(j.out, t)
@@ -319,21 +225,14 @@ def test_batches_split_at_the_lds_budget(n_out, names):
     n = 515
     g = torch.Generator().manual_seed(n_out)
     jobs = [_Job(n, 128, n_out, g) for _ in range(4)]
-    assert [p[0] for p in _plan([j.spec() for j in jobs], n)] == names
-    assert _run(jobs) == names
+    got, plan = _run(jobs)
+    assert got == names and [p[2] for p in plan] == ([[0], [1], [2], [3]] if n_out == 160 else [[0, 1], [2, 3]])
     for j in jobs:
         j.check()
         _same_bits_as_alone(j)
 
 
-_MIXED = [(16, 16, False), (64, 16, False), (128, 16, False),          # skinny, one per k class
-          (16, 64, False), (64, 100, False), (128, 64, False),         # persistent, one per k class
-          (128, 292, False),                                           # two column chunks
-          (16, 64, True), (128, 36, True),                             # gated
-          (160, 32, False), (576, 64, False), (136, 128, False), (132, 132, False)]   # deep
-
-
-@pytest.mark.parametrize('n_deep,deep_kernel', [(4, 'fallback'), (3, 'staged<4>'), (2, 'resident<2>')])
+@pytest.mark.parametrize('n_deep,deep_kernel', [(4, 'fallback'), (3, 'staged<4>'), (2, 'resident<2>')])     # DENSE_MIXED_DEEP
 @pytest.mark.parametrize('listed', [False, True])
 def test_one_call_with_every_class(n_deep, deep_kernel, listed):
     """All classes in one call.  The deep group's kernel follows from its largest k and n_out: with (132, 132) the fallback, with
@@ -341,24 +240,17 @@ def test_one_call_with_every_class(n_deep, deep_kernel, listed):
     depth in one launch).  Gated and ungated jobs share the persistent launches (2 column tiles per item for all of them)."""
     n = 1030
     g = torch.Generator().manual_seed(n_deep)
-    jobs = [_Job(n, k, c, g, gated=gt) for k, c, gt in _MIXED[:9 + n_deep]]
-    plan = _plan([j.spec() for j in jobs], n)
-    assert [(p[0], p[1]) for p in plan] == [
-        ('gemm_mfma_narrow', 'skinny<2>'), ('gemm_mfma_narrow', 'skinny<4>'), ('gemm_mfma_narrow', 'skinny<8>'),
-        ('gemm_mfma_batch', 'persist<16>'),       # k = 16 ungated + gated
-        ('gemm_mfma_shared', 'persist<32>'),
-        ('gemm_mfma_shared', 'persist<64>'),      # k = 128 x 64; the 288-column chunk does not fit beside it
-        ('gemm_mfma_shared', 'persist<64>'),      # the 288-column chunk
-        ('gemm_mfma_batch', 'persist<64>'),       # the 4-column chunk + the gated k = 128 job
-        ('gemm_mfma_deep', deep_kernel)]
+    jobs = [_Job(n, k, c, g, gated=gt) for k, c, gt in DENSE_MIXED[:9 + n_deep]]
+    assert deep_kernel == DENSE_MIXED_DEEP[n_deep]
     rows = _rows3(n) if listed else None
-    assert _run(jobs, rows=rows) == [p[0] for p in plan]
+    names, plan = _run(jobs, rows=rows)
+    assert plan == DENSE_MIXED_PLAN + [('gemm_mfma_deep', deep_kernel, list(range(9, 9 + n_deep)))]
     for j in jobs:
         j.check(rows)
     for j in jobs[:9]:          # not promised across the deep variants (the resident kernel pairs k with k + 4, the others k with k + 64)
         _same_bits_as_alone(j, rows)
     first = [j.out.clone() for j in jobs]
-    _run([j.reset() for j in jobs], rows=rows)
+    assert _run([j.reset() for j in jobs], rows=rows) == (names, plan)
     sel = slice(None) if rows is None else rows.long()
     assert all(_same_bits(j.out[sel], t[sel]) for j, t in zip(jobs, first)), 'two identical calls differ'
 
@@ -378,8 +270,8 @@ def test_chunked_gate_with_planted_zeros(n_out, count, listed):
     gated.want = torch.where(gated.gate > 0, gated.a.double() @ gated.w.double(), torch.zeros_like(gated.want))
     rows = _rows3(n) if listed else None
     # chunk images: 288 columns 148,608 B, the last chunk (<= 32 columns) 16,512 B, the 64-column job 33,024 B
-    names = _run([gated, plain], rows=rows)
-    assert names == [p[0] for p in _plan([gated.spec(), plain.spec()], n)] and len(names) == count
+    names, plan = _run([gated, plain], rows=rows)
+    assert len(names) == count and [p[2] for p in plan] == [[0]] * (count - 1) + [[0, 1]]     # the last chunk beside the plain job
     gated.check(rows)
     plain.check(rows)
     _same_bits_as_alone(gated, rows)
@@ -418,7 +310,7 @@ def test_operands_inside_nan_filled_buffers(k, n_out, gated, names, n):
     job = _Job(n, k, n_out, g, gated=gated, wide=True)
     assert job.w.stride(0) % 4 == 0 and job.w.stride(0) > n_out and job.a.stride(0) > k
     for rows in (None, _rows3(n)):
-        assert _run([job.reset()], rows=rows) == names
+        assert _run([job.reset()], rows=rows)[0] == names
         job.check(rows)
         dense = _nan(n, n_out)
         item = (job.a.contiguous(), job.w.contiguous(), dense) + ((job.gate.contiguous(),) if gated else ())
