@@ -169,6 +169,10 @@ SIGNATURES = {
     'pea_rows_unpack_batch': (_int, [_int, C.POINTER(XchgJob), _vp, _i64, _vp]),
     'pea_rows_select_owned': (_int, [_vp, _i64, _int, _i64, _vp, _i64, _i64, _int, _int, _int, _vp, _vp, _vp]),
     'pea_rank_eval': (_int, [_i64, _int, _int, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'pea_fuse_ablate': (_int, [_i64, _int, _int, _vp, _i64, C.POINTER(_int), _vp, _int, _vp, _vp, _vp]),
+    'pea_model_forward_ablate': (_int, [_vp, C.POINTER(_vp), _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+    'pea_rank_eval_multi': (_int, [_int, _i64, _int, _int, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                   _vp]),
     'pea_topk_workspace_bytes': (_sz, [_i64, _i64, _int, _int]),
     'pea_recommend_topk': (_int, [_i64, _int, _int, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                   _sz, _vp]),

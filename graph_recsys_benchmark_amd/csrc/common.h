@@ -437,9 +437,20 @@ int launch_fuse(int64_t N, int P, int R, const float *stack, int64_t ld, const C
                 const float *att, int masked, int mode, const int *rows, int64_t n_rows, float *out,
                 float *out_stack, hipStream_t stream, const FuseSelect *sel = nullptr);
 
+// metapath ablation (ablate.hip): all P + 1 fused variants of the stack in one pass.  out_tables [P + 1, N, R]: variant 0
+// unmasked, variant 1 + p = channel p zeroed, each bitwise launch_fuse with that mask; out_att [N, P] optional.
+int launch_fuse_ablate(int64_t N, int P, int R, const float *stack, int64_t ld, const ChanCols &col_of_channel,
+                       const float *att, int mode, float *out_tables, float *out_att, hipStream_t stream);
+struct AblateOut {
+    float *tables = nullptr;   // [P + 1, N, R]
+    float *att = nullptr;      // [N, P] or null
+};
+
+// abl (single GPU): the final fusion launch is replaced by launch_fuse_ablate on the stack where the schedule left it
 int model_forward(pea_model *m, int stage, const float *const *params, const float *x, int64_t ldx, const float *att,
                   int masked, float *wsf, float *out_repr, float *out_stack, float *out_x, int64_t ld_out_x,
-                  int relu_last, hipStream_t stream, bool training, int part = 0, const FuseSelect *sel = nullptr);
+                  int relu_last, hipStream_t stream, bool training, int part = 0, const FuseSelect *sel = nullptr,
+                  const AblateOut *abl = nullptr);
 
 }  // namespace pea
 float *aligned_ws(void *workspace);

@@ -6,12 +6,10 @@
 #include <algorithm>
 #include <mutex>
 
-#include "common.h"
+#include "score_common.h"
 
 namespace pea {
 namespace {
-
-__device__ __forceinline__ float4 ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
 
 // G lanes x float4 cover the R columns of one node; 64/G nodes per wave.  Softmax over the P channels
 // is taken online in channel order.
@@ -71,74 +69,6 @@ __global__ __launch_bounds__(256) void fuse_kernel(int64_t n_rows, const int *__
     if (!active || !dst_row) return;
     const float inv = mode == PEA_FUSE_MEAN ? 1.0f / (float)P : 1.0f / s;
     *reinterpret_cast<float4 *>(dst_row + c4) = make_float4(acc.x * inv, acc.y * inv, acc.z * inv, acc.w * inv);
-}
-
-// fc2(relu(fc1([u || i])))  with fc1_w [R, 2R] staged in LDS by the caller
-__device__ __forceinline__ float mlp_score(const float *__restrict__ ur, const float *__restrict__ ir, int R,
-                                           const float *w1, const float *b1, const float *w2, float b2) {
-    float o = 0.f;
-    for (int k = 0; k < R; ++k) {
-        const float *w = w1 + k * 2 * R;
-        float a = 0.f;
-        for (int c = 0; c < R; c += 4) {
-            const float4 u = ld4(ur + c), wu = ld4(w + c);
-            a += (u.x * wu.x + u.y * wu.y) + (u.z * wu.z + u.w * wu.w);
-        }
-        for (int c = 0; c < R; c += 4) {
-            const float4 v = ld4(ir + c), wi = ld4(w + R + c);
-            a += (v.x * wi.x + v.y * wi.y) + (v.z * wi.z + v.w * wi.w);
-        }
-        a += b1[k];
-        o = fmaf(fmaxf(a, 0.f), w2[k], o);
-    }
-    return o + b2;
-}
-
-// same arithmetic with both rows held in registers (R = 4*R4 known at compile time)
-template <int R4>
-__device__ __forceinline__ float mlp_score_reg(const float4 (&u)[R4], const float4 (&v)[R4], const float *w1, const float *b1,
-                                               const float *w2, float b2) {
-    constexpr int R = 4 * R4;
-    float o = 0.f;
-    for (int k = 0; k < R; ++k) {
-        const float *w = w1 + k * 2 * R;
-        float a = 0.f;
-#pragma unroll
-        for (int c = 0; c < R4; ++c) {
-            const float4 wu = ld4(w + 4 * c);
-            a += (u[c].x * wu.x + u[c].y * wu.y) + (u[c].z * wu.z + u[c].w * wu.w);
-        }
-#pragma unroll
-        for (int c = 0; c < R4; ++c) {
-            const float4 wi = ld4(w + R + 4 * c);
-            a += (v[c].x * wi.x + v[c].y * wi.y) + (v[c].z * wi.z + v[c].w * wi.w);
-        }
-        a += b1[k];
-        o = fmaf(fmaxf(a, 0.f), w2[k], o);
-    }
-    return o + b2;
-}
-
-template <int R4>
-__device__ __forceinline__ void load_row(const float *p, float4 (&r)[R4]) {
-#pragma unroll
-    for (int c = 0; c < R4; ++c) r[c] = ld4(p + 4 * c);
-}
-
-extern __shared__ float smem[];
-
-__device__ __forceinline__ void stage_mlp(int R, const float *fc1_w, const float *fc1_b, const float *fc2_w) {
-    for (int i = threadIdx.x; i < 2 * R * R; i += blockDim.x) smem[i] = fc1_w[i];
-    for (int i = threadIdx.x; i < R; i += blockDim.x) {
-        smem[2 * R * R + i] = fc1_b[i];
-        smem[2 * R * R + R + i] = fc2_w[i];
-    }
-    __syncthreads();
-}
-
-__device__ __forceinline__ float log_sigmoid_ref(float d) {
-    // the reference takes sigmoid then log in fp32 with no clamp (may give -inf); keep that
-    return logf(1.0f / (1.0f + expf(-d)));
 }
 
 __global__ __launch_bounds__(256) void bpr_kernel(int64_t B, int R, int64_t N, const float *__restrict__ repr,
@@ -285,12 +215,6 @@ __global__ __launch_bounds__(256) void rank_kernel(int64_t U, int C, int R, int6
     }
 }
 
-int lanes_for_r(int R) {
-    int g = 1;
-    while (g * 4 < R) g <<= 1;
-    return g;
-}
-
 }  // namespace
 
 int launch_fuse(int64_t N, int P, int R, const float *stack, int64_t ld, const ChanCols &col_of_channel,
@@ -338,6 +262,8 @@ int launch_fuse(int64_t N, int P, int R, const float *stack, int64_t ld, const C
 
 // ---------------------------------------------------------------------------------------------- C ABI
 using pea::set_error;
+using pea::err_flag_for_current_device;
+using pea::read_err_flag;
 
 extern "C" size_t pea_bpr_workspace_bytes(int64_t B) {
     const int64_t blocks = (B + 255) / 256;
@@ -352,7 +278,7 @@ static int check_r(int R) {
 // One 4-byte error flag per device, allocated on first use and kept for the life of the process (pea_predict /
 // pea_rank_eval used to hipMalloc + hipFree one per call).  The callers are the reference's single Python thread; two
 // host threads scoring at once on one device would share the flag (an error is then reported to at least one of them).
-static int *err_flag_for_current_device() {
+int *pea::err_flag_for_current_device() {
     static std::mutex mu;
     static int *flags[64] = {nullptr};
     int dev = 0;
@@ -362,7 +288,7 @@ static int *err_flag_for_current_device() {
     return flags[dev];
 }
 
-static int read_err_flag(int *err_dev, hipStream_t stream, const char *what) {
+int pea::read_err_flag(int *err_dev, hipStream_t stream, const char *what) {
     int h = 0;
     PEA_HIP(hipMemcpyAsync(&h, err_dev, sizeof(int), hipMemcpyDeviceToHost, stream));
     PEA_HIP(hipStreamSynchronize(stream));

@@ -408,7 +408,7 @@ int init_model(pea_model *m, const pea_plan *plan, const pea_model_desc *desc) {
 // entry points); relu_last applies relu to last layers too.
 int model_forward(pea_model *m, int stage, const float *const *params, const float *x, int64_t ldx, const float *att,
                   int masked, float *wsf, float *out_repr, float *out_stack, float *out_x, int64_t ld_out_x, int relu_last,
-                  hipStream_t stream, bool training, int part, const FuseSelect *sel) {
+                  hipStream_t stream, bool training, int part, const FuseSelect *sel, const AblateOut *abl) {
     const pea_model_desc &d = m->d;
     pea_plan *plan = const_cast<pea_plan *>(m->plan);
     const int64_t N = plan->N;
@@ -1018,7 +1018,10 @@ int model_forward(pea_model *m, int stage, const float *const *params, const flo
             PEA_TRY(run_groups(k, kind == PEA_KIND_GAT ? AGG_GAT : kind == PEA_KIND_GCN ? AGG_GCN : AGG_MEAN));
             if (k + 1 < n_levels) PEA_TRY(run_gemm(k + 1));
         }
-        if (k == n_levels - 1 && (out_repr || out_stack))
+        if (k == n_levels - 1 && abl)
+            PEA_TRY(launch_fuse_ablate(N, d.num_channels, d.repr_dim, X, ldX, m->x_col, att, d.fuse_mode, abl->tables, abl->att,
+                                       stream));
+        else if (k == n_levels - 1 && (out_repr || out_stack))
             PEA_TRY(launch_fuse(N, d.num_channels, d.repr_dim, X, ldX, m->x_col, att, masked, d.fuse_mode, own_rows, n_own,
                                 out_repr, out_stack, stream, sel));
     }

@@ -257,43 +257,7 @@ class PEAEngine:
         the others (one launch with the fusion; the caller all-reduces them: ShardLayout.reduce_rows)."""
         lib = _lib.load()
         n = self.plan.num_nodes
-        if x.shape != (n, self.emb_dim) or x.dtype != torch.float32 or not x.is_cuda:
-            raise ValueError('x must be a CUDA float32 [%d, %d] tensor' % (n, self.emb_dim))
-        if len(layer_params) != self.n_layers:
-            raise ValueError('expected %d conv layers, got %d' % (self.n_layers, len(layer_params)))
-        keep = [x.contiguous()]
-        # The pointer table is rebuilt only when a parameter's storage moved (optimizers update in place): the checks and
-        # the ctypes stores below were 80 us of a 300 us step on the launch-bound presets.  A cached table is reused only if
-        # every tensor was contiguous float32 when it was built, so the raw pointers are the tensors' own.
-        sig = tuple(None if t is None else t.data_ptr() for lp in layer_params for t in lp)
-        cached = getattr(self, '_ptr_cache', None)
-        if cached is not None and cached[0] == sig:
-            ptrs = cached[1]
-        else:
-            ptrs = (C.c_void_p * (self.n_layers * self.slots))()
-            k, plain = 0, True
-            for lp in layer_params:
-                if len(lp) != self.slots:
-                    raise ValueError('each %s layer needs %d parameter tensors' % (self.kind, self.slots))
-                for t in lp:
-                    if t is None:
-                        ptrs[k] = None
-                    else:
-                        t = t.detach()
-                        if t.dtype != torch.float32 or not t.is_cuda:
-                            raise ValueError('parameters must be CUDA float32 tensors')
-                        plain = plain and t.is_contiguous()
-                        t = t.contiguous()
-                        keep.append(t)
-                        ptrs[k] = t.data_ptr()
-                    k += 1
-            self._ptr_cache = (sig, ptrs) if plain and len(sig) == self.n_layers * self.slots else None
-        att_t = None
-        if self.channel_aggr == 'att':
-            if att is None:
-                raise ValueError("att is required for channel_aggr='att'")
-            att_t = att.detach().reshape(self.P, self.repr_dim).contiguous()
-            keep.append(att_t)
+        ptrs, keep, att_t = self._launch_args(layer_params, x, att)
         if out is None:
             out = torch.empty((n, self.repr_dim), dtype=torch.float32, device=x.device)
         stack = torch.empty((n, self.P, self.repr_dim), dtype=torch.float32, device=x.device) if want_stack else None
@@ -354,6 +318,66 @@ class PEAEngine:
         if select_ids is not None:
             return out, picked
         return (out, stack) if want_stack else out
+
+    def _launch_args(self, layer_params, x, att):
+        """Checks x / the parameters / att and returns (parameter pointer table, tensors to keep alive with x first, att as
+        [P, repr_dim] or None): what every pea_model_forward* call is handed."""
+        n = self.plan.num_nodes
+        if x.shape != (n, self.emb_dim) or x.dtype != torch.float32 or not x.is_cuda:
+            raise ValueError('x must be a CUDA float32 [%d, %d] tensor' % (n, self.emb_dim))
+        if len(layer_params) != self.n_layers:
+            raise ValueError('expected %d conv layers, got %d' % (self.n_layers, len(layer_params)))
+        keep = [x.contiguous()]
+        # The pointer table is rebuilt only when a parameter's storage moved (optimizers update in place): the checks and
+        # the ctypes stores below were 80 us of a 300 us step on the launch-bound presets.  A cached table is reused only if
+        # every tensor was contiguous float32 when it was built, so the raw pointers are the tensors' own.
+        sig = tuple(None if t is None else t.data_ptr() for lp in layer_params for t in lp)
+        cached = getattr(self, '_ptr_cache', None)
+        if cached is not None and cached[0] == sig:
+            ptrs = cached[1]
+        else:
+            ptrs = (C.c_void_p * (self.n_layers * self.slots))()
+            k, plain = 0, True
+            for lp in layer_params:
+                if len(lp) != self.slots:
+                    raise ValueError('each %s layer needs %d parameter tensors' % (self.kind, self.slots))
+                for t in lp:
+                    if t is None:
+                        ptrs[k] = None
+                    else:
+                        t = t.detach()
+                        if t.dtype != torch.float32 or not t.is_cuda:
+                            raise ValueError('parameters must be CUDA float32 tensors')
+                        plain = plain and t.is_contiguous()
+                        t = t.contiguous()
+                        keep.append(t)
+                        ptrs[k] = t.data_ptr()
+                    k += 1
+            self._ptr_cache = (sig, ptrs) if plain and len(sig) == self.n_layers * self.slots else None
+        att_t = None
+        if self.channel_aggr == 'att':
+            if att is None:
+                raise ValueError("att is required for channel_aggr='att'")
+            att_t = att.detach().reshape(self.P, self.repr_dim).contiguous()
+            keep.append(att_t)
+        return ptrs, keep, att_t
+
+    def forward_ablate(self, layer_params, x, att=None, want_att=False):
+        """One forward, every ablation variant (include/peahip.h, pea_model_forward_ablate): returns tables
+        [P + 1, N, repr_dim] -- tables[0] bitwise forward(masked=None), tables[1 + p] bitwise forward(masked=p) -- and, with
+        want_att, the unmasked fusion weights [N, P] (1 / P under 'mean'), else None.  Single GPU."""
+        if self.sharded:
+            raise NotImplementedError('the ablation sweep is single-GPU (this engine is sharded)')
+        lib = _lib.load()
+        check_pending_errors()
+        n = self.plan.num_nodes
+        ptrs, keep, att_t = self._launch_args(layer_params, x, att)
+        tables = torch.empty((self.P + 1, n, self.repr_dim), dtype=torch.float32, device=x.device)
+        weights = torch.empty((n, self.P), dtype=torch.float32, device=x.device) if want_att else None
+        _lib.check(lib.pea_model_forward_ablate(self._h, ptrs, _lib.ptr(keep[0]), _lib.ptr(att_t), _lib.ptr(self._ws),
+                                                self.workspace_bytes, _lib.ptr(tables), _lib.ptr(weights),
+                                                _lib.current_stream()))
+        return tables, weights
 
     # ------------------------------------------------------------------ sharded loss step, launches replayed from hipGraphs
     def _param_table(self, layer_params):
@@ -827,6 +851,67 @@ def rank_eval(repr_, unids, cand, fc1_w, fc1_b, fc2_w, fc2_b):
     rc = lib.pea_rank_eval(u, c, repr_.shape[1], repr_.shape[0], _lib.ptr(args[0]), _lib.ptr(unids), _lib.ptr(cand),
                            _lib.ptr(args[1]), _lib.ptr(args[2]), _lib.ptr(args[3]), _lib.ptr(args[4]),
                            _lib.ptr(scores), _lib.ptr(rank), _lib.ptr(auc), _lib.ptr(loss), _lib.current_stream())
+    if rc == -2:
+        raise IndexError(_lib.last_error())
+    _lib.check(rc)
+    return scores, rank, auc, loss
+
+
+def fuse_ablate(stack, att, mode='att', want_att=True):
+    """Every ablation variant of a channel stack [N, P, R] in one pass (include/peahip.h, pea_fuse_ablate): returns tables
+    [P + 1, N, R] -- tables[0] the unmasked fusion (reference models/base.py:196-203), tables[1 + p] with channel p zeroed
+    first (:194-195) -- and the unmasked fusion weights [N, P] (None unless want_att).  att: [P, R] (or [1, P, R]) for
+    mode 'att', ignored for 'mean'."""
+    lib = _lib.require_device()
+    check_pending_errors()
+    if mode not in ('att', 'mean'):
+        raise NotImplementedError('Other aggr methods not implemeted!')
+    if stack.dim() != 3 or stack.dtype != torch.float32 or not stack.is_cuda:
+        raise ValueError('stack must be a CUDA float32 [N, P, R] tensor')
+    stack = stack.detach().contiguous()
+    n, p, r = stack.shape
+    att_t = None
+    if mode == 'att':
+        if att is None:
+            raise ValueError("att is required for mode 'att'")
+        att_t = att.detach().reshape(p, r).contiguous()
+    cols = (C.c_int * p)(*[q * r for q in range(p)])
+    tables = torch.empty((p + 1, n, r), dtype=torch.float32, device=stack.device)
+    weights = torch.empty((n, p), dtype=torch.float32, device=stack.device) if want_att else None
+    _lib.check(lib.pea_fuse_ablate(n, p, r, _lib.ptr(stack), p * r, cols, _lib.ptr(att_t),
+                                   _lib.FUSE_ATT if mode == 'att' else _lib.FUSE_MEAN, _lib.ptr(tables), _lib.ptr(weights),
+                                   _lib.current_stream()))
+    return tables, weights
+
+
+def rank_eval_multi(tables, unids, cand, fc1_w, fc1_b, fc2_w, fc2_b):
+    """rank_eval over V tables [V, N, R] in one launch (include/peahip.h, pea_rank_eval_multi).  cand [U, C]: every variant
+    ranks the same candidates; cand [V, U, C]: variant v ranks cand[v].  Returns scores [V, U, C], rank [V, U] (int32),
+    auc [V, U], eval loss [V, U]; row v is bitwise rank_eval(tables[v], unids, cand or cand[v], ...)."""
+    lib = _lib.require_device()
+    check_pending_errors()
+    if tables.dim() != 3 or tables.dtype != torch.float32:
+        raise ValueError('tables must be float32 [V, N, R]')
+    tables = tables.detach().contiguous()
+    v, n, r = tables.shape
+    unids = unids.to(torch.int64).contiguous()
+    cand = cand.to(torch.int64).contiguous()
+    u = unids.shape[0]
+    if cand.dim() == 2 and cand.shape[0] == u:
+        c, stride = cand.shape[1], 0
+    elif cand.dim() == 3 and cand.shape[0] == v and cand.shape[1] == u:
+        c, stride = cand.shape[2], u * cand.shape[2]
+    else:
+        raise ValueError('cand must be [U, C] (shared by all variants) or [V, U, C]')
+    dev = tables.device
+    scores = torch.empty((v, u, c), dtype=torch.float32, device=dev)
+    rank = torch.empty((v, u), dtype=torch.int32, device=dev)
+    auc = torch.empty((v, u), dtype=torch.float32, device=dev)
+    loss = torch.empty((v, u), dtype=torch.float32, device=dev)
+    args = [t.detach().contiguous() for t in (fc1_w, fc1_b, fc2_w, fc2_b)]
+    rc = lib.pea_rank_eval_multi(v, u, c, r, n, _lib.ptr(tables), _lib.ptr(unids), _lib.ptr(cand), stride, _lib.ptr(args[0]),
+                                 _lib.ptr(args[1]), _lib.ptr(args[2]), _lib.ptr(args[3]), _lib.ptr(scores), _lib.ptr(rank),
+                                 _lib.ptr(auc), _lib.ptr(loss), _lib.current_stream())
     if rc == -2:
         raise IndexError(_lib.last_error())
     _lib.check(rc)

@@ -152,6 +152,7 @@ class PEABaseRecsysModel(GraphRecsysModel):
         self._train_engine = None
         self._plan = None
         self._shard = (0, 1, 256)
+        self.ablation_repr = self.ablation_att = None      # set by eval_ablation()
 
     def shard(self, rank, world, tile=256):
         """Multi-GPU: this process computes the destination rows it owns (row i -> rank (i // tile) % world);
@@ -224,6 +225,58 @@ class PEABaseRecsysModel(GraphRecsysModel):
         eng = self._get_engine()
         return eng.forward(self._layer_params(), self.x.detach(), getattr(self, 'att', None), masked=metapath_idx,
                            want_stack=return_stack)
+
+    # ------------------------------------------------------------------ metapath ablation (reference solvers.py:224-241)
+    def train(self, mode=True):
+        """nn.Module.train(); leaving (or re-entering, nn.Module.eval() comes through here) a mode drops the ablation tables
+        of eval_ablation(): they describe the parameters of the moment they were computed."""
+        self.ablation_repr = self.ablation_att = None
+        return super().train(mode)
+
+    def _require_single_gpu(self, what):
+        if self._shard[1] > 1:
+            raise NotImplementedError('%s is single-GPU (this model is sharded over %d ranks)' % (what, self._shard[1]))
+
+    def _require_ablation(self, what):
+        if getattr(self, 'ablation_repr', None) is None or self.training:
+            raise RuntimeError('%s reads the ablation tables: call model.eval_ablation() first' % what)
+
+    def eval_ablation(self, keep_att=True):
+        """nn.Module.eval() + ONE full-graph forward that caches every ablation variant:
+            ablation_repr [P + 1, N, repr_dim]   [0] = what eval() caches, [1 + p] = what eval(p) caches (bitwise both)
+            ablation_att  [N, P]                 the unmasked fusion weights per node (None with keep_att=False)
+            cached_repr = ablation_repr[0]       (a view)
+        so predict / recommend / metrics / metrics_full read the same bytes as after eval().  The reference gets the same
+        tables from P + 1 forwards (solvers.py:224-241: model.eval(metapath_idx) per metapath, models/base.py:191-195);
+        unlike that loop, which leaves the LAST-masked table cached, the model ends in the unmasked state here.
+        eval(...) and train() drop the ablation tables.  Single GPU."""
+        self._require_single_gpu('eval_ablation()')
+        if not self.x.is_cuda:
+            raise RuntimeError('the HIP path needs the model on a GPU (there is no CPU fallback)')
+        torch.nn.Module.eval(self)
+        self._repr_partial = False
+        _engine.check_pending_errors()
+        with torch.no_grad():
+            tables, att = self._get_engine().forward_ablate(self._layer_params(), self.x.detach(), getattr(self, 'att', None),
+                                                            want_att=keep_att)
+        self.ablation_repr, self.ablation_att = tables, att
+        self.cached_repr = tables[0]
+        return self
+
+    def explain(self, unids, inids):
+        """Which metapaths carried the score of each pair (unids[b], inids[b]); needs eval_ablation() first.  Returns a dict:
+            score          [B]     predict() on the unmasked table (bitwise)
+            score_without  [B, P]  column p: predict() with metapath p zeroed before fusion (what eval(p) would score)
+            att_user, att_item [B, P]  the unmasked fusion weights of the two nodes (None after eval_ablation(keep_att=False))"""
+        self._require_single_gpu('explain()')
+        self._require_ablation('explain()')
+        fc = (self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias)
+        preds = [_engine.predict(t, unids, inids, *fc).view(-1) for t in self.ablation_repr]
+        att = self.ablation_att
+        u = torch.as_tensor(unids, device=self.ablation_repr.device).to(torch.int64)
+        i = torch.as_tensor(inids, device=self.ablation_repr.device).to(torch.int64)
+        return {'score': preds[0], 'score_without': torch.stack(preds[1:], dim=1),
+                'att_user': None if att is None else att[u], 'att_item': None if att is None else att[i]}
 
     def _forward_autograd(self, metapath_idx, return_stack):
         """Differentiable forward: conv stack forward + backward in HIP, fusion (models/base.py:194-203) in torch ops."""

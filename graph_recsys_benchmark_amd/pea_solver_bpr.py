@@ -10,6 +10,7 @@ sequence on the synthetic preset of the dataset the flags name:
     model.train(); loss(batch) [+ backward + optimizer step with --train_step true]   solvers.py:211-218
     model.eval()                                                                      solvers.py:227 / models/base.py:88-96
     metrics(model, dataset)                                                           solvers.py:33-104
+    [--metapath_test true, the default] metrics per metapath p with p zeroed          solvers.py:229-241
 
 and prints one JSON object.  The processed datasets are absent, so `--dataset/--dataset_name` select the
 SyntheticHIN preset of the same shape.  Needs a GPU (no CPU fallback).
@@ -160,7 +161,12 @@ def main(argv=None, dataset=None):
             loss = model.loss(batch)
     train_loss = float(loss.detach().cpu().item())
 
-    model.eval()                                         # solvers.py:227
+    # solvers.py:227.  With --metapath_test the same forward also caches the masked tables (eval_ablation: the unmasked
+    # table it leaves in cached_repr is bitwise eval()'s)
+    if train_args['metapath_test']:
+        model.eval_ablation(keep_att=False)
+    else:
+        model.eval()
     if not hasattr(dataset, 'test_pos_unid_inid_map'):
         dataset.eval_split(num_users=args.eval_users or None)
     with torch.no_grad():
@@ -170,6 +176,15 @@ def main(argv=None, dataset=None):
            'HR@5': float(hr[0]), 'HR@10': float(hr[5]), 'HR@20': float(hr[15]),
            'NDCG@5': float(ndcg[0]), 'NDCG@10': float(ndcg[5]), 'NDCG@20': float(ndcg[15]),
            'AUC': float(auc[0]), 'eval_loss': float(eval_loss[0]), 'eval_users': len(dataset.test_pos_unid_inid_map)}
+    if train_args['metapath_test']:
+        # solvers.py:229-241: after the unmasked metrics, one metrics() per metapath with fresh candidate draws, in order
+        with torch.no_grad():
+            hrs, ndcgs, aucs, losses = solvers.metapath_ablation(model, dataset, train_args['num_neg_candidates'],
+                                                                 variants=range(1, len(steps) + 1))
+        out['metapath_test'] = [{'metapath_idx': k, 'HR@5': float(hrs[k][0]), 'HR@10': float(hrs[k][5]),
+                                 'HR@20': float(hrs[k][15]), 'NDCG@5': float(ndcgs[k][0]), 'NDCG@10': float(ndcgs[k][5]),
+                                 'NDCG@20': float(ndcgs[k][15]), 'AUC': float(aucs[k]), 'eval_loss': float(losses[k])}
+                                for k in range(len(steps))]
     main.last_model = model                              # tests look at the model afterwards
     return out
 

@@ -38,6 +38,8 @@
  *   pea_sample_negatives     datasets/movielens.py:920-940 (an on-GPU sampler NEXT TO the bit-exact host mirror)
  *   pea_entity_reg           models/base.py:50-73 (entity-aware regulariser of the loss, value + gradient rows)
  *   pea_bpr_train            models/base.py:193-214 + 46-48 under autograd (fusion + scorer + BPR loss, forward + backward)
+ *   pea_fuse_ablate, pea_model_forward_ablate, pea_rank_eval_multi
+ *                            solvers.py:224-241 (the --metapath_test sweep: eval(metapath_idx) + metrics() per metapath)
  *   pea_recommend_topk, pea_rank_full   models/base.py:208-214 over the WHOLE item catalogue: the K best unseen items per
  *                            user, and solvers.py:85-96 with every unseen item as a negative instead of 99 sampled ones
  *   pea_model_forward_stage[_train], pea_model_backward_level (phases), pea_rows_pack / _unpack / _select_owned,
@@ -468,6 +470,38 @@ int pea_kg_attention(const pea_plan *plan, int relation, int mode, int emb, cons
 int pea_fuse(int64_t num_nodes, int P, int R, const float *stack, int64_t ld_stack,
              const int *col_of_channel_host, const float *att, int masked_channel, int fuse_mode,
              float *out, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Metapath ablation in one pass (csrc/ablate.hip).  The reference's --metapath_test loop (solvers.py:224-241, 371-387)
+ * calls model.eval(metapath_idx) -- a full-graph forward with one channel zeroed before fusion, models/base.py:191-195 --
+ * and metrics() once per metapath.  The conv stack does not depend on the masked channel, so ONE forward, one fusion
+ * pass that writes all P + 1 variants and one ranking launch over them give the same table.
+ *
+ * pea_fuse_ablate: pea_fuse for every mask at once.  out_tables [P + 1, N, R]: variant 0 = no channel masked, variant
+ *   1 + p = channel p zeroed (it stays in the fusion: logit 0 in the 'att' softmax, divisor P under 'mean' -- the
+ *   reference's behaviour).  Each row's P channel vectors are read once (P <= 16: held in registers; above: re-read
+ *   through the cache).  EVERY VARIANT IS BITWISE pea_fuse(masked_channel = v - 1) on the same stack: the same online
+ *   softmax in channel order per variant, nothing reassociated across variants.  out_att (may be NULL) [N, P]: the softmax
+ *   weights of variant 0 (1 / P under 'mean').  Accepts every (P, R, ld_stack, column table) pea_fuse accepts; 64-bit
+ *   indexing; no atomics.
+ * pea_model_forward_ablate: pea_model_forward's schedule with the final fusion launch replaced by the ablation fusion,
+ *   reading the stack where the schedule left it in the workspace.  out_tables[0] is bitwise pea_model_forward(masked = -1),
+ *   out_tables[1 + p] bitwise pea_model_forward(masked = p).  Single GPU: a sharded model returns PEA_ERR_ARG.
+ * pea_rank_eval_multi: pea_rank_eval over V tables [V, N, R] in one launch, same users for every variant.  cand:
+ *   cand_variant_stride = 0: one [U, C] block shared by all variants (a paired comparison; the ids are loaded once);
+ *   U * C: cand is [V, U, C] (a fresh draw per variant, as the reference's loop makes).  scores [V, U, C] (may be NULL),
+ *   rank [V, U], auc [V, U], loss [V, U]; for every v bitwise pea_rank_eval(tables[v], cand[v]).  Synchronises the stream
+ *   once to report ids outside [0, num_nodes) as PEA_ERR_RANGE.
+ * ---------------------------------------------------------------------------------------------- */
+int pea_fuse_ablate(int64_t num_nodes, int P, int R, const float *stack, int64_t ld_stack,
+                    const int *col_of_channel_host, const float *att, int fuse_mode, float *out_tables /* [P+1, N, R] */,
+                    float *out_att /* [N, P] or NULL */, void *stream);
+int pea_model_forward_ablate(pea_model *model, const float *const *params_host, const float *x, const float *att,
+                             void *workspace, size_t workspace_bytes, float *out_tables, float *out_att, void *stream);
+int pea_rank_eval_multi(int V, int64_t U, int C, int R, int64_t num_nodes, const float *tables /* [V, N, R] */,
+                        const int64_t *unids, const int64_t *cand, int64_t cand_variant_stride, const float *fc1_w,
+                        const float *fc1_b, const float *fc2_w, const float *fc2_b, float *scores /* [V, U, C] or NULL */,
+                        int32_t *rank /* [V, U] */, float *auc, float *loss, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * BPR scoring (models/base.py:208-214, 46-48): for each of B rows (u, i+, i-) of `triples`
