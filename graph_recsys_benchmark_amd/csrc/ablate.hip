@@ -267,14 +267,21 @@ extern "C" int pea_fuse_ablate(int64_t num_nodes, int P, int R, const float *sta
 extern "C" int pea_model_forward_ablate(pea_model *model, const float *const *params_host, const float *x, const float *att,
                                         void *workspace, size_t workspace_bytes, float *out_tables, float *out_att,
                                         void *stream) {
-    PEA_REQUIRE(model && params_host && x && workspace && out_tables, PEA_ERR_ARG, "forward_ablate: null argument");
-    PEA_REQUIRE(model->plan->shard_world == 1, PEA_ERR_ARG, "forward_ablate: single GPU only (the plan is sharded)");
-    PEA_REQUIRE(workspace_bytes >= pea_model_workspace_bytes(model), PEA_ERR_NOMEM, "forward_ablate: workspace %zu < %zu bytes",
-                workspace_bytes, pea_model_workspace_bytes(model));
+    PEA_REQUIRE(out_tables, PEA_ERR_ARG, "forward_ablate: null argument");
+    PEA_REQUIRE(!model || model->plan->shard_world == 1, PEA_ERR_ARG, "forward_ablate: single GPU only (the plan is sharded)");
+    PEA_TRY(check_forward_args("forward_ablate", model, params_host, x, workspace, workspace_bytes, -1, nullptr));
     PEA_REQUIRE(model->d.fuse_mode == PEA_FUSE_MEAN || att, PEA_ERR_ARG, "forward_ablate: att is required for 'att' fusion");
     const AblateOut abl{out_tables, out_att};
-    return model_forward(model, -1, params_host, x, model->d.emb_dim, att, -1, aligned_ws(workspace), nullptr, nullptr, nullptr,
-                         0, 0, (hipStream_t)stream, false, PEA_PART_ALL, nullptr, &abl);
+    ForwardCall c;
+    c.model = model;
+    c.params = params_host;
+    c.x = x;
+    c.ldx = model->d.emb_dim;
+    c.att = att;
+    c.wsf = aligned_ws(workspace);
+    c.stream = (hipStream_t)stream;
+    c.abl = &abl;
+    return model_forward(c);
 }
 
 extern "C" int pea_rank_eval_multi(int V, int64_t U, int C, int R, int64_t num_nodes, const float *tables,

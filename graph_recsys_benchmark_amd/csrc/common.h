@@ -446,14 +446,36 @@ struct AblateOut {
     float *att = nullptr;      // [N, P] or null
 };
 
-// abl (single GPU): the final fusion launch is replaced by launch_fuse_ablate on the stack where the schedule left it
-int model_forward(pea_model *m, int stage, const float *const *params, const float *x, int64_t ldx, const float *att,
-                  int masked, float *wsf, float *out_repr, float *out_stack, float *out_x, int64_t ld_out_x,
-                  int relu_last, hipStream_t stream, bool training, int part = 0, const FuseSelect *sel = nullptr,
-                  const AblateOut *abl = nullptr);
+// ---------------------------------------------------------------- the model schedule (model.hip)
+// One call of the forward schedule.  Callers fill the fields they use by name.
+struct ForwardCall {
+    pea_model *model = nullptr;
+    int stage = -1;                    // -1: every stage back to back; k: stage k of a sharded plan
+    int part = PEA_PART_ALL;           // sharded ranks: which part of the stage (peahip.h: PEA_PART_*)
+    const float *const *params = nullptr;  // [sum steps][slots] device pointers, channel-major
+    const float *x = nullptr;
+    int64_t ldx = 0;                   // row stride of x
+    const float *att = nullptr;
+    int masked = -1;
+    float *wsf = nullptr;              // aligned workspace
+    float *out_repr = nullptr, *out_stack = nullptr;
+    // single-conv entry points: when out_x is set the last-layer outputs go there instead of the workspace X, and
+    // relu_last applies relu to last layers too
+    float *out_x = nullptr;
+    int64_t ld_out_x = 0;
+    int relu_last = 0;
+    hipStream_t stream = nullptr;
+    bool training = false;
+    const FuseSelect *sel = nullptr;   // batch-row selection riding in the last stage's fusion launch
+    // single GPU: the final fusion launch is replaced by launch_fuse_ablate on the stack where the schedule left it
+    const AblateOut *abl = nullptr;
+};
+int model_forward(const ForwardCall &call);
+
+// The checks every forward-family entry point `who` makes: no null model / params / x / workspace, the stage in range
+// (stage null: the entry point takes none), the workspace large enough, the masked channel in [-1, P).
+int check_forward_args(const char *who, const pea_model *model, const float *const *params, const float *x,
+                       const void *workspace, size_t workspace_bytes, int masked, const int *stage);
 
 }  // namespace pea
 float *aligned_ws(void *workspace);
-namespace pea {
-
-}  // namespace pea

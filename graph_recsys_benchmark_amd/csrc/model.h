@@ -10,7 +10,7 @@ struct Unit {  // one channel at one level
     bool last = false;
     int in_col = 0;    // column of the input block (level 0: 0 in x; else in O_{s-1})
     int t_col = 0;     // column in T_s (GAT/GCN) or of its mean block in M_s (SAGE)
-    int a_k = 0;       // first attention index in A_s
+    int a_k = 0;       // first attention head of the unit among the level's heads
     int o_col = 0;     // column in O_s (non-last) or X (last)
     size_t b_off = 0;  // packed weight block (floats from the pack base)
     int ldb = 0;
@@ -36,8 +36,8 @@ struct Level {
     std::vector<Unit> units;  // in buffer (column) order
     std::vector<GroupPlan> groups;
     int n_cols = 0, n_heads = 0;             // sum HF, sum heads (GAT/GCN)
-    int ld_t = 0, ld_a = 0, ld_o = 0;        // strides of T_s (or M_s), A_s, O_s
-    size_t off_t = 0, off_a = 0, off_o = 0;  // float offsets in the workspace
+    int ld_t = 0, ld_o = 0;                  // strides of T_s (or M_s), O_s
+    size_t off_t = 0, off_o = 0;             // float offsets in the workspace
     bool shared_input = false;               // level 0 of GAT/GCN: one concatenated GEMM job
     size_t b_off = 0, bias_off = 0;          // concatenated weight block / per-level bias block
     size_t att_src_off = 0, att_dst_off = 0; // per-level att_j / att_i rows in column order (GAT)
@@ -45,7 +45,6 @@ struct Level {
     // training / backward (allocated when the model was created with enable_backward)
     int ld_stats = 0, ld_k = 0, ld_side = 0;             // strides of stats [N,2*heads], d a_* [N,heads], side [N,4*heads]
     size_t off_stats = 0, off_dt = 0, off_do = 0, off_side = 0, off_dad = 0, off_das = 0;
-    size_t gatt_src_off = 0, gatt_dst_off = 0, gbias_off = 0;  // gradient rows (floats from the grad-pack base), column order
 };
 
 }  // namespace pea

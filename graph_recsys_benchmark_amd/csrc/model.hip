@@ -19,7 +19,7 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "model.h"
+#include "agg_build.h"
 
 namespace pea {
 namespace {
@@ -49,6 +49,64 @@ int slots_of(const pea_model *m, int rel) {
 }
 
 int rel_at(const pea_model *m, int p, int s) { return m->relation_of[(size_t)(m->chan_first[(size_t)p] + s)]; }
+
+// Statistics of the finished schedule: messages and the algorithmic-byte yardstick of SURVEY.md 8(d), and the compulsory
+// HBM bytes of THIS schedule (not of the reference's): x read once; per level T_s written once and read once (however
+// often its rows are gathered afterwards: re-reads can come from cache), O_s of the channels that continue written once
+// and read once, every group's index arrays read once; X written and read once; the fused table written once.
+// step time x 8 TB/s over this = how far the whole step is from the DRAM floor.
+// A rank of a sharded plan writes and reads its own rows only (x is replicated: read whole).
+void schedule_statistics(pea_model *m) {
+    const pea_model_desc &d = m->d;
+    const pea_plan *plan = m->plan;
+    const int P = d.num_channels;
+    const int64_t N = plan->N;
+    const bool gat = d.kind == PEA_KIND_GAT;
+    const double Nn = (double)N;
+    const double Nr = (plan->shard_world > 1 && plan->n_owned > 0) ? (double)plan->n_owned : Nn;
+    m->messages = 0;
+    m->alg_bytes = 0.0;
+    m->compulsory_bytes = 4.0 * Nn * d.emb_dim;
+    int x_cols = 0;
+    for (size_t s = 0; s < m->levels.size(); ++s) {
+        const Level &L = m->levels[s];
+        double cont_cols = 0.0;
+        for (const Unit &u : L.units) {
+            if (u.last) x_cols += u.HF;
+            else cont_cols += u.HF;
+        }
+        if (m->fused2 && s == 0) {
+            // two-step schedule: no T_0 / O_0; per channel its index arrays and the aggregates A_0 of the rows that
+            // have incoming edges (written once, read once)
+            int prev_rel = -1;
+            for (const Unit &u : L.units) {   // (SAGE: one mean per distinct relation, shared by its channels)
+                if (d.kind == PEA_KIND_SAGE && u.rel == prev_rel) continue;
+                prev_rel = u.rel;
+                const Relation &R = plan->rels[(size_t)u.rel];
+                const double rows_with_edges = (double)(R.n_short - R.n_short0) + R.n_direct + R.n_hub;
+                m->compulsory_bytes += 4.0 * (double)R.e_kept + 4.0 * (Nr + 1.0) + 8.0 * rows_with_edges * d.emb_dim;
+            }
+        } else {
+            m->compulsory_bytes += 8.0 * Nr * L.n_cols + 8.0 * Nr * cont_cols;
+            for (const GroupPlan &g : L.groups)
+                m->compulsory_bytes += 4.0 * (double)plan->rels[(size_t)g.rel].e_kept + 4.0 * (Nr + 1.0);
+        }
+        for (const Unit &u : L.units) {
+            const Relation &R = plan->rels[(size_t)u.rel];
+            if (d.kind == PEA_KIND_SAGE) {  // the yardstick counts the reference's conv calls, whatever the schedule
+                m->messages += R.e_kept;
+                m->alg_bytes += (double)R.e_kept * (4.0 * u.in_w + 4.0) + 4.0 * (Nn + 1) + 4.0 * Nn * u.in_w + 4.0 * Nn * u.HF;
+            } else {
+                const double M = (double)R.e_kept + Nn;
+                m->messages += R.e_kept + N;
+                m->alg_bytes += M * (4.0 * u.HF + 4.0 + 4.0 * u.heads) + 4.0 * (Nn + 1) + 4.0 * Nn * u.in_w + 8.0 * Nn * u.HF +
+                                (gat ? 8.0 * Nn * u.heads : 0.0);
+            }
+        }
+    }
+    m->alg_bytes += 4.0 * Nn * P * d.repr_dim + 4.0 * Nn * d.repr_dim;
+    m->compulsory_bytes += 8.0 * Nr * x_cols + 4.0 * Nr * d.repr_dim;
+}
 
 int build_schedule(pea_model *m) {
     const pea_model_desc &d = m->d;
@@ -82,15 +140,6 @@ int build_schedule(pea_model *m) {
     std::vector<int> in_w((size_t)P, d.emb_dim), in_col((size_t)P, 0);
     int x_cols = 0;
     size_t pack = 0, ws = 0, partial_max = 0, xch = 0;
-    m->messages = 0;
-    m->alg_bytes = 0.0;
-    // Compulsory HBM bytes of THIS schedule (not of the reference's): x read once; per level T_s written once and read
-    // once (however often its rows are gathered afterwards: re-reads can come from cache), O_s of the channels that
-    // continue written once and read once, every group's index arrays read once; X written and read once; the fused
-    // table written once.  step time x 8 TB/s over this = how far the whole step is from the DRAM floor.
-    // A rank of a sharded plan writes and reads its own rows only (x is replicated: read whole).
-    const double Nr = (plan->shard_world > 1 && plan->n_owned > 0) ? (double)plan->n_owned : (double)N;
-    m->compulsory_bytes = 4.0 * (double)N * d.emb_dim;
 
     for (int s = 0; s < Smax; ++s) {
         Level &L = m->levels[(size_t)s];
@@ -128,7 +177,6 @@ int build_schedule(pea_model *m) {
         L.n_cols = col;
         L.n_heads = ak;
         L.ld_t = pad_ld(col);
-        L.ld_a = 0;
         // outputs of channels that continue: GAT/GCN keep the T_s column order; SAGE lays O_s out in the order the
         // NEXT level aggregates it (same relation side by side)
         std::vector<Unit *> cont;
@@ -280,44 +328,8 @@ int build_schedule(pea_model *m) {
         }
         L.off_t = ws;
         ws = pad_off(ws + (size_t)N * (size_t)((m->fused2 && s == 0) ? std::max(L.ld_t, m->ld_a0) : L.ld_t));
-        L.off_a = ws;
         L.off_o = ws;
         ws = pad_off(ws + (size_t)N * (size_t)L.ld_o);
-        {
-            double cont_cols = 0.0;
-            for (const Unit &u : L.units)
-                if (!u.last) cont_cols += u.HF;
-            if (m->fused2 && s == 0) {
-                // two-step schedule: no T_0 / O_0; per channel its index arrays and the aggregates A_0 of the rows that
-                // have incoming edges (written once, read once)
-                int prev_rel = -1;
-                for (const Unit &u : L.units) {   // (SAGE: one mean per distinct relation, shared by its channels)
-                    if (d.kind == PEA_KIND_SAGE && u.rel == prev_rel) continue;
-                    prev_rel = u.rel;
-                    const Relation &R = plan->rels[(size_t)u.rel];
-                    const double rows_with_edges = (double)(R.n_short - R.n_short0) + R.n_direct + R.n_hub;
-                    m->compulsory_bytes += 4.0 * (double)R.e_kept + 4.0 * (Nr + 1.0) + 8.0 * rows_with_edges * d.emb_dim;
-                }
-            } else {
-                m->compulsory_bytes += 8.0 * Nr * L.n_cols + 8.0 * Nr * cont_cols;
-                for (const GroupPlan &g : L.groups)
-                    m->compulsory_bytes += 4.0 * (double)plan->rels[(size_t)g.rel].e_kept + 4.0 * (Nr + 1.0);
-            }
-        }
-        // statistics: messages and the algorithmic-byte yardstick of SURVEY.md 8(d)
-        for (const Unit &u : L.units) {
-            const Relation &R = plan->rels[(size_t)u.rel];
-            const double Nn = (double)N;
-            if (d.kind == PEA_KIND_SAGE) {  // the yardstick counts the reference's conv calls, whatever the schedule
-                m->messages += R.e_kept;
-                m->alg_bytes += (double)R.e_kept * (4.0 * u.in_w + 4.0) + 4.0 * (Nn + 1) + 4.0 * Nn * u.in_w + 4.0 * Nn * u.HF;
-            } else {
-                const double M = (double)R.e_kept + Nn;
-                m->messages += R.e_kept + N;
-                m->alg_bytes += M * (4.0 * u.HF + 4.0 + 4.0 * u.heads) + 4.0 * (Nn + 1) + 4.0 * Nn * u.in_w + 8.0 * Nn * u.HF +
-                                (gat ? 8.0 * Nn * u.heads : 0.0);
-            }
-        }
     }
     if (m->fused2 || m->fused2_train) {
         m->mlp2_img_off = pack;
@@ -326,13 +338,10 @@ int build_schedule(pea_model *m) {
         pack = pad_off(pack + (size_t)2 * P * (size_t)d.emb_dim);
     }
     m->ld_x = pad_ld(x_cols);
-    m->alg_bytes += 4.0 * (double)N * P * d.repr_dim + 4.0 * (double)N * d.repr_dim;
-    m->compulsory_bytes += 8.0 * Nr * x_cols + 4.0 * Nr * d.repr_dim;
     m->pack_floats = pad_off(pack);
     size_t off = m->pack_floats;
     for (Level &L : m->levels) {
         L.off_t += off;
-        L.off_a += off;
         L.off_o += off;
     }
     off += ws;
@@ -366,6 +375,7 @@ int build_schedule(pea_model *m) {
         m->off_colsum = off;  off = pad_off(off + (size_t)2 * kColsumParts * (size_t)std::max(max_w, m->ld_x));  // two sums per pass
     }
     m->total_floats = off;
+    schedule_statistics(m);
     return PEA_OK;
 }
 
@@ -401,630 +411,556 @@ int init_model(pea_model *m, const pea_plan *plan, const pea_model_desc *desc) {
     return build_schedule(m);
 }
 
-}  // namespace
+// ------------------------------------------------------------------------------------------------ forward
+// What every step of one forward call reads, derived once per call.
+struct Fwd {
+    const ForwardCall &c;
+    pea_model *m;
+    pea_plan *plan;
+    float *pack;           // packed weights: the head of the workspace
+    float *X;              // last-layer outputs of every channel: the workspace X, or the caller's buffer (single conv)
+    int64_t ldX;
+    float *partial;        // hub partial records
+    bool sharded;
+    const int *own_rows;   // rows this rank owns (null: all N)
+    int64_t n_own;
+    bool hot_on;           // PEA_HOT, read per forward: tests and A/B runs flip it inside one process
 
-// params: [sum steps][slots] device pointers, channel-major.  ldx: row stride of x.
-// out_x / ld_out_x: when non-null the last-layer outputs go there instead of the workspace X (single-conv
-// entry points); relu_last applies relu to last layers too.
-int model_forward(pea_model *m, int stage, const float *const *params, const float *x, int64_t ldx, const float *att,
-                  int masked, float *wsf, float *out_repr, float *out_stack, float *out_x, int64_t ld_out_x, int relu_last,
-                  hipStream_t stream, bool training, int part, const FuseSelect *sel, const AblateOut *abl) {
-    const pea_model_desc &d = m->d;
-    pea_plan *plan = const_cast<pea_plan *>(m->plan);
-    const int64_t N = plan->N;
-    const int kind = d.kind;
-    const int slots = m->n_slots_per_layer;
-    float *pack = wsf;
-    float *X = out_x ? out_x : wsf + m->off_x;
-    const int64_t ldX = out_x ? ld_out_x : m->ld_x;
-    float *partial = wsf + m->off_partial;
-    auto param = [&](const Unit &u, int slot) -> const float * {
-        return params[(size_t)(m->chan_first[(size_t)u.p] + u.s) * (size_t)slots + (size_t)slot];
-    };
+    explicit Fwd(const ForwardCall &call)
+        : c(call), m(call.model), plan(const_cast<pea_plan *>(call.model->plan)), pack(call.wsf),
+          X(call.out_x ? call.out_x : call.wsf + call.model->off_x), ldX(call.out_x ? call.ld_out_x : call.model->ld_x),
+          partial(call.wsf + call.model->off_partial), sharded(plan->shard_world > 1),
+          own_rows(sharded ? plan->owned_rows : nullptr), n_own(sharded ? plan->n_owned : plan->N) {
+        const char *hot_env = getenv("PEA_HOT");
+        hot_on = hot_env && atoi(hot_env) != 0;
+    }
+    const float *param(const Unit &u, int slot) const {
+        return c.params[(size_t)(m->chan_first[(size_t)u.p] + u.s) * (size_t)m->n_slots_per_layer + (size_t)slot];
+    }
+    bool self_loops() const { return (plan->flags & PEA_PLAN_SELF_LOOPS) != 0; }
+};
 
-    const bool sharded = plan->shard_world > 1;
-    const int n_levels = (int)m->levels.size();
-    if (sharded) PEA_REQUIRE(plan->owned_rows != nullptr || plan->n_owned == 0, PEA_ERR_ARG, "sharded plan without owned rows");
-    const int *own_rows = sharded ? plan->owned_rows : nullptr;
-    const int64_t n_own = sharded ? plan->n_owned : N;
+// buffers of level s: T_s (SAGE in the reference's order: M_s), O_s, the level's input and where its outputs go
+struct LevelIO {
+    Level &L;
+    float *T, *O;
+    const float *In;
+    int ldIn;
+    LevelOut out;
+};
+LevelIO level_io(const Fwd &f, int s) {
+    pea_model *m = f.m;
+    Level &L = m->levels[(size_t)s];
+    float *O = f.c.wsf + L.off_o;
+    return LevelIO{L,
+                   f.c.wsf + L.off_t,
+                   O,
+                   s == 0 ? f.c.x : f.c.wsf + m->levels[(size_t)s - 1].off_o,
+                   s == 0 ? (int)f.c.ldx : m->levels[(size_t)s - 1].ld_o,
+                   LevelOut{f.X, (int)f.ldX, O, L.ld_o, f.c.relu_last}};
+}
 
-    // ---- pack weights (they change every optimizer step) ----
-    auto pack_weights = [&]() -> int {
+// ---- pack weights (they change every optimizer step) ----
+int pack_weights(const Fwd &f) {
+    const pea_model *m = f.m;
+    const int kind = m->d.kind;
+    float *pack = f.pack;
     std::vector<PackJob> pj;
-        for (Level &L : m->levels) {
-            for (size_t ui = 0; ui < L.units.size(); ++ui) {
-                const Unit &u = L.units[ui];
-                PackJob j{};
-                j.kind = kind;
-                j.B = pack + u.b_off;
-                j.ldb = u.ldb;
-                j.in = u.in_w;
-                j.HF = u.HF;
-                j.F = u.F;
-                j.bias = pack + u.bias_off;
-                j.w0 = param(u, 0);
-                PEA_REQUIRE(j.w0 != nullptr, PEA_ERR_ARG, "forward: null weight pointer (channel %d step %d)", u.p, u.s);
-                if (kind == PEA_KIND_GAT) {
-                    j.w1 = param(u, 1);
-                    j.w2 = param(u, 2);
-                    j.w3 = param(u, 3);
-                    PEA_REQUIRE(j.w1 && j.w2, PEA_ERR_ARG, "forward: null att_i/att_j (channel %d step %d)", u.p, u.s);
-                    j.att_src = pack + L.att_src_off + u.t_col;
-                    j.att_dst = pack + L.att_dst_off + u.t_col;
-                } else if (kind == PEA_KIND_GCN) {
-                    j.w3 = param(u, 1);
-                } else {
-                    j.w3 = param(u, 1);
-                    j.w1 = param(u, 2);
-                    PEA_REQUIRE(j.w1 != nullptr, PEA_ERR_ARG, "forward: null lin_root.weight (channel %d step %d)", u.p, u.s);
-                    if (m->sage2) {
-                        j.kind = PEA_PACK_SAGE2;
-                        j.B2 = pack + u.root_off;
-                        j.ldb2 = u.ld_root;
-                    }
-                }
-                if (L.shared_input) {  // the last unit clears the block's padding columns
-                    if (ui + 1 == L.units.size()) {
-                        const int used = L.n_cols;
-                        j.zero_col = used - u.t_col;
-                        j.zero_n = L.n_out - used;
-                    }
-                } else {
-                    const int used = u.HF;
-                    j.zero_col = used;
-                    j.zero_n = u.ldb - used;
-                }
-                pj.push_back(j);
-            }
-        }
-        PEA_TRY(launch_pack(pj.data(), (int)pj.size(), stream));
-
-        return PEA_OK;
-    };
-
-    auto level_io = [&](int s, float *&T, float *&O, const float *&In, int64_t &ldIn) {
-        Level &L = m->levels[(size_t)s];
-        T = wsf + L.off_t;
-        O = wsf + L.off_o;
-        In = s == 0 ? x : wsf + m->levels[(size_t)s - 1].off_o;
-        ldIn = s == 0 ? ldx : m->levels[(size_t)s - 1].ld_o;
-    };
-
-    // neighbour aggregation of level s
-    auto run_groups = [&](int s, AggMode mode) -> int {
-        Level &L = m->levels[(size_t)s];
-        float *T, *O;
-        const float *In;
-        int64_t ldIn;
-        level_io(s, T, O, In, ldIn);
-        std::vector<AggGroup> gs;
-        for (const GroupPlan &g : L.groups) {
-            Relation &R = plan->rels[(size_t)g.rel];
-            const bool via_slots = sharded && s > 0;  // gather sources arrive through the exchange buffer
-            if (via_slots) PEA_REQUIRE(R.col_slot != nullptr, PEA_ERR_ARG, "relation %d has no exchange layout (pea_plan_set_sources)", g.rel);
-            AggGroup a{};
-            a.rowptr = R.rowptr;
-            a.col = via_slots ? R.col_slot : R.col;
-            a.short_rows = R.short_rows;
-            a.long_items = R.long_items;
-            a.hub_rows = R.hub_rows;
-            a.hub_first = R.hub_first;
-            a.hub_count = R.hub_count;
-            a.n_short = R.n_short;
-            // rows without incoming edges of a layer that feeds another layer are not aggregated at all: the next
-            // transform reads T_s for them (GemmJob::a1_mask)
-            const bool skip0 = mode != AGG_MEAN && !g.last && (plan->flags & PEA_PLAN_SELF_LOOPS) && !training;
-            const bool mean2 = mode == AGG_MEAN && m->sage2;  // SAGE on the GAT/GCN schedule: mean of T_s rows, added to the root term
-            // ... whose rows without incoming edges already hold their final value up to the relu (mean = 0): they are
-            // skipped too, and the next level's transforms apply the relu when they load them (GemmJob::a1_mask)
-            const bool skip0_mean = mean2 && !g.last && !training;
-            if (training && mode == AGG_GAT) {  // keep (max, denominator) per (row, head) for the backward
-                a.stats = wsf + L.off_stats + 2 * g.a_k;
-                a.ld_stats = L.ld_stats;
-            }
-            if (skip0 || skip0_mean) {
-                a.short_rows = R.short_rows + R.n_short0;
-                a.n_short = R.n_short - R.n_short0;
-            }
-            a.n_long = R.n_long;
-            a.n_hub = R.n_hub;
-            a.W = g.W;
-            a.F = g.F;
-            a.partial = partial + g.partial_off;
-            a.neg_slope = d.negative_slope;
-            {
-                const double loops = (mode != AGG_MEAN && (plan->flags & PEA_PLAN_SELF_LOOPS)) ? 1.0 : 0.0;
-                a.msgs_short = (double)R.edges_short + loops * a.n_short;
-                a.msgs_long = (double)R.edges_long + loops * R.n_direct;
-                a.idx_share = mode == AGG_MEAN ? 1.0 : (double)g.n_convs;
-                a.table_rows = via_slots ? (double)R.slots_per_rank * plan->shard_world : (double)R.src_span;
-            }
-            if (mean2) {
-                a.feat = via_slots ? wsf + g.xch_off : T + g.col;
-                a.ld_feat = via_slots ? g.xch_ld : L.ld_t;
-                a.feat_self = T + g.col;  // unused (no self loop)
-                a.ld_self = L.ld_t;
-                a.accum = 1;              // out already holds lin_root(x_i) + bias (run_gemm)
-                if (g.last) {
-                    a.out = X + g.out_col;
-                    a.ld_out = (int)ldX;
-                    a.relu = relu_last;
-                } else {
-                    a.out = O + g.out_col;
-                    a.ld_out = L.ld_o;
-                    a.relu = 1;
-                }
-            } else if (mode == AGG_MEAN) {
-                a.feat = via_slots ? wsf + g.xch_off : In + g.col;
-                a.ld_feat = via_slots ? g.xch_ld : (int)ldIn;
-                a.feat_self = In + g.col;  // unused (no self loop)
-                a.ld_self = (int)ldIn;
-                a.out = T + g.out_col;
-                a.ld_out = L.ld_t;
-            } else {
-                a.feat = via_slots ? wsf + g.xch_off : T + g.col;
-                a.ld_feat = via_slots ? g.xch_ld : L.ld_t;
-                a.feat_self = T + g.col;
-                a.ld_self = L.ld_t;
-                a.att_src = pack + L.att_src_off + g.col;
-                a.att_dst = pack + L.att_dst_off + g.col;
-                a.bias = pack + g.bias_off;
-                a.self_loop = (plan->flags & PEA_PLAN_SELF_LOOPS) ? 1 : 0;
-                if (g.last) {
-                    a.out = X + g.out_col;
-                    a.ld_out = (int)ldX;
-                    a.relu = relu_last;
-                } else {
-                    a.out = O + g.out_col;
-                    a.ld_out = L.ld_o;
-                    a.relu = 1;
-                }
-                if (mode == AGG_GCN) {
-                    const bool fc = d.gcn_deg_from_col != 0;
-                    PEA_TRY(ensure_dinv(plan, g.rel, fc, stream));
-                    a.dinv_self = fc ? R.dinv_col : R.dinv_row;
-                    a.dinv = a.dinv_self;
-                    if (via_slots) {
-                        PEA_TRY(ensure_dinv_slots(plan, g.rel, fc, stream));
-                        a.dinv = fc ? R.dinv_col_slot : R.dinv_row_slot;
-                    }
-                }
-            }
-            // LDS image of the relation's most frequent sources for the long-row kernel (item popularity is Zipf-like:
-            // a few hundred item rows serve a large share of the item -> user messages).  OFF unless PEA_HOT=1: measured
-            // slower than the plain kernel on the 25m-shaped graph, kept for the record
-            // and for graphs with heavier skew.
-            {
-                const char *hot_env = getenv("PEA_HOT");   // read per forward: tests and A/B runs flip it inside one process
-                const bool hot_on = hot_env && atoi(hot_env) != 0;
-                if (hot_on && R.n_long > 0 && a.W >= 16) {
-                    const int K = std::min(1024, (160 * 1024 - 2048) / (4 * a.W + 4)) & ~7;
-                    const HotVariant *hv = nullptr;
-                    PEA_TRY(ensure_hot(plan, g.rel, K, via_slots, stream, &hv));
-                    if (hv) {
-                        a.hot_col = hv->col;
-                        a.hot_nodes = hv->nodes;
-                        a.hot_K = hv->K;
-                        a.hot_frac = R.e_kept > 0 ? (double)hv->hot_edges / (double)R.e_kept : 0.0;
-                    }
-                }
-            }
-            gs.push_back(a);
-        }
-        for (size_t b = 0; b < gs.size(); b += kMaxAggGroups)
-            PEA_TRY(launch_aggregate(mode, gs.data() + b, (int)std::min<size_t>(kMaxAggGroups, gs.size() - b), stream));
-        return PEA_OK;
-    };
-
-    // dense transform of level s (GAT/GCN: before the aggregation; SAGE: after it)
-    auto run_gemm = [&](int s) -> int {
-        Level &L = m->levels[(size_t)s];
-        float *T, *O;
-        const float *In;
-        int64_t ldIn;
-        level_io(s, T, O, In, ldIn);
-        // SAGE on the GAT/GCN schedule: besides T_s = In W_rel^T (the gather source, built like GCN's below) every unit
-        // gets its root term  In W_root^T + bias  written where the aggregation will add the neighbour mean
-        auto push_root_jobs = [&](std::vector<GemmJob> &jobs) {
-            if (!m->sage2) return;
-            for (const Unit &u : L.units) {
-                GemmJob J{};
-                J.A1 = In + u.in_col;
-                J.lda1 = (int)ldIn;
-                J.K1 = u.in_w;
-                J.B = pack + u.root_off;
-                J.ldb = u.ld_root;
-                J.n_out = u.ld_root;
-                J.bias = pack + u.bias_off;
-                J.n_seg = 1;
-                J.seg[0].c0 = 0;
-                J.seg[0].c1 = u.HF;
-                J.seg[0].dst = u.last ? X + u.o_col : O + u.o_col;
-                J.seg[0].ld = u.last ? (int)ldX : L.ld_o;
-                J.seg[0].relu = 0;          // relu comes after the mean has been added (finish_row)
-                if (s > 0 && !training) {   // see the per-unit jobs below: edge-less rows of the previous layer, relu on load
-                    for (const Unit &up : m->levels[(size_t)s - 1].units) {
-                        if (up.p != u.p) continue;
-                        J.a1_mask = plan->rels[(size_t)up.rel].deg0;
-                        J.a1_alt = J.A1;
-                        J.lda_alt = J.lda1;
-                    }
-                }
-                if (sharded) {
-                    J.rows = own_rows;
-                    J.n_rows = n_own;
-                }
-                jobs.push_back(J);
-            }
-        };
-        if (kind == PEA_KIND_SAGE && !m->sage2) {
-            std::vector<GemmJob> jobs;
-            for (const Unit &u : L.units) {
-                GemmJob J{};
-                J.A1 = T + u.t_col;
-                J.lda1 = L.ld_t;
-                J.K1 = u.in_w;
-                J.A2 = In + u.in_col;
-                J.lda2 = (int)ldIn;
-                J.K2 = u.in_w;
-                J.B = pack + u.b_off;
-                J.ldb = u.ldb;
-                J.n_out = u.ldb;
-                J.bias = pack + u.bias_off;
-                J.n_seg = 1;
-                J.seg[0].c0 = 0;
-                J.seg[0].c1 = u.HF;
-                if (u.last) {
-                    J.seg[0].dst = X + u.o_col;
-                    J.seg[0].ld = (int)ldX;
-                    J.seg[0].relu = relu_last;
-                } else {
-                    J.seg[0].dst = O + u.o_col;
-                    J.seg[0].ld = L.ld_o;
-                    J.seg[0].relu = 1;
-                }
-                jobs.push_back(J);
-            }
-            return launch_gemm_batch(jobs.data(), (int)jobs.size(), own_rows, n_own, stream);
-        }
-        if (L.shared_input && !sharded) {
-            GemmJob J{};
-            J.A1 = In;
-            J.lda1 = (int)ldIn;
-            J.K1 = d.emb_dim;
-            J.B = pack + L.b_off;
-            J.ldb = L.ldb;
-            J.n_out = L.n_out;
-            J.n_seg = 1;
-            J.seg[0].c0 = 0;
-            J.seg[0].c1 = L.n_cols;
-            J.seg[0].dst = T;
-            J.seg[0].ld = L.ld_t;
-            J.no_narrow = 1;  // same kernel family as the per-relation jobs of a sharded plan (bit-identical results)
-            PEA_TRY(launch_gemm(J, nullptr, N, stream));
-            std::vector<GemmJob> roots;
-            push_root_jobs(roots);
-            return launch_gemm_batch(roots.data(), (int)roots.size(), nullptr, N, stream);
-        }
-        if (L.shared_input) {
-            // sharded level 0: x is replicated, so each rank transforms, per relation, exactly the rows it will
-            // read: its own rows plus that relation's source nodes (plan need_rows)
-            std::vector<GemmJob> rel_jobs;
-            size_t i = 0;
-            while (i < L.units.size()) {
-                size_t j = i;
-                const Relation &R = plan->rels[(size_t)L.units[i].rel];
-                // one job per run of channels whose relations read the same row list (same relation, or relations
-                // the host gave one shared list: own rows + the union of their few source nodes) and whose columns are
-                // contiguous: wider jobs reuse the input fragment over more column tiles
-                while (j < L.units.size()) {
-                    const Relation &Rj = plan->rels[(size_t)L.units[j].rel];
-                    const bool same_rows = L.units[j].rel == L.units[i].rel || (Rj.n_need == R.n_need && Rj.need_hash == R.need_hash);
-                    const bool contiguous = j == i || L.units[j].t_col == L.units[j - 1].t_col + L.units[j - 1].HF;
-                    if (!same_rows || !contiguous) break;
-                    ++j;
-                }
-                PEA_REQUIRE(R.need_rows != nullptr || R.n_need == 0, PEA_ERR_ARG, "relation %d has no need_rows (pea_plan_set_sources)", L.units[i].rel);
-                const int c_beg = L.units[i].t_col, c_end = L.units[j - 1].t_col + L.units[j - 1].HF;
-                GemmJob J{};
-                J.A1 = In;
-                J.lda1 = (int)ldIn;
-                J.K1 = d.emb_dim;
-                J.B = pack + L.b_off + c_beg;
-                J.ldb = L.ldb;
-                J.n_out = c_end - c_beg;
-                J.n_seg = 1;
-                J.seg[0].c0 = 0;
-                J.seg[0].c1 = c_end - c_beg;
-                J.seg[0].dst = T + c_beg;
-                J.seg[0].ld = L.ld_t;
-                J.no_narrow = 1;
-                J.rows = R.need_rows;       // one launch for all relations, each job with its own row list
-                J.n_rows = R.n_need;
-                rel_jobs.push_back(J);
-                i = j;
-            }
-            push_root_jobs(rel_jobs);
-            PEA_TRY(launch_gemm_batch(rel_jobs.data(), (int)rel_jobs.size(), nullptr, 0, stream));
-            return PEA_OK;
-        }
-        std::vector<GemmJob> jobs;
-        Level &Lp = m->levels[(size_t)s - 1];
-        for (const Unit &u : L.units) {
-            GemmJob J{};
-            J.A1 = In + u.in_col;
-            J.lda1 = (int)ldIn;
-            J.K1 = u.in_w;
-            J.B = pack + u.b_off;
-            J.ldb = u.ldb;
-            J.n_out = u.ldb;
-            J.n_seg = 1;
-            J.seg[0].c0 = 0;
-            J.seg[0].c1 = u.HF;
-            J.seg[0].dst = T + u.t_col;
-            J.seg[0].ld = L.ld_t;
-            if (m->sage2 && !training) {  // edge-less rows of the previous layer hold root + bias: relu on load
-                for (const Unit &up : Lp.units) {
-                    if (up.p != u.p) continue;
-                    J.a1_mask = plan->rels[(size_t)up.rel].deg0;
-                    J.a1_alt = J.A1;
-                    J.lda_alt = J.lda1;
-                }
-            }
-            if ((plan->flags & PEA_PLAN_SELF_LOOPS) && !training) {  // edge-less rows of the previous layer: read T_{s-1} (see run_groups)
-                for (const Unit &up : Lp.units) {
-                    if (up.p != u.p) continue;
-                    Relation &Rp = plan->rels[(size_t)up.rel];
-                    J.a1_mask = Rp.deg0;
-                    J.a1_alt = wsf + Lp.off_t + up.t_col;
-                    J.lda_alt = Lp.ld_t;
-                    J.a1_bias = pack + Lp.bias_off + up.t_col;
-                    if (kind == PEA_KIND_GCN) {
-                        const bool fc = d.gcn_deg_from_col != 0;
-                        PEA_TRY(ensure_dinv(plan, up.rel, fc, stream));
-                        J.a1_scale = fc ? Rp.dinv_col : Rp.dinv_row;
-                    }
-                }
-            }
-            jobs.push_back(J);
-        }
-        push_root_jobs(jobs);
-        return launch_gemm_batch(jobs.data(), (int)jobs.size(), own_rows, n_own, stream);
-    };
-
-    // ---- two-step inference schedule, stage 0: aggregate x per channel, then both transforms in one kernel -> T_1
-    // `part` (sharded ranks, pea_model_forward_part): PEA_PART_SOURCES = weight packing, the first-layer aggregation and the
-    // transforms of the first n_owned_first owned rows (the ones other ranks gather from: written into this rank's block of
-    // the exchange buffers as well, so the host can start the all-gather); PEA_PART_REST = the transforms of the other
-    // owned rows (nobody else reads them: they run behind the all-gather); PEA_PART_ALL = both.
-    auto run_fused2_stage0 = [&]() -> int {
-        Level &L0 = m->levels[0], &L1 = m->levels[1];
-        const int64_t n_first = (sharded && plan->n_owned_first >= 0) ? std::min<int64_t>(plan->n_owned_first, n_own) : n_own;
-        const bool do_first = part != PEA_PART_REST, do_rest = part != PEA_PART_SOURCES;
-        auto run_mlp2 = [&](const Mlp2Launch &ML) -> int {
-            if (part == PEA_PART_ALL) return launch_mlp2(ML, own_rows, n_own, stream);
-            if (do_first) return launch_mlp2(ML, own_rows, n_first, stream);
-            return launch_mlp2(ML, own_rows + n_first, n_own - n_first, stream);
-        };
-        // sharded: a channel's T_1 rows that are gather sources of layer 2 also go into the exchange buffer of its group
-        auto set_exchange = [&](Mlp2Chan &C, const Unit &u1) -> int {
-            C.x_slot = nullptr;
-            C.x_buf = nullptr;
-            C.x_ld = 0;
-            if (!sharded) return PEA_OK;
-            for (const GroupPlan &g : L1.groups) {
-                if (u1.t_col < g.col || u1.t_col >= g.col + g.W) continue;
-                const Relation &R2 = plan->rels[(size_t)g.rel];
-                PEA_REQUIRE(R2.slot_of_node != nullptr && g.xch_ld > 0, PEA_ERR_ARG,
-                            "relation %d has no exchange layout (pea_plan_set_sources)", g.rel);
-                C.x_slot = R2.slot_of_node;
-                C.x_buf = wsf + g.xch_off + (u1.t_col - g.col);
-                C.x_ld = g.xch_ld;
-                return PEA_OK;
-            }
-            PEA_REQUIRE(false, PEA_ERR_ARG, "fused schedule: channel %d has no layer-2 group", u1.p);
-        };
-        float *A0 = wsf + L0.off_t;
-        Mlp2Launch ML{};
-        ML.kind = kind;
-        ML.n = (int)L0.units.size();
-        ML.emb = d.emb_dim;
-        ML.hid = d.hidden_size;
-        ML.out = d.repr_dim;
-        ML.x = x;
-        ML.ldx = ldx;
-        ML.a0 = A0;
-        ML.ld_a0 = m->ld_a0;
-        ML.t1 = wsf + L1.off_t;
-        ML.ld_t1 = L1.ld_t;
-        ML.images = pack + m->mlp2_img_off;
-        if (training) {   // fused2_train: keep H (= O_0) for the backward
-            ML.h0 = wsf + L0.off_o;
-            ML.ld_h0 = L0.ld_o;
-            m->last_x = x;
-            m->last_ldx = ldx;
-        }
-        ML.bias1 = pack + L1.bias_off;
-        ML.att_src1 = kind == PEA_KIND_GAT ? pack + L1.att_src_off : nullptr;
-        ML.att_dst1 = kind == PEA_KIND_GAT ? pack + L1.att_dst_off : nullptr;
-        const bool fc = d.gcn_deg_from_col != 0;
-        std::vector<AggGroup> gs;
-        size_t part_off = 0;
-        if (kind == PEA_KIND_SAGE) {
-            // one mean of x rows per distinct first relation (units are sorted by relation), shared by its channels; rows
-            // without incoming edges are not visited (their mean is 0: mlp2 feeds zeros)
-            ML.r1 = X;
-            ML.ld_r1 = ldX;
-            int n_rel = 0, prev_rel = -1;
-            for (size_t ui = 0; ui < L0.units.size(); ++ui) {
-                const Unit &u = L0.units[ui];
-                const Unit *u1 = nullptr;
-                for (const Unit &c : L1.units)
-                    if (c.p == u.p) u1 = &c;
-                PEA_REQUIRE(u1 != nullptr, PEA_ERR_ARG, "fused schedule: channel %d has no second layer", u.p);
-                Relation &R = plan->rels[(size_t)u.rel];
-                if (u.rel != prev_rel) {
-                    prev_rel = u.rel;
-                    AggGroup a{};
-                    a.rowptr = R.rowptr;
-                    a.col = R.col;
-                    a.short_rows = R.short_rows + R.n_short0;
-                    a.n_short = R.n_short - R.n_short0;
-                    a.long_items = R.long_items;
-                    a.n_long = R.n_long;
-                    a.hub_rows = R.hub_rows;
-                    a.hub_first = R.hub_first;
-                    a.hub_count = R.hub_count;
-                    a.n_hub = R.n_hub;
-                    a.W = d.emb_dim;
-                    a.F = d.emb_dim;
-                    a.feat = x;
-                    a.ld_feat = (int)ldx;
-                    a.feat_self = x;
-                    a.ld_self = (int)ldx;
-                    a.out = A0 + (size_t)n_rel * d.emb_dim;
-                    a.ld_out = m->ld_a0;
-                    a.partial = partial + part_off;
-                    part_off += (size_t)slots_of(m, u.rel) * partial_record_floats(d.emb_dim, d.emb_dim);
-                    a.msgs_short = (double)R.edges_short;
-                    a.msgs_long = (double)R.edges_long;
-                    a.idx_share = 1.0;
-                    a.table_rows = (double)R.src_span;
-                    gs.push_back(a);
-                    ++n_rel;
-                }
-                Mlp2Chan &C = ML.c[ui];
-                C.w0 = param(u, 0);          // lin_rel.weight
-                C.b0 = param(u, 1);          // lin_rel.bias
-                C.w0_root = param(u, 2);     // lin_root.weight
-                C.w1 = param(*u1, 0);
-                C.b1 = param(*u1, 1);
-                C.w1_root = param(*u1, 2);
-                PEA_REQUIRE(C.w0 && C.w1 && C.w0_root && C.w1_root, PEA_ERR_ARG, "forward: null weight pointer (channel %d)", u.p);
-                C.a0_col = (n_rel - 1) * d.emb_dim;
-                C.t1_col = u1->t_col;
-                C.r1_col = u1->o_col;
-                C.h0_col = u.t_col;
-                C.deg0 = R.deg0;
-                PEA_TRY(set_exchange(C, *u1));
-            }
-            if (do_first) {
-                PEA_TRY(launch_mlp2_pack(ML, stream));
-                for (size_t b = 0; b < gs.size(); b += kMaxAggGroups)
-                    PEA_TRY(launch_aggregate(AGG_MEAN, gs.data() + b, (int)std::min<size_t>(kMaxAggGroups, gs.size() - b), stream));
-            }
-            return run_mlp2(ML);
-        }
-        for (size_t ui = 0; ui < L0.units.size(); ++ui) {
-            const Unit &u = L0.units[ui];
-            const Unit *u1 = nullptr;
-            for (const Unit &c : L1.units)
-                if (c.p == u.p) u1 = &c;
-            PEA_REQUIRE(u1 != nullptr, PEA_ERR_ARG, "fused schedule: channel %d has no second layer", u.p);
-            Relation &R = plan->rels[(size_t)u.rel];
-            Mlp2Chan &C = ML.c[ui];
-            C.w0 = param(u, 0);
-            C.w1 = param(*u1, 0);
-            PEA_REQUIRE(C.w0 && C.w1, PEA_ERR_ARG, "forward: null weight pointer (channel %d)", u.p);
-            C.ws = pack + m->mlp2_att_off + (size_t)2 * ui * d.emb_dim;
-            C.wd = C.ws + d.emb_dim;
-            C.a0_col = (int)ui * d.emb_dim;
-            C.t1_col = u1->t_col;
-            C.h0_col = u.t_col;
-            C.deg0 = R.deg0;
-            PEA_TRY(set_exchange(C, *u1));
+    for (const Level &L : m->levels) {
+        for (size_t ui = 0; ui < L.units.size(); ++ui) {
+            const Unit &u = L.units[ui];
+            PackJob j{};
+            j.kind = kind;
+            j.B = pack + u.b_off;
+            j.ldb = u.ldb;
+            j.in = u.in_w;
+            j.HF = u.HF;
+            j.F = u.F;
+            j.bias = pack + u.bias_off;
+            j.w0 = f.param(u, 0);
+            PEA_REQUIRE(j.w0 != nullptr, PEA_ERR_ARG, "forward: null weight pointer (channel %d step %d)", u.p, u.s);
             if (kind == PEA_KIND_GAT) {
-                C.att_dst0 = param(u, 1);   // att_i multiplies the TARGET row
-                C.att_src0 = param(u, 2);   // att_j multiplies the SOURCE row
-                C.b0 = param(u, 3);
-                C.att_dst1 = param(*u1, 1);
-                C.att_src1 = param(*u1, 2);
-                C.b1 = param(*u1, 3);
-                PEA_REQUIRE(C.att_src0 && C.att_dst0 && C.att_src1 && C.att_dst1, PEA_ERR_ARG,
-                            "forward: null att_i/att_j (channel %d)", u.p);
+                j.w1 = f.param(u, 1);
+                j.w2 = f.param(u, 2);
+                j.w3 = f.param(u, 3);
+                PEA_REQUIRE(j.w1 && j.w2, PEA_ERR_ARG, "forward: null att_i/att_j (channel %d step %d)", u.p, u.s);
+                j.att_src = pack + L.att_src_off + u.t_col;
+                j.att_dst = pack + L.att_dst_off + u.t_col;
+            } else if (kind == PEA_KIND_GCN) {
+                j.w3 = f.param(u, 1);
             } else {
-                C.b0 = param(u, 1);
-                C.b1 = param(*u1, 1);
-                PEA_TRY(ensure_dinv(plan, u.rel, fc, stream));
-                C.dinv = fc ? R.dinv_col : R.dinv_row;
+                j.w3 = f.param(u, 1);
+                j.w1 = f.param(u, 2);
+                PEA_REQUIRE(j.w1 != nullptr, PEA_ERR_ARG, "forward: null lin_root.weight (channel %d step %d)", u.p, u.s);
+                if (m->sage2) {
+                    j.kind = PEA_PACK_SAGE2;
+                    j.B2 = pack + u.root_off;
+                    j.ldb2 = u.ld_root;
+                }
             }
-            // the channel's first-layer aggregation of x: rows without incoming edges are not visited (mlp2 reads x)
-            AggGroup a{};
-            a.rowptr = R.rowptr;
-            a.col = R.col;
-            a.short_rows = R.short_rows + R.n_short0;
-            a.n_short = R.n_short - R.n_short0;
-            a.long_items = R.long_items;
-            a.n_long = R.n_long;
-            a.hub_rows = R.hub_rows;
-            a.hub_first = R.hub_first;
-            a.hub_count = R.hub_count;
-            a.n_hub = R.n_hub;
-            a.W = d.emb_dim;
-            a.F = d.emb_dim;
-            a.feat = x;
-            a.ld_feat = (int)ldx;
-            a.feat_self = x;
-            a.ld_self = (int)ldx;
+            if (L.shared_input) {  // the last unit clears the block's padding columns
+                if (ui + 1 == L.units.size()) {
+                    j.zero_col = L.n_cols - u.t_col;
+                    j.zero_n = L.n_out - L.n_cols;
+                }
+            } else {
+                j.zero_col = u.HF;
+                j.zero_n = u.ldb - u.HF;
+            }
+            pj.push_back(j);
+        }
+    }
+    return launch_pack(pj.data(), (int)pj.size(), f.c.stream);
+}
+
+// LDS image of the relation's most frequent sources for the long-row kernel (item popularity is Zipf-like: a few hundred
+// item rows serve a large share of the item -> user messages).  OFF unless PEA_HOT=1: measured slower than the plain
+// kernel on the 25m-shaped graph, kept for the record and for graphs with heavier skew.
+int attach_hot_sources(const Fwd &f, int rel, bool via_slots, AggGroup &a) {
+    const Relation &R = f.plan->rels[(size_t)rel];
+    if (!f.hot_on || R.n_long <= 0 || a.W < 16) return PEA_OK;
+    const int K = std::min(1024, (160 * 1024 - 2048) / (4 * a.W + 4)) & ~7;
+    const HotVariant *hv = nullptr;
+    PEA_TRY(ensure_hot(f.plan, rel, K, via_slots, f.c.stream, &hv));
+    if (hv) {
+        a.hot_col = hv->col;
+        a.hot_nodes = hv->nodes;
+        a.hot_K = hv->K;
+        a.hot_frac = R.e_kept > 0 ? (double)hv->hot_edges / (double)R.e_kept : 0.0;
+    }
+    return PEA_OK;
+}
+
+AggMode forward_mode(int kind) { return kind == PEA_KIND_GAT ? AGG_GAT : kind == PEA_KIND_GCN ? AGG_GCN : AGG_MEAN; }
+
+// neighbour aggregation of level s
+int aggregate_level(const Fwd &f, int s, AggMode mode) {
+    const pea_model *m = f.m;
+    pea_plan *plan = f.plan;
+    const pea_model_desc &d = m->d;
+    const bool training = f.c.training;
+    float *wsf = f.c.wsf;
+    const LevelIO io = level_io(f, s);
+    const Level &L = io.L;
+    const bool via_slots = f.sharded && s > 0;  // gather sources arrive through the exchange buffer
+    const bool mean2 = mode == AGG_MEAN && m->sage2;  // SAGE on the GAT/GCN schedule: mean of T_s rows, added to the root term
+    std::vector<AggGroup> gs;
+    for (const GroupPlan &g : L.groups) {
+        Relation &R = plan->rels[(size_t)g.rel];
+        if (via_slots) PEA_REQUIRE(R.col_slot != nullptr, PEA_ERR_ARG, "relation %d has no exchange layout (pea_plan_set_sources)", g.rel);
+        AggGroup a = agg_over(R);
+        // rows without incoming edges of a layer that feeds another layer are not aggregated at all: the next
+        // transform reads T_s for them (GemmJob::a1_mask)
+        const bool skip0 = mode != AGG_MEAN && !g.last && f.self_loops() && !training;
+        // ... and under mean2 such rows already hold their final value up to the relu (mean = 0): they are skipped too,
+        // and the next level's transforms apply the relu when they load them (GemmJob::a1_mask)
+        const bool skip0_mean = mean2 && !g.last && !training;
+        if (skip0 || skip0_mean) skip_edgeless(a, R);
+        if (training && mode == AGG_GAT) {  // keep (max, denominator) per (row, head) for the backward
+            a.stats = wsf + L.off_stats + 2 * g.a_k;
+            a.ld_stats = L.ld_stats;
+        }
+        a.W = g.W;
+        a.F = g.F;
+        a.partial = f.partial + g.partial_off;
+        a.neg_slope = d.negative_slope;
+        set_traffic(a, R, mode != AGG_MEAN && f.self_loops() ? 1.0 : 0.0, mode == AGG_MEAN ? 1.0 : (double)g.n_convs,
+                    table_rows(R, plan, via_slots));
+        const Dest out = io.out.at(g.last, g.out_col);
+        if (mode == AGG_MEAN && !mean2) {  // the reference's order: M_s = mean of the INPUT rows
+            a.feat = io.In + g.col;
+            a.ld_feat = io.ldIn;
+            a.out = io.T + g.out_col;
+            a.ld_out = L.ld_t;
+        } else {
+            a.feat = io.T + g.col;
+            a.ld_feat = L.ld_t;
+            a.out = out.ptr;
+            a.ld_out = out.ld;
+            a.relu = out.relu;
+        }
+        a.feat_self = a.feat;  // the row's own term (unused by the means: no self loop)
+        a.ld_self = a.ld_feat;
+        if (via_slots) gather_from_exchange(a, R, wsf + g.xch_off, g.xch_ld);
+        if (mean2) {
+            a.accum = 1;  // out already holds lin_root(x_i) + bias (root_jobs)
+        } else if (mode != AGG_MEAN) {
+            a.att_src = f.pack + L.att_src_off + g.col;
+            a.att_dst = f.pack + L.att_dst_off + g.col;
+            a.bias = f.pack + g.bias_off;
+            a.self_loop = f.self_loops() ? 1 : 0;
+            if (mode == AGG_GCN) {
+                const bool fc = d.gcn_deg_from_col != 0;
+                PEA_TRY(ensure_dinv(plan, g.rel, fc, f.c.stream));
+                a.dinv_self = fc ? R.dinv_col : R.dinv_row;
+                a.dinv = a.dinv_self;
+                if (via_slots) {
+                    PEA_TRY(ensure_dinv_slots(plan, g.rel, fc, f.c.stream));
+                    a.dinv = fc ? R.dinv_col_slot : R.dinv_row_slot;
+                }
+            }
+        }
+        PEA_TRY(attach_hot_sources(f, g.rel, via_slots, a));
+        gs.push_back(a);
+    }
+    return launch_groups(mode, gs, f.c.stream);
+}
+
+// ---- the dense transform of a level (GAT/GCN: before its aggregation; SAGE in the reference's order: after it) ----
+
+// Inference: the previous level's aggregation skipped the rows without incoming edges (aggregate_level), whose buffer
+// row still holds the value from before the aggregation.  A job that reads such rows through A1 finishes them on load:
+// relu_on_load: the row is final up to the relu (SAGE: root term + bias, mean 0).
+void relu_on_load(const Fwd &f, int s, const Unit &u, GemmJob &J) {
+    if (const Unit *up = unit_of_channel(f.m->levels[(size_t)s - 1], u.p)) {
+        J.a1_mask = f.plan->rels[(size_t)up->rel].deg0;
+        J.a1_alt = J.A1;
+        J.lda_alt = J.lda1;
+    }
+}
+// conv_on_load: the row was never written; conv(x)_i = h_i + bias (GAT: alpha_ii = 1; GCN: dinv_i^2 h_i) is read from T_{s-1}
+int conv_on_load(const Fwd &f, int s, const Unit &u, GemmJob &J) {
+    const Level &Lp = f.m->levels[(size_t)s - 1];
+    if (const Unit *up = unit_of_channel(Lp, u.p)) {
+        Relation &Rp = f.plan->rels[(size_t)up->rel];
+        J.a1_mask = Rp.deg0;
+        J.a1_alt = f.c.wsf + Lp.off_t + up->t_col;
+        J.lda_alt = Lp.ld_t;
+        J.a1_bias = f.pack + Lp.bias_off + up->t_col;
+        if (f.m->d.kind == PEA_KIND_GCN) {
+            const bool fc = f.m->d.gcn_deg_from_col != 0;
+            PEA_TRY(ensure_dinv(f.plan, up->rel, fc, f.c.stream));
+            J.a1_scale = fc ? Rp.dinv_col : Rp.dinv_row;
+        }
+    }
+    return PEA_OK;
+}
+
+// one job: columns [0, n_cols) of  A1 [., k] x B  ->  dst
+GemmJob gemm_job(const float *A1, int lda1, int k, const float *B, int ldb, int n_out, int n_cols, float *dst, int ld_dst) {
+    GemmJob J{};
+    J.A1 = A1;
+    J.lda1 = lda1;
+    J.K1 = k;
+    J.B = B;
+    J.ldb = ldb;
+    J.n_out = n_out;
+    J.n_seg = 1;
+    J.seg[0].c0 = 0;
+    J.seg[0].c1 = n_cols;
+    J.seg[0].dst = dst;
+    J.seg[0].ld = ld_dst;
+    return J;
+}
+
+// SAGE on the GAT/GCN schedule: besides T_s = In W_rel^T (the gather source, built like GCN's) every unit gets its root
+// term  In W_root^T + bias  written where the aggregation will add the neighbour mean (relu comes after that: finish_row)
+void root_jobs(const Fwd &f, int s, std::vector<GemmJob> &jobs) {
+    if (!f.m->sage2) return;
+    const LevelIO io = level_io(f, s);
+    for (const Unit &u : io.L.units) {
+        const Dest out = io.out.at(u.last, u.o_col);
+        GemmJob J = gemm_job(io.In + u.in_col, io.ldIn, u.in_w, f.pack + u.root_off, u.ld_root, u.ld_root, u.HF, out.ptr, out.ld);
+        J.bias = f.pack + u.bias_off;
+        if (s > 0 && !f.c.training) relu_on_load(f, s, u, J);
+        if (f.sharded) {
+            J.rows = f.own_rows;
+            J.n_rows = f.n_own;
+        }
+        jobs.push_back(J);
+    }
+}
+
+// SAGE in the reference's order: O_s = [M_s | In] [W_rel | W_root]^T + bias per unit
+int transform_mean_first(const Fwd &f, int s) {
+    const LevelIO io = level_io(f, s);
+    std::vector<GemmJob> jobs;
+    for (const Unit &u : io.L.units) {
+        const Dest out = io.out.at(u.last, u.o_col);
+        GemmJob J = gemm_job(io.T + u.t_col, io.L.ld_t, u.in_w, f.pack + u.b_off, u.ldb, u.ldb, u.HF, out.ptr, out.ld);
+        J.A2 = io.In + u.in_col;
+        J.lda2 = io.ldIn;
+        J.K2 = u.in_w;
+        J.bias = f.pack + u.bias_off;
+        J.seg[0].relu = out.relu;
+        jobs.push_back(J);
+    }
+    return launch_gemm_batch(jobs.data(), (int)jobs.size(), f.own_rows, f.n_own, f.c.stream);
+}
+
+// level 0 of GAT/GCN on one GPU: every channel reads x: one concatenated job
+int transform_shared(const Fwd &f) {
+    const LevelIO io = level_io(f, 0);
+    const Level &L = io.L;
+    GemmJob J = gemm_job(io.In, io.ldIn, f.m->d.emb_dim, f.pack + L.b_off, L.ldb, L.n_out, L.n_cols, io.T, L.ld_t);
+    J.no_narrow = 1;  // same kernel family as the per-relation jobs of a sharded plan (bit-identical results)
+    PEA_TRY(launch_gemm(J, nullptr, f.plan->N, f.c.stream));
+    std::vector<GemmJob> roots;
+    root_jobs(f, 0, roots);
+    return launch_gemm_batch(roots.data(), (int)roots.size(), nullptr, f.plan->N, f.c.stream);
+}
+
+// sharded level 0: x is replicated, so each rank transforms, per relation, exactly the rows it will read: its own
+// rows plus that relation's source nodes (plan need_rows)
+int transform_shared_sharded(const Fwd &f) {
+    const LevelIO io = level_io(f, 0);
+    const Level &L = io.L;
+    std::vector<GemmJob> jobs;
+    size_t i = 0;
+    while (i < L.units.size()) {
+        size_t j = i;
+        const Relation &R = f.plan->rels[(size_t)L.units[i].rel];
+        // one job per run of channels whose relations read the same row list (same relation, or relations
+        // the host gave one shared list: own rows + the union of their few source nodes) and whose columns are
+        // contiguous: wider jobs reuse the input fragment over more column tiles
+        while (j < L.units.size()) {
+            const Relation &Rj = f.plan->rels[(size_t)L.units[j].rel];
+            const bool same_rows = L.units[j].rel == L.units[i].rel || (Rj.n_need == R.n_need && Rj.need_hash == R.need_hash);
+            const bool contiguous = j == i || L.units[j].t_col == L.units[j - 1].t_col + L.units[j - 1].HF;
+            if (!same_rows || !contiguous) break;
+            ++j;
+        }
+        PEA_REQUIRE(R.need_rows != nullptr || R.n_need == 0, PEA_ERR_ARG, "relation %d has no need_rows (pea_plan_set_sources)", L.units[i].rel);
+        const int c_beg = L.units[i].t_col, c_end = L.units[j - 1].t_col + L.units[j - 1].HF;
+        GemmJob J = gemm_job(io.In, io.ldIn, f.m->d.emb_dim, f.pack + L.b_off + c_beg, L.ldb, c_end - c_beg, c_end - c_beg,
+                             io.T + c_beg, L.ld_t);
+        J.no_narrow = 1;
+        J.rows = R.need_rows;       // one launch for all relations, each job with its own row list
+        J.n_rows = R.n_need;
+        jobs.push_back(J);
+        i = j;
+    }
+    root_jobs(f, 0, jobs);
+    return launch_gemm_batch(jobs.data(), (int)jobs.size(), nullptr, 0, f.c.stream);
+}
+
+// levels >= 1 of GAT/GCN (and SAGE on their schedule): one job per unit, T_s = O_{s-1} W
+int transform_units(const Fwd &f, int s) {
+    const LevelIO io = level_io(f, s);
+    std::vector<GemmJob> jobs;
+    for (const Unit &u : io.L.units) {
+        GemmJob J = gemm_job(io.In + u.in_col, io.ldIn, u.in_w, f.pack + u.b_off, u.ldb, u.ldb, u.HF, io.T + u.t_col, io.L.ld_t);
+        if (f.m->sage2 && !f.c.training) relu_on_load(f, s, u, J);
+        if (f.self_loops() && !f.c.training) PEA_TRY(conv_on_load(f, s, u, J));
+        jobs.push_back(J);
+    }
+    root_jobs(f, s, jobs);
+    return launch_gemm_batch(jobs.data(), (int)jobs.size(), f.own_rows, f.n_own, f.c.stream);
+}
+
+int transform_level(const Fwd &f, int s) {
+    if (f.m->d.kind == PEA_KIND_SAGE && !f.m->sage2) return transform_mean_first(f, s);
+    if (!f.m->levels[(size_t)s].shared_input) return transform_units(f, s);
+    return f.sharded ? transform_shared_sharded(f) : transform_shared(f);
+}
+
+// ---- two-step schedule, stage 0: aggregate x per channel, then both transforms in one kernel -> T_1 ----
+
+// sharded: a channel's T_1 rows that are gather sources of layer 2 also go into the exchange buffer of its group
+int set_exchange(const Fwd &f, const Unit &u1, Mlp2Chan &C) {
+    C.x_slot = nullptr;
+    C.x_buf = nullptr;
+    C.x_ld = 0;
+    if (!f.sharded) return PEA_OK;
+    for (const GroupPlan &g : f.m->levels[1].groups) {
+        if (u1.t_col < g.col || u1.t_col >= g.col + g.W) continue;
+        const Relation &R2 = f.plan->rels[(size_t)g.rel];
+        PEA_REQUIRE(R2.slot_of_node != nullptr && g.xch_ld > 0, PEA_ERR_ARG,
+                    "relation %d has no exchange layout (pea_plan_set_sources)", g.rel);
+        C.x_slot = R2.slot_of_node;
+        C.x_buf = f.c.wsf + g.xch_off + (u1.t_col - g.col);
+        C.x_ld = g.xch_ld;
+        return PEA_OK;
+    }
+    PEA_REQUIRE(false, PEA_ERR_ARG, "fused schedule: channel %d has no layer-2 group", u1.p);
+}
+
+// the two layers' parameters of one channel (u: its first step, u1: its second), by kind
+int sage_channel(const Fwd &f, const Unit &u, const Unit &u1, Mlp2Chan &C) {
+    C.w0 = f.param(u, 0);          // lin_rel.weight
+    C.b0 = f.param(u, 1);          // lin_rel.bias
+    C.w0_root = f.param(u, 2);     // lin_root.weight
+    C.w1 = f.param(u1, 0);
+    C.b1 = f.param(u1, 1);
+    C.w1_root = f.param(u1, 2);
+    PEA_REQUIRE(C.w0 && C.w1 && C.w0_root && C.w1_root, PEA_ERR_ARG, "forward: null weight pointer (channel %d)", u.p);
+    C.r1_col = u1.o_col;           // the root term of layer 2 goes where its aggregation adds the neighbour mean
+    return PEA_OK;
+}
+int gat_channel(const Fwd &f, const Unit &u, const Unit &u1, Mlp2Chan &C) {
+    C.w0 = f.param(u, 0);
+    C.w1 = f.param(u1, 0);
+    PEA_REQUIRE(C.w0 && C.w1, PEA_ERR_ARG, "forward: null weight pointer (channel %d)", u.p);
+    C.att_dst0 = f.param(u, 1);   // att_i multiplies the TARGET row
+    C.att_src0 = f.param(u, 2);   // att_j multiplies the SOURCE row
+    C.b0 = f.param(u, 3);
+    C.att_dst1 = f.param(u1, 1);
+    C.att_src1 = f.param(u1, 2);
+    C.b1 = f.param(u1, 3);
+    PEA_REQUIRE(C.att_src0 && C.att_dst0 && C.att_src1 && C.att_dst1, PEA_ERR_ARG, "forward: null att_i/att_j (channel %d)", u.p);
+    return PEA_OK;
+}
+int gcn_channel(const Fwd &f, const Unit &u, const Unit &u1, Mlp2Chan &C) {
+    C.w0 = f.param(u, 0);
+    C.w1 = f.param(u1, 0);
+    PEA_REQUIRE(C.w0 && C.w1, PEA_ERR_ARG, "forward: null weight pointer (channel %d)", u.p);
+    C.b0 = f.param(u, 1);
+    C.b1 = f.param(u1, 1);
+    const bool fc = f.m->d.gcn_deg_from_col != 0;
+    PEA_TRY(ensure_dinv(f.plan, u.rel, fc, f.c.stream));
+    const Relation &R = f.plan->rels[(size_t)u.rel];
+    C.dinv = fc ? R.dinv_col : R.dinv_row;
+    return PEA_OK;
+}
+
+// `part` (sharded ranks, pea_model_forward_part): PEA_PART_SOURCES = weight packing, the first-layer aggregation and the
+// transforms of the first n_owned_first owned rows (the ones other ranks gather from: written into this rank's block of
+// the exchange buffers as well, so the host can start the all-gather); PEA_PART_REST = the transforms of the other
+// owned rows (nobody else reads them: they run behind the all-gather); PEA_PART_ALL = both.
+int two_step_stage0(const Fwd &f) {
+    pea_model *m = f.m;
+    const pea_model_desc &d = m->d;
+    const int kind = d.kind, E0 = d.emb_dim;
+    const bool sage = kind == PEA_KIND_SAGE;
+    float *wsf = f.c.wsf;
+    Level &L0 = m->levels[0], &L1 = m->levels[1];
+    float *A0 = wsf + L0.off_t;
+    Mlp2Launch ML{};
+    ML.kind = kind;
+    ML.n = (int)L0.units.size();
+    ML.emb = E0;
+    ML.hid = d.hidden_size;
+    ML.out = d.repr_dim;
+    ML.x = f.c.x;
+    ML.ldx = f.c.ldx;
+    ML.a0 = A0;
+    ML.ld_a0 = m->ld_a0;
+    ML.t1 = wsf + L1.off_t;
+    ML.ld_t1 = L1.ld_t;
+    ML.images = f.pack + m->mlp2_img_off;
+    if (f.c.training) {   // fused2_train: keep H (= O_0) for the backward
+        ML.h0 = wsf + L0.off_o;
+        ML.ld_h0 = L0.ld_o;
+        m->last_x = f.c.x;
+        m->last_ldx = f.c.ldx;
+    }
+    ML.bias1 = f.pack + L1.bias_off;
+    ML.att_src1 = kind == PEA_KIND_GAT ? f.pack + L1.att_src_off : nullptr;
+    ML.att_dst1 = kind == PEA_KIND_GAT ? f.pack + L1.att_dst_off : nullptr;
+    if (sage) {
+        ML.r1 = f.X;
+        ML.ld_r1 = f.ldX;
+    }
+    // The first layer's aggregation of x -- GAT / GCN: one group per channel; SAGE: one mean per distinct first relation
+    // (units are sorted by relation), shared by its channels.  Rows without incoming edges are not visited: mlp2 reads x
+    // for them (SAGE: their mean is 0, mlp2 feeds zeros).
+    std::vector<AggGroup> gs;
+    size_t part_off = 0;
+    int prev_rel = -1;
+    for (size_t ui = 0; ui < L0.units.size(); ++ui) {
+        const Unit &u = L0.units[ui];
+        const Unit *u1 = unit_of_channel(L1, u.p);
+        PEA_REQUIRE(u1 != nullptr, PEA_ERR_ARG, "fused schedule: channel %d has no second layer", u.p);
+        const Relation &R = f.plan->rels[(size_t)u.rel];
+        Mlp2Chan &C = ML.c[ui];
+        const bool new_group = !sage || u.rel != prev_rel;
+        prev_rel = u.rel;
+        C.a0_col = (int)(gs.size() - (new_group ? 0 : 1)) * E0;
+        C.t1_col = u1->t_col;
+        C.h0_col = u.t_col;
+        C.deg0 = R.deg0;
+        C.ws = sage ? nullptr : f.pack + m->mlp2_att_off + (size_t)2 * ui * E0;
+        C.wd = sage ? nullptr : C.ws + E0;
+        PEA_TRY(sage ? sage_channel(f, u, *u1, C) : kind == PEA_KIND_GAT ? gat_channel(f, u, *u1, C) : gcn_channel(f, u, *u1, C));
+        PEA_TRY(set_exchange(f, *u1, C));
+        if (!new_group) continue;
+        AggGroup a = agg_over(R);
+        skip_edgeless(a, R);
+        a.W = E0;
+        a.F = E0;
+        a.feat = f.c.x;
+        a.ld_feat = (int)f.c.ldx;
+        a.feat_self = f.c.x;
+        a.ld_self = (int)f.c.ldx;
+        a.out = A0 + C.a0_col;
+        a.ld_out = m->ld_a0;
+        a.partial = f.partial + part_off;
+        part_off += (size_t)slots_of(m, u.rel) * partial_record_floats(E0, E0);
+        if (!sage) {
             a.att_src = C.ws;
             a.att_dst = C.wd;
-            a.out = A0 + C.a0_col;
-            a.ld_out = m->ld_a0;
-            if (training && kind == PEA_KIND_GAT) {   // (max, denominator) per (row, channel) for the x-space backward
+            a.dinv = C.dinv;
+            a.dinv_self = C.dinv;
+            a.self_loop = 1;
+            a.neg_slope = d.negative_slope;
+            if (f.c.training && kind == PEA_KIND_GAT) {   // (max, denominator) per (row, channel) for the x-space backward
                 a.stats = wsf + L0.off_stats + 2 * (int)ui;
                 a.ld_stats = L0.ld_stats;
             }
-            a.self_loop = 1;
-            a.neg_slope = d.negative_slope;
-            a.partial = partial + part_off;
-            part_off += (size_t)slots_of(m, u.rel) * partial_record_floats(d.emb_dim, d.emb_dim);
-            a.dinv = C.dinv;
-            a.dinv_self = C.dinv;
-            a.msgs_short = (double)R.edges_short + a.n_short;
-            a.msgs_long = (double)R.edges_long + R.n_direct;
-            a.idx_share = 1.0;
-            a.table_rows = (double)R.src_span;
-            gs.push_back(a);
         }
-        if (do_first) {
-            PEA_TRY(launch_mlp2_pack(ML, stream));
-            const AggMode mode = kind == PEA_KIND_GAT ? AGG_GAT : AGG_GCN;
-            for (size_t b = 0; b < gs.size(); b += kMaxAggGroups)
-                PEA_TRY(launch_aggregate(mode, gs.data() + b, (int)std::min<size_t>(kMaxAggGroups, gs.size() - b), stream));
-        }
-        return run_mlp2(ML);
-    };
-
-    // Stage k = the work between two exchanges of gather sources (all stages back to back when not sharded):
-    //   GAT/GCN: [k == 0: pack, transform_0]  aggregate_k  [transform_{k+1}]        SAGE: [pack]  aggregate_k  transform_k
-    // After stage k < last, the gather source of level k+1 is complete on its owner rows (T_{k+1} resp. O_k).
-    const int s_beg = stage < 0 ? 0 : stage, s_end = stage < 0 ? n_levels : stage + 1;
-    PEA_REQUIRE(s_beg >= 0 && s_end <= n_levels, PEA_ERR_ARG, "forward: stage %d of %d", stage, n_levels);
-    PEA_REQUIRE(part == PEA_PART_ALL || (sharded && stage >= 0), PEA_ERR_ARG, "forward: parts are stages of a sharded plan");
-    const bool splits = m->fused2 && !training;   // only stage 0 of the two-step schedule has a part nobody else reads
-    const bool two_step = (m->fused2 && !training) || (m->fused2_train && training);
-    for (int k = s_beg; k < s_end; ++k) {
-        if (part == PEA_PART_REST && !(splits && k == 0)) continue;   // everything ran with PEA_PART_SOURCES
-        // the two-step schedule packs everything it reads in its own launch (launch_mlp2_pack)
-        if (k == 0 && !two_step) PEA_TRY(pack_weights());
-        if (two_step) {
-            if (k == 0) PEA_TRY(run_fused2_stage0());
-            else PEA_TRY(run_groups(k, kind == PEA_KIND_GAT ? AGG_GAT : kind == PEA_KIND_GCN ? AGG_GCN : AGG_MEAN));
-        } else if (kind == PEA_KIND_SAGE && !m->sage2) {
-            PEA_TRY(run_groups(k, AGG_MEAN));
-            PEA_TRY(run_gemm(k));
-        } else {
-            if (k == 0) PEA_TRY(run_gemm(0));
-            PEA_TRY(run_groups(k, kind == PEA_KIND_GAT ? AGG_GAT : kind == PEA_KIND_GCN ? AGG_GCN : AGG_MEAN));
-            if (k + 1 < n_levels) PEA_TRY(run_gemm(k + 1));
-        }
-        if (k == n_levels - 1 && abl)
-            PEA_TRY(launch_fuse_ablate(N, d.num_channels, d.repr_dim, X, ldX, m->x_col, att, d.fuse_mode, abl->tables, abl->att,
-                                       stream));
-        else if (k == n_levels - 1 && (out_repr || out_stack))
-            PEA_TRY(launch_fuse(N, d.num_channels, d.repr_dim, X, ldX, m->x_col, att, masked, d.fuse_mode, own_rows, n_own,
-                                out_repr, out_stack, stream, sel));
+        set_traffic(a, R, sage ? 0.0 : 1.0, 1.0, table_rows(R, f.plan, false));
+        gs.push_back(a);
     }
+    const int part = f.c.part;
+    if (part != PEA_PART_REST) {
+        PEA_TRY(launch_mlp2_pack(ML, f.c.stream));
+        PEA_TRY(launch_groups(forward_mode(kind), gs, f.c.stream));
+    }
+    const int64_t n_first = (f.sharded && f.plan->n_owned_first >= 0) ? std::min<int64_t>(f.plan->n_owned_first, f.n_own) : f.n_own;
+    if (part == PEA_PART_ALL) return launch_mlp2(ML, f.own_rows, f.n_own, f.c.stream);
+    if (part == PEA_PART_SOURCES) return launch_mlp2(ML, f.own_rows, n_first, f.c.stream);
+    return launch_mlp2(ML, f.own_rows + n_first, f.n_own - n_first, f.c.stream);
+}
+
+}  // namespace
+
+// Stage k = the work between two exchanges of gather sources (all stages back to back when not sharded):
+//   GAT/GCN: [k == 0: pack, transform_0]  aggregate_k  [transform_{k+1}]        SAGE: [pack]  aggregate_k  transform_k
+// After stage k < last, the gather source of level k+1 is complete on its owner rows (T_{k+1} resp. O_k).
+int model_forward(const ForwardCall &c) {
+    pea_model *m = c.model;
+    const pea_model_desc &d = m->d;
+    const int n_levels = (int)m->levels.size();
+    const Fwd f(c);
+    if (f.sharded) PEA_REQUIRE(f.plan->owned_rows != nullptr || f.plan->n_owned == 0, PEA_ERR_ARG, "sharded plan without owned rows");
+    const int s_beg = c.stage < 0 ? 0 : c.stage, s_end = c.stage < 0 ? n_levels : c.stage + 1;
+    PEA_REQUIRE(s_beg >= 0 && s_end <= n_levels, PEA_ERR_ARG, "forward: stage %d of %d", c.stage, n_levels);
+    PEA_REQUIRE(c.part == PEA_PART_ALL || (f.sharded && c.stage >= 0), PEA_ERR_ARG, "forward: parts are stages of a sharded plan");
+    const bool splits = m->fused2 && !c.training;   // only stage 0 of the two-step schedule has a part nobody else reads
+    const bool two_step = (m->fused2 && !c.training) || (m->fused2_train && c.training);
+    const bool mean_first = d.kind == PEA_KIND_SAGE && !m->sage2;
+    const AggMode mode = forward_mode(d.kind);
+    for (int k = s_beg; k < s_end; ++k) {
+        if (c.part == PEA_PART_REST && !(splits && k == 0)) continue;   // everything ran with PEA_PART_SOURCES
+        if (two_step) {   // packs everything it reads in its own launch (launch_mlp2_pack)
+            PEA_TRY(k == 0 ? two_step_stage0(f) : aggregate_level(f, k, mode));
+        } else {
+            if (k == 0) PEA_TRY(pack_weights(f));
+            if (k == 0 && !mean_first) PEA_TRY(transform_level(f, 0));
+            PEA_TRY(aggregate_level(f, k, mode));
+            if (mean_first) PEA_TRY(transform_level(f, k));
+            else if (k + 1 < n_levels) PEA_TRY(transform_level(f, k + 1));
+        }
+        if (k != n_levels - 1) continue;
+        if (c.abl)
+            PEA_TRY(launch_fuse_ablate(f.plan->N, d.num_channels, d.repr_dim, f.X, f.ldX, m->x_col, c.att, d.fuse_mode, c.abl->tables,
+                                       c.abl->att, c.stream));
+        else if (c.out_repr || c.out_stack)
+            PEA_TRY(launch_fuse(f.plan->N, d.num_channels, d.repr_dim, f.X, f.ldX, m->x_col, c.att, c.masked, d.fuse_mode, f.own_rows,
+                                f.n_own, c.out_repr, c.out_stack, c.stream, c.sel));
+    }
+    return PEA_OK;
+}
+
+// the argument checks of the forward-family entry points (common.h)
+int check_forward_args(const char *who, const pea_model *model, const float *const *params, const float *x,
+                       const void *workspace, size_t workspace_bytes, int masked, const int *stage) {
+    PEA_REQUIRE(model && params && x && workspace, PEA_ERR_ARG, "%s: null argument", who);
+    const int n_stages = (int)model->levels.size();
+    if (stage) PEA_REQUIRE(*stage >= 0 && *stage < n_stages, PEA_ERR_ARG, "%s: stage %d of %d", who, *stage, n_stages);
+    PEA_REQUIRE(workspace_bytes >= pea_model_workspace_bytes(model), PEA_ERR_NOMEM, "%s: workspace %zu < %zu bytes", who,
+                workspace_bytes, pea_model_workspace_bytes(model));
+    PEA_REQUIRE(masked >= -1 && masked < model->d.num_channels, PEA_ERR_ARG, "%s: masked channel %d", who, masked);
     return PEA_OK;
 }
 
@@ -1071,29 +1007,41 @@ float *aligned_ws(void *workspace) {
     return reinterpret_cast<float *>(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
 }
 
+// the fields every entry point of the C ABI fills the same way
+static ForwardCall model_call(pea_model *model, const float *const *params, const float *x, const float *att, int masked,
+                              void *workspace, float *out_repr, float *out_stack, void *stream) {
+    ForwardCall c;
+    c.model = model;
+    c.params = params;
+    c.x = x;
+    c.ldx = model->d.emb_dim;
+    c.att = att;
+    c.masked = masked;
+    c.wsf = aligned_ws(workspace);
+    c.out_repr = out_repr;
+    c.out_stack = out_stack;
+    c.stream = (hipStream_t)stream;
+    return c;
+}
+
 extern "C" int pea_model_forward(pea_model *model, const float *const *params_host, const float *x, const float *att,
                                  int masked_channel, void *workspace, size_t workspace_bytes, float *out_repr,
                                  float *out_stack, void *stream) {
-    PEA_REQUIRE(model && params_host && x && workspace, PEA_ERR_ARG, "forward: null argument");
-    PEA_REQUIRE(workspace_bytes >= pea_model_workspace_bytes(model), PEA_ERR_NOMEM, "forward: workspace %zu < %zu bytes",
-                workspace_bytes, pea_model_workspace_bytes(model));
-    PEA_REQUIRE(masked_channel >= -1 && masked_channel < model->d.num_channels, PEA_ERR_ARG, "forward: masked channel %d", masked_channel);
+    PEA_TRY(check_forward_args("forward", model, params_host, x, workspace, workspace_bytes, masked_channel, nullptr));
     PEA_REQUIRE(out_repr || out_stack, PEA_ERR_ARG, "forward: no output requested");
     PEA_REQUIRE(model->d.fuse_mode == PEA_FUSE_MEAN || att || !out_repr, PEA_ERR_ARG, "forward: att is required for 'att' fusion");
-    return model_forward(model, -1, params_host, x, model->d.emb_dim, att, masked_channel, aligned_ws(workspace), out_repr,
-                         out_stack, nullptr, 0, 0, (hipStream_t)stream, false);
+    return model_forward(model_call(model, params_host, x, att, masked_channel, workspace, out_repr, out_stack, stream));
 }
 
 extern "C" int pea_model_forward_train(pea_model *model, const float *const *params_host, const float *x, const float *att,
                                        int masked_channel, void *workspace, size_t workspace_bytes, float *out_repr,
                                        float *out_stack, void *stream) {
-    PEA_REQUIRE(model && params_host && x && workspace, PEA_ERR_ARG, "forward_train: null argument");
-    PEA_REQUIRE(model->backward, PEA_ERR_ARG, "forward_train: the model was created without enable_backward");
-    PEA_REQUIRE(workspace_bytes >= pea_model_workspace_bytes(model), PEA_ERR_NOMEM, "forward_train: workspace too small");
-    PEA_REQUIRE(masked_channel >= -1 && masked_channel < model->d.num_channels, PEA_ERR_ARG, "forward_train: masked channel");
+    PEA_REQUIRE(!model || model->backward, PEA_ERR_ARG, "forward_train: the model was created without enable_backward");
+    PEA_TRY(check_forward_args("forward_train", model, params_host, x, workspace, workspace_bytes, masked_channel, nullptr));
     PEA_REQUIRE(out_repr || out_stack, PEA_ERR_ARG, "forward_train: no output requested");
-    return model_forward(model, -1, params_host, x, model->d.emb_dim, att, masked_channel, aligned_ws(workspace), out_repr,
-                         out_stack, nullptr, 0, 0, (hipStream_t)stream, true);
+    ForwardCall c = model_call(model, params_host, x, att, masked_channel, workspace, out_repr, out_stack, stream);
+    c.training = true;
+    return model_forward(c);
 }
 
 extern "C" int pea_model_num_stages(const pea_model *model) { return model ? (int)model->levels.size() : 0; }
@@ -1101,26 +1049,20 @@ extern "C" int pea_model_num_stages(const pea_model *model) { return model ? (in
 extern "C" int pea_model_forward_stage(pea_model *model, int stage, const float *const *params_host, const float *x,
                                        const float *att, int masked_channel, void *workspace, size_t workspace_bytes,
                                        float *out_repr, float *out_stack, void *stream) {
-    PEA_REQUIRE(model && params_host && x && workspace, PEA_ERR_ARG, "forward_stage: null argument");
-    PEA_REQUIRE(stage >= 0 && stage < (int)model->levels.size(), PEA_ERR_ARG, "forward_stage: stage %d of %d", stage,
-                (int)model->levels.size());
-    PEA_REQUIRE(workspace_bytes >= pea_model_workspace_bytes(model), PEA_ERR_NOMEM, "forward_stage: workspace too small");
-    PEA_REQUIRE(masked_channel >= -1 && masked_channel < model->d.num_channels, PEA_ERR_ARG, "forward_stage: masked channel %d", masked_channel);
-    return model_forward(model, stage, params_host, x, model->d.emb_dim, att, masked_channel, aligned_ws(workspace), out_repr,
-                         out_stack, nullptr, 0, 0, (hipStream_t)stream, false);
+    PEA_TRY(check_forward_args("forward_stage", model, params_host, x, workspace, workspace_bytes, masked_channel, &stage));
+    ForwardCall c = model_call(model, params_host, x, att, masked_channel, workspace, out_repr, out_stack, stream);
+    c.stage = stage;
+    return model_forward(c);
 }
 
-// One PART of a stage (see run_fused2_stage0) + the optional batch-row selection in the last stage's fusion launch.
+// One PART of a stage (see two_step_stage0) + the optional batch-row selection in the last stage's fusion launch.
 extern "C" int pea_model_forward_part(pea_model *model, int stage, const pea_stage_opts *opts, const float *const *params_host,
                                       const float *x, const float *att, int masked_channel, void *workspace,
                                       size_t workspace_bytes, float *out_repr, float *out_stack, void *stream) {
-    PEA_REQUIRE(model && opts && params_host && x && workspace, PEA_ERR_ARG, "forward_part: null argument");
-    PEA_REQUIRE(stage >= 0 && stage < (int)model->levels.size(), PEA_ERR_ARG, "forward_part: stage %d of %d", stage,
-                (int)model->levels.size());
+    PEA_REQUIRE(opts, PEA_ERR_ARG, "forward_part: null argument");
     PEA_REQUIRE(opts->part == PEA_PART_ALL || opts->part == PEA_PART_SOURCES || opts->part == PEA_PART_REST, PEA_ERR_ARG,
                 "forward_part: part %d", opts->part);
-    PEA_REQUIRE(workspace_bytes >= pea_model_workspace_bytes(model), PEA_ERR_NOMEM, "forward_part: workspace too small");
-    PEA_REQUIRE(masked_channel >= -1 && masked_channel < model->d.num_channels, PEA_ERR_ARG, "forward_part: masked channel %d", masked_channel);
+    PEA_TRY(check_forward_args("forward_part", model, params_host, x, workspace, workspace_bytes, masked_channel, &stage));
     FuseSelect sel;
     const bool last = stage == (int)model->levels.size() - 1;
     if (opts->n_sel > 0) {
@@ -1135,8 +1077,11 @@ extern "C" int pea_model_forward_part(pea_model *model, int stage, const pea_sta
         sel.world = model->plan->shard_world;
         sel.tile = model->plan->shard_tile;
     }
-    return model_forward(model, stage, params_host, x, model->d.emb_dim, att, masked_channel, aligned_ws(workspace), out_repr,
-                         out_stack, nullptr, 0, 0, (hipStream_t)stream, false, opts->part, opts->n_sel > 0 ? &sel : nullptr);
+    ForwardCall c = model_call(model, params_host, x, att, masked_channel, workspace, out_repr, out_stack, stream);
+    c.stage = stage;
+    c.part = opts->part;
+    c.sel = opts->n_sel > 0 ? &sel : nullptr;
+    return model_forward(c);
 }
 
 // 1 when stage `stage` writes this rank's rows of the NEXT level's exchange buffers itself (the two-step schedule's fused
@@ -1150,14 +1095,12 @@ extern "C" int pea_model_stage_fills_exchange(const pea_model *model, int stage)
 extern "C" int pea_model_forward_stage_train(pea_model *model, int stage, const float *const *params_host, const float *x,
                                              const float *att, int masked_channel, void *workspace, size_t workspace_bytes,
                                              float *out_repr, float *out_stack, void *stream) {
-    PEA_REQUIRE(model && params_host && x && workspace, PEA_ERR_ARG, "forward_stage_train: null argument");
-    PEA_REQUIRE(model->backward, PEA_ERR_ARG, "forward_stage_train: the model was created without enable_backward");
-    PEA_REQUIRE(stage >= 0 && stage < (int)model->levels.size(), PEA_ERR_ARG, "forward_stage_train: stage %d of %d", stage,
-                (int)model->levels.size());
-    PEA_REQUIRE(workspace_bytes >= pea_model_workspace_bytes(model), PEA_ERR_NOMEM, "forward_stage_train: workspace too small");
-    PEA_REQUIRE(masked_channel >= -1 && masked_channel < model->d.num_channels, PEA_ERR_ARG, "forward_stage_train: masked channel %d", masked_channel);
-    return model_forward(model, stage, params_host, x, model->d.emb_dim, att, masked_channel, aligned_ws(workspace), out_repr,
-                         out_stack, nullptr, 0, 0, (hipStream_t)stream, true);
+    PEA_REQUIRE(!model || model->backward, PEA_ERR_ARG, "forward_stage_train: the model was created without enable_backward");
+    PEA_TRY(check_forward_args("forward_stage_train", model, params_host, x, workspace, workspace_bytes, masked_channel, &stage));
+    ForwardCall c = model_call(model, params_host, x, att, masked_channel, workspace, out_repr, out_stack, stream);
+    c.stage = stage;
+    c.training = true;
+    return model_forward(c);
 }
 
 extern "C" int pea_model_num_exchanges(const pea_model *model, int level) {
@@ -1211,8 +1154,17 @@ static int single_conv(int kind, const pea_plan *plan, int relation, int in_chan
     PEA_REQUIRE(ldx >= in_channels && ldx % 4 == 0 && ldo >= (int64_t)heads * out_channels && ldo % 4 == 0, PEA_ERR_ARG,
                 "conv: row strides (%lld, %lld) must be multiples of 4 covering the row", (long long)ldx, (long long)ldo);
     PEA_REQUIRE(workspace_bytes >= m.total_floats * sizeof(float) + 256, PEA_ERR_NOMEM, "conv: workspace too small");
-    return model_forward(&m, -1, params, x, ldx, nullptr, -1, aligned_ws(workspace), nullptr, nullptr, out, ldo, relu,
-                         (hipStream_t)stream, false);
+    ForwardCall c;
+    c.model = &m;
+    c.params = params;
+    c.x = x;
+    c.ldx = ldx;
+    c.wsf = aligned_ws(workspace);
+    c.out_x = out;
+    c.ld_out_x = ldo;
+    c.relu_last = relu;
+    c.stream = (hipStream_t)stream;
+    return model_forward(c);
 }
 
 extern "C" int pea_gat_conv(const pea_plan *plan, int relation, int in_channels, int heads, int out_channels, const float *x,

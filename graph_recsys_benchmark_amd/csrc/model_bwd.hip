@@ -7,7 +7,7 @@
 // dO_s [N, ld_o] gradient of the relu(conv) outputs, dT_s [N, ld_t] gradient of the transformed features (SAGE: of the
 // neighbour means), side_s / dad_s / das_s GAT per-head records, gpack: bias / att gradients at the SAME offsets as
 // their values in the weight pack.
-#include "model.h"
+#include "agg_build.h"
 
 namespace pea {
 namespace {
@@ -49,17 +49,359 @@ int ensure_sage_arrays(pea_plan *plan, int rel, hipStream_t stream) {
     return PEA_OK;
 }
 
-void fill_lists(AggGroup &a, const Relation &R) {
-    a.rowptr = R.rowptr;
-    a.col = R.col;
-    a.short_rows = R.short_rows;
-    a.long_items = R.long_items;
-    a.hub_rows = R.hub_rows;
-    a.hub_first = R.hub_first;
-    a.hub_count = R.hub_count;
-    a.n_short = R.n_short;
-    a.n_long = R.n_long;
-    a.n_hub = R.n_hub;
+// What every schedule of the backward of one level reads, derived once per call.
+struct Bwd {
+    pea_model *m;
+    pea_plan *plan;
+    const Level &L;
+    int level;
+    hipStream_t stream;
+    float *wsf, *pack, *gpack, *colsum_part, *partial;
+    float *T, *O, *X, *dT, *dO, *dX;
+    bool loops, sharded;
+    RowMap own;            // the rows this rank owns: what every row-wise reduction walks
+    LevelOut grads, outs;  // the level's output gradients (dX | dO_s) and outputs (X | O_s), split like the forward's outputs
+
+    Bwd(pea_model *model, int lvl, float *ws, hipStream_t s)
+        : m(model), plan(const_cast<pea_plan *>(model->plan)), L(model->levels[(size_t)lvl]), level(lvl), stream(s), wsf(ws),
+          pack(ws), gpack(ws + model->off_gpack), colsum_part(ws + model->off_colsum), partial(ws + model->off_partial),
+          T(ws + L.off_t), O(ws + L.off_o), X(ws + model->off_x), dT(ws + L.off_dt), dO(ws + L.off_do), dX(ws + model->off_dx),
+          loops((plan->flags & PEA_PLAN_SELF_LOOPS) != 0), sharded(plan->shard_world > 1),
+          own(make_rowmap(plan->N, plan->shard_tile, plan->shard_world, plan->shard_rank)),
+          grads{dX, model->ld_x, dO, L.ld_o, 0}, outs{X, model->ld_x, O, L.ld_o, 0} {}
+    // level 0 of the two-step schedule: the rows whose gradient is not identically zero, when the host listed them
+    RowMap live_rows() const {
+        return m->active0_list ? make_rowmap_list(plan->N, m->active0_list, m->active0_count, plan->N) : own;
+    }
+    int bias_gradient(const RowMap &rows, int W, const float *G, int ldg, size_t bias_off) const {
+        return launch_colsum(rows, W, W, G, ldg, nullptr, 0, 1.0f, colsum_part, gpack + bias_off, stream);
+    }
+};
+
+// The batch's row flags (pea_model_set_active_rows) as a bitmap: the gathers over the reversed relation test one flag
+// per GATHERED row, and as a bitmap the flags of all nodes fit a CU's L1 (AggGroup::row_active_bits)
+int build_active_bits(const Bwd &b, const unsigned **bits) {
+    pea_model *m = b.m;
+    const int64_t N = b.plan->N;
+    if (!m->active_bits) PEA_HIP(hipMalloc((void **)&m->active_bits, (size_t)((N + 63) / 64) * 2 * sizeof(unsigned)));
+    PEA_LAUNCH(flags_to_bits_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, b.stream, N, m->active_rows, m->active_bits);
+    PEA_HIP(hipGetLastError());
+    *bits = m->active_bits;
+    return PEA_OK;
+}
+
+// Two-step training schedule, SAGE (forward: model.hip two_step_stage0 / mlp2_sage_kernel).  Layer 2 is transform
+// first -- out = mean_j T_1[j] + R_1[i], T_1 = H lin_rel1^T, R_1 = H lin_root1^T + bias1 -- so its backward is a
+// 16-wide gather:   level 1:  d bias1 = colsum dX;  dT_1[j] = sum_{i: j -> i} dX[i] / deg_i  (reversed relation).
+// Level 0 (x space; the host mirror has run csrc/mlp2_bwd.hip: dZ_0 in dO_0, dM_0 = dZ_0 lin_rel0 per channel in the
+// dT_0 region, the root term's gradient dZ_0 lin_root0 per channel in the side region):  d bias0 = colsum dZ_0 over
+// the live rows;  per channel  dXp_j = sum_{i: j -> i} dM_0[i] / deg_i + (dZ_0 lin_root0)[j]  written over A_0 (dead
+// once the weight gradients have read the means); the host sums the channel blocks into dx.
+int sage_two_step_1(const Bwd &b) {
+    const pea_model *m = b.m;
+    const Level &L = b.L;
+    PEA_TRY(b.bias_gradient(b.own, L.n_cols, b.dX, m->ld_x, L.bias_off));
+    const unsigned *active_bits = nullptr;   // only the batch's rows of dX are non-zero: the others are not fetched (csrc/agg.hip)
+    if (m->active_rows) PEA_TRY(build_active_bits(b, &active_bits));
+    std::vector<AggGroup> gs;
+    for (const GroupPlan &g : L.groups) {
+        const Relation *Rr;
+        PEA_TRY(reverse_relation(m, g.rel, g.partial_off, g.W, g.F, &Rr, nullptr));
+        PEA_REQUIRE(g.last && g.out_col == g.col, PEA_ERR_ARG, "backward: two-step SAGE expects X in the T_1 column order");
+        PEA_TRY(ensure_sage_arrays(b.plan, g.rel, b.stream));
+        // weights: 1 / max(deg_i, 1) of the gathered (forward destination) node
+        AggGroup a = reverse_wsum(*Rr, g.W, g.W, b.dX + g.out_col, m->ld_x, b.plan->rels[(size_t)g.rel].invdeg, b.plan->ones,
+                                  b.dT + g.col, L.ld_t);
+        a.row_active = m->active_rows;
+        a.row_active_bits = active_bits;
+        a.partial = b.partial + g.partial_off;
+        set_traffic(a, *Rr, 0.0, 1.0, table_rows(*Rr, b.plan, false));
+        gs.push_back(a);
+    }
+    // with the batch's row flags: the batch-sparse walk of the backward kernels (only flagged rows are fetched)
+    return launch_groups(m->active_rows ? AGG_SUM_BWD_S : AGG_GCN, gs, b.stream);
+}
+
+int sage_two_step_0(const Bwd &b) {
+    const pea_model *m = b.m;
+    const Level &L = b.L;
+    const int E0 = m->d.emb_dim;
+    PEA_TRY(b.bias_gradient(b.live_rows(), L.n_cols, b.dO, L.ld_o, L.bias_off));
+    std::vector<AggGroup> gs;
+    size_t part_off = 0, span = 0;
+    for (size_t ui = 0; ui < L.units.size(); ++ui) {
+        const Unit &u = L.units[ui];
+        const Relation *Rr;
+        PEA_TRY(reverse_relation(m, u.rel, part_off, E0, E0, &Rr, &span));
+        PEA_TRY(ensure_sage_arrays(b.plan, u.rel, b.stream));
+        AggGroup a = reverse_wsum(*Rr, E0, E0, b.dT + ui * E0, L.ld_t, b.plan->rels[(size_t)u.rel].invdeg, b.plan->ones,
+                                  b.T + ui * E0, L.ld_t);
+        a.feat_self = b.wsf + L.off_side + ui * E0;   // the root term's gradient rides as the row's own term (weight 1)
+        a.self_loop = 1;
+        a.partial = b.partial + part_off;
+        part_off += span;
+        set_traffic(a, *Rr, 0.0, 1.0, table_rows(*Rr, b.plan, false));
+        gs.push_back(a);
+    }
+    return launch_groups(AGG_GCN, gs, b.stream);
+}
+
+// SAGE in the reference's order.  phase 0: relu masks + bias gradients; phase 1: reverse mean aggregation of dM_s
+// (written by the host into the dT_s region) -> side_s region
+int sage_level(const Bwd &b, int phase) {
+    const Level &L = b.L;
+    if (phase == 0) {
+        for (const Unit &u : L.units) {
+            const Dest G = b.grads.at(u.last, u.o_col);
+            if (!u.last) PEA_TRY(launch_relu_mask(b.own, u.HF, G.ptr, G.ld, b.outs.at(u.last, u.o_col).ptr, G.ld, b.stream));
+            PEA_TRY(b.bias_gradient(b.own, u.HF, G.ptr, G.ld, u.bias_off));
+        }
+        return PEA_OK;
+    }
+    std::vector<AggGroup> gs;
+    for (const GroupPlan &g : L.groups) {
+        const Relation *Rr;
+        PEA_TRY(reverse_relation(b.m, g.rel, g.partial_off, g.W, g.W, &Rr, nullptr));
+        PEA_TRY(ensure_sage_arrays(b.plan, g.rel, b.stream));
+        // dM columns of this group -> gradient wrt the gathered input columns, M_s column layout
+        AggGroup a = reverse_wsum(*Rr, g.W, g.W, b.dT + g.out_col, L.ld_t, b.plan->rels[(size_t)g.rel].invdeg, b.plan->ones,
+                                  b.wsf + L.off_side + g.out_col, L.ld_t);
+        a.partial = b.partial + g.partial_off;
+        gs.push_back(a);
+    }
+    return launch_groups(AGG_GCN, gs, b.stream);
+}
+
+// Two-step training schedule, first layer of GAT / GCN, in x space.  Inputs (host mirror: autograd.py): dO_0 = dZ_0, the
+// gradient of the first transform's pre-activations (relu mask applied by the gated product that wrote it); dA_0 = dZ_0 W_0
+// in the dT_0 region; A_0 (the aggregates of the rows with incoming edges) in the T_0 region; the forward's softmax
+// statistics.  Here: the bias gradient, the D pass (destination rows, gathers x rows, c_i = dA_i . A_i), the S pass (source
+// rows over the reversed relation, gathers dA_i and the side records; per channel
+// dXp_j = sum_i alpha_ij dA_i + ws d a_src_j + wd d a_dst_j  with ws / wd = W_0^T att_j / att_i) -- written over A_0, which
+// is dead once the D pass has read it.  The host then sums the channel blocks into dx and reduces d ws / d wd (d a_src /
+// d a_dst against x).
+// GCN: the aggregation is linear, its backward is the same weighted sum over the REVERSED relation, in x space:
+// dXp_j = sum_i dinv_j dinv_i dA_i + dinv_j^2 dA_j (norm of the forward relation: GCNConv)
+int two_step_0(const Bwd &b) {
+    const pea_model *m = b.m;
+    const pea_model_desc &d = m->d;
+    const Level &L = b.L;
+    PEA_REQUIRE(m->last_x != nullptr, PEA_ERR_ARG, "backward: no training forward ran on this model");
+    const float *xin = m->last_x;
+    const int ldx = (int)m->last_ldx;
+    const int E0 = d.emb_dim;
+    float *wsf = b.wsf, *A0 = b.T, *dA0 = b.dT;
+    PEA_MEMSET_ASYNC(wsf + L.off_dad, 0, (size_t)b.plan->N * (size_t)L.ld_k * sizeof(float), b.stream);
+    PEA_TRY(b.bias_gradient(b.live_rows(), L.n_cols, b.dO, L.ld_o, L.bias_off));
+    std::vector<AggGroup> gd, gs;
+    size_t part_off = 0, span = 0;
+    for (size_t ui = 0; ui < L.units.size(); ++ui) {
+        const Unit &u = L.units[ui];
+        const Relation *Rr;
+        PEA_TRY(reverse_relation(m, u.rel, part_off, E0, E0, &Rr, &span));
+        Relation &R = b.plan->rels[(size_t)u.rel];
+        float *dA = dA0 + ui * E0, *A = A0 + ui * E0;   // the channel's blocks
+        if (d.kind == PEA_KIND_GCN) {
+            const bool fc = d.gcn_deg_from_col != 0;
+            PEA_TRY(ensure_dinv(b.plan, u.rel, fc, b.stream));
+            const float *dinv = fc ? R.dinv_col : R.dinv_row;
+            AggGroup a = reverse_wsum(*Rr, E0, E0, dA, L.ld_t, dinv, dinv, A, L.ld_t);
+            a.self_loop = 1;
+            a.partial = b.partial + part_off;
+            part_off += span;
+            set_traffic(a, *Rr, 0.0, 1.0, table_rows(*Rr, b.plan, false));
+            gs.push_back(a);
+            continue;
+        }
+        AggGroup a{};
+        a.W = E0;
+        a.F = E0;
+        a.neg_slope = d.negative_slope;
+        a.self_loop = 1;
+        a.partial = b.partial + part_off;
+        part_off += span;
+        a.att_src = b.pack + m->mlp2_att_off + (size_t)2 * ui * E0;   // ws = W_0^T att_j (mlp2_pack_kernel)
+        a.att_dst = a.att_src + E0;                                  // wd = W_0^T att_i
+        a.ld_side = L.ld_side;
+        a.ld_k = L.ld_k;
+        a.ld_g = L.ld_t;
+        a.row_active = m->active0;   // D: rows with a zero gradient are not gathered for; S: their rows are not gathered
+        AggGroup D = agg_over(R, a);
+        skip_edgeless(D, R);         // edge-less rows: not visited (no side record, d a_dst = 0)
+        D.feat = xin;
+        D.ld_feat = ldx;
+        D.feat_self = xin;
+        D.ld_self = ldx;
+        D.g_self = dA;
+        D.o_self = A;
+        D.stats = wsf + L.off_stats + 2 * (int)ui;
+        D.ld_stats = L.ld_stats;
+        D.side_out = wsf + L.off_side + 4 * (int)ui;
+        D.ksum = wsf + L.off_dad + (int)ui;
+        set_traffic(D, R, 0.0, 0.0, table_rows(R, b.plan, false));
+        gd.push_back(D);
+        AggGroup S = agg_over(*Rr, a);
+        S.feat = dA;
+        S.ld_feat = L.ld_t;
+        S.feat_self = xin;
+        S.ld_self = ldx;
+        S.side = wsf + L.off_side + 4 * (int)ui;
+        S.da_dst = wsf + L.off_dad + (int)ui;
+        S.ksum = wsf + L.off_das + (int)ui;
+        S.out = A;
+        S.ld_out = L.ld_t;
+        S.deg0_self = R.deg0;
+        set_traffic(S, *Rr, 0.0, 0.0, table_rows(*Rr, b.plan, false));
+        gs.push_back(S);
+    }
+    PEA_TRY(launch_groups(AGG_GAT_BWD_D, gd, b.stream));
+    return launch_groups(d.kind == PEA_KIND_GCN ? AGG_GCN : AGG_GAT_BWD_S, gs, b.stream);
+}
+
+// relu between the steps (reference models/base.py:138): the output gradient of the channels that continue is masked
+// in place, one launch per run of groups whose columns are contiguous in dO (a 2-step model's first level: the whole row)
+int mask_continuing(const Bwd &b) {
+    const Level &L = b.L;
+    size_t ri = 0;
+    while (ri < L.groups.size()) {
+        const GroupPlan &g0 = L.groups[ri];
+        size_t rj = ri + 1;
+        int W = g0.W;
+        while (!g0.last && rj < L.groups.size() && !L.groups[rj].last && L.groups[rj].out_col == g0.out_col + W) W += L.groups[rj++].W;
+        if (!g0.last) PEA_TRY(launch_relu_mask(b.own, W, b.dO + g0.out_col, L.ld_o, b.O + g0.out_col, L.ld_o, b.stream));
+        ri = rj;
+    }
+    return PEA_OK;
+}
+
+// Gradient reductions of a GAT / GCN level, one launch per run of groups whose columns (and heads) are contiguous:
+//   d bias[c] = sum_n g[n, c];   d att_j[c] = sum_n d a_src[n, head(c)] T[n, c];   d att_i likewise with d a_dst
+int reduce_level(const Bwd &b, bool part_a, bool part_b) {
+    const Level &L = b.L;
+    size_t gi = 0;
+    while (gi < L.groups.size()) {
+        const GroupPlan &g0 = L.groups[gi];
+        size_t gj = gi + 1;
+        int W = g0.W;
+        while (gj < L.groups.size() && L.groups[gj].last == g0.last && L.groups[gj].F == g0.F &&
+               L.groups[gj].col == g0.col + W && L.groups[gj].out_col == g0.out_col + W)
+            W += L.groups[gj++].W;
+        const Dest G = b.grads.at(g0.last, g0.out_col);
+        if (part_a) PEA_TRY(b.bias_gradient(b.own, W, G.ptr, G.ld, g0.bias_off));
+        if (b.m->d.kind == PEA_KIND_GAT) {
+            const float *Tg = b.T + g0.col;
+            float *das = b.wsf + L.off_das + g0.a_k, *dad = b.wsf + L.off_dad + g0.a_k;
+            float *d_att_src = b.gpack + L.att_src_off + g0.col, *d_att_dst = b.gpack + L.att_dst_off + g0.col;
+            if (part_a && part_b) {  // one GPU: both attention-vector gradients weight T_s: one pass over it
+                PEA_TRY(launch_colsum2(b.own, W, g0.F, Tg, L.ld_t, das, dad, L.ld_k, 1.0f, b.colsum_part, d_att_src, d_att_dst, b.stream));
+            } else {
+                if (part_b) PEA_TRY(launch_colsum(b.own, W, g0.F, Tg, L.ld_t, das, L.ld_k, 1.0f, b.colsum_part, d_att_src, b.stream));
+                if (part_a) PEA_TRY(launch_colsum(b.own, W, g0.F, Tg, L.ld_t, dad, L.ld_k, 1.0f, b.colsum_part, d_att_dst, b.stream));
+            }
+        }
+        gi = gj;
+    }
+    return PEA_OK;
+}
+
+// A GAT / GCN level, level-wise.  On one GPU phase 0 runs both parts; sharded, phase 0 = part a and phase 2 = part b
+// (see pea_model_backward_level):
+//   part a: masks, D pass, reductions over what own rows already hold
+//   part b: gathers over the reversed relation, reductions of their results
+int level_wise(const Bwd &b, bool part_a, bool part_b, bool premasked) {
+    const pea_model *m = b.m;
+    const pea_model_desc &d = m->d;
+    const Level &L = b.L;
+    float *wsf = b.wsf;
+    const bool via_slots = b.sharded && b.level > 0;  // the gather sources of this level sit in the forward's exchange buffer (slot order)
+    if (d.kind == PEA_KIND_GAT && part_a) {
+        // rows whose softmax is their self loop alone are skipped by the D pass (alpha = 1, d z = 0): their d a_dst reads 0
+        PEA_MEMSET_ASYNC(wsf + L.off_dad, 0, (size_t)b.plan->N * (size_t)L.ld_k * sizeof(float), b.stream);
+    }
+    if (part_a && !premasked) PEA_TRY(mask_continuing(b));
+    // only the final outputs' gradient is known to be batch-sparse
+    // (GCN: the reverse aggregation skips the gathered rows known to be zero, csrc/agg.hip)
+    const unsigned *active_bits = nullptr;
+    if (m->active_rows && part_b && std::any_of(L.groups.begin(), L.groups.end(), [](const GroupPlan &g) { return g.last; }))
+        PEA_TRY(build_active_bits(b, &active_bits));
+    std::vector<AggGroup> gd, gsrc, gsrc_batch;
+    for (const GroupPlan &g : L.groups) {
+        const Relation *Rr;
+        PEA_TRY(reverse_relation(m, g.rel, g.partial_off, g.W, g.F, &Rr, nullptr));
+        Relation &R = b.plan->rels[(size_t)g.rel];
+        const Dest G = b.grads.at(g.last, g.out_col);
+        float *partial = b.partial + g.partial_off;  // every group its own region (sized for the relation and its reverse: slots_of)
+        if (d.kind == PEA_KIND_GCN) {
+            const bool fc = d.gcn_deg_from_col != 0;
+            PEA_TRY(ensure_dinv(b.plan, g.rel, fc, b.stream));
+            const float *dinv = fc ? R.dinv_col : R.dinv_row;
+            AggGroup a = reverse_wsum(*Rr, g.W, g.F, G.ptr, G.ld, dinv, dinv, b.dT + g.col, L.ld_t);
+            a.neg_slope = d.negative_slope;
+            a.self_loop = b.loops ? 1 : 0;
+            a.partial = partial;
+            if (g.last && active_bits) {   // only the batch's rows of dX are non-zero: the batch-sparse walk (agg_bwd.hip)
+                a.row_active = m->active_rows;
+                a.row_active_bits = active_bits;
+                if (part_b) gsrc_batch.push_back(a);
+            } else if (part_b) {
+                gsrc.push_back(a);
+            }
+            continue;
+        }
+        AggGroup a{};
+        a.W = g.W;
+        a.F = g.F;
+        a.neg_slope = d.negative_slope;
+        a.self_loop = b.loops ? 1 : 0;
+        a.partial = partial;
+        a.att_src = b.pack + L.att_src_off + g.col;
+        a.att_dst = b.pack + L.att_dst_off + g.col;
+        a.bias = b.pack + g.bias_off;
+        a.ld_side = L.ld_side;
+        a.ld_k = L.ld_k;
+        a.ld_g = G.ld;
+        a.row_active = g.last ? m->active_rows : nullptr;
+        a.row_active_bits = g.last ? active_bits : nullptr;
+        // D pass: destination rows of the forward relation, gathers T_j
+        AggGroup D = agg_over(R, a);
+        D.feat = b.T + g.col;
+        D.ld_feat = L.ld_t;
+        D.feat_self = D.feat;
+        D.ld_self = L.ld_t;
+        D.g_self = G.ptr;
+        D.o_self = b.outs.at(g.last, g.out_col).ptr;
+        D.stats = wsf + L.off_stats + 2 * g.a_k;
+        D.ld_stats = L.ld_stats;
+        D.side_out = wsf + L.off_side + 4 * g.a_k;
+        D.ksum = wsf + L.off_dad + g.a_k;
+        if (via_slots) {
+            PEA_REQUIRE(R.col_slot != nullptr && g.xch_ld > 0, PEA_ERR_ARG, "backward: relation %d has no exchange layout", g.rel);
+            gather_from_exchange(D, R, wsf + g.xch_off, g.xch_ld);
+        }
+        if (b.loops) skip_edgeless(D, R);  // edge-less rows: not visited (no side record, d a_dst = 0)
+        set_traffic(D, R, 0.0, 0.0, table_rows(R, b.plan, via_slots));   // bookkeeping for the live roofline (agg_bwd.hip: launch_bwd_g)
+        if (part_a) gd.push_back(D);
+        // S pass: source rows = destination rows of the reversed relation, gathers g_i and the side records
+        AggGroup S = agg_over(*Rr, a);
+        S.feat = G.ptr;
+        S.ld_feat = G.ld;
+        S.feat_self = b.T + g.col;
+        S.ld_self = L.ld_t;
+        S.side = wsf + L.off_side + 4 * g.a_k;
+        S.da_dst = wsf + L.off_dad + g.a_k;
+        S.ksum = wsf + L.off_das + g.a_k;
+        S.out = b.dT + g.col;
+        S.ld_out = L.ld_t;
+        S.deg0_self = b.loops ? R.deg0 : nullptr;
+        set_traffic(S, *Rr, 0.0, 0.0, table_rows(*Rr, b.plan, false));
+        if (part_b) gsrc.push_back(S);
+    }
+    // all groups of the level side by side in one set of launches per pass (the S pass of a group reads what the D pass
+    // of the same group wrote: every D launch precedes every S launch on the stream)
+    PEA_TRY(launch_groups(AGG_GAT_BWD_D, gd, b.stream));
+    PEA_TRY(launch_groups(d.kind == PEA_KIND_GCN ? AGG_GCN : AGG_GAT_BWD_S, gsrc, b.stream));
+    PEA_TRY(launch_groups(AGG_SUM_BWD_S, gsrc_batch, b.stream));   // GCN, last layer
+    return reduce_level(b, part_a, part_b);
 }
 
 }  // namespace
@@ -94,432 +436,28 @@ extern "C" int pea_model_set_active_rows(pea_model *m, const unsigned char *row_
 // the node-indexed dX / dO_s / side_s buffers), and
 // phase 2 runs the rest: GAT S pass / GCN reverse aggregation -> dT_s on own rows, att_j reduction.  (SAGE: the host
 // fills in dM_s rows between phase 0 and phase 1.)  Every row-wise reduction walks the rank's own rows (RowMap).
+// The four schedules are the ones the host mirror names (autograd.py: sage_two_step_*, sage_level, two_step_0, level).
 extern "C" int pea_model_backward_level(pea_model *m, int level, int phase, void *workspace, size_t workspace_bytes,
                                         void *stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
     PEA_REQUIRE(m && workspace && m->backward, PEA_ERR_ARG, "backward: model without enable_backward");
     const bool premasked = (phase & PEA_BWD_PREMASKED) != 0;   // the producer of this level's output gradients applied the relu mask
     phase &= ~PEA_BWD_PREMASKED;
     PEA_REQUIRE(level >= 0 && level < (int)m->levels.size() && phase >= 0 && phase <= 2, PEA_ERR_ARG, "backward: level %d phase %d", level, phase);
     PEA_REQUIRE(workspace_bytes >= pea_model_workspace_bytes(m), PEA_ERR_NOMEM, "backward: workspace too small");
-    float *wsf = aligned_ws(workspace);
-    pea_plan *plan = const_cast<pea_plan *>(m->plan);
-    const pea_model_desc &d = m->d;
-    const int64_t N = plan->N;
-    Level &L = m->levels[(size_t)level];
-    float *pack = wsf, *gpack = wsf + m->off_gpack, *colsum_part = wsf + m->off_colsum;
-    float *T = wsf + L.off_t, *O = wsf + L.off_o, *X = wsf + m->off_x;
-    float *dT = wsf + L.off_dt, *dO = wsf + L.off_do, *dX = wsf + m->off_dx;
-    float *partial = wsf + m->off_partial;
-    const bool loops = plan->flags & PEA_PLAN_SELF_LOOPS;
-    const bool sharded = plan->shard_world > 1;
-    const RowMap own = make_rowmap(N, plan->shard_tile, plan->shard_world, plan->shard_rank);
-
-    if (d.kind == PEA_KIND_SAGE && m->fused2_train) {
-        // Two-step training schedule, SAGE (forward: model.hip run_fused2_stage0 / mlp2_sage_kernel).  Layer 2 is transform
-        // first -- out = mean_j T_1[j] + R_1[i], T_1 = H lin_rel1^T, R_1 = H lin_root1^T + bias1 -- so its backward is a
-        // 16-wide gather:   level 1:  d bias1 = colsum dX;  dT_1[j] = sum_{i: j -> i} dX[i] / deg_i  (reversed relation).
-        // Level 0 (x space; the host mirror has run csrc/mlp2_bwd.hip: dZ_0 in dO_0, dM_0 = dZ_0 lin_rel0 per channel in the
-        // dT_0 region, the root term's gradient dZ_0 lin_root0 per channel in the side region):  d bias0 = colsum dZ_0 over
-        // the live rows;  per channel  dXp_j = sum_{i: j -> i} dM_0[i] / deg_i + (dZ_0 lin_root0)[j]  written over A_0 (dead
-        // once the weight gradients have read the means); the host sums the channel blocks into dx.
-        PEA_REQUIRE(phase == 0 && !sharded && level <= 1, PEA_ERR_ARG, "backward: the two-step training schedule is single-GPU, phase 0");
-        std::vector<AggGroup> gs;
-        if (level == 1) {
-            PEA_TRY(launch_colsum(own, L.n_cols, L.n_cols, dX, m->ld_x, nullptr, 0, 1.0f, colsum_part, gpack + L.bias_off, stream));
-            const unsigned *active_bits = nullptr;
-            if (m->active_rows) {   // only the batch's rows of dX are non-zero: the others are not fetched (csrc/agg.hip)
-                if (!m->active_bits) PEA_HIP(hipMalloc((void **)&m->active_bits, (size_t)((N + 63) / 64) * 2 * sizeof(unsigned)));
-                PEA_LAUNCH(flags_to_bits_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream, N, m->active_rows, m->active_bits);
-                PEA_HIP(hipGetLastError());
-                active_bits = m->active_bits;
-            }
-            for (const GroupPlan &g : L.groups) {
-                const int rr = m->reverse_of[(size_t)g.rel];
-                PEA_REQUIRE(rr >= 0, PEA_ERR_ARG, "backward: relation %d has no reversed relation in the plan", g.rel);
-                PEA_REQUIRE(g.last && g.out_col == g.col, PEA_ERR_ARG, "backward: two-step SAGE expects X in the T_1 column order");
-                Relation &R = plan->rels[(size_t)g.rel], &Rr = plan->rels[(size_t)rr];
-                PEA_REQUIRE(g.partial_off + (size_t)std::max(R.n_slots, Rr.n_slots) * partial_record_floats(g.W, g.F) <= m->partial_floats,
-                            PEA_ERR_NOMEM, "backward: hub partial buffer too small for relation %d and its reverse", g.rel);
-                PEA_TRY(ensure_sage_arrays(plan, g.rel, stream));
-                AggGroup a{};
-                fill_lists(a, Rr);
-                a.W = g.W;
-                a.F = g.W;
-                a.feat = dX + g.out_col;
-                a.ld_feat = m->ld_x;
-                a.feat_self = a.feat;
-                a.ld_self = m->ld_x;
-                a.dinv = R.invdeg;           // 1 / max(deg_i, 1) of the gathered (forward destination) node
-                a.dinv_self = plan->ones;
-                a.row_active = m->active_rows;
-                a.row_active_bits = active_bits;
-                a.out = dT + g.col;
-                a.ld_out = L.ld_t;
-                a.partial = partial + g.partial_off;
-                a.msgs_short = (double)Rr.edges_short;
-                a.msgs_long = (double)Rr.edges_long;
-                a.idx_share = 1.0;
-                a.table_rows = (double)Rr.src_span;
-                gs.push_back(a);
-            }
-        } else {
-            const int E0 = d.emb_dim;
-            const RowMap live = m->active0_list ? make_rowmap_list(N, m->active0_list, m->active0_count, N) : own;
-            PEA_TRY(launch_colsum(live, L.n_cols, L.n_cols, dO, L.ld_o, nullptr, 0, 1.0f, colsum_part, gpack + L.bias_off, stream));
-            size_t part_off = 0;
-            for (size_t ui = 0; ui < L.units.size(); ++ui) {
-                const Unit &u = L.units[ui];
-                const int rr = m->reverse_of[(size_t)u.rel];
-                PEA_REQUIRE(rr >= 0, PEA_ERR_ARG, "backward: relation %d has no reversed relation in the plan", u.rel);
-                Relation &R = plan->rels[(size_t)u.rel], &Rr = plan->rels[(size_t)rr];
-                const size_t rec = partial_record_floats(E0, E0);
-                PEA_REQUIRE(part_off + (size_t)std::max(R.n_slots, Rr.n_slots) * rec <= m->partial_floats, PEA_ERR_NOMEM,
-                            "backward: hub partial buffer too small for relation %d and its reverse", u.rel);
-                PEA_TRY(ensure_sage_arrays(plan, u.rel, stream));
-                AggGroup a{};
-                fill_lists(a, Rr);
-                a.W = E0;
-                a.F = E0;
-                a.self_loop = 1;             // the root term's gradient rides as the row's own term (weight 1)
-                a.partial = partial + part_off;
-                part_off += (size_t)std::max(R.n_slots, Rr.n_slots) * rec;
-                a.feat = dT + (size_t)ui * E0;
-                a.ld_feat = L.ld_t;
-                a.feat_self = wsf + L.off_side + (size_t)ui * E0;
-                a.ld_self = L.ld_t;
-                a.dinv = R.invdeg;
-                a.dinv_self = plan->ones;
-                a.out = T + (size_t)ui * E0;
-                a.ld_out = L.ld_t;
-                a.msgs_short = (double)Rr.edges_short;
-                a.msgs_long = (double)Rr.edges_long;
-                a.idx_share = 1.0;
-                a.table_rows = (double)Rr.src_span;
-                gs.push_back(a);
-            }
-        }
-        // level 1 with the batch's row flags: the batch-sparse walk of the backward kernels (only flagged rows are fetched)
-        const bool batch_walk = level == 1 && m->active_rows != nullptr;
-        for (size_t b = 0; b < gs.size(); b += kMaxAggGroups) {
-            const int nb = (int)std::min<size_t>(kMaxAggGroups, gs.size() - b);
-            if (batch_walk) PEA_TRY(launch_gat_backward(AGG_SUM_BWD_S, gs.data() + b, nb, stream));
-            else PEA_TRY(launch_aggregate(AGG_GCN, gs.data() + b, nb, stream));
-        }
-        return PEA_OK;
+    const Bwd b(m, level, aligned_ws(workspace), (hipStream_t)stream_);
+    const bool sage = m->d.kind == PEA_KIND_SAGE;
+    if (m->fused2_train && (sage || level == 0)) {
+        PEA_REQUIRE(phase == 0 && !b.sharded && (!sage || level <= 1), PEA_ERR_ARG,
+                    "backward: the two-step training schedule is single-GPU, phase 0");
+        return !sage ? two_step_0(b) : level == 1 ? sage_two_step_1(b) : sage_two_step_0(b);
     }
-    if (d.kind == PEA_KIND_SAGE) {
+    if (sage) {
         PEA_REQUIRE(phase <= 1, PEA_ERR_ARG, "backward: SAGE levels have phases 0 and 1");
-        if (phase == 0) {
-            for (const Unit &u : L.units) {
-                float *G = u.last ? dX + u.o_col : dO + u.o_col;
-                const float *Out = u.last ? X + u.o_col : O + u.o_col;
-                const int ldg = u.last ? m->ld_x : L.ld_o;
-                if (!u.last) PEA_TRY(launch_relu_mask(own, u.HF, G, ldg, Out, ldg, stream));
-                PEA_TRY(launch_colsum(own, u.HF, u.HF, G, ldg, nullptr, 0, 1.0f, colsum_part, gpack + u.bias_off, stream));
-            }
-            return PEA_OK;
-        }
-        std::vector<AggGroup> gs;
-        for (const GroupPlan &g : L.groups) {
-            const int rr = m->reverse_of[(size_t)g.rel];
-            PEA_REQUIRE(rr >= 0, PEA_ERR_ARG, "backward: relation %d has no reversed relation in the plan", g.rel);
-            PEA_TRY(ensure_sage_arrays(plan, g.rel, stream));
-            AggGroup a{};
-            fill_lists(a, plan->rels[(size_t)rr]);
-            a.W = g.W;
-            a.F = g.W;
-            a.feat = dT + g.out_col;  // dM columns of this group
-            a.ld_feat = L.ld_t;
-            a.feat_self = a.feat;
-            a.ld_self = L.ld_t;
-            a.dinv = plan->rels[(size_t)g.rel].invdeg;  // 1 / max(deg_i, 1) of the gathered (forward destination) node
-            a.dinv_self = plan->ones;
-            a.out = wsf + L.off_side + g.out_col;       // gradient wrt the gathered input columns, M_s column layout
-            a.ld_out = L.ld_t;
-            a.partial = partial + g.partial_off;
-            gs.push_back(a);
-        }
-        for (size_t b = 0; b < gs.size(); b += kMaxAggGroups)
-            PEA_TRY(launch_aggregate(AGG_GCN, gs.data() + b, (int)std::min<size_t>(kMaxAggGroups, gs.size() - b), stream));
-        return PEA_OK;
-    }
-
-    if (m->fused2_train && level == 0) {
-        // Two-step training schedule, first layer, in x space.  Inputs (host mirror: autograd.py): dO_0 = dZ_0, the gradient of
-        // the first transform's pre-activations (relu mask applied by the gated product that wrote it); dA_0 = dZ_0 W_0 in
-        // the dT_0 region; A_0 (the aggregates of the rows with incoming edges) in the T_0 region; the forward's softmax statistics.  Here: the bias
-        // gradient, the D pass (destination rows, gathers x rows, c_i = dA_i . A_i), the S pass (source rows over the reversed
-        // relation, gathers dA_i and the side records; per channel  dXp_j = sum_i alpha_ij dA_i + ws d a_src_j + wd d a_dst_j
-        // with ws / wd = W_0^T att_j / att_i) -- written over A_0, which is dead once the D pass has read it.  The host then
-        // sums the channel blocks into dx and reduces d ws / d wd (d a_src / d a_dst against x).
-        PEA_REQUIRE(phase == 0 && !sharded, PEA_ERR_ARG, "backward: the two-step training schedule is single-GPU, phase 0");
-        PEA_REQUIRE(m->last_x != nullptr, PEA_ERR_ARG, "backward: no training forward ran on this model");
-        const float *xin = m->last_x;
-        const int ldx = (int)m->last_ldx;
-        const int E0 = d.emb_dim;
-        float *A0 = T, *dA0 = dT;
-        PEA_MEMSET_ASYNC(wsf + L.off_dad, 0, (size_t)N * (size_t)L.ld_k * sizeof(float), stream);
-        const RowMap live = m->active0_list ? make_rowmap_list(N, m->active0_list, m->active0_count, N) : own;
-        PEA_TRY(launch_colsum(live, L.n_cols, L.n_cols, dO, L.ld_o, nullptr, 0, 1.0f, colsum_part, gpack + L.bias_off, stream));
-        std::vector<AggGroup> gd, gs;
-        size_t part_off = 0;
-        for (size_t ui = 0; ui < L.units.size(); ++ui) {
-            const Unit &u = L.units[ui];
-            const int rr = m->reverse_of[(size_t)u.rel];
-            PEA_REQUIRE(rr >= 0, PEA_ERR_ARG, "backward: relation %d has no reversed relation in the plan", u.rel);
-            Relation &R = plan->rels[(size_t)u.rel], &Rr = plan->rels[(size_t)rr];
-            const size_t rec = partial_record_floats(E0, E0);
-            PEA_REQUIRE(part_off + (size_t)std::max(R.n_slots, Rr.n_slots) * rec <= m->partial_floats, PEA_ERR_NOMEM,
-                        "backward: hub partial buffer too small for relation %d and its reverse", u.rel);
-            if (d.kind == PEA_KIND_GCN) {
-                // GCN: the aggregation is linear, its backward is the same weighted sum over the REVERSED relation, in x space:
-                // dXp_j = sum_i dinv_j dinv_i dA_i + dinv_j^2 dA_j (norm of the forward relation: GCNConv)
-                const bool fc = d.gcn_deg_from_col != 0;
-                PEA_TRY(ensure_dinv(plan, u.rel, fc, stream));
-                AggGroup a{};
-                fill_lists(a, Rr);
-                a.W = E0;
-                a.F = E0;
-                a.self_loop = 1;
-                a.partial = partial + part_off;
-                part_off += (size_t)std::max(R.n_slots, Rr.n_slots) * rec;
-                a.feat = dA0 + (size_t)ui * E0;
-                a.ld_feat = L.ld_t;
-                a.feat_self = a.feat;
-                a.ld_self = L.ld_t;
-                a.dinv = fc ? R.dinv_col : R.dinv_row;
-                a.dinv_self = a.dinv;
-                a.out = A0 + (size_t)ui * E0;
-                a.ld_out = L.ld_t;
-                a.msgs_short = (double)Rr.edges_short;
-                a.msgs_long = (double)Rr.edges_long;
-                a.idx_share = 1.0;
-                a.table_rows = (double)Rr.src_span;
-                gs.push_back(a);
-                continue;
-            }
-            AggGroup a{};
-            a.W = E0;
-            a.F = E0;
-            a.neg_slope = d.negative_slope;
-            a.self_loop = 1;
-            a.partial = partial + part_off;
-            part_off += (size_t)std::max(R.n_slots, Rr.n_slots) * rec;
-            a.att_src = pack + m->mlp2_att_off + (size_t)2 * ui * E0;   // ws = W_0^T att_j (mlp2_pack_kernel)
-            a.att_dst = a.att_src + E0;                                  // wd = W_0^T att_i
-            a.bias = nullptr;
-            a.ld_side = L.ld_side;
-            a.ld_k = L.ld_k;
-            a.ld_g = L.ld_t;
-            a.row_active = m->active0;   // D: rows with a zero gradient are not gathered for; S: their rows are not gathered
-            AggGroup D = a;
-            fill_lists(D, R);
-            D.feat = xin;
-            D.ld_feat = ldx;
-            D.feat_self = xin;
-            D.ld_self = ldx;
-            D.g_self = dA0 + (size_t)ui * E0;
-            D.o_self = A0 + (size_t)ui * E0;
-            D.stats = wsf + L.off_stats + 2 * (int)ui;
-            D.ld_stats = L.ld_stats;
-            D.side_out = wsf + L.off_side + 4 * (int)ui;
-            D.ksum = wsf + L.off_dad + (int)ui;
-            D.short_rows = R.short_rows + R.n_short0;   // edge-less rows: not visited (no side record, d a_dst = 0)
-            D.n_short = R.n_short - R.n_short0;
-            D.msgs_short = (double)R.edges_short;
-            D.msgs_long = (double)R.edges_long;
-            D.table_rows = (double)R.src_span;
-            gd.push_back(D);
-            AggGroup S = a;
-            fill_lists(S, Rr);
-            S.feat = dA0 + (size_t)ui * E0;
-            S.ld_feat = L.ld_t;
-            S.feat_self = xin;
-            S.ld_self = ldx;
-            S.side = wsf + L.off_side + 4 * (int)ui;
-            S.da_dst = wsf + L.off_dad + (int)ui;
-            S.ksum = wsf + L.off_das + (int)ui;
-            S.out = A0 + (size_t)ui * E0;
-            S.ld_out = L.ld_t;
-            S.deg0_self = R.deg0;
-            S.msgs_short = (double)Rr.edges_short;
-            S.msgs_long = (double)Rr.edges_long;
-            S.table_rows = (double)Rr.src_span;
-            gs.push_back(S);
-        }
-        for (size_t b = 0; b < gd.size(); b += kMaxAggGroups)
-            PEA_TRY(launch_gat_backward(AGG_GAT_BWD_D, gd.data() + b, (int)std::min<size_t>(kMaxAggGroups, gd.size() - b), stream));
-        for (size_t b = 0; b < gs.size(); b += kMaxAggGroups) {
-            const int nb = (int)std::min<size_t>(kMaxAggGroups, gs.size() - b);
-            if (d.kind == PEA_KIND_GCN) PEA_TRY(launch_aggregate(AGG_GCN, gs.data() + b, nb, stream));
-            else PEA_TRY(launch_gat_backward(AGG_GAT_BWD_S, gs.data() + b, nb, stream));
-        }
-        return PEA_OK;
+        return sage_level(b, phase);
     }
     PEA_REQUIRE(phase == 0 || phase == 2, PEA_ERR_ARG, "backward: GAT/GCN levels have phases 0 and (sharded) 2");
-    PEA_REQUIRE(phase == 0 || sharded, PEA_ERR_ARG, "backward: phase 2 is the second half of a SHARDED level");
-    const bool part_a = phase == 0;               // masks, D pass, reductions over what own rows already hold
-    const bool part_b = phase == 2 || !sharded;   // gathers over the reversed relation, reductions of their results
-    if (d.kind == PEA_KIND_GAT && part_a) {
-        // rows whose softmax is their self loop alone are skipped by the D pass (alpha = 1, d z = 0): their d a_dst reads 0
-        PEA_MEMSET_ASYNC(wsf + L.off_dad, 0, (size_t)N * (size_t)L.ld_k * sizeof(float), stream);
-    }
-    // relu between the steps (reference models/base.py:138): the output gradient of the channels that continue is masked
-    // in place, one launch per run of groups whose columns are contiguous in dO (a 2-step model's first level: the whole row)
-    if (part_a && !premasked) {
-        size_t ri = 0;
-        while (ri < L.groups.size()) {
-            const GroupPlan &g0 = L.groups[ri];
-            size_t rj = ri + 1;
-            int W = g0.W;
-            while (!g0.last && rj < L.groups.size() && !L.groups[rj].last && L.groups[rj].out_col == g0.out_col + W) W += L.groups[rj++].W;
-            if (!g0.last) PEA_TRY(launch_relu_mask(own, W, dO + g0.out_col, L.ld_o, O + g0.out_col, L.ld_o, stream));
-            ri = rj;
-        }
-    }
-    const unsigned *active_bits = nullptr;
-    if (m->active_rows && part_b) {   // (GCN: the reverse aggregation skips the gathered rows known to be zero, csrc/agg.hip)
-        bool any_last = false;
-        for (const GroupPlan &g : L.groups) any_last = any_last || g.last;
-        if (any_last) {   // the S pass tests one flag per gathered row: as a bitmap the flags of all nodes fit a CU's L1
-            if (!m->active_bits) PEA_HIP(hipMalloc((void **)&m->active_bits, (size_t)((N + 63) / 64) * 2 * sizeof(unsigned)));
-            PEA_LAUNCH(flags_to_bits_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream, N, m->active_rows, m->active_bits);
-            PEA_HIP(hipGetLastError());
-            active_bits = m->active_bits;
-        }
-    }
-    std::vector<AggGroup> gd, gsrc, gsrc_batch;
-    for (const GroupPlan &g : L.groups) {
-        const int rr = m->reverse_of[(size_t)g.rel];
-        PEA_REQUIRE(rr >= 0, PEA_ERR_ARG, "backward: relation %d has no reversed relation in the plan", g.rel);
-        Relation &R = plan->rels[(size_t)g.rel], &Rr = plan->rels[(size_t)rr];
-        PEA_REQUIRE(g.partial_off + (size_t)std::max(R.n_slots, Rr.n_slots) * partial_record_floats(g.W, g.F) <= m->partial_floats,
-                    PEA_ERR_NOMEM, "backward: hub partial buffer too small for relation %d and its reverse", g.rel);
-        float *G = g.last ? dX + g.out_col : dO + g.out_col;
-        const float *Out = g.last ? X + g.out_col : O + g.out_col;
-        const int ldg = g.last ? m->ld_x : L.ld_o;
-        AggGroup a{};
-        a.W = g.W;
-        a.F = g.F;
-        a.neg_slope = d.negative_slope;
-        a.self_loop = loops ? 1 : 0;
-        a.partial = partial + g.partial_off;  // every group its own region (sized for the relation and its reverse: slots_of)
-        if (d.kind == PEA_KIND_GCN) {
-            const bool fc = d.gcn_deg_from_col != 0;
-            PEA_TRY(ensure_dinv(plan, g.rel, fc, stream));
-            fill_lists(a, Rr);
-            a.feat = G;
-            a.ld_feat = ldg;
-            a.feat_self = G;
-            a.ld_self = ldg;
-            a.dinv = fc ? R.dinv_col : R.dinv_row;
-            a.dinv_self = a.dinv;
-            a.out = dT + g.col;
-            a.ld_out = L.ld_t;
-            if (g.last && active_bits) {   // only the batch's rows of dX are non-zero: the batch-sparse walk (agg_bwd.hip)
-                a.row_active = m->active_rows;
-                a.row_active_bits = active_bits;
-                if (part_b) gsrc_batch.push_back(a);
-            } else if (part_b) {
-                gsrc.push_back(a);
-            }
-            continue;
-        }
-        a.att_src = pack + L.att_src_off + g.col;
-        a.att_dst = pack + L.att_dst_off + g.col;
-        a.bias = pack + g.bias_off;
-        a.ld_side = L.ld_side;
-        a.ld_k = L.ld_k;
-        a.ld_g = ldg;
-        a.row_active = g.last ? m->active_rows : nullptr;  // only the final outputs' gradient is known to be batch-sparse
-        a.row_active_bits = g.last ? active_bits : nullptr;
-        // D pass: destination rows of the forward relation, gathers T_j
-        AggGroup D = a;
-        fill_lists(D, R);
-        D.feat = T + g.col;
-        D.ld_feat = L.ld_t;
-        D.feat_self = D.feat;
-        D.ld_self = L.ld_t;
-        D.g_self = G;
-        D.o_self = Out;
-        D.stats = wsf + L.off_stats + 2 * g.a_k;
-        D.ld_stats = L.ld_stats;
-        D.side_out = wsf + L.off_side + 4 * g.a_k;
-        D.ksum = wsf + L.off_dad + g.a_k;
-        if (sharded && level > 0) {  // the gather sources of this level sit in the forward's exchange buffer (slot order)
-            PEA_REQUIRE(R.col_slot != nullptr && g.xch_ld > 0, PEA_ERR_ARG, "backward: relation %d has no exchange layout", g.rel);
-            D.col = R.col_slot;
-            D.feat = wsf + g.xch_off;
-            D.ld_feat = g.xch_ld;
-        }
-        if (loops) {  // edge-less rows come first in the short-row list: not visited (no side record, d a_dst = 0)
-            D.short_rows = R.short_rows + R.n_short0;
-            D.n_short = R.n_short - R.n_short0;
-        }
-        D.msgs_short = (double)R.edges_short;   // bookkeeping for the live roofline (agg_bwd.hip: launch_bwd_g)
-        D.msgs_long = (double)R.edges_long;
-        D.table_rows = (sharded && level > 0) ? (double)R.slots_per_rank * plan->shard_world : (double)R.src_span;
-        if (part_a) gd.push_back(D);
-        // S pass: source rows = destination rows of the reversed relation, gathers g_i and the side records
-        AggGroup S = a;
-        fill_lists(S, Rr);
-        S.feat = G;
-        S.ld_feat = ldg;
-        S.feat_self = T + g.col;
-        S.ld_self = L.ld_t;
-        S.side = wsf + L.off_side + 4 * g.a_k;
-        S.da_dst = wsf + L.off_dad + g.a_k;
-        S.ksum = wsf + L.off_das + g.a_k;
-        S.out = dT + g.col;
-        S.ld_out = L.ld_t;
-        S.deg0_self = loops ? R.deg0 : nullptr;
-        S.msgs_short = (double)Rr.edges_short;
-        S.msgs_long = (double)Rr.edges_long;
-        S.table_rows = (double)Rr.src_span;
-        if (part_b) gsrc.push_back(S);
-    }
-    // all groups of the level side by side in one set of launches per pass (the S pass of a group reads what the D pass
-    // of the same group wrote: every D launch precedes every S launch on the stream)
-    for (size_t b = 0; b < gd.size(); b += kMaxAggGroups)
-        PEA_TRY(launch_gat_backward(AGG_GAT_BWD_D, gd.data() + b, (int)std::min<size_t>(kMaxAggGroups, gd.size() - b), stream));
-    for (size_t b = 0; b < gsrc.size(); b += kMaxAggGroups) {
-        const int nb = (int)std::min<size_t>(kMaxAggGroups, gsrc.size() - b);
-        if (d.kind == PEA_KIND_GCN) PEA_TRY(launch_aggregate(AGG_GCN, gsrc.data() + b, nb, stream));
-        else PEA_TRY(launch_gat_backward(AGG_GAT_BWD_S, gsrc.data() + b, nb, stream));
-    }
-    for (size_t b = 0; b < gsrc_batch.size(); b += kMaxAggGroups)   // GCN, last layer
-        PEA_TRY(launch_gat_backward(AGG_SUM_BWD_S, gsrc_batch.data() + b, (int)std::min<size_t>(kMaxAggGroups, gsrc_batch.size() - b), stream));
-    // Gradient reductions, one launch per run of groups whose columns (and heads) are contiguous:
-    //   d bias[c] = sum_n g[n, c];   d att_j[c] = sum_n d a_src[n, head(c)] T[n, c];   d att_i likewise with d a_dst
-    size_t gi = 0;
-    while (gi < L.groups.size()) {
-        const GroupPlan &g0 = L.groups[gi];
-        size_t gj = gi + 1;
-        int W = g0.W;
-        while (gj < L.groups.size() && L.groups[gj].last == g0.last && L.groups[gj].F == g0.F &&
-               L.groups[gj].col == g0.col + W && L.groups[gj].out_col == g0.out_col + W)
-            W += L.groups[gj++].W;
-        float *G = g0.last ? dX + g0.out_col : dO + g0.out_col;
-        const int ldg = g0.last ? m->ld_x : L.ld_o;
-        if (part_a) PEA_TRY(launch_colsum(own, W, W, G, ldg, nullptr, 0, 1.0f, colsum_part, gpack + g0.bias_off, stream));
-        if (d.kind == PEA_KIND_GAT) {
-            float *das = wsf + L.off_das + g0.a_k, *dad = wsf + L.off_dad + g0.a_k;
-            if (part_a && part_b) {  // one GPU: both attention-vector gradients weight T_s: one pass over it
-                PEA_TRY(launch_colsum2(own, W, g0.F, T + g0.col, L.ld_t, das, dad, L.ld_k, 1.0f, colsum_part,
-                                       gpack + L.att_src_off + g0.col, gpack + L.att_dst_off + g0.col, stream));
-            } else {
-                if (part_b)
-                    PEA_TRY(launch_colsum(own, W, g0.F, T + g0.col, L.ld_t, das, L.ld_k, 1.0f, colsum_part,
-                                          gpack + L.att_src_off + g0.col, stream));
-                if (part_a)
-                    PEA_TRY(launch_colsum(own, W, g0.F, T + g0.col, L.ld_t, dad, L.ld_k, 1.0f, colsum_part,
-                                          gpack + L.att_dst_off + g0.col, stream));
-            }
-        }
-        gi = gj;
-    }
-    return PEA_OK;
+    PEA_REQUIRE(phase == 0 || b.sharded, PEA_ERR_ARG, "backward: phase 2 is the second half of a SHARDED level");
+    return level_wise(b, phase == 0, phase == 2 || !b.sharded, premasked);
 }
 
 // Flat description of the schedule for the host mirror (all offsets in floats from the 256-byte aligned workspace base):
@@ -574,8 +512,7 @@ extern "C" int pea_weighted_aggregate(const pea_plan *plan, int relation, int wi
     float *partial = aligned_ws(workspace);
     std::vector<AggGroup> gs;
     for (int c = 0; c < width; c += 256) {
-        AggGroup a{};
-        fill_lists(a, R);
+        AggGroup a = agg_over(R);
         a.eid = R.eid;
         a.edge_w = edge_weight;
         a.W = std::min(256, width - c);
@@ -590,7 +527,5 @@ extern "C" int pea_weighted_aggregate(const pea_plan *plan, int relation, int wi
         partial += (size_t)R.n_slots * partial_record_floats(a.W, a.F);
         gs.push_back(a);
     }
-    for (size_t b = 0; b < gs.size(); b += kMaxAggGroups)
-        PEA_TRY(launch_aggregate(AGG_WSUM, gs.data() + b, (int)std::min<size_t>(kMaxAggGroups, gs.size() - b), (hipStream_t)stream));
-    return PEA_OK;
+    return launch_groups(AGG_WSUM, gs, (hipStream_t)stream);
 }
