@@ -9,23 +9,34 @@
 // graph, written once and read once) are never materialised, x is the only gather source of the first layer, and a
 // sharded rank transforms exactly the rows it owns (x is replicated: no source-row redundancy).
 //
-// Per wave: 32 rows.  GEMM 1 (hidden^T = W0^T x^T) keeps the data row on the lane: v_mfma_f32_32x32x2_f32 with the weights
-// as the A operand and the row's inputs as B, so the accumulator tile [hidden unit][row] has its column (the data row) on
-// the lane and feeds GEMM 2 (out^T = W1^T hidden^T) as the B operand with no lane movement and no LDS (guide: "an
-// accumulator tile as the next MFMA's operand"): step (t, v) of GEMM 2 takes register v of tile t, bias + relu applied on
-// the way, against W1 rows laid out in the k order the accumulator registers carry (unit 32 t + (v & 3) + 8 (v >> 2) + 4 half).
+// Per wave: 32 rows as two 16-row halves, both products on v_mfma_f32_16x16x4_f32.  Lane (n, g) = (lane & 15, lane >> 4).
+// GEMM 1 (hidden^T = W0^T x^T) keeps the data row on the lane: the weights are the A operand (unit 16 t + n, k slot g), the
+// row's inputs the B operand (k slot g, row n), so the accumulator tile [hidden unit][row] has its column (the data row) on
+// the lane and hidden units 16 t + 4 g + v in its 4 registers, and feeds GEMM 2 (out^T = W1^T hidden^T) as the B operand with
+// no lane movement and no LDS (guide: "an accumulator tile as the next MFMA's operand"): step (t, v) of GEMM 2 takes
+// register v of tile t, bias + relu applied on the way, against W1 rows laid out in that k order.  One LDS read of a weight
+// fragment feeds the MFMAs of both halves (two independent accumulator chains per product).  GEMM 2 issues one 16-row
+// output tile per 16 outputs (the second one behind a uniform branch outside the MFMA chains): repr_dim <= 16 takes exactly
+// one, no instruction multiplies only padding.
+// Lane (n, g) loads float4 j of its row at column 16 j + 4 g (the four lanes of a row cover 64 contiguous bytes per load).
 // fp32 products, fp32 accumulation (f32-input MFMA = an fmaf chain in k order): exact fp32 like the level-wise kernels.
+// Summation order, the same for every row in every instantiation (TRAIN or not, row list or not, any rank):
+//     hidden unit i:  for j in [0, emb / 16)  for e in [0, 4)  for g in [0, 4):  += W0(i, 16 j + 4 g + e) * in[16 j + 4 g + e]
+//     output o:       for t in [0, hid / 16)  for v in [0, 4)  for g in [0, 4):  += W1(o, 16 t + 4 g + v) * h[16 t + 4 g + v]
+// (mlp2_sage_kernel keeps v_mfma_f32_32x32x2_f32: at repr_dim = 16 its second product fills all 32 output rows.)
 #include "common.h"
 
 namespace pea {
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ float4 ld4m(const float *p) { return *reinterpret_cast<const float4 *>(p); }
 
 
-// image of one channel, in floats: [Wt0: HT * ET * 64 * 4][Wt1: HT * 4 * 64 * 4][b0p: 2 * HT * 16]
+// image of one channel, in floats: [Wt0: HT * ET * 64 * 4][Wt1: HT * 4 * 64 * 4][b0p: 2 * HT * 16]  (ET = K / 8, HT = hidden / 32;
+// GAT / GCN: Wt0 = hidden / 16 x emb / 16 fragments of 64 lanes x 4, Wt1 = 2 output tiles x hidden / 16 fragments, b0 natural)
 __host__ __device__ inline int mlp2_image_floats(int ET, int HT) { return HT * ET * 256 + HT * 1024 + 2 * HT * 16; }
 
 // gridDim.x / n blocks per channel (the launch is pure latency: 2048 image elements per block): the LDS images of its two
@@ -64,23 +75,22 @@ __global__ __launch_bounds__(256) void mlp2_pack_kernel(const Mlp2Launch L) {
     float *img = L.images + (size_t)chan * mlp2_image_floats(ET, HT);
     float *wt0 = img, *wt1 = img + HT * ET * 256, *b0p = wt1 + HT * 1024;
     const bool gat = L.kind == PEA_KIND_GAT;
-    // W0(i, k): hidden unit i from input k.  GAT lin.weight is [HID, EMB] (out-major), GCN weight is [EMB, HID]
-    for (int idx = t0; idx < HT * ET * 256; idx += ts) {
-        const int e = idx & 3, lane = (idx >> 2) & 63, q = (idx >> 8) % ET, t = (idx >> 8) / ET;
-        const int i = 32 * t + (lane & 31), k = 4 * (2 * q + (lane >> 5)) + e;
+    // W0(i, k): hidden unit i from input k.  GAT lin.weight is [HID, EMB] (out-major), GCN weight is [EMB, HID].
+    // Fragment (t, j), lane (n, g), element e: unit 16 t + n, input 16 j + 4 g + e (the column the lane loads, mlp2_load)
+    const int EJ = EMB / 16, HJ = HID / 16;
+    for (int idx = t0; idx < HJ * EJ * 256; idx += ts) {
+        const int e = idx & 3, lane = (idx >> 2) & 63, j = (idx >> 8) % EJ, t = (idx >> 8) / EJ;
+        const int i = 16 * t + (lane & 15), k = 16 * j + 4 * (lane >> 4) + e;
         wt0[idx] = gat ? C.w0[(size_t)i * EMB + k] : C.w0[(size_t)k * HID + i];
     }
-    // W1(j, i): output j from hidden unit i, rows >= OUT are zero.  GAT: [OUT, HID]; GCN: [HID, OUT]
-    for (int idx = t0; idx < HT * 1024; idx += ts) {
-        const int e = idx & 3, lane = (idx >> 2) & 63, g = (idx >> 8) & 3, t = idx >> 10;
-        const int j = lane & 31, i = 32 * t + 8 * g + 4 * (lane >> 5) + e;
-        wt1[idx] = j < OUT ? (gat ? C.w1[(size_t)j * HID + i] : C.w1[(size_t)i * OUT + j]) : 0.f;
+    // W1(o, i): output o from hidden unit i, rows >= OUT are zero.  GAT: [OUT, HID]; GCN: [HID, OUT].
+    // Fragment (output tile u, t), lane (n, g), element v: output 16 u + n, unit 16 t + 4 g + v (register v of hidden tile t)
+    for (int idx = t0; idx < 2 * HJ * 256; idx += ts) {
+        const int v = idx & 3, lane = (idx >> 2) & 63, t = (idx >> 8) % HJ, u = (idx >> 8) / HJ;
+        const int o = 16 * u + (lane & 15), i = 16 * t + 4 * (lane >> 4) + v;
+        wt1[idx] = o < OUT ? (gat ? C.w1[(size_t)o * HID + i] : C.w1[(size_t)i * OUT + o]) : 0.f;
     }
-    for (int idx = t0; idx < 2 * HT * 16; idx += ts) {
-        const int v = idx & 15, t = (idx >> 4) % HT, half = (idx >> 4) / HT;
-        const int i = 32 * t + (v & 3) + 8 * (v >> 2) + 4 * half;
-        b0p[idx] = C.b0 ? C.b0[i] : 0.f;
-    }
+    for (int i = t0; i < HID; i += ts) b0p[i] = C.b0 ? C.b0[i] : 0.f;
     for (int o = t0; o < OUT; o += ts) {
         L.bias1[C.t1_col + o] = C.b1 ? C.b1[o] : 0.f;
         if (gat) {
@@ -116,38 +126,184 @@ struct Mlp2Cfg {
 // NEXT item are loaded before the current item's MFMA chains start
 template <int ET>
 struct Mlp2In {
-    float4 xa[ET];
-    int64_t row;
-    bool valid;
+    float4 xa[2][ET / 2];   // [16-row half][float4 j]: columns 16 j + 4 g .. + 3 of row 16 half + n
+    float sc[2];            // what mlp2_take multiplies the loaded row by
+    int row[2];             // node ids fit an int (the row list and the edge index are int)
+    bool valid[2];
 };
 
 template <int ET>
-__device__ __forceinline__ void mlp2_load(const Mlp2Launch &L, const int *rows, int64_t n_rows, int64_t tile, int ch, int r32,
-                                          int half, Mlp2In<ET> &in) {
+__device__ __forceinline__ void mlp2_load(const Mlp2Launch &L, const int *rows, int64_t n_rows, int64_t tile, int ch, int n16,
+                                          int g, Mlp2In<ET> &in) {
     const Mlp2Chan &C = L.c[ch];
-    const int64_t q0 = tile * 32 + r32;
-    in.valid = q0 < n_rows;
-    in.row = in.valid ? (rows ? (int64_t)rows[q0] : q0) : 0;
-    // input row: the first layer's aggregate, or x itself where the row has no incoming edge there
-    const bool lone = C.deg0[in.row] != 0;
-    const float *src = lone ? L.x + in.row * L.ldx : L.a0 + in.row * L.ld_a0 + C.a0_col;
-    float sc = 1.f;
-    if (C.dinv && lone) {   // GCN: the self loop alone, norm = dinv_i^2
-        const float di = C.dinv[in.row];
-        sc = di * di;
-    }
-    if (!in.valid) sc = 0.f;
+    const float *src[2];
+    // both halves' row lookups first, then all row loads: the two dependent chains (row id -> deg0 -> row) overlap
 #pragma unroll
-    for (int q = 0; q < ET; ++q) {
-        const float4 t4 = ld4m(src + 4 * (2 * q + half));
-        in.xa[q] = make_float4(sc * t4.x, sc * t4.y, sc * t4.z, sc * t4.w);
+    for (int h = 0; h < 2; ++h) {
+        const int64_t q0 = tile * 32 + 16 * h + n16;
+        in.valid[h] = q0 < n_rows;
+        in.row[h] = in.valid[h] ? (rows ? rows[q0] : (int)q0) : 0;
+    }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        // input row: the first layer's aggregate, or x itself where the row has no incoming edge there
+        const bool lone = C.deg0[in.row[h]] != 0;
+        src[h] = (lone ? L.x + (int64_t)in.row[h] * L.ldx : L.a0 + (int64_t)in.row[h] * L.ld_a0 + C.a0_col) + 4 * g;
+        in.sc[h] = 1.f;
+        if (C.dinv) {   // GCN: the self loop alone, norm = dinv_i^2
+            const float di = C.dinv[in.row[h]];
+            in.sc[h] = lone ? di * di : 1.f;
+        }
+        if (!in.valid[h]) in.sc[h] = 0.f;
+    }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+#pragma unroll
+        for (int j = 0; j < ET / 2; ++j) in.xa[h][j] = ld4m(src[h] + 16 * j);
+    }
+}
+
+// the loaded item becomes the current one: the scale is applied here, after the MFMA chains the loads travelled behind (a
+// multiply next to the loads would wait for them before the chains start)
+template <int ET>
+__device__ __forceinline__ void mlp2_take(Mlp2In<ET> &cur, const Mlp2In<ET> &in) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        cur.row[h] = in.row[h];
+        cur.valid[h] = in.valid[h];
+#pragma unroll
+        for (int j = 0; j < ET / 2; ++j) {
+            const float4 t4 = in.xa[h][j];
+            cur.xa[h][j] = make_float4(in.sc[h] * t4.x, in.sc[h] * t4.y, in.sc[h] * t4.z, in.sc[h] * t4.w);
+        }
+    }
+}
+
+// GEMM 1 for the 64 hidden units of tiles t0 .. t0 + 3, both halves, bias + relu applied in place: register v of acc[h][t] =
+// hidden unit 16 (t0 + t) + 4 g + v of row 16 h + n (training keeps the tile: one float4 store in natural unit order)
+template <int ET, int HT, bool TRAIN>
+__device__ __forceinline__ void mlp2_hidden(const Mlp2Launch &L, const Mlp2Chan &C, const float *img, const Mlp2In<ET> &cur, int lane,
+                                            int t0, f32x4 (&acc)[2][4]) {
+    constexpr int EJ = ET / 2;
+    const int g = lane >> 4;
+    const float *wt0 = img, *b0p = img + HT * ET * 256 + HT * 1024;
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int t = 0; t < 4; ++t) acc[h][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < EJ; ++j) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {   // one LDS read of the weight fragment, two independent chains
+            const float4 w = ld4m(wt0 + ((size_t)((t0 + t) * EJ + j) * 64 + lane) * 4);
+            acc[0][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.x, cur.xa[0][j].x, acc[0][t], 0, 0, 0);
+            acc[1][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.x, cur.xa[1][j].x, acc[1][t], 0, 0, 0);
+            acc[0][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.y, cur.xa[0][j].y, acc[0][t], 0, 0, 0);
+            acc[1][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.y, cur.xa[1][j].y, acc[1][t], 0, 0, 0);
+            acc[0][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.z, cur.xa[0][j].z, acc[0][t], 0, 0, 0);
+            acc[1][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.z, cur.xa[1][j].z, acc[1][t], 0, 0, 0);
+            acc[0][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.w, cur.xa[0][j].w, acc[0][t], 0, 0, 0);
+            acc[1][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.w, cur.xa[1][j].w, acc[1][t], 0, 0, 0);
+        }
+    }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        float *hrow = (TRAIN && cur.valid[h]) ? L.h0 + (int64_t)cur.row[h] * L.ld_h0 + C.h0_col + 16 * t0 + 4 * g : nullptr;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const float4 b = ld4m(b0p + 16 * (t0 + t) + 4 * g);
+            acc[h][t] = f32x4{fmaxf(acc[h][t][0] + b.x, 0.f), fmaxf(acc[h][t][1] + b.y, 0.f), fmaxf(acc[h][t][2] + b.z, 0.f),
+                              fmaxf(acc[h][t][3] + b.w, 0.f)};
+            if (TRAIN && hrow)
+                *reinterpret_cast<float4 *>(hrow + 16 * t) = make_float4(acc[h][t][0], acc[h][t][1], acc[h][t][2], acc[h][t][3]);
+        }
+    }
+}
+
+// GEMM 2, the steps of 4 hidden tiles into one 16-row output tile; wf = the W1 fragments of (output tile, first hidden tile)
+__device__ __forceinline__ void mlp2_out_steps(const float *wf, int lane, const f32x4 (&acc)[2][4], f32x4 (&out)[2]) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const float4 w = ld4m(wf + ((size_t)t * 64 + lane) * 4);
+        out[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.x, acc[0][t][0], out[0], 0, 0, 0);
+        out[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.x, acc[1][t][0], out[1], 0, 0, 0);
+        out[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.y, acc[0][t][1], out[0], 0, 0, 0);
+        out[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.y, acc[1][t][1], out[1], 0, 0, 0);
+        out[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.z, acc[0][t][2], out[0], 0, 0, 0);
+        out[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.z, acc[1][t][2], out[1], 0, 0, 0);
+        out[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.w, acc[0][t][3], out[0], 0, 0, 0);
+        out[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.w, acc[1][t][3], out[1], 0, 0, 0);
+    }
+}
+
+// where lane (n, g) stores its outputs 4 g .. + 3 of row 16 h + n: the T_1 row and, sharded, the exchange row of a row that
+// layer 2 gathers (null where there is nothing to store)
+struct Mlp2Dst {
+    float *t1[2], *x[2];
+};
+
+template <int ET>
+__device__ __forceinline__ Mlp2Dst mlp2_dst(const Mlp2Launch &L, const Mlp2Chan &C, const Mlp2In<ET> &cur, int g) {
+    Mlp2Dst d;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        d.t1[h] = cur.valid[h] ? L.t1 + (int64_t)cur.row[h] * L.ld_t1 + C.t1_col + 4 * g : nullptr;
+        const int slot = (cur.valid[h] && C.x_slot) ? C.x_slot[cur.row[h]] : -1;
+        d.x[h] = slot >= 0 ? C.x_buf + (int64_t)slot * C.x_ld + 4 * g : nullptr;
+    }
+    return d;
+}
+
+// output tile u: registers 0 .. 3 of lane (n, g) = outputs 16 u + 4 g .. + 3 of row 16 h + n, one float4 store
+__device__ __forceinline__ void mlp2_store_tile(const Mlp2Dst &d, int n_out, int g, int u, const f32x4 (&out)[2]) {
+    if (16 * u + 4 * g >= n_out) return;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const float4 o = make_float4(out[h][0], out[h][1], out[h][2], out[h][3]);
+        if (d.t1[h]) *reinterpret_cast<float4 *>(d.t1[h] + 16 * u) = o;
+        if (d.x[h]) *reinterpret_cast<float4 *>(d.x[h] + 16 * u) = o;
+    }
+}
+
+// both products of one item.  The second product has one 16-row output tile per 16 outputs; the second one (out > 16) sits
+// behind a uniform branch outside the MFMA chains.  hidden = 64: GEMM 1 once, then a loop over the output tiles.  hidden =
+// 128: GEMM 2 consumes 64 hidden units before GEMM 1 starts the next 64 (the same t order; half the accumulator registers).
+template <int ET, int HT, bool TRAIN>
+__device__ __forceinline__ void mlp2_item(const Mlp2Launch &L, const Mlp2Chan &C, const float *img, const Mlp2In<ET> &cur, int lane,
+                                          bool two_tiles) {
+    constexpr int HJ = 2 * HT;
+    const float *wt1 = img + HT * ET * 256;
+    const int g = lane >> 4;
+    f32x4 acc[2][4];
+    if constexpr (HJ == 4) {
+        mlp2_hidden<ET, HT, TRAIN>(L, C, img, cur, lane, 0, acc);
+        const Mlp2Dst d = mlp2_dst<ET>(L, C, cur, g);
+        const int n_tiles = two_tiles ? 2 : 1;
+        for (int u = 0; u < n_tiles; ++u) {   // not unrolled
+            f32x4 out[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+            mlp2_out_steps(wt1 + (size_t)u * HJ * 256, lane, acc, out);
+            mlp2_store_tile(d, L.out, g, u, out);
+        }
+    } else {
+        f32x4 out0[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+        f32x4 out1[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+        for (int t0 = 0; t0 < HJ; t0 += 4) {
+            mlp2_hidden<ET, HT, TRAIN>(L, C, img, cur, lane, t0, acc);
+            mlp2_out_steps(wt1 + (size_t)t0 * 256, lane, acc, out0);
+            if (two_tiles) mlp2_out_steps(wt1 + (size_t)(HJ + t0) * 256, lane, acc, out1);
+        }
+        const Mlp2Dst d = mlp2_dst<ET>(L, C, cur, g);
+        mlp2_store_tile(d, L.out, g, 0, out0);
+        if (two_tiles) mlp2_store_tile(d, L.out, g, 1, out1);
     }
 }
 
 template <int ET, int HT, bool TRAIN>
 __global__ __launch_bounds__((Mlp2Cfg<ET, HT>::kThreads)) void mlp2_kernel(const Mlp2Launch L, const int *__restrict__ rows, int64_t n_rows) {
     constexpr int IMG = HT * ET * 256 + HT * 1024 + 2 * HT * 16;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, r32 = lane & 31;
+    const int lane = threadIdx.x & 63, g = lane >> 4, n16 = lane & 15;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // scalar: the item bookkeeping stays out of the VGPRs
     const int64_t n_tiles = (n_rows + 31) / 32;
     constexpr int kMlp2Threads = Mlp2Cfg<ET, HT>::kThreads;
     constexpr int WPB = kMlp2Threads / 64;
@@ -162,67 +318,20 @@ __global__ __launch_bounds__((Mlp2Cfg<ET, HT>::kThreads)) void mlp2_kernel(const
             *reinterpret_cast<float4 *>(mlp2_lds + idx) = ld4m(L.images + (size_t)c0 * IMG + idx);
         __syncthreads();
         const int64_t n_items = n_tiles * nc;
+        const bool two_tiles = L.out > 16;   // uniform: the second output tile exists only for out > 16
         Mlp2In<ET> cur, nxt;
-        if (wave_global < n_items) mlp2_load<ET>(L, rows, n_rows, wave_global / nc, c0 + (int)(wave_global % nc), r32, half, cur);
+        if (wave_global < n_items) {
+            mlp2_load<ET>(L, rows, n_rows, wave_global / nc, c0 + (int)(wave_global % nc), n16, g, nxt);
+            mlp2_take<ET>(cur, nxt);
+        }
         for (int64_t item = wave_global; item < n_items; item += n_waves) {
             const int cc = (int)(item % nc);
             const int64_t item2 = item + n_waves;
-            if (item2 < n_items) mlp2_load<ET>(L, rows, n_rows, item2 / nc, c0 + (int)(item2 % nc), r32, half, nxt);
+            if (item2 < n_items) mlp2_load<ET>(L, rows, n_rows, item2 / nc, c0 + (int)(item2 % nc), n16, g, nxt);
             const Mlp2Chan &C = L.c[c0 + cc];
             const float *img = mlp2_lds + (size_t)cc * IMG;
-            const float *wt0 = img, *wt1 = img + HT * ET * 256, *b0p = wt1 + HT * 1024 + half * HT * 16;
-            f32x16 acc[HT];
-#pragma unroll
-            for (int t = 0; t < HT; ++t)
-#pragma unroll
-                for (int v = 0; v < 16; ++v) acc[t][v] = 0.f;
-#pragma unroll
-            for (int q = 0; q < ET; ++q) {
-#pragma unroll
-                for (int t = 0; t < HT; ++t) {
-                    const float4 w = ld4m(wt0 + ((size_t)(t * ET + q) * 64 + lane) * 4);
-                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(w.x, cur.xa[q].x, acc[t], 0, 0, 0);
-                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(w.y, cur.xa[q].y, acc[t], 0, 0, 0);
-                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(w.z, cur.xa[q].z, acc[t], 0, 0, 0);
-                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(w.w, cur.xa[q].w, acc[t], 0, 0, 0);
-                }
-            }
-            f32x16 out;
-#pragma unroll
-            for (int v = 0; v < 16; ++v) out[v] = 0.f;
-            // training: keep the hidden tile (register v of tile t = hidden unit 32 t + (v & 3) + 8 (v >> 2) + 4 half of the
-            // lane's row: registers 4g .. 4g+3 are 4 consecutive units, one float4 store)
-            float *hrow = (TRAIN && cur.valid) ? L.h0 + cur.row * L.ld_h0 + C.h0_col + 4 * half : nullptr;
-#pragma unroll
-            for (int t = 0; t < HT; ++t) {
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const float4 w = ld4m(wt1 + ((size_t)(t * 4 + g) * 64 + lane) * 4);
-                    const float4 b = ld4m(b0p + t * 16 + 4 * g);
-                    const float4 hv = make_float4(fmaxf(acc[t][4 * g + 0] + b.x, 0.f), fmaxf(acc[t][4 * g + 1] + b.y, 0.f),
-                                                  fmaxf(acc[t][4 * g + 2] + b.z, 0.f), fmaxf(acc[t][4 * g + 3] + b.w, 0.f));
-                    if (TRAIN && hrow) *reinterpret_cast<float4 *>(hrow + 32 * t + 8 * g) = hv;
-                    out = __builtin_amdgcn_mfma_f32_32x32x2f32(w.x, hv.x, out, 0, 0, 0);
-                    out = __builtin_amdgcn_mfma_f32_32x32x2f32(w.y, hv.y, out, 0, 0, 0);
-                    out = __builtin_amdgcn_mfma_f32_32x32x2f32(w.z, hv.z, out, 0, 0, 0);
-                    out = __builtin_amdgcn_mfma_f32_32x32x2f32(w.w, hv.w, out, 0, 0, 0);
-                }
-            }
-            if (cur.valid) {
-                float *dst = L.t1 + cur.row * L.ld_t1 + C.t1_col;
-                const int slot = C.x_slot ? C.x_slot[cur.row] : -1;   // sharded: a gather source of layer 2 -> its exchange row too
-                float *dst_x = C.x_buf + (int64_t)(slot < 0 ? 0 : slot) * C.x_ld;
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {   // registers 4g .. 4g+3 = outputs 8g + 4 half .. + 3
-                    const int j0 = 8 * g + 4 * half;
-                    if (j0 < L.out) {
-                        const float4 o = make_float4(out[4 * g], out[4 * g + 1], out[4 * g + 2], out[4 * g + 3]);
-                        *reinterpret_cast<float4 *>(dst + j0) = o;
-                        if (slot >= 0) *reinterpret_cast<float4 *>(dst_x + j0) = o;
-                    }
-                }
-            }
-            cur = nxt;
+            mlp2_item<ET, HT, TRAIN>(L, C, img, cur, lane, two_tiles);
+            mlp2_take<ET>(cur, nxt);
         }
     }
 }
