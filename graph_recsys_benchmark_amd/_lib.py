@@ -178,6 +178,11 @@ SIGNATURES = {
                                   _sz, _vp]),
     'pea_rank_full': (_int, [_i64, _int, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                              _sz, _vp]),
+    'pea_dot_predict': (_int, [_i64, _int, _i64, _vp, _vp, _vp, _vp, _vp]),
+    'pea_dot_rank_eval': (_int, [_i64, _int, _int, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'pea_dot_topk_workspace_bytes': (_sz, [_i64, _i64, _int, _int]),
+    'pea_dot_recommend_topk': (_int, [_i64, _int, _int, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'pea_dot_rank_full': (_int, [_i64, _int, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

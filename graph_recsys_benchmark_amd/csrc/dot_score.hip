@@ -1,0 +1,535 @@
+// Inner-product scoring for gfx950: the scorer of the KGAT / KGCN / NGCF baselines (graph_recsys_benchmark/models/
+// kgat.py, kgcn.py, ngcf.py: predict = sum(repr[u] * repr[i])) and of every embedding model (MF, LightGCN, two-tower).
+//   s(u, i) = fma chain over d = 0 .. D-1 ascending of repr[u, d] * repr[i, d], from +0                       (dot_pair)
+//   predict / rank_eval   one pair per thread / one user per wave, plain fmaf (the build has -ffp-contract=off)
+//   recommend_topk / rank_full   the catalogue scan is a GEMM: v_mfma_f32_16x16x4_f32, k-steps ascending, accumulator
+//     from zero.  A step's four k values are d = 4t .. 4t+3 (lane group g holds d = 4t + g), so the tile's accumulation
+//     order is the order of dot_pair; the f32-input MFMA rounds like an fmaf chain, which makes a pair's score the same
+//     bits in all four entry points (tests/test_gpu_dot_score.py checks that on the hardware).
+// No float atomics; every reduction has a fixed order.
+#include <algorithm>
+#include <atomic>
+
+#include "score_common.h"
+#include "topk_select.h"
+
+namespace pea {
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int kTI = 32;             // items of one LDS tile: two 16-row MFMA operands
+constexpr int kUW = 32;             // users of one wave: two 16-column MFMA operands, one list per (lane, half)
+constexpr int kMaxSplits = 64;
+constexpr int kMaxScanLds = 160 * 1024;     // a CU's LDS
+constexpr int kMaxDevices = 64;
+constexpr int kListLdsBudget = 78 * 1024;   // lists + tile of one workgroup: two workgroups fit a CU's 160 KB
+
+// the one definition of a pair's score outside the MFMA tiles
+__device__ __forceinline__ float dot_pair(const float *__restrict__ u, const float *__restrict__ v, int D) {
+    float o = 0.f;
+    for (int d = 0; d < D; d += 4) {
+        const float4 a = ld4(u + d), b = ld4(v + d);
+        o = fmaf(a.x, b.x, o);
+        o = fmaf(a.y, b.y, o);
+        o = fmaf(a.z, b.z, o);
+        o = fmaf(a.w, b.w, o);
+    }
+    return o;
+}
+
+// ---------------------------------------------------------------------------------------------- pair kernels
+__global__ __launch_bounds__(256) void dot_predict_kernel(int64_t B, int D, int64_t N, const float *__restrict__ repr,
+                                                          const int64_t *__restrict__ unids,
+                                                          const int64_t *__restrict__ inids, float *pred, int *err) {
+    const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (b >= B) return;
+    const int64_t u = unids[b], i = inids[b];
+    if (u < 0 || u >= N || i < 0 || i >= N) {
+        atomicOr(err, 1);
+        return;
+    }
+    pred[b] = dot_pair(repr + u * D, repr + i * D, D);
+}
+
+// one wave per user: lanes score candidates, then rank / auc / loss by wave reductions (rank_kernel of fuse_score.hip
+// with the inner-product scorer)
+__global__ __launch_bounds__(256) void dot_rank_kernel(int64_t U, int C, int D, int64_t N, const float *__restrict__ repr,
+                                                       const int64_t *__restrict__ unids,
+                                                       const int64_t *__restrict__ cand, float *scores, int32_t *rank,
+                                                       float *auc, float *loss, int *err) {
+    const int lane = threadIdx.x % kWave;
+    const int64_t uidx = (int64_t)blockIdx.x * (256 / kWave) + threadIdx.x / kWave;
+    if (uidx >= U) return;
+    const int64_t u = unids[uidx];
+    if (u < 0 || u >= N) {
+        if (lane == 0) atomicOr(err, 1);
+        return;
+    }
+    float pos = 0.f;
+    int higher = 0, gt = 0;
+    float lsum = 0.f;
+    for (int base = 0; base < C; base += kWave) {
+        const int c = base + lane;
+        float sc = 0.f;
+        bool ok = c < C;
+        if (ok) {
+            const int64_t i = cand[uidx * C + c];
+            if (i < 0 || i >= N) {
+                atomicOr(err, 1);
+                ok = false;
+            } else {
+                sc = dot_pair(repr + u * D, repr + i * D, D);
+                if (scores) scores[uidx * C + c] = sc;
+            }
+        }
+        if (base == 0) pos = __shfl(sc, 0);
+        if (ok && c > 0) {
+            // torch.sort(descending, stable): a negative goes ahead of the positive only if it scores strictly higher
+            higher += sc > pos ? 1 : 0;
+            gt += pos > sc ? 1 : 0;
+            lsum += log_sigmoid_ref(pos - sc);
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        higher += __shfl_xor(higher, off);
+        gt += __shfl_xor(gt, off);
+        lsum += __shfl_xor(lsum, off);
+    }
+    if (lane == 0) {
+        if (rank) rank[uidx] = higher;
+        if (auc) auc[uidx] = (float)gt / (float)(C - 1);
+        if (loss) loss[uidx] = -lsum;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------- catalogue scan
+struct Layout {
+    int DP = 32, NW = 4, S = 1, LD = 8;
+    int64_t span = 0;
+    size_t off_pos = 0, off_part = 0, bytes = 0, lds = 0;
+};
+
+size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// LDS row stride of the item tile in floats: D + 4 or D + 8, whichever makes LD / 4 odd, so that the sixteen rows one
+// MFMA operand load touches start in sixteen different 4-bank groups
+int tile_ld(int D) { return 4 * ((D / 4 + 1) | 1); }
+
+// How a call is cut.  A wave owns kUW users; a workgroup has NW waves that share the item tile; the catalogue is cut in S
+// ranges of `span` items so that few users still fill the machine.  rank (K = 0 here) keeps no lists.  Depends on
+// (U, n_items, K, D) only, so the workspace query and the call agree.
+Layout make_layout(int64_t U, int64_t n_items, int K, int D, bool rank) {
+    Layout L;
+    L.DP = D <= 32 ? 32 : (D <= 64 ? 64 : (D <= 128 ? 128 : 256));
+    L.LD = tile_ld(D);
+    const size_t tile_bytes = (size_t)kTI * L.LD * 4;
+    const size_t list_wave = rank ? 0 : (size_t)kWave * 2 * K * 8;      // two lists per lane
+    L.NW = 4;
+    while (L.NW > 1 && L.NW * list_wave + tile_bytes > (size_t)kListLdsBudget) L.NW >>= 1;
+    L.lds = L.NW * list_wave + tile_bytes;
+    if (L.lds > (size_t)kMaxScanLds) {          // K > 126 at D = 256 only: give up the conflict-free row stride to fit the CU's LDS
+        L.LD = D;
+        L.lds = L.NW * list_wave + (size_t)kTI * D * 4;
+    }
+    const int cols_per_split = 4;                                       // the four lane groups of a user keep own lists
+    const int64_t user_blocks = std::max<int64_t>((U + kUW * L.NW - 1) / (kUW * L.NW), 1);
+    int64_t s = (1024 + user_blocks - 1) / user_blocks;
+    s = std::min<int64_t>(s, std::max<int64_t>(n_items / 512, 1));      // an item range is worth >= 512 items
+    s = std::min<int64_t>(s, std::min<int64_t>(kMaxSplits, kMaxMerge / (cols_per_split * std::max(K, 1))));
+    s = std::max<int64_t>(s, 1);
+    int64_t span = (std::max<int64_t>(n_items, 1) + s - 1) / s;
+    span = (span + kTI - 1) / kTI * kTI;
+    L.span = span;
+    L.S = (int)std::max<int64_t>((n_items + span - 1) / span, 1);
+    size_t o = 256;                                                     // error flag
+    L.off_pos = o;  o = align256(o + (size_t)std::max<int64_t>(U, 1) * 4);
+    L.off_part = o;
+    o = align256(o + (size_t)L.S * cols_per_split * std::max(K, 1) * std::max<int64_t>(U, 1) * 8);
+    L.bytes = o;
+    return L;
+}
+
+struct ScanArgs {
+    int64_t U, N, n_items, item_lo, span;
+    int K, D, LD;
+    const float *repr;
+    const int64_t *unids;
+    const float *pos_s;   // rank: the positives' scores [U]
+    const int64_t *excl_rowptr, *excl_items;
+    float *part_s;        // top-K: [S * 4, K, U] scores          rank: unused
+    int *part_i;          // top-K: [S * 4, K, U] catalogue index  rank: [S * 4, 2, U] counts of (s > pos), (s < pos)
+    int *err;
+};
+
+// the item tile at the base is written as float4
+extern __shared__ __attribute__((aligned(16))) float dot_smem[];
+
+// Workgroup = NW waves; wave w owns users [32 (NW blockIdx.x + w), + 32) as two 16-column B operands held in registers
+// (lane (n, g) = (lane & 15, lane >> 4) holds repr[user n, 4t + g] for every step t).  The workgroup streams its item
+// range through an LDS tile of 32 rows = two 16-row A operands; a tile costs D / 4 steps of four independent MFMA chains
+// (2 item halves x 2 user halves) and leaves lane (n, g) with the scores of user n (of either half) against items
+// 4g .. 4g + 3 of either item half.  Selection is per lane, as in topk_scan_kernel: the lane's items arrive in ascending
+// id, so only a strictly higher score displaces the worst of its K-entry LDS column; the four lane groups of a user keep
+// separate columns (each over its own quarter of the items) and topk_merge_kernel folds them with the item ranges'.
+//   RANK: two counters per (lane, user half) instead of a list; exclusions are taken out by dot_rank_finish_kernel.
+template <int DP, bool RANK>
+__global__ __launch_bounds__(256) void dot_scan_kernel(const ScanArgs g) {
+    const int NT = blockDim.x;
+    float *tile = dot_smem;
+    float *ls = dot_smem + kTI * g.LD;                         // [2][K][NT]
+    int *li = reinterpret_cast<int *>(ls + (RANK ? 0 : 2 * g.K * NT));
+    const int tid = threadIdx.x;
+    const int lane = tid % kWave, n = lane & 15, grp = lane >> 4;
+    const int D = g.D, LD = g.LD, K = g.K;
+    const int64_t q0 = ((int64_t)blockIdx.x * (NT / kWave) + tid / kWave) * kUW + n;
+    int64_t q[2];
+    bool valid[2];
+    float ub[2][DP / 4];
+    float pos[2] = {0.f, 0.f}, thr[2];
+    int hi[2] = {0, 0}, lo[2] = {0, 0}, wslot[2] = {0, 0};
+    int64_t ex_lo[2] = {0, 0}, ex_hi[2] = {0, 0};
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        q[h] = q0 + 16 * h;
+        valid[h] = q[h] < g.U;
+        // a slot past the last user rides along in the MFMA on a copy of user U - 1; no score passes its threshold, so it
+        // keeps no list and searches no exclusions
+        thr[h] = valid[h] ? -INFINITY : INFINITY;
+        const int64_t qr = valid[h] ? q[h] : g.U - 1;
+        int64_t node = g.unids[qr];
+        if (node < 0 || node >= g.N) {
+            if (grp == 0) atomicOr(g.err, 1);
+            node = 0;
+        }
+        const float *row = g.repr + node * D + grp;
+#pragma unroll
+        for (int t = 0; t < DP / 4; ++t) ub[h][t] = 4 * t < D ? row[4 * t] : 0.f;
+        if (RANK) {
+            pos[h] = g.pos_s[qr];
+        } else if (valid[h]) {
+            for (int j = 0; j < K; ++j) {
+                ls[(h * K + j) * NT + tid] = -INFINITY;
+                li[(h * K + j) * NT + tid] = kEmpty;
+            }
+            if (g.excl_rowptr) {
+                ex_lo[h] = g.excl_rowptr[qr];
+                ex_hi[h] = g.excl_rowptr[qr + 1];
+            }
+        }
+    }
+    const int64_t i0 = (int64_t)blockIdx.y * g.span;
+    const int64_t i1 = i0 + g.span < g.n_items ? i0 + g.span : g.n_items;
+    const int d4 = D / 4;
+    const float *a_row0 = tile + n * LD + grp, *a_row1 = tile + (16 + n) * LD + grp;
+    for (int64_t t0 = i0; t0 < i1; t0 += kTI) {
+        __syncthreads();
+        // rows past the end of the range are zero rows: they score 0 and are skipped below
+        for (int x = tid; x < kTI * d4; x += NT) {
+            const int r = x / d4, c4 = x - r * d4;
+            const float4 v = t0 + r < i1 ? ld4(g.repr + (g.item_lo + t0 + r) * D + 4 * c4) : make_float4(0.f, 0.f, 0.f, 0.f);
+            *reinterpret_cast<float4 *>(tile + r * LD + 4 * c4) = v;
+        }
+        __syncthreads();
+        f32x4 acc[2][2];
+#pragma unroll
+        for (int is = 0; is < 2; ++is)
+#pragma unroll
+            for (int h = 0; h < 2; ++h) acc[is][h] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int t = 0; t < DP / 4; ++t) {
+            if (4 * t >= D) break;
+            const float a0 = a_row0[4 * t], a1 = a_row1[4 * t];
+            acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, ub[0][t], acc[0][0], 0, 0, 0);
+            acc[0][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, ub[1][t], acc[0][1], 0, 0, 0);
+            acc[1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, ub[0][t], acc[1][0], 0, 0, 0);
+            acc[1][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, ub[1][t], acc[1][1], 0, 0, 0);
+        }
+#pragma unroll
+        for (int is = 0; is < 2; ++is) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int64_t it = t0 + 16 * is + 4 * grp + j;
+                if (it >= i1) continue;
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const float s = acc[is][h][j];
+                    if (RANK) {
+                        hi[h] += s > pos[h] ? 1 : 0;
+                        lo[h] += s < pos[h] ? 1 : 0;
+                    } else if (s > thr[h]) {
+                        if (ex_lo[h] < ex_hi[h] && in_sorted(g.excl_items, ex_lo[h], ex_hi[h], g.item_lo + it)) continue;
+                        float *cs = ls + (h * K) * NT + tid;
+                        int *ci = li + (h * K) * NT + tid;
+                        cs[wslot[h] * NT] = s;
+                        ci[wslot[h] * NT] = (int)it;
+                        float w = cs[0];
+                        int wi = ci[0];
+                        int ws = 0;
+                        for (int m = 1; m < K; ++m) {
+                            const float sc = cs[m * NT];
+                            const int id = ci[m * NT];
+                            if (sc < w || (sc == w && id > wi)) {
+                                w = sc;
+                                wi = id;
+                                ws = m;
+                            }
+                        }
+                        wslot[h] = ws;
+                        thr[h] = w;
+                    }
+                }
+            }
+        }
+    }
+    const int64_t col = (int64_t)blockIdx.y * 4 + grp;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        if (!valid[h]) continue;
+        if (RANK) {
+            g.part_i[(col * 2) * g.U + q[h]] = hi[h];
+            g.part_i[(col * 2 + 1) * g.U + q[h]] = lo[h];
+        } else {
+            for (int j = 0; j < K; ++j) {
+                const int64_t o = (col * K + j) * g.U + q[h];
+                g.part_s[o] = ls[(h * K + j) * NT + tid];
+                g.part_i[o] = li[(h * K + j) * NT + tid];
+            }
+        }
+    }
+}
+
+// the positives' scores, one thread per user (rank_full scores the positive whether or not it is in the catalogue)
+__global__ __launch_bounds__(256) void dot_pos_kernel(int64_t U, int D, int64_t N, const float *__restrict__ repr,
+                                                      const int64_t *__restrict__ unids,
+                                                      const int64_t *__restrict__ pos_items, float *pos_s, int *err) {
+    const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (q >= U) return;
+    const int64_t u = unids[q], p = pos_items[q];
+    if (u < 0 || u >= N || p < 0 || p >= N) {
+        atomicOr(err, 1);
+        pos_s[q] = 0.f;
+        return;
+    }
+    pos_s[q] = dot_pair(repr + u * D, repr + p * D, D);
+}
+
+// One thread per user: sums the columns' counters, then walks the user's exclusion list once and takes out what those
+// items contributed (dot_pair gives the bits the scan compared).
+__global__ __launch_bounds__(64) void dot_rank_finish_kernel(int64_t U, int cols, int D, int64_t N, int64_t n_items,
+                                                             int64_t item_lo, const float *__restrict__ repr,
+                                                             const int64_t *__restrict__ unids,
+                                                             const int64_t *__restrict__ pos_items,
+                                                             const float *__restrict__ pos_s,
+                                                             const int64_t *__restrict__ excl_rowptr,
+                                                             const int64_t *__restrict__ excl_items,
+                                                             const int *__restrict__ part, int32_t *rank, float *auc,
+                                                             float *pos_score) {
+    const int64_t q = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (q >= U) return;
+    int64_t u = unids[q];
+    if (u < 0 || u >= N) u = 0;        // reported by dot_pos_kernel
+    const float pos = pos_s[q];
+    int64_t hi = 0, lo = 0;
+    for (int c = 0; c < cols; ++c) {
+        hi += part[((int64_t)c * 2) * U + q];
+        lo += part[((int64_t)c * 2 + 1) * U + q];
+    }
+    const int64_t pn = pos_items[q];
+    const bool pos_in = pn >= item_lo && pn < item_lo + n_items;
+    int64_t others = n_items - (pos_in ? 1 : 0);
+    // the scan counted the positive's own catalogue row: it compares equal to itself, so it is in neither counter
+    if (excl_rowptr) {
+        for (int64_t e = excl_rowptr[q]; e < excl_rowptr[q + 1]; ++e) {
+            const int64_t node = excl_items[e];
+            if (node < item_lo || node >= item_lo + n_items || node == pn) continue;
+            const float s = dot_pair(repr + u * D, repr + node * D, D);
+            hi -= s > pos ? 1 : 0;
+            lo -= s < pos ? 1 : 0;
+            --others;
+        }
+    }
+    if (rank) rank[q] = (int32_t)hi;
+    if (auc) auc[q] = others > 0 ? (float)lo / (float)others : 0.f;
+    if (pos_score) pos_score[q] = pos;
+}
+
+template <int DP, bool RANK>
+int launch_scan_dp(const Layout &L, const ScanArgs &g, hipStream_t stream) {
+    if (L.lds > 64 * 1024) {
+        // raised once per instantiation and device, to the most any layout asks for, not on every call
+        static std::atomic<bool> raised[kMaxDevices];
+        int dev = 0;
+        PEA_HIP(hipGetDevice(&dev));
+        PEA_REQUIRE(dev >= 0 && dev < kMaxDevices, PEA_ERR_HIP, "dot scan: device %d", dev);
+        if (!raised[dev].load(std::memory_order_acquire)) {
+            PEA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&dot_scan_kernel<DP, RANK>),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, kMaxScanLds));
+            raised[dev].store(true, std::memory_order_release);
+        }
+    }
+    const int users_wg = kUW * L.NW;
+    const dim3 grid((unsigned)((g.U + users_wg - 1) / users_wg), (unsigned)L.S);
+    PEA_LAUNCH((dot_scan_kernel<DP, RANK>), grid, dim3(kWave * L.NW), L.lds, stream, g);
+    PEA_HIP(hipGetLastError());
+    return PEA_OK;
+}
+
+template <bool RANK>
+int launch_scan(const Layout &L, const ScanArgs &g, hipStream_t stream) {
+    if (L.DP == 32) return launch_scan_dp<32, RANK>(L, g, stream);
+    if (L.DP == 64) return launch_scan_dp<64, RANK>(L, g, stream);
+    if (L.DP == 128) return launch_scan_dp<128, RANK>(L, g, stream);
+    return launch_scan_dp<256, RANK>(L, g, stream);
+}
+
+int check_d(const char *what, int D) {
+    PEA_REQUIRE(D >= 4 && D % 4 == 0 && D <= 256, PEA_ERR_ARG, "%s: width %d must be a multiple of 4 in 4..256", what, D);
+    return PEA_OK;
+}
+
+int check_common(const char *what, int64_t U, int D, int64_t num_nodes, int64_t item_lo, int64_t n_items) {
+    PEA_TRY(check_d(what, D));
+    PEA_REQUIRE(U >= 0 && num_nodes > 0 && n_items >= 0 && n_items < ((int64_t)1 << 31) - 1, PEA_ERR_ARG,
+                "%s: U=%lld n_items=%lld", what, (long long)U, (long long)n_items);
+    PEA_REQUIRE(item_lo >= 0 && item_lo + n_items <= num_nodes, PEA_ERR_RANGE,
+                "%s: catalogue [%lld, %lld) outside [0, num_nodes = %lld)", what, (long long)item_lo,
+                (long long)(item_lo + n_items), (long long)num_nodes);
+    return PEA_OK;
+}
+
+}  // namespace
+}  // namespace pea
+
+// ---------------------------------------------------------------------------------------------- C ABI
+extern "C" int pea_dot_predict(int64_t B, int D, int64_t num_nodes, const float *repr, const int64_t *unids,
+                               const int64_t *inids, float *pred, void *stream_) {
+    using namespace pea;
+    hipStream_t stream = (hipStream_t)stream_;
+    PEA_TRY(check_d("dot_predict", D));
+    PEA_REQUIRE(B >= 0 && repr && unids && inids && pred, PEA_ERR_ARG, "dot_predict: bad argument");
+    if (B == 0) return PEA_OK;
+    int *err = err_flag_for_current_device();
+    PEA_REQUIRE(err != nullptr, PEA_ERR_HIP, "dot_predict: no error-flag buffer on this device");
+    PEA_MEMSET_ASYNC(err, 0, sizeof(int), stream);
+    {
+        ProfScope ps("dot_predict", stream, (double)B * (8.0 * D + 20.0));
+        PEA_LAUNCH(dot_predict_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, stream, B, D, num_nodes, repr, unids,
+                   inids, pred, err);
+        PEA_HIP(hipGetLastError());
+    }
+    return read_err_flag(err, stream, "dot_predict");
+}
+
+extern "C" int pea_dot_rank_eval(int64_t U, int C, int D, int64_t num_nodes, const float *repr, const int64_t *unids,
+                                 const int64_t *cand, float *scores, int32_t *rank, float *auc, float *loss,
+                                 void *stream_) {
+    using namespace pea;
+    hipStream_t stream = (hipStream_t)stream_;
+    PEA_TRY(check_d("dot_rank_eval", D));
+    PEA_REQUIRE(U >= 0 && C >= 2 && repr && unids && cand, PEA_ERR_ARG, "dot_rank_eval: bad argument");
+    if (U == 0) return PEA_OK;
+    int *err = err_flag_for_current_device();
+    PEA_REQUIRE(err != nullptr, PEA_ERR_HIP, "dot_rank_eval: no error-flag buffer on this device");
+    PEA_MEMSET_ASYNC(err, 0, sizeof(int), stream);
+    {
+        ProfScope ps("dot_rank_eval", stream, (double)U * C * (4.0 * D + 12.0));
+        PEA_LAUNCH(dot_rank_kernel, dim3((unsigned)((U + 3) / 4)), dim3(256), 0, stream, U, C, D, num_nodes, repr, unids, cand,
+                   scores, rank, auc, loss, err);
+        PEA_HIP(hipGetLastError());
+    }
+    return read_err_flag(err, stream, "dot_rank_eval");
+}
+
+extern "C" size_t pea_dot_topk_workspace_bytes(int64_t U, int64_t n_items, int K, int D) {
+    if (U < 0 || n_items < 0 || K < 1 || K > 128 || D < 4 || D > 256 || D % 4 != 0) return 0;
+    return pea::make_layout(U, n_items, K, D, false).bytes;
+}
+
+extern "C" int pea_dot_recommend_topk(int64_t U, int K, int D, int64_t num_nodes, const float *repr, const int64_t *unids,
+                                      int64_t item_lo, int64_t n_items, const int64_t *excl_rowptr,
+                                      const int64_t *excl_items, int64_t *out_items, float *out_scores, void *workspace,
+                                      size_t workspace_bytes, void *stream_) {
+    using namespace pea;
+    hipStream_t stream = (hipStream_t)stream_;
+    PEA_REQUIRE(K >= 1 && K <= 128, PEA_ERR_ARG, "dot_recommend_topk: K=%d (1..128)", K);
+    PEA_TRY(check_common("dot_recommend_topk", U, D, num_nodes, item_lo, n_items));
+    PEA_REQUIRE(repr && unids && out_items && out_scores && workspace, PEA_ERR_ARG, "dot_recommend_topk: null pointer");
+    PEA_REQUIRE(!excl_rowptr || excl_items, PEA_ERR_ARG, "dot_recommend_topk: excl_rowptr without excl_items");
+    const Layout L = make_layout(U, n_items, K, D, false);
+    PEA_REQUIRE(workspace_bytes >= L.bytes, PEA_ERR_NOMEM, "dot_recommend_topk: workspace too small (%zu < %zu)",
+                workspace_bytes, L.bytes);
+    if (U == 0) return PEA_OK;
+    char *ws = (char *)workspace;
+    PEA_MEMSET_ASYNC((int *)ws, 0, sizeof(int), stream);
+    const int cols = L.S * 4;
+    ScanArgs g;
+    g.U = U; g.N = num_nodes; g.n_items = n_items; g.item_lo = item_lo; g.span = L.span;
+    g.K = K; g.D = D; g.LD = L.LD;
+    g.repr = repr; g.unids = unids; g.pos_s = nullptr;
+    g.excl_rowptr = excl_rowptr; g.excl_items = excl_items;
+    g.part_s = (float *)(ws + L.off_part);
+    g.part_i = (int *)(ws + L.off_part + (size_t)cols * K * U * 4);
+    g.err = (int *)ws;
+    {
+        ProfScope ps("dot_topk_scan", stream, 2.0 * (double)U * (double)n_items * D);
+        PEA_TRY(launch_scan<false>(L, g, stream));
+    }
+    {
+        ProfScope ps("dot_topk_merge", stream, 8.0 * (double)U * K * (cols + 1.5));
+        int p2 = 2;
+        while (p2 < cols * K) p2 <<= 1;      // <= kMaxMerge: make_layout keeps 4 S K <= 2048
+        PEA_LAUNCH(topk_merge_kernel, dim3((unsigned)U), dim3(p2 <= 128 ? 64 : 256), 0, stream, U, K, cols, p2, item_lo,
+                   (const float *)g.part_s, (const int *)g.part_i, out_items, out_scores);
+        PEA_HIP(hipGetLastError());
+    }
+    return read_err_flag((int *)ws, stream, "dot_recommend_topk");
+}
+
+extern "C" int pea_dot_rank_full(int64_t U, int D, int64_t num_nodes, const float *repr, const int64_t *unids,
+                                 const int64_t *pos_items, int64_t item_lo, int64_t n_items, const int64_t *excl_rowptr,
+                                 const int64_t *excl_items, int32_t *rank, float *auc, float *pos_score, void *workspace,
+                                 size_t workspace_bytes, void *stream_) {
+    using namespace pea;
+    hipStream_t stream = (hipStream_t)stream_;
+    PEA_TRY(check_common("dot_rank_full", U, D, num_nodes, item_lo, n_items));
+    PEA_REQUIRE(repr && unids && pos_items && workspace, PEA_ERR_ARG, "dot_rank_full: null pointer");
+    PEA_REQUIRE(!excl_rowptr || excl_items, PEA_ERR_ARG, "dot_rank_full: excl_rowptr without excl_items");
+    // the workspace is the one the K = 1 query sizes: a rank column (two int counters) takes the 8 bytes of a list entry
+    const Layout Lq = make_layout(U, n_items, 1, D, false);
+    PEA_REQUIRE(workspace_bytes >= Lq.bytes, PEA_ERR_NOMEM, "dot_rank_full: workspace too small (%zu < %zu)",
+                workspace_bytes, Lq.bytes);
+    const Layout L = make_layout(U, n_items, 1, D, true);
+    PEA_REQUIRE(L.bytes <= Lq.bytes, PEA_ERR_NOMEM, "dot_rank_full: workspace layout mismatch");
+    if (U == 0) return PEA_OK;
+    char *ws = (char *)workspace;
+    PEA_MEMSET_ASYNC((int *)ws, 0, sizeof(int), stream);
+    const int cols = L.S * 4;
+    ScanArgs g;
+    g.U = U; g.N = num_nodes; g.n_items = n_items; g.item_lo = item_lo; g.span = L.span;
+    g.K = 0; g.D = D; g.LD = L.LD;
+    g.repr = repr; g.unids = unids; g.pos_s = (const float *)(ws + L.off_pos);
+    g.excl_rowptr = nullptr; g.excl_items = nullptr;
+    g.part_s = nullptr;
+    g.part_i = (int *)(ws + L.off_part);
+    g.err = (int *)ws;
+    {
+        ProfScope ps("dot_rank_pos", stream, (double)U * (8.0 * D + 20.0));
+        PEA_LAUNCH(dot_pos_kernel, dim3((unsigned)((U + 255) / 256)), dim3(256), 0, stream, U, D, num_nodes, repr, unids,
+                   pos_items, (float *)(ws + L.off_pos), (int *)ws);
+        PEA_HIP(hipGetLastError());
+    }
+    {
+        ProfScope ps("dot_rank_scan", stream, 2.0 * (double)U * (double)n_items * D);
+        PEA_TRY(launch_scan<true>(L, g, stream));
+    }
+    {
+        ProfScope ps("dot_rank_finish", stream, 8.0 * (double)U * cols);
+        PEA_LAUNCH(dot_rank_finish_kernel, dim3((unsigned)((U + 63) / 64)), dim3(64), 0, stream, U, cols, D, num_nodes,
+                   n_items, item_lo, repr, unids, pos_items, g.pos_s, excl_rowptr, excl_items, (const int *)g.part_i, rank,
+                   auc, pos_score);
+        PEA_HIP(hipGetLastError());
+    }
+    return read_err_flag((int *)ws, stream, "dot_rank_full");
+}

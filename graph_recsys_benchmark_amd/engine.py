@@ -994,6 +994,115 @@ def rank_full(repr_, unids, pos_items, item_range, fc1_w, fc1_b, fc2_w, fc2_b, e
     return rank, auc, pos_score
 
 
+def _dot_table(repr_):
+    """Validation shared by the inner-product entry points (include/peahip.h, pea_dot_*): a CUDA float32 [N, D] table, D a
+    multiple of 4 and <= 256; returned detached and contiguous."""
+    if not torch.is_tensor(repr_) or repr_.dim() != 2 or repr_.dtype != torch.float32:
+        raise ValueError('the table must be a float32 [N, D] tensor')
+    if not repr_.is_cuda:
+        raise ValueError('the table must live on the GPU (there is no CPU fallback)')
+    d = repr_.shape[1]
+    if d < 4 or d % 4 != 0 or d > 256:
+        raise ValueError('the table width %d must be a multiple of 4 in 4..256' % d)
+    return repr_.detach().contiguous()
+
+
+def dot_predict(repr_, unids, inids):
+    """sum(repr[u] * repr[i]) -> [B]  (reference models/kgat.py, kgcn.py, ngcf.py: predict), as one fma chain over the
+    columns in ascending order (include/peahip.h, pea_dot_predict)."""
+    lib = _lib.require_device()
+    check_pending_errors()
+    table = _dot_table(repr_)
+    unids = unids.to(torch.int64).contiguous()
+    inids = inids.to(torch.int64).contiguous()
+    if unids.shape != inids.shape or unids.dim() != 1:
+        raise ValueError('unids / inids must be 1-d of equal length')
+    b = unids.shape[0]
+    out = torch.empty(b, dtype=torch.float32, device=table.device)
+    rc = lib.pea_dot_predict(b, table.shape[1], table.shape[0], _lib.ptr(table), _lib.ptr(unids), _lib.ptr(inids),
+                             _lib.ptr(out), _lib.current_stream())
+    if rc == -2:
+        raise IndexError(_lib.last_error())
+    _lib.check(rc)
+    return out
+
+
+def dot_rank_eval(repr_, unids, cand):
+    """rank_eval with the inner-product scorer: cand [U, C], column 0 = the held-out positive.  Returns scores [U, C], rank
+    of the positive [U] (int32), auc [U], eval loss [U]."""
+    lib = _lib.require_device()
+    check_pending_errors()
+    table = _dot_table(repr_)
+    unids = unids.to(torch.int64).contiguous()
+    cand = cand.to(torch.int64).contiguous()
+    if cand.dim() != 2 or unids.dim() != 1 or cand.shape[0] != unids.shape[0]:
+        raise ValueError('cand must be [U, C] with one row per user of unids')
+    u, c = cand.shape
+    dev = table.device
+    scores = torch.empty((u, c), dtype=torch.float32, device=dev)
+    rank = torch.empty(u, dtype=torch.int32, device=dev)
+    auc = torch.empty(u, dtype=torch.float32, device=dev)
+    loss = torch.empty(u, dtype=torch.float32, device=dev)
+    rc = lib.pea_dot_rank_eval(u, c, table.shape[1], table.shape[0], _lib.ptr(table), _lib.ptr(unids), _lib.ptr(cand),
+                               _lib.ptr(scores), _lib.ptr(rank), _lib.ptr(auc), _lib.ptr(loss), _lib.current_stream())
+    if rc == -2:
+        raise IndexError(_lib.last_error())
+    _lib.check(rc)
+    return scores, rank, auc, loss
+
+
+def dot_recommend_topk(repr_, unids, k, item_range, exclude=None):
+    """recommend_topk with the inner-product scorer: the k best items of the catalogue item_range = (lo, hi) for every user
+    of `unids`, ordered by (score descending, node id ascending), `exclude` = (rowptr [U + 1], items) left out.  Returns
+    (items int64 [U, k], scores float32 [U, k]) with a (-1, -inf) tail.  The catalogue scan is an MFMA GEMM whose score
+    tiles are selected from in registers (include/peahip.h, pea_dot_recommend_topk); the [U, items] score matrix is never
+    written."""
+    lib = _lib.require_device()
+    check_pending_errors()
+    table = _dot_table(repr_)
+    unids, item_lo, n_items, rowptr, items = _catalogue_args(table, unids, item_range, exclude)
+    u, k, d = unids.shape[0], int(k), table.shape[1]
+    dev = table.device
+    out_items = torch.empty((u, max(k, 0)), dtype=torch.int64, device=dev)
+    out_scores = torch.empty((u, max(k, 0)), dtype=torch.float32, device=dev)
+    ws_bytes = int(lib.pea_dot_topk_workspace_bytes(u, n_items, k, d))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    rc = lib.pea_dot_recommend_topk(u, k, d, table.shape[0], _lib.ptr(table), _lib.ptr(unids), item_lo, n_items,
+                                    _lib.ptr(rowptr), _lib.ptr(items), _lib.ptr(out_items), _lib.ptr(out_scores),
+                                    _lib.ptr(ws), ws_bytes, _lib.current_stream())
+    if rc == -2:
+        raise IndexError(_lib.last_error())
+    _lib.check(rc)
+    return out_items, out_scores
+
+
+def dot_rank_full(repr_, unids, pos_items, item_range, exclude=None):
+    """rank_full with the inner-product scorer: per user the number of eligible other items scoring strictly higher than
+    the held-out positive, the share scoring strictly lower, and the positive's score.  Returns (rank int32 [U], auc [U],
+    pos_score [U]).  include/peahip.h, pea_dot_rank_full."""
+    lib = _lib.require_device()
+    check_pending_errors()
+    table = _dot_table(repr_)
+    unids, item_lo, n_items, rowptr, items = _catalogue_args(table, unids, item_range, exclude)
+    pos_items = pos_items.to(torch.int64).contiguous()
+    if pos_items.shape != unids.shape:
+        raise ValueError('one positive per requested user')
+    u, d = unids.shape[0], table.shape[1]
+    dev = table.device
+    rank = torch.empty(u, dtype=torch.int32, device=dev)
+    auc = torch.empty(u, dtype=torch.float32, device=dev)
+    pos_score = torch.empty(u, dtype=torch.float32, device=dev)
+    ws_bytes = int(lib.pea_dot_topk_workspace_bytes(u, n_items, 1, d))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    rc = lib.pea_dot_rank_full(u, d, table.shape[0], _lib.ptr(table), _lib.ptr(unids), _lib.ptr(pos_items), item_lo, n_items,
+                               _lib.ptr(rowptr), _lib.ptr(items), _lib.ptr(rank), _lib.ptr(auc), _lib.ptr(pos_score),
+                               _lib.ptr(ws), ws_bytes, _lib.current_stream())
+    if rc == -2:
+        raise IndexError(_lib.last_error())
+    _lib.check(rc)
+    return rank, auc, pos_score
+
+
 def bpr_train_raw(picked, att, fc1_w, fc1_b, fc2_w, fc2_b):
     """One launch of csrc/bpr_train.hip + the two fixed-order reductions (pea_grad_weight): returns
     (loss, grad_rows [3B, P*R], (d_att | None, d_fc1_w, d_fc1_b, d_fc2_w, d_fc2_b)) for picked [3B, P, R]."""

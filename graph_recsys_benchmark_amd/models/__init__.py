@@ -2,6 +2,10 @@ from .base import GraphRecsysModel, PEABaseChannel, PEABaseRecsysModel
 from .peagat import PEAGATChannel, PEAGATRecsysModel
 from .peagcn import PEAGCNChannel, PEAGCNRecsysModel
 from .peasage import PEASageChannel, PEASageRecsysModel
+from .kgat import KGATRecsysModel
+from .kgcn import KGCNRecsysModel
+from .ngcf import NGCFRecsysModel
 
 __all__ = ['GraphRecsysModel', 'PEABaseChannel', 'PEABaseRecsysModel', 'PEAGATChannel', 'PEAGATRecsysModel',
-           'PEAGCNChannel', 'PEAGCNRecsysModel', 'PEASageChannel', 'PEASageRecsysModel']
+           'PEAGCNChannel', 'PEAGCNRecsysModel', 'PEASageChannel', 'PEASageRecsysModel', 'KGATRecsysModel', 'KGCNRecsysModel',
+           'NGCFRecsysModel']

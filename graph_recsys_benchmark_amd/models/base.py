@@ -22,6 +22,10 @@ from ..nn.inits import glorot
 
 
 class GraphRecsysModel(torch.nn.Module):
+    # how predict() scores a pair of cached_repr rows, and so which entry points loss(), recommend() and solvers.metrics*
+    # take: 'mlp' = fc2(relu(fc1([u || i]))) (the PEA models), 'dot' = sum(u * i) (KGAT / KGCN / NGCF)
+    scorer = 'mlp'
+
     def __init__(self, **kwargs):
         super().__init__()
         self._init(**kwargs)
@@ -48,6 +52,10 @@ class GraphRecsysModel(torch.nn.Module):
             pos_pred = self.predict(pos_neg_pair_t[:, 0], pos_neg_pair_t[:, 1])
             neg_pred = self.predict(pos_neg_pair_t[:, 0], pos_neg_pair_t[:, 2])
             cf_loss = -(pos_pred - neg_pred).sigmoid().log().sum()
+        elif self.scorer == 'dot':
+            pos_pred = _engine.dot_predict(self.cached_repr, pos_neg_pair_t[:, 0], pos_neg_pair_t[:, 1])
+            neg_pred = _engine.dot_predict(self.cached_repr, pos_neg_pair_t[:, 0], pos_neg_pair_t[:, 2])
+            cf_loss = -torch.nn.functional.logsigmoid(pos_pred - neg_pred).sum()
         else:
             cf_loss = _engine.bpr_score(self.cached_repr, pos_neg_pair_t, self.fc1.weight, self.fc1.bias,
                                         self.fc2.weight, self.fc2.bias)
@@ -74,10 +82,13 @@ class GraphRecsysModel(torch.nn.Module):
         """The k best items of the catalogue item_range = (first item node id, one past the last) for every user of
         `unids`, from the eval-mode cache: call model.eval() first.  exclude = (rowptr, items) leaves out per requested
         user the items named there (utils.interactions.seen_items_csr).  Returns (items int64 [U, k], scores [U, k]),
-        ordered by (score descending, node id ascending) -- engine.recommend_topk."""
+        ordered by (score descending, node id ascending) -- engine.recommend_topk, or engine.dot_recommend_topk for a model
+        whose scorer is 'dot'."""
         cached = getattr(self, 'cached_repr', None)
         if cached is None or self.training or getattr(self, '_repr_partial', False) or cached.requires_grad:
             raise RuntimeError('recommend() reads the eval-mode table: call model.eval() first')
+        if self.scorer == 'dot':
+            return _engine.dot_recommend_topk(cached, unids, k, item_range, exclude=exclude)
         return _engine.recommend_topk(cached, unids, k, item_range, self.fc1.weight, self.fc1.bias, self.fc2.weight,
                                       self.fc2.bias, exclude=exclude)
 

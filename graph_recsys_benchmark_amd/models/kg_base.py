@@ -1,0 +1,91 @@
+"""What the reference's three graph baselines share (graph_recsys_benchmark/models/kgat.py, kgcn.py, ngcf.py): three convs
+of widths H, H/2, H/4 with dropout after each, the table = cat of their L2-normalised outputs ([N, H + H/2 + H/4]), and
+the inner-product scorer predict = sum(repr[u] * repr[i]).
+
+The convs are nn/kg_conv.py (sparse half in HIP, differentiable); everything that reads the finished table without
+autograd -- predict, the evaluation loss, recommend, solvers.metrics / metrics_full -- goes to csrc/dot_score.hip.
+"""
+import torch
+import torch.nn.functional as F
+from torch.nn import Parameter
+
+from .. import engine as _engine
+from ..nn.inits import glorot
+from .base import GraphRecsysModel
+
+
+class DotRecsysModel(GraphRecsysModel):
+    scorer = 'dot'
+    # the loss of GraphRecsysModel reads these; the KG models have no entity-aware term, NGCF sets them from its kwargs
+    entity_aware = False
+    entity_aware_coff = 0.0
+
+    def _stack(self, *conv_args):
+        """conv1..3 + dropout, then the concatenation of the normalised outputs (models/kgat.py:45-51)."""
+        x_1 = F.dropout(self.conv1(self.x, self.edge_index, *conv_args), p=self.dropout, training=self.training)
+        x_2 = F.dropout(self.conv2(x_1, self.edge_index, *conv_args), p=self.dropout, training=self.training)
+        x_3 = F.dropout(self.conv3(x_2, self.edge_index, *conv_args), p=self.dropout, training=self.training)
+        return torch.cat([F.normalize(x_1, dim=-1), F.normalize(x_2, dim=-1), F.normalize(x_3, dim=-1)], dim=-1)
+
+    def predict(self, unids, inids):
+        if self.cached_repr.requires_grad:      # training: the reference's formula, differentiable
+            return torch.sum(self.cached_repr[unids] * self.cached_repr[inids], dim=-1)
+        return _engine.dot_predict(self.cached_repr, unids, inids)
+
+
+class KGBaseRecsysModel(DotRecsysModel):
+    """KGAT and KGCN: node embeddings x, relation embeddings r, a projection proj_mat, and convs that take the att_map the
+    solver recomputes per epoch (experiments/kgat_solver_bpr.py:311-320)."""
+    conv_class = None
+
+    def _init(self, **kwargs):
+        self.dropout = kwargs['dropout']
+        emb, hidden = kwargs['emb_dim'], kwargs['hidden_size']
+        self.x = Parameter(torch.Tensor(kwargs['dataset']['num_nodes'], emb))
+        self.r = Parameter(torch.Tensor(kwargs['dataset'].num_edge_types, emb))
+        self.proj_mat = Parameter(torch.Tensor(emb, emb))
+        self.edge_index, self.edge_attr = self.update_graph_input(kwargs['dataset'])
+        self.conv1 = self.conv_class(emb, hidden)
+        self.conv2 = self.conv_class(hidden, hidden // 2)
+        self.conv3 = self.conv_class(hidden // 2, hidden // 4)
+
+    def reset_parameters(self):
+        glorot(self.x)
+        glorot(self.r)
+        glorot(self.proj_mat)
+        self.conv1.reset_parameters()
+        self.conv2.reset_parameters()
+        self.conv3.reset_parameters()
+
+    def forward(self, att_map):
+        return self._stack(att_map)
+
+    def kg_eval(self):
+        torch.nn.Module.eval(self)
+
+    def cf_eval(self, att_map):
+        torch.nn.Module.eval(self)
+        self._repr_partial = False
+        with torch.no_grad():
+            self.cached_repr = self.forward(att_map)
+
+    def attention_map(self):
+        """att_map of the model's own tensors over its own graph, without grad (the concrete model picks the formula)."""
+        raise NotImplementedError
+
+    def loss(self, batch, att_map):
+        """BPR loss as the reference's experiment subclass writes it (experiments/kgat_solver_bpr.py:101-108)."""
+        if self.training:
+            self.cached_repr = self.forward(att_map)
+        pos_pred = self.predict(batch[:, 0], batch[:, 1])
+        neg_pred = self.predict(batch[:, 0], batch[:, 2])
+        return -(pos_pred - neg_pred).sigmoid().log().sum()
+
+    def kg_loss(self, batch):
+        """TransR-style loss over (head, tail+, tail-, relation) rows (experiments/kgat_solver_bpr.py:110-124); plain torch."""
+        head = torch.mm(self.x[batch[:, 0]], self.proj_mat) + self.r[batch[:, 3]]
+        pos_diff = head - torch.mm(self.x[batch[:, 1]], self.proj_mat)
+        neg_diff = head - torch.mm(self.x[batch[:, 2]], self.proj_mat)
+        pos_pred = (pos_diff * pos_diff).sum(-1)
+        neg_pred = (neg_diff * neg_diff).sum(-1)
+        return -(pos_pred - neg_pred).sigmoid().log().sum()

@@ -29,7 +29,8 @@ def metrics_from_ranks(rank):
 
 def metrics(model, dataset, num_neg_candidates=99):
     """Returns (HR[16], NDCG[16], AUC[1], eval_loss[1]) means over the test users, like BaseSolver.metrics.
-    `model` must be in eval() mode (cached_repr refreshed)."""
+    `model` must be in eval() mode (cached_repr refreshed; for KGAT / KGCN: model.cf_eval(att_map), as the reference's
+    solver does).  A model whose scorer is 'dot' is ranked by engine.dot_rank_eval."""
     u_nids = list(dataset.test_pos_unid_inid_map.keys())
     cand = np.empty((len(u_nids), 1 + num_neg_candidates), dtype=np.int64)
     for idx, u_nid in enumerate(u_nids):
@@ -42,9 +43,12 @@ def metrics(model, dataset, num_neg_candidates=99):
         cand[idx, 0] = pos_i_nids[0]
         cand[idx, 1:] = neg_i_nids
     dev = model.cached_repr.device
-    scores, rank, auc, loss = engine.rank_eval(model.cached_repr, torch.as_tensor(np.asarray(u_nids, dtype=np.int64), device=dev),
-                                               torch.from_numpy(cand).to(dev), model.fc1.weight, model.fc1.bias,
-                                               model.fc2.weight, model.fc2.bias)
+    u_t = torch.as_tensor(np.asarray(u_nids, dtype=np.int64), device=dev)
+    if getattr(model, 'scorer', 'mlp') == 'dot':      # KGAT / KGCN (after model.cf_eval(att_map)) / NGCF
+        scores, rank, auc, loss = engine.dot_rank_eval(model.cached_repr, u_t, torch.from_numpy(cand).to(dev))
+    else:
+        scores, rank, auc, loss = engine.rank_eval(model.cached_repr, u_t, torch.from_numpy(cand).to(dev), model.fc1.weight,
+                                                   model.fc1.bias, model.fc2.weight, model.fc2.bias)
     hr, ndcg = metrics_from_ranks(rank.cpu().numpy())
     return hr.mean(axis=0), ndcg.mean(axis=0), np.array([auc.double().mean().item()]), np.array([loss.double().mean().item()])
 
@@ -125,9 +129,13 @@ def metrics_full(model, u_nids, pos_items, item_range, exclude=None):
     AUC[1]) means through the same metrics_from_ranks as `metrics`; no eval loss at full catalogue.  `model` must be
     in eval() mode; exclude = (rowptr, items) on the model's device (utils.interactions.seen_items_csr)."""
     dev = model.cached_repr.device
-    rank, auc, _ = engine.rank_full(model.cached_repr, torch.as_tensor(np.asarray(u_nids, dtype=np.int64), device=dev),
-                                    torch.as_tensor(np.asarray(pos_items, dtype=np.int64), device=dev), item_range,
-                                    model.fc1.weight, model.fc1.bias, model.fc2.weight, model.fc2.bias, exclude=exclude)
+    u_t = torch.as_tensor(np.asarray(u_nids, dtype=np.int64), device=dev)
+    pos_t = torch.as_tensor(np.asarray(pos_items, dtype=np.int64), device=dev)
+    if getattr(model, 'scorer', 'mlp') == 'dot':
+        rank, auc, _ = engine.dot_rank_full(model.cached_repr, u_t, pos_t, item_range, exclude=exclude)
+    else:
+        rank, auc, _ = engine.rank_full(model.cached_repr, u_t, pos_t, item_range, model.fc1.weight, model.fc1.bias,
+                                        model.fc2.weight, model.fc2.bias, exclude=exclude)
     return metrics_full_from_ranks(rank.cpu().numpy(), auc.double().cpu().numpy())
 
 

@@ -573,6 +573,42 @@ int pea_rank_full(int64_t U, int R, int64_t num_nodes, const float *repr, const 
                   size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Inner-product scoring (csrc/dot_score.hip): the scorer of models/kgat.py, kgcn.py and ngcf.py (predict =
+ * sum(repr[u] * repr[i])) and of any embedding model.  repr [num_nodes, D] contiguous fp32, D a multiple of 4 in 4..256.
+ *   s(u, i):  o = +0;  for d = 0 .. D-1 ascending:  o = fmaf(repr[u, d], repr[i, d], o)
+ * SAME PAIR, SAME BITS from all four entry points, whatever U, K, the place of u in unids, the exclusion lists or the
+ * way the library cuts the catalogue (the catalogue scan runs the chain on f32-input MFMA tiles, k-steps ascending from
+ * a zero accumulator).  No float atomics.
+ *
+ * pea_dot_predict:   pred[b] = s(unids[b], inids[b]).
+ * pea_dot_rank_eval: pea_rank_eval's contract with this scorer: cand [U, C], candidate 0 the positive; rank = number
+ *   of negatives placed before the positive by torch.sort(descending, stable); auc = (negatives scoring strictly
+ *   lower) / (C - 1); loss[u] = -sum_c log(sigmoid(pos - neg_c)), fp32, no clamp.  scores [U, C] may be NULL.
+ * pea_dot_recommend_topk / pea_dot_rank_full: the contracts of pea_recommend_topk / pea_rank_full above, word for word
+ *   (catalogue block, ascending exclusion lists with entries outside the catalogue ignored, (score descending, node id
+ *   ascending) order also inside a tie group at the K-th place, (-1, -inf) tail, NaN and -inf never returned, K in
+ *   1..128, the positive scored wherever it is and never counted among the others, the same error codes at the same
+ *   times) without the four fc pointers.  workspace: pea_dot_topk_workspace_bytes(U, n_items, K, D) bytes
+ *   (pea_dot_rank_full: K = 1); 0 = bad arguments.
+ * pea_dot_predict and pea_dot_rank_eval synchronise the stream once to report ids outside [0, num_nodes) as
+ * PEA_ERR_RANGE, as pea_predict does.
+ * ---------------------------------------------------------------------------------------------- */
+int pea_dot_predict(int64_t B, int D, int64_t num_nodes, const float *repr, const int64_t *unids,
+                    const int64_t *inids, float *pred, void *stream);
+int pea_dot_rank_eval(int64_t U, int C, int D, int64_t num_nodes, const float *repr, const int64_t *unids,
+                      const int64_t *cand /*[U, C]*/, float *scores /*[U, C] or NULL*/, int32_t *rank, float *auc,
+                      float *loss, void *stream);
+size_t pea_dot_topk_workspace_bytes(int64_t U, int64_t n_items, int K, int D);
+int pea_dot_recommend_topk(int64_t U, int K, int D, int64_t num_nodes, const float *repr, const int64_t *unids,
+                           int64_t item_lo, int64_t n_items, const int64_t *excl_rowptr /* [U+1] or NULL */,
+                           const int64_t *excl_items, int64_t *out_items /* [U, K] */, float *out_scores /* [U, K] */,
+                           void *workspace, size_t workspace_bytes, void *stream);
+int pea_dot_rank_full(int64_t U, int D, int64_t num_nodes, const float *repr, const int64_t *unids,
+                      const int64_t *pos_items /* [U] */, int64_t item_lo, int64_t n_items, const int64_t *excl_rowptr,
+                      const int64_t *excl_items, int32_t *rank, float *auc, float *pos_score, void *workspace,
+                      size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Entity-aware regulariser of the loss (models/base.py:50-73, only with --entity_aware=true):
  *   reg = -sum_b log sigmoid((|x[i]-x[e+]|^2 - |x[i]-x[e-]|^2) * m_i) - sum_b log sigmoid((|x[u]-x[f+]|^2 - |x[u]-x[f-]|^2) * m_u)
  * over the B rows (u, i+, i-, e+, e-, m_i, f+, f-, m_u) of `batch` (int64, row stride >= 9).  One launch gathers the six
