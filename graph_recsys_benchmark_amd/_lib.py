@@ -183,7 +183,18 @@ SIGNATURES = {
     'pea_dot_topk_workspace_bytes': (_sz, [_i64, _i64, _int, _int]),
     'pea_dot_recommend_topk': (_int, [_i64, _int, _int, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'pea_dot_rank_full': (_int, [_i64, _int, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'pea_kg_update_supported': (_int, [_int, _int, _int]),
+    'pea_kg_update_forward': (_int, [_i64, _int, _int, _int, _vp, _i64, _vp, _i64, _vp, _vp, _vp, C.c_float, _vp, C.c_float, _vp,
+                                     _i64, _vp]),
+    'pea_kg_update_backward_workspace_bytes': (_sz, [_int, _int, _int]),
+    'pea_kg_update_backward': (_int, [_i64, _int, _int, _int, _vp, _i64, _vp, _i64, _vp, _vp, _vp, C.c_float, _vp, C.c_float, _vp,
+                                      _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'pea_dot_bpr_train_workspace_bytes': (_sz, [_i64]),
+    'pea_dot_bpr_train': (_int, [_i64, _int, C.POINTER(_vp), C.POINTER(_i64), C.POINTER(_int), _i64, _vp, _i64, _vp, _vp, _vp,
+                                 _sz, _vp]),
 }
+
+KGU_KGAT, KGU_KGCN, KGU_NGCF = 0, 1, 2     # include/peahip.h PEA_KGU_*
 
 _lib = None
 

@@ -1176,3 +1176,88 @@ def bpr_train_loss(picked, att, fc1_w, fc1_b, fc2_w, fc2_b):
     negative of triple b): channel fusion ('att' with the [.., P, R] attention tensor, 'mean' with att=None), the fc1 / fc2
     scorer and the loss, forward and backward in HIP."""
     return _BprTrainLoss.apply(picked, att, fc1_w, fc1_b, fc2_w, fc2_b)
+
+
+DOT_TRAIN_MAX_BLOCKS = 4      # column blocks pea_dot_bpr_train takes (include/peahip.h)
+
+
+def dot_bpr_train_raw(blocks, batch):
+    """One launch of csrc/dot_train.hip: (loss, grad_rows [3B, D], error flag) for the raw conv outputs `blocks` (a list of
+    [N, w_k] tensors whose normalised concatenation is the models' table) and the int64 [B, >= 3] triples `batch`."""
+    lib = _lib.require_device()
+    if batch.dtype != torch.int64 or batch.dim() != 2 or batch.shape[1] < 3:
+        raise ValueError('batch must be int64 [B, >=3]')
+    if not 1 <= len(blocks) <= DOT_TRAIN_MAX_BLOCKS:
+        raise ValueError('1..%d column blocks expected' % DOT_TRAIN_MAX_BLOCKS)
+    if batch.stride(1) != 1:
+        batch = batch.contiguous()
+    rows = []
+    for t in blocks:
+        t = _rows2d(t.detach())
+        if t.stride(0) % 4 or t.data_ptr() % 16:
+            t = t.contiguous()
+        rows.append(t)
+    n, b, dev = rows[0].shape[0], batch.shape[0], rows[0].device
+    if any(t.shape[0] != n for t in rows):
+        raise ValueError('the blocks must have the same number of rows')
+    k = len(rows)
+    d = sum(t.shape[1] for t in rows)
+    ptrs = (C.c_void_p * k)(*[t.data_ptr() for t in rows])
+    lds = (C.c_int64 * k)(*[t.stride(0) for t in rows])
+    widths = (C.c_int * k)(*[t.shape[1] for t in rows])
+    grad_rows = torch.empty((3 * b, d), dtype=torch.float32, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    ws_bytes = int(lib.pea_dot_bpr_train_workspace_bytes(b))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    _lib.check(lib.pea_dot_bpr_train(b, k, ptrs, lds, widths, n, _lib.ptr(batch), batch.stride(0), _lib.ptr(loss),
+                                     _lib.ptr(grad_rows), _lib.ptr(ws), ws_bytes, _lib.current_stream()))
+    return loss, grad_rows, ws[:4].view(torch.int32)[0]
+
+
+class _DotBprLoss(torch.autograd.Function):
+    """loss = -sum_b log sigmoid(pos_b - neg_b) under the inner-product scorer over cat_k normalize(block_k), with its whole
+    backward from the same launch (csrc/dot_train.hip); backward scatters the batch's gradient rows into one dense gradient
+    per block with pea_rows_scatter_sum (fixed order).  Reference: models/kgat.py:45-57 + experiments/kgat_solver_bpr.py:
+    101-108 under loss.backward()."""
+
+    @staticmethod
+    def forward(ctx, batch, *blocks):
+        loss, grad_rows, flag = dot_bpr_train_raw(blocks, batch)
+        if len(_pending_err) >= 64:
+            check_pending_errors()
+        _pending_err.append(flag)
+        ctx.ids = batch[:, :3].reshape(-1).contiguous()
+        ctx.grad_rows = grad_rows
+        ctx.shapes = [tuple(t.shape) for t in blocks]
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        rows = ctx.grad_rows * g
+        grads, off = [], 0
+        for i, (n, w) in enumerate(ctx.shapes):
+            if ctx.needs_input_grad[1 + i]:
+                dst = torch.zeros((n, w), dtype=torch.float32, device=rows.device)
+                rows_scatter_sum(ctx.ids, rows[:, off:off + w], 1, w, [0], dst)
+                grads.append(dst)
+            else:
+                grads.append(None)
+            off += w
+        return (None,) + tuple(grads)
+
+
+def dot_bpr_supported(widths, batch_size):
+    """Whether dot_bpr_loss takes these block widths and this batch (else the caller stays on autograd)."""
+    return (1 <= len(widths) <= DOT_TRAIN_MAX_BLOCKS and all(w >= 4 and w % 4 == 0 for w in widths) and sum(widths) <= 256
+            and 3 * int(batch_size) <= ROWS_SCATTER_MAX)
+
+
+def dot_bpr_loss(blocks, batch):
+    """Differentiable BPR loss of the int64 [B, >= 3] triples `batch` from the UN-normalised conv outputs `blocks` (a list of
+    [N, w_k] float32 tensors; the table the reference scores is cat_k normalize(block_k), which is never formed here).
+    backward() gives one dense [N, w_k] gradient per block.  3 B <= ROWS_SCATTER_MAX (dot_bpr_supported)."""
+    blocks = list(blocks)
+    if not dot_bpr_supported([int(t.shape[1]) for t in blocks], batch.shape[0]):
+        raise ValueError('dot_bpr_loss: block widths (multiples of 4, sum <= 256, at most %d blocks) or batch size (3 B <= %d) '
+                         'not supported' % (DOT_TRAIN_MAX_BLOCKS, ROWS_SCATTER_MAX))
+    return _DotBprLoss.apply(batch, *blocks)

@@ -4,6 +4,13 @@ the inner-product scorer predict = sum(repr[u] * repr[i]).
 
 The convs are nn/kg_conv.py (sparse half in HIP, differentiable); everything that reads the finished table without
 autograd -- predict, the evaluation loss, recommend, solvers.metrics / metrics_full -- goes to csrc/dot_score.hip.
+
+native_train=True (constructor kwarg, default off) sends a training step's loss() through HIP end to end: per conv the
+aggregate + the fused dense update of csrc/kg_update.hip (nn.kg_update), then the BPR loss of csrc/dot_train.hip on the
+un-normalised conv outputs (engine.dot_bpr_loss).  The dropout masks are then drawn by torch.rand(...) >= p, which is NOT
+the random stream of F.dropout: with dropout > 0 the two paths see different masks of the same distribution.  In this
+mode no table is built while training: cached_repr is None and predict() raises until cf_eval() / eval() has run.  Widths
+the kernels refuse, an att_map that requires grad and batches of more than 5461 triples take the autograd path silently.
 """
 import torch
 import torch.nn.functional as F
@@ -20,6 +27,35 @@ class DotRecsysModel(GraphRecsysModel):
     entity_aware = False
     entity_aware_coff = 0.0
 
+    native_train = False
+
+    def _convs(self):
+        return (self.conv1, self.conv2, self.conv3)
+
+    def _native_ok(self, batch, *conv_args):
+        """Whether this training step can take the HIP path (see the module docstring)."""
+        if not (self.native_train and self.training and 0 <= self.dropout < 1):
+            return False
+        if any(torch.is_tensor(a) and a.requires_grad for a in conv_args):
+            return False
+        convs = self._convs()
+        return (all(c.update_supported() for c in convs)
+                and _engine.dot_bpr_supported([c.out_channels for c in convs], batch.shape[0]))
+
+    def _native_loss(self, batch, *conv_args):
+        """conv1..3 as aggregate -> kg_update with the dropout mask folded in, then the BPR loss on the raw outputs."""
+        x, blocks = self.x, []
+        for conv in self._convs():
+            s = conv.aggregate(x, self.edge_index, *conv_args)
+            keep, scale = None, 1.0
+            if self.dropout > 0:
+                keep = (torch.rand((x.shape[0], conv.out_channels), device=x.device) >= self.dropout).to(torch.uint8)
+                scale = 1.0 / (1.0 - self.dropout)
+            x = conv.update(x, s, keep, scale)
+            blocks.append(x)
+        self.cached_repr = None
+        return _engine.dot_bpr_loss(blocks, batch)
+
     def _stack(self, *conv_args):
         """conv1..3 + dropout, then the concatenation of the normalised outputs (models/kgat.py:45-51)."""
         x_1 = F.dropout(self.conv1(self.x, self.edge_index, *conv_args), p=self.dropout, training=self.training)
@@ -28,6 +64,8 @@ class DotRecsysModel(GraphRecsysModel):
         return torch.cat([F.normalize(x_1, dim=-1), F.normalize(x_2, dim=-1), F.normalize(x_3, dim=-1)], dim=-1)
 
     def predict(self, unids, inids):
+        if getattr(self, 'cached_repr', None) is None:
+            raise RuntimeError('native_train builds no table while training: call cf_eval() / eval() before predict()')
         if self.cached_repr.requires_grad:      # training: the reference's formula, differentiable
             return torch.sum(self.cached_repr[unids] * self.cached_repr[inids], dim=-1)
         return _engine.dot_predict(self.cached_repr, unids, inids)
@@ -40,6 +78,7 @@ class KGBaseRecsysModel(DotRecsysModel):
 
     def _init(self, **kwargs):
         self.dropout = kwargs['dropout']
+        self.native_train = bool(kwargs.get('native_train', False))
         emb, hidden = kwargs['emb_dim'], kwargs['hidden_size']
         self.x = Parameter(torch.Tensor(kwargs['dataset']['num_nodes'], emb))
         self.r = Parameter(torch.Tensor(kwargs['dataset'].num_edge_types, emb))
@@ -75,6 +114,8 @@ class KGBaseRecsysModel(DotRecsysModel):
 
     def loss(self, batch, att_map):
         """BPR loss as the reference's experiment subclass writes it (experiments/kgat_solver_bpr.py:101-108)."""
+        if self._native_ok(batch, att_map):
+            return self._native_loss(batch, att_map)
         if self.training:
             self.cached_repr = self.forward(att_map)
         pos_pred = self.predict(batch[:, 0], batch[:, 1])

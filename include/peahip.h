@@ -609,6 +609,58 @@ int pea_dot_rank_full(int64_t U, int D, int64_t num_nodes, const float *repr, co
                       size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Training step of the KGAT / KGCN / NGCF baselines (csrc/kg_update.hip, csrc/dot_train.hip).
+ *
+ * Dense update of one conv (nn/kgat_conv.py:46-54, nn/kgcn_conv.py:39-44, nn/ngcf_conv.py:46-48).  s [N, in] = the weighted
+ * neighbour sum of x (pea_weighted_aggregate) is an input; A1 = x + s, A2 = x * s; w1 / w2 [in, out] contiguous:
+ *   PEA_KGU_KGAT  y = lrelu(A1 w1) + lrelu(A2 w2) + bias        (bias may be NULL)
+ *   PEA_KGU_KGCN  y = relu(A1 w1 + bias)                         (w2 must be NULL; bias may be NULL)
+ *   PEA_KGU_NGCF  y = lrelu(A1 w1 + A2 w2)                       (bias must be NULL).  The reference writes
+ *                 x W_1 + s W_1 + (x * s) W_2: the first two products are merged into one over x + s (rounding differs)
+ *   out = y * keep * keep_scale, keep an optional byte mask [N, out] (contiguous; NULL: no dropout, keep_scale is ignored).
+ * pea_kg_update_supported: in and out multiples of 4 in 4..128 and a known kind; pure, needs no device.
+ * pea_kg_update_backward: given g_out = d loss / d out it RECOMPUTES the pre-activations z from x and s (nothing is kept
+ *   between the two calls) and writes, with g = g_out * keep * keep_scale and the mask z > 0 ? 1 : slope (0 for the relu;
+ *   z == 0 takes the slope side, as torch does; NGCF: one mask on z1 + z2, KGCN: on z1 + bias):
+ *     dx = dA1 + dA2 * s, ds = dA1 + dA2 * x   (dA = dZ w^T; the caller adds the reverse aggregate of ds to dx)
+ *     dw1 = A1^T dZ1, dw2 = A2^T dZ2 [in, out], dbias [out] = column sum of g (KGAT) / dZ1 (KGCN); dbias may be NULL
+ * x, s, out, g_out, dx, ds may be column blocks of wider buffers: every ld is a multiple of 4 and at least the width, the
+ * blocks start on 16-byte boundaries; columns outside stay untouched.  Both kernels run on v_mfma_f32_16x16x4_f32 (k
+ * ascending from a zero accumulator); the weight gradients are one partial per workgroup added in workgroup order: no
+ * float atomics, bitwise reproducible, 64-bit row indexing.  Argument errors return PEA_ERR_ARG (a short workspace
+ * PEA_ERR_NOMEM) before anything is launched.  workspace: pea_kg_update_backward_workspace_bytes (0 = unsupported).
+ *
+ * pea_dot_bpr_train: the BPR loss of B triples (int64 rows (u, i, j), row stride triple_stride >= 3) under the
+ *   inner-product scorer over table = cat_k normalize(X_k), and its gradient, in one launch; the normalised table is never
+ *   formed.  X_k [num_nodes, widths[k]] (row stride ld[k]) are n_blocks <= 4 column blocks (host arrays of device pointers,
+ *   strides and widths; every width a multiple of 4, D = sum <= 256):
+ *     n_k(r) = X_k[r] / max(||X_k[r]||_2, 1e-12),  pos = sum_k n_k(u) . n_k(i),  neg likewise with j,
+ *     *out_loss = -sum_b log sigmoid(pos_b - neg_b)  (sigmoid then log in fp32, block sums in index order),
+ *     grad_rows [3B, D] (rows 3b, 3b + 1, 3b + 2 = u, i, j): d loss / d X[r] through the normalisation; a row whose norm is
+ *     below 1e-12 gets dn / 1e-12.  The caller scatters column block k into a zero-filled [N, widths[k]] gradient with
+ *     pea_rows_scatter_sum (P = 1, R = widths[k], src + column offset, ld_src = D; 3B <= 16384).
+ *   Stays asynchronous: a triple with an id outside [0, num_nodes) contributes nothing (zero gradient rows) and sets the
+ *   int at workspace[0] to 1.  workspace: pea_dot_bpr_train_workspace_bytes(B).
+ * ---------------------------------------------------------------------------------------------- */
+#define PEA_KGU_KGAT 0
+#define PEA_KGU_KGCN 1
+#define PEA_KGU_NGCF 2
+int pea_kg_update_supported(int kind, int in_width, int out_width);
+int pea_kg_update_forward(int64_t N, int kind, int in_width, int out_width, const float *x, int64_t ldx, const float *s,
+                          int64_t lds, const float *w1, const float *w2, const float *bias, float negative_slope,
+                          const unsigned char *keep, float keep_scale, float *out, int64_t ldo, void *stream);
+size_t pea_kg_update_backward_workspace_bytes(int kind, int in_width, int out_width);
+int pea_kg_update_backward(int64_t N, int kind, int in_width, int out_width, const float *x, int64_t ldx, const float *s,
+                           int64_t lds, const float *w1, const float *w2, const float *bias, float negative_slope,
+                           const unsigned char *keep, float keep_scale, const float *g_out, int64_t ldg, float *dx,
+                           int64_t lddx, float *ds, int64_t ldds, float *dw1, float *dw2, float *dbias, void *workspace,
+                           size_t workspace_bytes, void *stream);
+size_t pea_dot_bpr_train_workspace_bytes(int64_t B);
+int pea_dot_bpr_train(int64_t B, int n_blocks, const float *const *blocks_host, const int64_t *ld_host,
+                      const int *widths_host, int64_t num_nodes, const int64_t *triples, int64_t triple_stride,
+                      float *out_loss, float *grad_rows, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Entity-aware regulariser of the loss (models/base.py:50-73, only with --entity_aware=true):
  *   reg = -sum_b log sigmoid((|x[i]-x[e+]|^2 - |x[i]-x[e-]|^2) * m_i) - sum_b log sigmoid((|x[u]-x[f+]|^2 - |x[u]-x[f-]|^2) * m_u)
  * over the B rows (u, i+, i-, e+, e-, m_i, f+, f-, m_u) of `batch` (int64, row stride >= 9).  One launch gathers the six
