@@ -701,12 +701,8 @@ int launch_for_g(const AggLaunch &base, const int *sel, int n_sel, hipStream_t s
         L.blk_start[0] = 0;
         L.g[0] = g;
         const size_t lds = (size_t)g.hot_K * g.W * sizeof(float) + (MODE == AGG_GCN ? (size_t)g.hot_K * sizeof(float) : 0);
-        static size_t lds_set = 0;  // per instantiation: raise the dynamic-LDS cap once (160 KiB per workgroup on gfx950)
-        if (lds > lds_set) {
-            PEA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&agg_long_hot_kernel<G, MODE, F4T>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            lds_set = lds;
-        }
+        // 160 KiB per workgroup on gfx950
+        PEA_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(&agg_long_hot_kernel<G, MODE, F4T>), lds));
         const int n_virtual = (g.n_long + 3) / 4;
         const int grid = std::max(8, std::min(256, (n_virtual + 3) / 4 + 7 & ~7));
         const double per_msg = 4.0 * g.W + 4.0 * g.idx_share + (MODE == AGG_GAT ? 4.0 * (g.W / g.F) : MODE == AGG_GCN ? 4.0 * g.idx_share : 0.0);

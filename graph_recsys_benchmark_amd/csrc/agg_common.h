@@ -18,8 +18,6 @@ struct AggLaunch {
     AggGroup g[kMaxAggGroups];
 };
 
-__device__ __forceinline__ float4 ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
-__device__ __forceinline__ void st4(float *p, float4 v) { *reinterpret_cast<float4 *>(p) = v; }
 __device__ __forceinline__ float4 fma4(float w, float4 h, float4 a) {
     return make_float4(fmaf(w, h.x, a.x), fmaf(w, h.y, a.y), fmaf(w, h.z, a.z), fmaf(w, h.w, a.w));
 }

@@ -23,8 +23,6 @@ constexpr int kTB = 64;   // triples per workgroup (B = 4096 -> 64 workgroups)
 
 extern __shared__ float tsm[];
 
-__device__ __forceinline__ float4 ld4t(const float *p) { return *reinterpret_cast<const float4 *>(p); }
-
 // channel score of one row chunk list, summed in the order fuse_kernel sums it (per float4 (xy) + (zw), then a pairwise
 // tree over the G = pow2 >= R4 lane slots of that kernel)
 template <int R4>
@@ -34,7 +32,7 @@ __device__ __forceinline__ float chan_score(const float4 (&x)[R4], const float *
 #pragma unroll
     for (int i = 0; i < G; ++i) {
         if (i < R4) {
-            const float4 w = ld4t(a + 4 * i);
+            const float4 w = ld4(a + 4 * i);
             q[i] = (x[i].x * w.x + x[i].y * w.y) + (x[i].z * w.z + x[i].w * w.w);
         } else {
             q[i] = 0.f;
@@ -86,7 +84,7 @@ __global__ __launch_bounds__(kTB) void bpr_train_kernel(int64_t B, int P, const 
             for (int p = 0; p < P; ++p) {
                 float4 x[R4];
 #pragma unroll
-                for (int c = 0; c < R4; ++c) x[c] = ld4t(row + p * R + 4 * c);
+                for (int c = 0; c < R4; ++c) x[c] = ld4(row + p * R + 4 * c);
                 if (!att) {
 #pragma unroll
                     for (int c = 0; c < R4; ++c) {
@@ -126,12 +124,12 @@ __global__ __launch_bounds__(kTB) void bpr_train_kernel(int64_t B, int P, const 
                 float a = 0.f;
 #pragma unroll
                 for (int c = 0; c < R4; ++c) {
-                    const float4 wu = ld4t(w + 4 * c);
+                    const float4 wu = ld4(w + 4 * c);
                     a += (f[0][c].x * wu.x + f[0][c].y * wu.y) + (f[0][c].z * wu.z + f[0][c].w * wu.w);
                 }
 #pragma unroll
                 for (int c = 0; c < R4; ++c) {
-                    const float4 wi = ld4t(w + R + 4 * c);
+                    const float4 wi = ld4(w + R + 4 * c);
                     a += (f[1 + e][c].x * wi.x + f[1 + e][c].y * wi.y) + (f[1 + e][c].z * wi.z + f[1 + e][c].w * wi.w);
                 }
                 a += b1[k];
@@ -169,7 +167,7 @@ __global__ __launch_bounds__(kTB) void bpr_train_kernel(int64_t B, int P, const 
                 const float *w = w1 + k * 2 * R;
 #pragma unroll
                 for (int c = 0; c < R4; ++c) {
-                    const float4 wu = ld4t(w + 4 * c), wi = ld4t(w + R + 4 * c);
+                    const float4 wu = ld4(w + 4 * c), wi = ld4(w + R + 4 * c);
                     df[0][c].x = fmaf(dh, wu.x, df[0][c].x);
                     df[0][c].y = fmaf(dh, wu.y, df[0][c].y);
                     df[0][c].z = fmaf(dh, wu.z, df[0][c].z);
@@ -203,7 +201,7 @@ __global__ __launch_bounds__(kTB) void bpr_train_kernel(int64_t B, int P, const 
             for (int p = 0; p < P; ++p) {
                 float4 x[R4];
 #pragma unroll
-                for (int c = 0; c < R4; ++c) x[c] = ld4t(row + p * R + 4 * c);
+                for (int c = 0; c < R4; ++c) x[c] = ld4(row + p * R + 4 * c);
                 const float a = expf(chan_score<R4>(x, av + p * R) - fm[j]) * inv;
                 float da = 0.f;
 #pragma unroll
@@ -215,7 +213,7 @@ __global__ __launch_bounds__(kTB) void bpr_train_kernel(int64_t B, int P, const 
             for (int p = 0; p < P; ++p) {
                 float4 x[R4];
 #pragma unroll
-                for (int c = 0; c < R4; ++c) x[c] = ld4t(row + p * R + 4 * c);
+                for (int c = 0; c < R4; ++c) x[c] = ld4(row + p * R + 4 * c);
                 const float a = expf(chan_score<R4>(x, av + p * R) - fm[j]) * inv;
                 float da = 0.f;
 #pragma unroll
@@ -225,7 +223,7 @@ __global__ __launch_bounds__(kTB) void bpr_train_kernel(int64_t B, int P, const 
                 drow[p] = ds_p;
 #pragma unroll
                 for (int c = 0; c < R4; ++c) {
-                    const float4 w = ld4t(av + p * R + 4 * c);
+                    const float4 w = ld4(av + p * R + 4 * c);
                     *reinterpret_cast<float4 *>(grow + p * R + 4 * c) =
                         make_float4(fmaf(a, df[j][c].x, ds_p * w.x), fmaf(a, df[j][c].y, ds_p * w.y),
                                     fmaf(a, df[j][c].z, ds_p * w.z), fmaf(a, df[j][c].w, ds_p * w.w));
@@ -355,7 +353,7 @@ __global__ __launch_bounds__(256) void scatter_runs_kernel(int n, const unsigned
 #pragma unroll
             for (int v = 0; v < V; ++v) {
                 const int c4 = 4 * (lane + 64 * v);
-                t[u][v] = c4 < W ? ld4t(src + (int64_t)pos * ld_src + c4) : make_float4(0.f, 0.f, 0.f, 0.f);
+                t[u][v] = c4 < W ? ld4(src + (int64_t)pos * ld_src + c4) : make_float4(0.f, 0.f, 0.f, 0.f);
             }
         }
 #pragma unroll
@@ -400,13 +398,8 @@ extern "C" int pea_rows_scatter_sum(int64_t n, const int64_t *ids, const float *
         PEA_REQUIRE(col_of_channel_host[p] >= 0 && col_of_channel_host[p] % 4 == 0, PEA_ERR_ARG, "rows_scatter_sum: column %d", col_of_channel_host[p]);
         cols.c[p] = col_of_channel_host[p];
     }
-    unsigned long long *sorted = reinterpret_cast<unsigned long long *>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~uintptr_t(255));
-    static bool attr_set = false;
-    if (!attr_set) {
-        PEA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&sort_ids_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    kSortMax * 8));
-        attr_set = true;
-    }
+    unsigned long long *sorted = reinterpret_cast<unsigned long long *>(aligned_ws(workspace));
+    PEA_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(&sort_ids_kernel), (size_t)kSortMax * 8));
     ProfScope ps("scatter_sum", stream, (double)n * P * R * 8.0);
     PEA_LAUNCH(sort_ids_kernel, dim3(1), dim3(kSortThreads), (size_t)n * 8, stream, (int)n, num_rows, ids, sorted);
     PEA_HIP(hipGetLastError());

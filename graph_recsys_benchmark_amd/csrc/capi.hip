@@ -1,5 +1,8 @@
 // Library-wide entry points of the C ABI (include/peahip.h): version, thread-local error text, device probe.
 #include <cstring>
+#include <map>
+#include <mutex>
+#include <utility>
 
 #include "common.h"
 
@@ -26,6 +29,22 @@ int device_cu_count(int *n_cu) {
         cached = prop.multiProcessorCount;
     }
     *n_cu = cached;
+    return PEA_OK;
+}
+
+// The one place the library raises a kernel's dynamic-LDS limit.  The HIP attribute belongs to the kernel on one device,
+// so what has been asked for is remembered per (device, kernel).
+int ensure_dynamic_lds(const void *kernel, size_t bytes) {
+    if (bytes <= 64 * 1024) return PEA_OK;
+    static std::mutex mu;
+    static std::map<std::pair<int, const void *>, size_t> raised;
+    int dev = 0;
+    PEA_HIP(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lock(mu);
+    size_t &have = raised[{dev, kernel}];
+    if (bytes <= have) return PEA_OK;
+    PEA_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    have = bytes;
     return PEA_OK;
 }
 

@@ -78,6 +78,16 @@ inline void launch_rec(F f, hipStream_t stream) {
 
 // compute units of the current device, queried once per process (capi.hip)
 int device_cu_count(int *n_cu);
+// Lets `kernel` be launched with `bytes` of dynamic LDS (capi.hip).  Nothing to do at or below 64 KB; above, the limit is
+// raised when `bytes` exceeds what was asked for this (current device, kernel) before.  A caller whose layouts vary passes
+// the most any of them asks for, so that the limit is raised once.
+int ensure_dynamic_lds(const void *kernel, size_t bytes);
+
+// the helpers every translation unit needs: the MFMA accumulator vector, 16-byte row accesses, workspace rounding
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ float4 ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
+__device__ __forceinline__ void st4(float *p, float4 v) { *reinterpret_cast<float4 *>(p) = v; }
+inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 constexpr int kWave = 64;          // gfx950 wavefront
 constexpr int kShortDeg = 32;      // rows with <= this many kept edges go to the row-per-subgroup kernel

@@ -17,8 +17,6 @@
 namespace pea {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kGwRecords = 4096;  // (job, part) records of 16 x 256 floats in the workspace
 constexpr int kGwMaxJobs = 40;    // 64x64 blocks per launch (the job table travels as a kernel argument: < 4 KB)
 constexpr int kGwMaxParts = 512;  // row parts per job (grid.x), chosen per launch: gw_parts()
@@ -391,11 +389,7 @@ int tiles_of(int w) { return w <= 16 ? 1 : w <= 32 ? 2 : 4; }
 
 int launch_gw128(const GwBatch &Jb, const RowMap &rows, float *partial, double bytes, int64_t n_rows, hipStream_t stream) {
     constexpr size_t lds = (size_t)4 * 32 * kGwLd128 * sizeof(float);
-    static bool lds_set = false;
-    if (!lds_set) {
-        PEA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&gw_stage1_lds128), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        lds_set = true;
-    }
+    PEA_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(&gw_stage1_lds128), lds));
     // a record is 64 tiles (four of the 64 x 64 kind); two workgroups per CU
     int parts = gw_parts(2 * Jb.n, n_rows, true);
     parts = std::max(1, std::min(parts, kGwRecords / (4 * Jb.n)));
@@ -452,7 +446,7 @@ static int grad_weight_impl(const pea::RowMap &rowmap, int64_t n_rows, int n_job
                             size_t workspace_bytes, void *stream) {
     PEA_REQUIRE(n_jobs >= 0 && (jobs_host || n_jobs == 0), PEA_ERR_ARG, "grad_weight: bad arguments");
     PEA_REQUIRE(workspace && workspace_bytes >= pea_grad_weight_workspace_bytes(), PEA_ERR_NOMEM, "grad_weight: workspace too small");
-    float *partial = reinterpret_cast<float *>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~uintptr_t(255));
+    float *partial = aligned_ws(workspace);
     // cut every job into <= 64 x 64 blocks, group the blocks by tile shape, one pair of launches per shape and batch
     std::vector<GwJob> blocks[3][3], blocks128;
     // OFF unless PEA_GW128=1: measured slower on the Yelp-shaped presets (0.84 vs 0.73 ms per step for SAGE, 0.50 vs 0.44 GAT,

@@ -8,7 +8,6 @@
 //     bits in all four entry points (tests/test_gpu_dot_score.py checks that on the hardware).
 // No float atomics; every reduction has a fixed order.
 #include <algorithm>
-#include <atomic>
 
 #include "score_common.h"
 #include "topk_select.h"
@@ -16,13 +15,9 @@
 namespace pea {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kTI = 32;             // items of one LDS tile: two 16-row MFMA operands
 constexpr int kUW = 32;             // users of one wave: two 16-column MFMA operands, one list per (lane, half)
-constexpr int kMaxSplits = 64;
 constexpr int kMaxScanLds = 160 * 1024;     // a CU's LDS
-constexpr int kMaxDevices = 64;
 constexpr int kListLdsBudget = 78 * 1024;   // lists + tile of one workgroup: two workgroups fit a CU's 160 KB
 
 // the one definition of a pair's score outside the MFMA tiles
@@ -52,8 +47,7 @@ __global__ __launch_bounds__(256) void dot_predict_kernel(int64_t B, int D, int6
     pred[b] = dot_pair(repr + u * D, repr + i * D, D);
 }
 
-// one wave per user: lanes score candidates, then rank / auc / loss by wave reductions (rank_kernel of fuse_score.hip
-// with the inner-product scorer)
+// one wave per user: rank_one_user of score_common.h with the inner-product scorer
 __global__ __launch_bounds__(256) void dot_rank_kernel(int64_t U, int C, int D, int64_t N, const float *__restrict__ repr,
                                                        const int64_t *__restrict__ unids,
                                                        const int64_t *__restrict__ cand, float *scores, int32_t *rank,
@@ -66,42 +60,8 @@ __global__ __launch_bounds__(256) void dot_rank_kernel(int64_t U, int C, int D, 
         if (lane == 0) atomicOr(err, 1);
         return;
     }
-    float pos = 0.f;
-    int higher = 0, gt = 0;
-    float lsum = 0.f;
-    for (int base = 0; base < C; base += kWave) {
-        const int c = base + lane;
-        float sc = 0.f;
-        bool ok = c < C;
-        if (ok) {
-            const int64_t i = cand[uidx * C + c];
-            if (i < 0 || i >= N) {
-                atomicOr(err, 1);
-                ok = false;
-            } else {
-                sc = dot_pair(repr + u * D, repr + i * D, D);
-                if (scores) scores[uidx * C + c] = sc;
-            }
-        }
-        if (base == 0) pos = __shfl(sc, 0);
-        if (ok && c > 0) {
-            // torch.sort(descending, stable): a negative goes ahead of the positive only if it scores strictly higher
-            higher += sc > pos ? 1 : 0;
-            gt += pos > sc ? 1 : 0;
-            lsum += log_sigmoid_ref(pos - sc);
-        }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        higher += __shfl_xor(higher, off);
-        gt += __shfl_xor(gt, off);
-        lsum += __shfl_xor(lsum, off);
-    }
-    if (lane == 0) {
-        if (rank) rank[uidx] = higher;
-        if (auc) auc[uidx] = (float)gt / (float)(C - 1);
-        if (loss) loss[uidx] = -lsum;
-    }
+    rank_one_user([&](int64_t i) { return dot_pair(repr + u * D, repr + i * D, D); },
+                  [&](int, int c) { return cand[uidx * C + c]; }, C, N, lane, uidx, scores, rank, auc, loss, err);
 }
 
 // ---------------------------------------------------------------------------------------------- catalogue scan
@@ -110,8 +70,6 @@ struct Layout {
     int64_t span = 0;
     size_t off_pos = 0, off_part = 0, bytes = 0, lds = 0;
 };
-
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // LDS row stride of the item tile in floats: D + 4 or D + 8, whichever makes LD / 4 odd, so that the sixteen rows one
 // MFMA operand load touches start in sixteen different 4-bank groups
@@ -134,15 +92,8 @@ Layout make_layout(int64_t U, int64_t n_items, int K, int D, bool rank) {
         L.lds = L.NW * list_wave + (size_t)kTI * D * 4;
     }
     const int cols_per_split = 4;                                       // the four lane groups of a user keep own lists
-    const int64_t user_blocks = std::max<int64_t>((U + kUW * L.NW - 1) / (kUW * L.NW), 1);
-    int64_t s = (1024 + user_blocks - 1) / user_blocks;
-    s = std::min<int64_t>(s, std::max<int64_t>(n_items / 512, 1));      // an item range is worth >= 512 items
-    s = std::min<int64_t>(s, std::min<int64_t>(kMaxSplits, kMaxMerge / (cols_per_split * std::max(K, 1))));
-    s = std::max<int64_t>(s, 1);
-    int64_t span = (std::max<int64_t>(n_items, 1) + s - 1) / s;
-    span = (span + kTI - 1) / kTI * kTI;
-    L.span = span;
-    L.S = (int)std::max<int64_t>((n_items + span - 1) / span, 1);
+    catalogue_split(std::max<int64_t>((U + kUW * L.NW - 1) / (kUW * L.NW), 1), n_items, cols_per_split * std::max(K, 1), kTI,
+                    &L.S, &L.span);
     size_t o = 256;                                                     // error flag
     L.off_pos = o;  o = align256(o + (size_t)std::max<int64_t>(U, 1) * 4);
     L.off_part = o;
@@ -170,9 +121,9 @@ extern __shared__ __attribute__((aligned(16))) float dot_smem[];
 // (lane (n, g) = (lane & 15, lane >> 4) holds repr[user n, 4t + g] for every step t).  The workgroup streams its item
 // range through an LDS tile of 32 rows = two 16-row A operands; a tile costs D / 4 steps of four independent MFMA chains
 // (2 item halves x 2 user halves) and leaves lane (n, g) with the scores of user n (of either half) against items
-// 4g .. 4g + 3 of either item half.  Selection is per lane, as in topk_scan_kernel: the lane's items arrive in ascending
-// id, so only a strictly higher score displaces the worst of its K-entry LDS column; the four lane groups of a user keep
-// separate columns (each over its own quarter of the items) and topk_merge_kernel folds them with the item ranges'.
+// 4g .. 4g + 3 of either item half.  Selection is per lane, with the list of topk_select.h (the lane's items arrive in
+// ascending id); the four lane groups of a user keep separate columns (each over its own quarter of the items) and
+// topk_merge_kernel folds them with the item ranges'.
 //   RANK: two counters per (lane, user half) instead of a list; exclusions are taken out by dot_rank_finish_kernel.
 template <int DP, bool RANK>
 __global__ __launch_bounds__(256) void dot_scan_kernel(const ScanArgs g) {
@@ -209,10 +160,7 @@ __global__ __launch_bounds__(256) void dot_scan_kernel(const ScanArgs g) {
         if (RANK) {
             pos[h] = g.pos_s[qr];
         } else if (valid[h]) {
-            for (int j = 0; j < K; ++j) {
-                ls[(h * K + j) * NT + tid] = -INFINITY;
-                li[(h * K + j) * NT + tid] = kEmpty;
-            }
+            list_init(ls + (h * K) * NT, li + (h * K) * NT, NT, tid, K);
             if (g.excl_rowptr) {
                 ex_lo[h] = g.excl_rowptr[qr];
                 ex_hi[h] = g.excl_rowptr[qr + 1];
@@ -260,24 +208,9 @@ __global__ __launch_bounds__(256) void dot_scan_kernel(const ScanArgs g) {
                         lo[h] += s < pos[h] ? 1 : 0;
                     } else if (s > thr[h]) {
                         if (ex_lo[h] < ex_hi[h] && in_sorted(g.excl_items, ex_lo[h], ex_hi[h], g.item_lo + it)) continue;
-                        float *cs = ls + (h * K) * NT + tid;
-                        int *ci = li + (h * K) * NT + tid;
-                        cs[wslot[h] * NT] = s;
-                        ci[wslot[h] * NT] = (int)it;
-                        float w = cs[0];
-                        int wi = ci[0];
-                        int ws = 0;
-                        for (int m = 1; m < K; ++m) {
-                            const float sc = cs[m * NT];
-                            const int id = ci[m * NT];
-                            if (sc < w || (sc == w && id > wi)) {
-                                w = sc;
-                                wi = id;
-                                ws = m;
-                            }
-                        }
+                        int ws = wslot[h];     // a local, so that the rescan does not index wslot[] by h
+                        list_insert(ls + (h * K) * NT + tid, li + (h * K) * NT + tid, NT, 0, K, s, (int)it, ws, thr[h]);
                         wslot[h] = ws;
-                        thr[h] = w;
                     }
                 }
             }
@@ -291,11 +224,7 @@ __global__ __launch_bounds__(256) void dot_scan_kernel(const ScanArgs g) {
             g.part_i[(col * 2) * g.U + q[h]] = hi[h];
             g.part_i[(col * 2 + 1) * g.U + q[h]] = lo[h];
         } else {
-            for (int j = 0; j < K; ++j) {
-                const int64_t o = (col * K + j) * g.U + q[h];
-                g.part_s[o] = ls[(h * K + j) * NT + tid];
-                g.part_i[o] = li[(h * K + j) * NT + tid];
-            }
+            list_store(ls + (h * K) * NT, li + (h * K) * NT, NT, tid, K, col, g.U, q[h], g.part_s, g.part_i);
         }
     }
 }
@@ -315,8 +244,7 @@ __global__ __launch_bounds__(256) void dot_pos_kernel(int64_t U, int D, int64_t 
     pos_s[q] = dot_pair(repr + u * D, repr + p * D, D);
 }
 
-// One thread per user: sums the columns' counters, then walks the user's exclusion list once and takes out what those
-// items contributed (dot_pair gives the bits the scan compared).
+// One thread per user: rank_finish of topk_select.h with dot_pair (the bits the scan compared).
 __global__ __launch_bounds__(64) void dot_rank_finish_kernel(int64_t U, int cols, int D, int64_t N, int64_t n_items,
                                                              int64_t item_lo, const float *__restrict__ repr,
                                                              const int64_t *__restrict__ unids,
@@ -330,45 +258,14 @@ __global__ __launch_bounds__(64) void dot_rank_finish_kernel(int64_t U, int cols
     if (q >= U) return;
     int64_t u = unids[q];
     if (u < 0 || u >= N) u = 0;        // reported by dot_pos_kernel
-    const float pos = pos_s[q];
-    int64_t hi = 0, lo = 0;
-    for (int c = 0; c < cols; ++c) {
-        hi += part[((int64_t)c * 2) * U + q];
-        lo += part[((int64_t)c * 2 + 1) * U + q];
-    }
-    const int64_t pn = pos_items[q];
-    const bool pos_in = pn >= item_lo && pn < item_lo + n_items;
-    int64_t others = n_items - (pos_in ? 1 : 0);
-    // the scan counted the positive's own catalogue row: it compares equal to itself, so it is in neither counter
-    if (excl_rowptr) {
-        for (int64_t e = excl_rowptr[q]; e < excl_rowptr[q + 1]; ++e) {
-            const int64_t node = excl_items[e];
-            if (node < item_lo || node >= item_lo + n_items || node == pn) continue;
-            const float s = dot_pair(repr + u * D, repr + node * D, D);
-            hi -= s > pos ? 1 : 0;
-            lo -= s < pos ? 1 : 0;
-            --others;
-        }
-    }
-    if (rank) rank[q] = (int32_t)hi;
-    if (auc) auc[q] = others > 0 ? (float)lo / (float)others : 0.f;
-    if (pos_score) pos_score[q] = pos;
+    rank_finish(q, U, cols, n_items, item_lo, pos_s[q], pos_items[q], excl_rowptr, excl_items, part,
+                [&](int64_t node) { return dot_pair(repr + u * D, repr + node * D, D); }, rank, auc, pos_score);
 }
 
 template <int DP, bool RANK>
 int launch_scan_dp(const Layout &L, const ScanArgs &g, hipStream_t stream) {
-    if (L.lds > 64 * 1024) {
-        // raised once per instantiation and device, to the most any layout asks for, not on every call
-        static std::atomic<bool> raised[kMaxDevices];
-        int dev = 0;
-        PEA_HIP(hipGetDevice(&dev));
-        PEA_REQUIRE(dev >= 0 && dev < kMaxDevices, PEA_ERR_HIP, "dot scan: device %d", dev);
-        if (!raised[dev].load(std::memory_order_acquire)) {
-            PEA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&dot_scan_kernel<DP, RANK>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, kMaxScanLds));
-            raised[dev].store(true, std::memory_order_release);
-        }
-    }
+    // raised once per instantiation, to the most any layout asks for
+    if (L.lds > 64 * 1024) PEA_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(&dot_scan_kernel<DP, RANK>), kMaxScanLds));
     const int users_wg = kUW * L.NW;
     const dim3 grid((unsigned)((g.U + users_wg - 1) / users_wg), (unsigned)L.S);
     PEA_LAUNCH((dot_scan_kernel<DP, RANK>), grid, dim3(kWave * L.NW), L.lds, stream, g);
@@ -386,16 +283,6 @@ int launch_scan(const Layout &L, const ScanArgs &g, hipStream_t stream) {
 
 int check_d(const char *what, int D) {
     PEA_REQUIRE(D >= 4 && D % 4 == 0 && D <= 256, PEA_ERR_ARG, "%s: width %d must be a multiple of 4 in 4..256", what, D);
-    return PEA_OK;
-}
-
-int check_common(const char *what, int64_t U, int D, int64_t num_nodes, int64_t item_lo, int64_t n_items) {
-    PEA_TRY(check_d(what, D));
-    PEA_REQUIRE(U >= 0 && num_nodes > 0 && n_items >= 0 && n_items < ((int64_t)1 << 31) - 1, PEA_ERR_ARG,
-                "%s: U=%lld n_items=%lld", what, (long long)U, (long long)n_items);
-    PEA_REQUIRE(item_lo >= 0 && item_lo + n_items <= num_nodes, PEA_ERR_RANGE,
-                "%s: catalogue [%lld, %lld) outside [0, num_nodes = %lld)", what, (long long)item_lo,
-                (long long)(item_lo + n_items), (long long)num_nodes);
     return PEA_OK;
 }
 
@@ -454,7 +341,8 @@ extern "C" int pea_dot_recommend_topk(int64_t U, int K, int D, int64_t num_nodes
     using namespace pea;
     hipStream_t stream = (hipStream_t)stream_;
     PEA_REQUIRE(K >= 1 && K <= 128, PEA_ERR_ARG, "dot_recommend_topk: K=%d (1..128)", K);
-    PEA_TRY(check_common("dot_recommend_topk", U, D, num_nodes, item_lo, n_items));
+    PEA_TRY(check_d("dot_recommend_topk", D));
+    PEA_TRY(check_catalogue("dot_recommend_topk", U, num_nodes, item_lo, n_items));
     PEA_REQUIRE(repr && unids && out_items && out_scores && workspace, PEA_ERR_ARG, "dot_recommend_topk: null pointer");
     PEA_REQUIRE(!excl_rowptr || excl_items, PEA_ERR_ARG, "dot_recommend_topk: excl_rowptr without excl_items");
     const Layout L = make_layout(U, n_items, K, D, false);
@@ -493,7 +381,8 @@ extern "C" int pea_dot_rank_full(int64_t U, int D, int64_t num_nodes, const floa
                                  size_t workspace_bytes, void *stream_) {
     using namespace pea;
     hipStream_t stream = (hipStream_t)stream_;
-    PEA_TRY(check_common("dot_rank_full", U, D, num_nodes, item_lo, n_items));
+    PEA_TRY(check_d("dot_rank_full", D));
+    PEA_TRY(check_catalogue("dot_rank_full", U, num_nodes, item_lo, n_items));
     PEA_REQUIRE(repr && unids && pos_items && workspace, PEA_ERR_ARG, "dot_rank_full: null pointer");
     PEA_REQUIRE(!excl_rowptr || excl_items, PEA_ERR_ARG, "dot_rank_full: excl_rowptr without excl_items");
     // the workspace is the one the K = 1 query sizes: a rank column (two int counters) takes the 8 bytes of a list entry

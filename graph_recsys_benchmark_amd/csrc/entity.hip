@@ -12,7 +12,6 @@
 namespace pea {
 namespace {
 
-__device__ __forceinline__ float4 ld4e(const float *p) { return *reinterpret_cast<const float4 *>(p); }
 __device__ __forceinline__ float4 sub4(float4 a, float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
 __device__ __forceinline__ float sq4(float4 d) { return (d.x * d.x + d.y * d.y) + (d.z * d.z + d.w * d.w); }
 __device__ __forceinline__ float4 mul4(float4 a, float f) { return make_float4(a.x * f, a.y * f, a.z * f, a.w * f); }
@@ -43,7 +42,7 @@ __global__ __launch_bounds__(256) void entity_kernel(int64_t B, int F, int64_t N
     }
     float4 r[6];
 #pragma unroll
-    for (int q = 0; q < 6; ++q) r[q] = (valid && active) ? ld4e(x + id[q] * ldx + c4) : make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int q = 0; q < 6; ++q) r[q] = (valid && active) ? ld4(x + id[q] * ldx + c4) : make_float4(0.f, 0.f, 0.f, 0.f);
     const float4 dip = sub4(r[0], r[1]), din = sub4(r[0], r[2]), dup = sub4(r[3], r[4]), dun = sub4(r[3], r[5]);
     float ip = sq4(dip), in_ = sq4(din), up = sq4(dup), un = sq4(dun);
 #pragma unroll

@@ -12,16 +12,13 @@
 namespace pea {
 namespace {
 
-__device__ __forceinline__ float4 ld4g(const float *p) { return *reinterpret_cast<const float4 *>(p); }
-__device__ __forceinline__ void st4g(float *p, float4 v) { *reinterpret_cast<float4 *>(p) = v; }
-
 __global__ __launch_bounds__(256) void pack_rows_kernel(int64_t n, int w4, const float *__restrict__ table, int64_t ld,
                                                         const int *__restrict__ nodes, float *__restrict__ dst, int64_t dst_ld) {
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (t >= n * w4) return;
     const int64_t k = t / w4;
     const int c = (int)(t % w4) * 4;
-    st4g(dst + k * dst_ld + c, ld4g(table + (int64_t)nodes[k] * ld + c));
+    st4(dst + k * dst_ld + c, ld4(table + (int64_t)nodes[k] * ld + c));
 }
 
 __global__ __launch_bounds__(256) void unpack_rows_kernel(int64_t n, int w4, const float *__restrict__ src, int64_t src_ld,
@@ -32,7 +29,7 @@ __global__ __launch_bounds__(256) void unpack_rows_kernel(int64_t n, int w4, con
     const int64_t k = t / w4;
     const int c = (int)(t % w4) * 4;
     const int64_t s = src_rows ? (int64_t)src_rows[k] : k;
-    st4g(table + (int64_t)nodes[k] * ld + c, ld4g(src + s * src_ld + c));
+    st4(table + (int64_t)nodes[k] * ld + c, ld4(src + s * src_ld + c));
 }
 
 __global__ __launch_bounds__(256) void select_owned_kernel(int64_t n, int w4, int64_t N, const float *__restrict__ table, int64_t ld,
@@ -47,9 +44,9 @@ __global__ __launch_bounds__(256) void select_owned_kernel(int64_t n, int w4, in
     if (v < 0 || v >= N) {
         if (c == 0) atomicOr(err, 1);
     } else if ((int)((v / tile) % world) == rank) {
-        r = ld4g(table + v * ld + c);
+        r = ld4(table + v * ld + c);
     }
-    st4g(out + k * (int64_t)(w4 * 4) + c, r);
+    st4(out + k * (int64_t)(w4 * 4) + c, r);
 }
 
 // Batched forms: several (table, column block, node list) jobs against ONE rank-major exchange buffer whose rank blocks
@@ -83,10 +80,10 @@ __global__ __launch_bounds__(256) void xchg_batch_kernel(const XchgBatch B, floa
     const int c = (int)(e % J.w4) * 4;
     float *row = J.table + (int64_t)J.nodes[k] * J.ld + c;
     if (PACK) {   // buf = this rank's block
-        st4g(buf + J.buf_off + k * (int64_t)(J.w4 * 4) + c, ld4g(row));
+        st4(buf + J.buf_off + k * (int64_t)(J.w4 * 4) + c, ld4(row));
     } else {      // buf = rank 0's block
         const int s = J.slots[k];
-        st4g(row, ld4g(buf + (int64_t)(s / J.slots_per_rank) * rank_stride + J.buf_off + (int64_t)(s % J.slots_per_rank) * (J.w4 * 4) + c));
+        st4(row, ld4(buf + (int64_t)(s / J.slots_per_rank) * rank_stride + J.buf_off + (int64_t)(s % J.slots_per_rank) * (J.w4 * 4) + c));
     }
 }
 

@@ -1,7 +1,7 @@
 // Channel fusion, BPR scoring and the batched evaluator for gfx950.
 //   fuse_kernel   graph_recsys_benchmark/models/base.py:193-203  (stack, ablation mask, 'att'/'mean')
 //   bpr kernels   models/base.py:208-214 (predict) + models/base.py:46-48 (-sum log sigmoid(pos-neg))
-//   rank kernel   solvers.py:85-96 (score 1 + C-1 candidates, rank of the positive, auc, eval loss)
+//   rank kernel   solvers.py:85-96 (score 1 + C-1 candidates, rank of the positive, auc, eval loss), over V tables at once
 // All reductions have a fixed order (no float atomics): results are bitwise reproducible.
 #include <algorithm>
 #include <mutex>
@@ -53,18 +53,7 @@ __global__ __launch_bounds__(256) void fuse_kernel(int64_t n_rows, const int *__
             acc.x += x.x; acc.y += x.y; acc.z += x.z; acc.w += x.w;
             continue;
         }
-        const float4 a = ld4(att + p * R + c4);
-        float sc = sl * 4 < R ? (x.x * a.x + x.y * a.y) + (x.z * a.z + x.w * a.w) : 0.f;
-#pragma unroll
-        for (int off = 1; off < G; off <<= 1) sc += __shfl_xor(sc, off);
-        const float mn = fmaxf(m, sc);
-        const float f = expf(m - mn), w = expf(sc - mn);
-        s = s * f + w;
-        acc.x = acc.x * f + w * x.x;
-        acc.y = acc.y * f + w * x.y;
-        acc.z = acc.z * f + w * x.z;
-        acc.w = acc.w * f + w * x.w;
-        m = mn;
+        softmax_step(chan_logit<G>(x, ld4(att + p * R + c4), sl * 4 < R), x, m, s, acc);
     }
     if (!active || !dst_row) return;
     const float inv = mode == PEA_FUSE_MEAN ? 1.0f / (float)P : 1.0f / s;
@@ -152,14 +141,18 @@ __global__ __launch_bounds__(256) void predict_kernel(int64_t B, int R, int64_t 
     }
 }
 
-// one wave per user: lanes score candidates, then rank / auc / loss by wave reductions
-__global__ __launch_bounds__(256) void rank_kernel(int64_t U, int C, int R, int64_t N, const float *__restrict__ repr,
-                                                   const int64_t *__restrict__ unids,
-                                                   const int64_t *__restrict__ cand, const float *fc1_w,
-                                                   const float *fc1_b, const float *fc2_w, const float *fc2_b,
-                                                   float *scores, int32_t *rank, float *auc, float *loss, int *err) {
+// The batched evaluator (solvers.py:85-96) over V tables: one wave per user, and the wave walks the variants; V = 1 is
+// pea_rank_eval.  The staged fc1 / fc2 weights are loaded once per workgroup; with a shared candidate block
+// (cand_stride == 0) the ids of the first two wave passes (C <= 128 covers the reference's 1 + 99) are loaded once and kept
+// in registers.  Per variant the ranking is rank_one_user of score_common.h.
+__global__ __launch_bounds__(256) void rank_multi_kernel(int V, int64_t U, int C, int R, int64_t N,
+                                                         const float *__restrict__ tables,
+                                                         const int64_t *__restrict__ unids,
+                                                         const int64_t *__restrict__ cand, int64_t cand_stride,
+                                                         const float *fc1_w, const float *fc1_b, const float *fc2_w,
+                                                         const float *fc2_b, float *scores, int32_t *rank, float *auc,
+                                                         float *loss, int *err) {
     stage_mlp(R, fc1_w, fc1_b, fc2_w);
-    const float *w1 = smem, *b1 = smem + 2 * R * R, *w2 = b1 + R;
     const int lane = threadIdx.x % kWave;
     const int64_t uidx = (int64_t)blockIdx.x * (256 / kWave) + threadIdx.x / kWave;
     if (uidx >= U) return;
@@ -168,50 +161,18 @@ __global__ __launch_bounds__(256) void rank_kernel(int64_t U, int C, int R, int6
         if (lane == 0) atomicOr(err, 1);
         return;
     }
-    float pos = 0.f;
-    int higher = 0, gt = 0;
-    float lsum = 0.f;
-    float4 ur[4];
-    if (R == 16) load_row<4>(repr + u * R, ur);   // the reference's repr_dim: the user's row stays in registers
-    for (int base = 0; base < C; base += kWave) {
-        const int c = base + lane;
-        float sc = 0.f;
-        bool ok = c < C;
-        if (ok) {
-            const int64_t i = cand[uidx * C + c];
-            if (i < 0 || i >= N) {
-                atomicOr(err, 1);
-                ok = false;
-            } else {
-                if (R == 16) {   // same arithmetic, same order as mlp_score (rows held in registers)
-                    float4 ir[4];
-                    load_row<4>(repr + i * R, ir);
-                    sc = mlp_score_reg<4>(ur, ir, w1, b1, w2, fc2_b[0]);
-                } else {
-                    sc = mlp_score(repr + u * R, repr + i * R, R, w1, b1, w2, fc2_b[0]);
-                }
-                if (scores) scores[uidx * C + c] = sc;
-            }
-        }
-        if (base == 0) pos = __shfl(sc, 0);
-        if (ok && c > 0) {
-            // torch.sort(descending) places a negative ahead of the positive only if it scores strictly
-            // higher (stable order keeps index 0 first among ties)
-            higher += sc > pos ? 1 : 0;
-            gt += pos > sc ? 1 : 0;
-            lsum += log_sigmoid_ref(pos - sc);
-        }
+    const bool shared = cand_stride == 0;
+    int64_t keep0 = -1, keep1 = -1;
+    if (shared) {
+        if (lane < C) keep0 = cand[uidx * C + lane];
+        if (kWave + lane < C) keep1 = cand[uidx * C + kWave + lane];
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        higher += __shfl_xor(higher, off);
-        gt += __shfl_xor(gt, off);
-        lsum += __shfl_xor(lsum, off);
-    }
-    if (lane == 0) {
-        if (rank) rank[uidx] = higher;
-        if (auc) auc[uidx] = (float)gt / (float)(C - 1);
-        if (loss) loss[uidx] = -lsum;
+    const float b2 = fc2_b[0];
+    for (int v = 0; v < V; ++v) {
+        const int64_t *cv = cand + (int64_t)v * cand_stride + uidx * C;
+        const MlpScorer score(tables + (int64_t)v * N * R, u, R, b2);
+        rank_one_user(score, [&](int base, int c) { return shared && base == 0 ? keep0 : shared && base == kWave ? keep1 : cv[c]; },
+                      C, N, lane, (int64_t)v * U + uidx, scores, rank, auc, loss, err);
     }
 }
 
@@ -351,10 +312,37 @@ extern "C" int pea_rank_eval(int64_t U, int C, int R, int64_t num_nodes, const f
     PEA_REQUIRE(err != nullptr, PEA_ERR_HIP, "rank_eval: no error-flag buffer on this device");
     PEA_MEMSET_ASYNC(err, 0, sizeof(int), stream);
     const size_t sh = (size_t)(2 * R * R + 2 * R) * sizeof(float);
-    PEA_LAUNCH(pea::rank_kernel, dim3((unsigned)((U + 3) / 4)), dim3(256), sh, stream, U, C, R, num_nodes, repr,
-                       unids, cand, fc1_w, fc1_b, fc2_w, fc2_b, scores, rank, auc, loss, err);
+    // the V = 1 case of the multi-table evaluator, the candidates read per table (stride U * C: nothing register-cached)
+    PEA_LAUNCH(pea::rank_multi_kernel, dim3((unsigned)((U + 3) / 4)), dim3(256), sh, stream, 1, U, C, R, num_nodes, repr,
+               unids, cand, U * (int64_t)C, fc1_w, fc1_b, fc2_w, fc2_b, scores, rank, auc, loss, err);
     int rc = hipGetLastError() == hipSuccess ? PEA_OK : PEA_ERR_HIP;
     if (rc == PEA_OK) rc = read_err_flag(err, stream, "rank_eval");
+    return rc;
+}
+
+extern "C" int pea_rank_eval_multi(int V, int64_t U, int C, int R, int64_t num_nodes, const float *tables,
+                                   const int64_t *unids, const int64_t *cand, int64_t cand_variant_stride,
+                                   const float *fc1_w, const float *fc1_b, const float *fc2_w, const float *fc2_b,
+                                   float *scores, int32_t *rank, float *auc, float *loss, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    PEA_TRY(check_r(R));
+    PEA_REQUIRE(V >= 1 && U >= 0 && C >= 2 && num_nodes > 0 && tables && unids && cand && fc1_w && fc1_b && fc2_w && fc2_b,
+                PEA_ERR_ARG, "rank_eval_multi: bad argument");
+    PEA_REQUIRE(cand_variant_stride == 0 || cand_variant_stride == U * (int64_t)C, PEA_ERR_ARG,
+                "rank_eval_multi: cand_variant_stride %lld (0 = one shared [U, C] block, else U * C)",
+                (long long)cand_variant_stride);
+    if (U == 0) return PEA_OK;
+    int *err = err_flag_for_current_device();
+    PEA_REQUIRE(err != nullptr, PEA_ERR_HIP, "rank_eval_multi: no error-flag buffer on this device");
+    PEA_MEMSET_ASYNC(err, 0, sizeof(int), stream);
+    const size_t sh = (size_t)(2 * R * R + 2 * R) * sizeof(float);
+    {
+        pea::ProfScope ps("rank_eval_multi", stream, (double)V * U * C * (4.0 * R + 12.0));
+        PEA_LAUNCH(pea::rank_multi_kernel, dim3((unsigned)((U + 3) / 4)), dim3(256), sh, stream, V, U, C, R, num_nodes, tables, unids,
+                   cand, cand_variant_stride, fc1_w, fc1_b, fc2_w, fc2_b, scores, rank, auc, loss, err);
+    }
+    int rc = hipGetLastError() == hipSuccess ? PEA_OK : PEA_ERR_HIP;
+    if (rc == PEA_OK) rc = read_err_flag(err, stream, "rank_eval_multi");
     return rc;
 }
 

@@ -35,8 +35,6 @@ struct GemmBatch {
     GemmJob j[kMaxBatch];
 };
 
-__device__ __forceinline__ float4 ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
-
 // Branch-free A fragment load: every lane issues all its float4 loads back to back (invalid rows / k-ranges are
 // clamped to a valid address and zeroed afterwards), then the edge-less-row transform is applied with selects.
 template <int KH, bool IL = false>
@@ -553,7 +551,6 @@ __global__ __launch_bounds__(KH > 32 ? 512 : 1024) void gemm_persist_kernel(cons
 // 16 float4 input loads (all four groups) are issued before anything waits on them: twice the bytes in flight per
 // wave of the 32-row kernel.  k order per lane: float4 chunks 4i + q of the row (the four lanes of a row read 64
 // contiguous bytes per instruction); the weight image in LDS is read with the same permutation.
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct SkinnyArgs {
     // > 0: every job has this many 64-row tiles and item i is (tile i / n_jobs, job i % n_jobs): the jobs of a level read
@@ -998,22 +995,11 @@ static int plan_gemm_launches(const GemmJob *jobs_in, int n_jobs_in, bool rows_g
     return PEA_OK;
 }
 
-// Raises a kernel's dynamic-LDS limit, once per kernel.
-template <auto Kernel>
-static int max_dynamic_lds(int bytes) {
-    static bool done = false;
-    if (!done) {
-        PEA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-        done = true;
-    }
-    return PEA_OK;
-}
-
 // tables: the PersistArgs / SkinnyArgs of the launch.  PEA_LAUNCH captures the batch and the tables by value (tape replay).
 template <auto Kernel, class... Tables>
 static int issue(const GemmLaunch &L, dim3 grid, int threads, int lds_limit, const int *rows, int64_t n_rows, hipStream_t stream,
                  const Tables &...tables) {
-    if (lds_limit) PEA_TRY(max_dynamic_lds<Kernel>(lds_limit));
+    PEA_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(Kernel), (size_t)lds_limit));
     const GemmBatch &Bt = L.Bt;
     const size_t lds = L.lds;
     ProfScope ps(L.name, stream, L.bytes);

@@ -305,8 +305,8 @@ int es_launch_g(const EsArgs &A, const Relation &R, double gathered, double tabl
 }
 
 // workspace: [rec | fin] (n_slots float2 each) then the KG extras: scratch [e_kept], xp [N, emb] (KGAT)
-size_t ws_state_bytes(const Relation &R) { return ((size_t)R.n_slots * 2 * sizeof(float2) + 255) & ~(size_t)255; }
-size_t ws_scratch_bytes(const Relation &R) { return ((size_t)R.e_kept * sizeof(float) + 255) & ~(size_t)255; }
+size_t ws_state_bytes(const Relation &R) { return align256((size_t)R.n_slots * 2 * sizeof(float2)); }
+size_t ws_scratch_bytes(const Relation &R) { return align256((size_t)R.e_kept * sizeof(float)); }
 
 int check_plan(const pea_plan *plan, int relation, const char *who) {
     PEA_REQUIRE(plan && relation >= 0 && relation < (int)plan->rels.size(), PEA_ERR_ARG, "%s: bad relation", who);

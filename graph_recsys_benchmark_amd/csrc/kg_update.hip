@@ -28,8 +28,6 @@
 namespace pea {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / kWave;
 constexpr int kTR = 16;                       // rows of one tile: one MFMA operand
@@ -90,9 +88,6 @@ struct KguArgs {
 
 extern __shared__ __attribute__((aligned(16))) float kgu_smem[];
 
-__device__ __forceinline__ float4 ld4k(const float *p) { return *reinterpret_cast<const float4 *>(p); }
-__device__ __forceinline__ void st4k(float *p, float4 v) { *reinterpret_cast<float4 *>(p) = v; }
-
 // columns [c0, c0 + OC) of a [in, out] weight into its LDS image [IP][LDW]; rows >= in and columns >= out are zero
 __device__ __forceinline__ void stage_weight(const KguArgs &a, const float *w, float *img, int c0) {
     for (int i = threadIdx.x; i < a.IP * a.OC; i += kThreads) {
@@ -110,11 +105,11 @@ __device__ __forceinline__ void stage_rows(const KguArgs &a, int64_t row0, float
         const int64_t row = row0 + r;
         float4 xv = make_float4(0.f, 0.f, 0.f, 0.f), sv = xv;
         if (row < a.N) {
-            xv = ld4k(a.x + row * a.ldx + c);
-            sv = ld4k(a.s + row * a.lds + c);
+            xv = ld4(a.x + row * a.ldx + c);
+            sv = ld4(a.s + row * a.lds + c);
         }
-        st4k(A1t + r * a.LDA + c, make_float4(xv.x + sv.x, xv.y + sv.y, xv.z + sv.z, xv.w + sv.w));
-        if (TWO) st4k(A2t + r * a.LDA + c, make_float4(xv.x * sv.x, xv.y * sv.y, xv.z * sv.z, xv.w * sv.w));
+        st4(A1t + r * a.LDA + c, make_float4(xv.x + sv.x, xv.y + sv.y, xv.z + sv.z, xv.w + sv.w));
+        if (TWO) st4(A2t + r * a.LDA + c, make_float4(xv.x * sv.x, xv.y * sv.y, xv.z * sv.z, xv.w * sv.w));
     }
 }
 
@@ -174,7 +169,7 @@ __global__ __launch_bounds__(kThreads) void kg_update_fwd_kernel(const KguArgs a
                 if (row >= a.N || col >= a.out) continue;
                 float b[4] = {0.f, 0.f, 0.f, 0.f}, k[4], scale, y[4];
                 if (a.bias) {
-                    const float4 bv = ld4k(a.bias + col);
+                    const float4 bv = ld4(a.bias + col);
                     b[0] = bv.x; b[1] = bv.y; b[2] = bv.z; b[3] = bv.w;
                 }
                 keep4(a, row, col, k, scale);
@@ -188,7 +183,7 @@ __global__ __launch_bounds__(kThreads) void kg_update_fwd_kernel(const KguArgs a
                         y[r] = lrelu(z1[r] + z2[r], a.slope);
                     if (a.keep) y[r] = y[r] * k[r] * scale;
                 }
-                st4k(a.o + row * a.ldo + col, make_float4(y[0], y[1], y[2], y[3]));
+                st4(a.o + row * a.ldo + col, make_float4(y[0], y[1], y[2], y[3]));
             }
         }
     }
@@ -234,7 +229,7 @@ __global__ __launch_bounds__(kThreads) void kg_update_bwd_kernel(const KguArgs a
                 float gv[4] = {0.f, 0.f, 0.f, 0.f}, d1[4], d2[4];
                 float b[4] = {0.f, 0.f, 0.f, 0.f};
                 if (row < a.N && col < a.out) {
-                    const float4 t = ld4k(a.g + row * a.ldg + col);
+                    const float4 t = ld4(a.g + row * a.ldg + col);
                     float k[4], scale;
                     keep4(a, row, col, k, scale);
                     gv[0] = t.x; gv[1] = t.y; gv[2] = t.z; gv[3] = t.w;
@@ -243,7 +238,7 @@ __global__ __launch_bounds__(kThreads) void kg_update_bwd_kernel(const KguArgs a
                         for (int r = 0; r < 4; ++r) gv[r] = gv[r] * k[r] * scale;
                     }
                     if (a.bias) {
-                        const float4 bv = ld4k(a.bias + col);
+                        const float4 bv = ld4(a.bias + col);
                         b[0] = bv.x; b[1] = bv.y; b[2] = bv.z; b[3] = bv.w;
                     }
                 }
@@ -259,9 +254,9 @@ __global__ __launch_bounds__(kThreads) void kg_update_bwd_kernel(const KguArgs a
                         d1[r] = d2[r] = gv[r] * ((z1[r] + z2[r]) > 0.f ? 1.f : a.slope);
                     }
                 }
-                st4k(Z1t + n * a.LDZ + lc, make_float4(d1[0], d1[1], d1[2], d1[3]));
-                if (TWO) st4k(Z2t + n * a.LDZ + lc, make_float4(d2[0], d2[1], d2[2], d2[3]));
-                if (a.kind == PEA_KGU_KGAT) st4k(Gt + n * a.LDZ + lc, make_float4(gv[0], gv[1], gv[2], gv[3]));
+                st4(Z1t + n * a.LDZ + lc, make_float4(d1[0], d1[1], d1[2], d1[3]));
+                if (TWO) st4(Z2t + n * a.LDZ + lc, make_float4(d2[0], d2[1], d2[2], d2[3]));
+                if (a.kind == PEA_KGU_KGAT) st4(Gt + n * a.LDZ + lc, make_float4(gv[0], gv[1], gv[2], gv[3]));
             }
             __syncthreads();
             // ---- dA^T = W dZ^T per input tile v: register r of lane (n, g) = dA[row n][input 16 v + 4 g + r]
@@ -277,18 +272,18 @@ __global__ __launch_bounds__(kThreads) void kg_update_bwd_kernel(const KguArgs a
                 if (row >= a.N || col >= a.in) continue;
                 float4 rx = make_float4(e1[0], e1[1], e1[2], e1[3]), rs = rx;
                 if (TWO) {
-                    const float4 xv = ld4k(a.x + row * a.ldx + col), sv = ld4k(a.s + row * a.lds + col);
+                    const float4 xv = ld4(a.x + row * a.ldx + col), sv = ld4(a.s + row * a.lds + col);
                     rx = make_float4(e1[0] + e2[0] * sv.x, e1[1] + e2[1] * sv.y, e1[2] + e2[2] * sv.z, e1[3] + e2[3] * sv.w);
                     rs = make_float4(e1[0] + e2[0] * xv.x, e1[1] + e2[1] * xv.y, e1[2] + e2[2] * xv.z, e1[3] + e2[3] * xv.w);
                 }
                 float *px = a.dx + row * a.lddx + col, *ps = a.dsum + row * a.ldds + col;
                 if (c0 > 0) {      // a later output-column chunk adds its part to what the earlier ones left
-                    const float4 ox = ld4k(px), os = ld4k(ps);
+                    const float4 ox = ld4(px), os = ld4(ps);
                     rx = make_float4(ox.x + rx.x, ox.y + rx.y, ox.z + rx.z, ox.w + rx.w);
                     rs = make_float4(os.x + rs.x, os.y + rs.y, os.z + rs.z, os.w + rs.w);
                 }
-                st4k(px, rx);
-                st4k(ps, rs);
+                st4(px, rx);
+                st4(ps, rs);
             }
             // ---- dW += A^T dZ over the tile's 16 rows (4 k-steps): register r of lane (n, g) = dW[16 v + 4 g + r][16 u + n]
 #pragma unroll
@@ -341,17 +336,8 @@ __global__ __launch_bounds__(256) void kg_update_dw_kernel(int n_wg, int in, int
     *dst = acc;
 }
 
-// more than 64 KB of dynamic LDS must be asked for once per kernel (one device per process: include/peahip.h, conventions)
-int raise_lds(const void *kernel, size_t lds) {
-    static const void *raised[16];
-    static int n_raised = 0;
-    if (lds <= 64 * 1024) return PEA_OK;
-    for (int i = 0; i < n_raised; ++i)
-        if (raised[i] == kernel) return PEA_OK;
-    PEA_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget));
-    if (n_raised < 16) raised[n_raised++] = kernel;
-    return PEA_OK;
-}
+// what a kernel's dynamic-LDS limit is raised to: once, to the most any configuration asks for
+size_t lds_limit(const Cfg &c) { return c.lds > 64 * 1024 ? kLdsBudget : 0; }
 
 bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
@@ -393,10 +379,10 @@ extern "C" int pea_kg_update_forward(int64_t N, int kind, int in_width, int out_
     const double flop_bytes = (double)N * 4.0 * (2.0 * in_width + out_width) + (keep ? (double)N * out_width : 0.0);
     ProfScope ps("kg_update_fwd", stream, flop_bytes);
     if (c.nw == 2) {
-        PEA_TRY(raise_lds(reinterpret_cast<const void *>(&kg_update_fwd_kernel<true>), c.lds));
+        PEA_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(&kg_update_fwd_kernel<true>), lds_limit(c)));
         PEA_LAUNCH(kg_update_fwd_kernel<true>, grid, dim3(kThreads), c.lds, stream, a);
     } else {
-        PEA_TRY(raise_lds(reinterpret_cast<const void *>(&kg_update_fwd_kernel<false>), c.lds));
+        PEA_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(&kg_update_fwd_kernel<false>), lds_limit(c)));
         PEA_LAUNCH(kg_update_fwd_kernel<false>, grid, dim3(kThreads), c.lds, stream, a);
     }
     PEA_HIP(hipGetLastError());
@@ -415,10 +401,10 @@ int launch_bwd(const Cfg &c, const KguArgs &a, dim3 grid, hipStream_t stream) {
     if (c.nw == 2) {
         constexpr int NT2 = NT > 8 ? 8 : NT;      // make_cfg never asks for more with two weights
         PEA_REQUIRE(c.NT <= 8, PEA_ERR_ARG, "kg_update_backward: %d dW tiles per wave", c.NT);
-        PEA_TRY(raise_lds(reinterpret_cast<const void *>(&kg_update_bwd_kernel<NT2, true>), c.lds));
+        PEA_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(&kg_update_bwd_kernel<NT2, true>), lds_limit(c)));
         PEA_LAUNCH((kg_update_bwd_kernel<NT2, true>), grid, dim3(kThreads), c.lds, stream, a);
     } else {
-        PEA_TRY(raise_lds(reinterpret_cast<const void *>(&kg_update_bwd_kernel<NT, false>), c.lds));
+        PEA_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(&kg_update_bwd_kernel<NT, false>), lds_limit(c)));
         PEA_LAUNCH((kg_update_bwd_kernel<NT, false>), grid, dim3(kThreads), c.lds, stream, a);
     }
     PEA_HIP(hipGetLastError());
@@ -456,7 +442,7 @@ extern "C" int pea_kg_update_backward(int64_t N, int kind, int in_width, int out
     a.x = x; a.s = s; a.w1 = w1; a.w2 = w2; a.bias = bias; a.ldx = ldx; a.lds = lds;
     a.slope = negative_slope; a.keep = keep; a.keep_scale = keep_scale;
     a.g = g_out; a.ldg = ldg; a.dx = dx; a.dsum = ds; a.lddx = lddx; a.ldds = ldds;
-    a.part = reinterpret_cast<float *>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~uintptr_t(255));
+    a.part = aligned_ws(workspace);
     a.want_dbias = dbias ? 1 : 0;
     a.IP = c.IP; a.OC = c.OC; a.LDA = c.LDA; a.LDW = c.LDW; a.LDZ = c.LDZ;
     const int64_t tiles = (N + kTR - 1) / kTR;

@@ -30,10 +30,6 @@ namespace pea {
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float4 ld4m(const float *p) { return *reinterpret_cast<const float4 *>(p); }
-
 
 // image of one channel, in floats: [Wt0: HT * ET * 64 * 4][Wt1: HT * 4 * 64 * 4][b0p: 2 * HT * 16]  (ET = K / 8, HT = hidden / 32;
 // GAT / GCN: Wt0 = hidden / 16 x emb / 16 fragments of 64 lanes x 4, Wt1 = 2 output tiles x hidden / 16 fragments, b0 natural)
@@ -159,7 +155,7 @@ __device__ __forceinline__ void mlp2_load(const Mlp2Launch &L, const int *rows, 
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
 #pragma unroll
-        for (int j = 0; j < ET / 2; ++j) in.xa[h][j] = ld4m(src[h] + 16 * j);
+        for (int j = 0; j < ET / 2; ++j) in.xa[h][j] = ld4(src[h] + 16 * j);
     }
 }
 
@@ -195,7 +191,7 @@ __device__ __forceinline__ void mlp2_hidden(const Mlp2Launch &L, const Mlp2Chan 
     for (int j = 0; j < EJ; ++j) {
 #pragma unroll
         for (int t = 0; t < 4; ++t) {   // one LDS read of the weight fragment, two independent chains
-            const float4 w = ld4m(wt0 + ((size_t)((t0 + t) * EJ + j) * 64 + lane) * 4);
+            const float4 w = ld4(wt0 + ((size_t)((t0 + t) * EJ + j) * 64 + lane) * 4);
             acc[0][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.x, cur.xa[0][j].x, acc[0][t], 0, 0, 0);
             acc[1][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.x, cur.xa[1][j].x, acc[1][t], 0, 0, 0);
             acc[0][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.y, cur.xa[0][j].y, acc[0][t], 0, 0, 0);
@@ -211,7 +207,7 @@ __device__ __forceinline__ void mlp2_hidden(const Mlp2Launch &L, const Mlp2Chan 
         float *hrow = (TRAIN && cur.valid[h]) ? L.h0 + (int64_t)cur.row[h] * L.ld_h0 + C.h0_col + 16 * t0 + 4 * g : nullptr;
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-            const float4 b = ld4m(b0p + 16 * (t0 + t) + 4 * g);
+            const float4 b = ld4(b0p + 16 * (t0 + t) + 4 * g);
             acc[h][t] = f32x4{fmaxf(acc[h][t][0] + b.x, 0.f), fmaxf(acc[h][t][1] + b.y, 0.f), fmaxf(acc[h][t][2] + b.z, 0.f),
                               fmaxf(acc[h][t][3] + b.w, 0.f)};
             if (TRAIN && hrow)
@@ -224,7 +220,7 @@ __device__ __forceinline__ void mlp2_hidden(const Mlp2Launch &L, const Mlp2Chan 
 __device__ __forceinline__ void mlp2_out_steps(const float *wf, int lane, const f32x4 (&acc)[2][4], f32x4 (&out)[2]) {
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
-        const float4 w = ld4m(wf + ((size_t)t * 64 + lane) * 4);
+        const float4 w = ld4(wf + ((size_t)t * 64 + lane) * 4);
         out[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.x, acc[0][t][0], out[0], 0, 0, 0);
         out[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.x, acc[1][t][0], out[1], 0, 0, 0);
         out[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.y, acc[0][t][1], out[0], 0, 0, 0);
@@ -315,7 +311,7 @@ __global__ __launch_bounds__((Mlp2Cfg<ET, HT>::kThreads)) void mlp2_kernel(const
         const int c0 = grp * L.per_pass;
         const int nc = min(L.per_pass, L.n - c0);
         for (int idx = threadIdx.x * 4; idx < nc * IMG; idx += kMlp2Threads * 4)   // IMG is a multiple of 4
-            *reinterpret_cast<float4 *>(mlp2_lds + idx) = ld4m(L.images + (size_t)c0 * IMG + idx);
+            *reinterpret_cast<float4 *>(mlp2_lds + idx) = ld4(L.images + (size_t)c0 * IMG + idx);
         __syncthreads();
         const int64_t n_items = n_tiles * nc;
         const bool two_tiles = L.out > 16;   // uniform: the second output tile exists only for out > 16
@@ -356,7 +352,7 @@ __device__ __forceinline__ void sage_load_mean(const Mlp2Launch &L, const Mlp2Ch
     const bool have = valid && C.deg0[row] == 0;   // rows without incoming edges were not aggregated: their mean is 0
     const float *src = L.a0 + row * L.ld_a0 + C.a0_col;
 #pragma unroll
-    for (int q = 0; q < ET; ++q) a[q] = have ? ld4m(src + 4 * (2 * q + half)) : make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int q = 0; q < ET; ++q) a[q] = have ? ld4(src + 4 * (2 * q + half)) : make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
 template <int ET, int HT>
@@ -373,7 +369,7 @@ __global__ __launch_bounds__(512) void mlp2_sage_kernel(const Mlp2Launch L, cons
     const int c0 = grp * L.per_pass;
     const int nc = min(L.per_pass, L.n - c0);
     for (int idx = threadIdx.x * 4; idx < nc * IMG; idx += 512 * 4)
-        *reinterpret_cast<float4 *>(mlp2_lds + idx) = ld4m(L.images + (size_t)c0 * IMG + idx);
+        *reinterpret_cast<float4 *>(mlp2_lds + idx) = ld4(L.images + (size_t)c0 * IMG + idx);
     __syncthreads();
     const int64_t n_items = n_tiles * nc;
     float4 a[ET], b[ET];
@@ -391,7 +387,7 @@ __global__ __launch_bounds__(512) void mlp2_sage_kernel(const Mlp2Launch L, cons
         {
             const float *src = L.x + row * L.ldx;
 #pragma unroll
-            for (int q = 0; q < ET; ++q) b[q] = valid ? ld4m(src + 4 * (2 * q + half)) : make_float4(0.f, 0.f, 0.f, 0.f);
+            for (int q = 0; q < ET; ++q) b[q] = valid ? ld4(src + 4 * (2 * q + half)) : make_float4(0.f, 0.f, 0.f, 0.f);
         }
         f32x16 acc[HT];
 #pragma unroll
@@ -402,7 +398,7 @@ __global__ __launch_bounds__(512) void mlp2_sage_kernel(const Mlp2Launch L, cons
         for (int q = 0; q < ET; ++q) {
 #pragma unroll
             for (int t = 0; t < HT; ++t) {
-                const float4 w = ld4m(wt0 + ((size_t)(t * KT + q) * 64 + lane) * 4);
+                const float4 w = ld4(wt0 + ((size_t)(t * KT + q) * 64 + lane) * 4);
                 acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(w.x, a[q].x, acc[t], 0, 0, 0);
                 acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(w.y, a[q].y, acc[t], 0, 0, 0);
                 acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(w.z, a[q].z, acc[t], 0, 0, 0);
@@ -420,7 +416,7 @@ __global__ __launch_bounds__(512) void mlp2_sage_kernel(const Mlp2Launch L, cons
         for (int q = 0; q < ET; ++q) {
 #pragma unroll
             for (int t = 0; t < HT; ++t) {
-                const float4 w = ld4m(wt0 + ((size_t)(t * KT + ET + q) * 64 + lane) * 4);
+                const float4 w = ld4(wt0 + ((size_t)(t * KT + ET + q) * 64 + lane) * 4);
                 acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(w.x, b[q].x, acc[t], 0, 0, 0);
                 acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(w.y, b[q].y, acc[t], 0, 0, 0);
                 acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(w.z, b[q].z, acc[t], 0, 0, 0);
@@ -436,8 +432,8 @@ __global__ __launch_bounds__(512) void mlp2_sage_kernel(const Mlp2Launch L, cons
         for (int t = 0; t < HT; ++t) {
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                const float4 w = ld4m(wt1 + ((size_t)(t * 4 + g) * 64 + lane) * 4);
-                const float4 bb = ld4m(b0p + t * 16 + 4 * g);
+                const float4 w = ld4(wt1 + ((size_t)(t * 4 + g) * 64 + lane) * 4);
+                const float4 bb = ld4(b0p + t * 16 + 4 * g);
                 const float4 hv = make_float4(fmaxf(acc[t][4 * g + 0] + bb.x, 0.f), fmaxf(acc[t][4 * g + 1] + bb.y, 0.f),
                                               fmaxf(acc[t][4 * g + 2] + bb.z, 0.f), fmaxf(acc[t][4 * g + 3] + bb.w, 0.f));
                 if (hrow) *reinterpret_cast<float4 *>(hrow + 32 * t + 8 * g) = hv;
@@ -462,7 +458,7 @@ __global__ __launch_bounds__(512) void mlp2_sage_kernel(const Mlp2Launch L, cons
                 } else if (j0 < 2 * L.out) {
                     const int j = j0 - L.out;
                     if (C.b1) {
-                        const float4 b1 = ld4m(C.b1 + j);
+                        const float4 b1 = ld4(C.b1 + j);
                         o = make_float4(o.x + b1.x, o.y + b1.y, o.z + b1.z, o.w + b1.w);
                     }
                     *reinterpret_cast<float4 *>(dst_r + j) = o;
@@ -503,15 +499,10 @@ static int launch_mlp2_v(Mlp2Launch L, const int *rows, int64_t n_rows, hipStrea
     L.per_pass = (L.n + passes - 1) / passes;
     const size_t lds = (size_t)L.per_pass * img;
     const bool train = !SAGE && L.h0 != nullptr;
-    static size_t lds_set_v[2] = {0, 0};          // per kernel instantiation
-    size_t &lds_set = lds_set_v[train ? 1 : 0];
     const void *fn = SAGE ? reinterpret_cast<const void *>(&mlp2_sage_kernel<ET, HT>)
                           : train ? reinterpret_cast<const void *>(&mlp2_kernel<ET, HT, true>)
                                   : reinterpret_cast<const void *>(&mlp2_kernel<ET, HT, false>);
-    if (lds > lds_set) {
-        PEA_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        lds_set = lds;
-    }
+    PEA_TRY(ensure_dynamic_lds(fn, lds));
     int n_cu = 0;
     PEA_TRY(device_cu_count(&n_cu));
     const int64_t n_tiles = (n_rows + 31) / 32;

@@ -24,8 +24,6 @@ namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-__device__ __forceinline__ float4 ld4b(const float *p) { return *reinterpret_cast<const float4 *>(p); }
-
 constexpr int kMaxBwdChan = 32;
 struct Mlp2BwdChan {
     const float *w0, *w1;               // GAT lin.weight of layer 1 [hid, emb] and of layer 2 [out, hid] (SAGE: lin_rel.weight)
@@ -100,12 +98,12 @@ __device__ __forceinline__ void bwd_load(const Mlp2BwdLaunch &L, int64_t n_rows,
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
         const int c = 4 * (2 * q + half);
-        in.d[q] = (in.valid && c < L.out) ? ld4b((c < L.out_a ? dsrc : rsrc) + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+        in.d[q] = (in.valid && c < L.out) ? ld4((c < L.out_a ? dsrc : rsrc) + c) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
 #pragma unroll
     for (int t = 0; t < HT; ++t)
 #pragma unroll
-        for (int g = 0; g < 4; ++g) in.h[t * 4 + g] = ld4b(hsrc + 32 * t + 8 * g);   // row 0 for invalid lanes: harmless
+        for (int g = 0; g < 4; ++g) in.h[t * 4 + g] = ld4(hsrc + 32 * t + 8 * g);   // row 0 for invalid lanes: harmless
 }
 
 template <int HT, int OT, int NQ, bool SAGE>
@@ -122,7 +120,7 @@ __global__ __launch_bounds__(512) void mlp2_bwd_kernel(const Mlp2BwdLaunch L, in
     const int c0 = grp * L.per_pass;
     const int nc = min(L.per_pass, L.n - c0);
     for (int idx = threadIdx.x * 4; idx < nc * IMG; idx += 512 * 4)
-        *reinterpret_cast<float4 *>(bwd_lds + idx) = ld4b(L.images + (size_t)c0 * IMG + idx);
+        *reinterpret_cast<float4 *>(bwd_lds + idx) = ld4(L.images + (size_t)c0 * IMG + idx);
     __syncthreads();
     const int64_t n_items = n_tiles * nc;
     BwdIn<HT, NQ> cur, nxt;
@@ -143,7 +141,7 @@ __global__ __launch_bounds__(512) void mlp2_bwd_kernel(const Mlp2BwdLaunch L, in
         for (int q = 0; q < NQ; ++q) {
 #pragma unroll
             for (int t = 0; t < HT; ++t) {
-                const float4 w = ld4b(w1t + ((size_t)(t * NQ + q) * 64 + lane) * 4);
+                const float4 w = ld4(w1t + ((size_t)(t * NQ + q) * 64 + lane) * 4);
                 acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(w.x, cur.d[q].x, acc[t], 0, 0, 0);
                 acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(w.y, cur.d[q].y, acc[t], 0, 0, 0);
                 acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(w.z, cur.d[q].z, acc[t], 0, 0, 0);
@@ -166,7 +164,7 @@ __global__ __launch_bounds__(512) void mlp2_bwd_kernel(const Mlp2BwdLaunch L, in
                 if (cur.valid) *reinterpret_cast<float4 *>(zrow + 32 * t + 8 * g) = z;
 #pragma unroll
                 for (int te = 0; te < OT; ++te) {
-                    const float4 w = ld4b(w0t + ((size_t)((te * HT + t) * 4 + g) * 64 + lane) * 4);
+                    const float4 w = ld4(w0t + ((size_t)((te * HT + t) * 4 + g) * 64 + lane) * 4);
                     out[te] = __builtin_amdgcn_mfma_f32_32x32x2f32(w.x, z.x, out[te], 0, 0, 0);
                     out[te] = __builtin_amdgcn_mfma_f32_32x32x2f32(w.y, z.y, out[te], 0, 0, 0);
                     out[te] = __builtin_amdgcn_mfma_f32_32x32x2f32(w.z, z.z, out[te], 0, 0, 0);
@@ -198,7 +196,7 @@ __global__ __launch_bounds__(512) void mlp2_bwd_kernel(const Mlp2BwdLaunch L, in
                                                  hv.z > 0.f ? acc[t][4 * g + 2] : 0.f, hv.w > 0.f ? acc[t][4 * g + 3] : 0.f);
 #pragma unroll
                     for (int te = 0; te < OT; ++te) {
-                        const float4 w = ld4b(w0r + ((size_t)((te * HT + t) * 4 + g) * 64 + lane) * 4);
+                        const float4 w = ld4(w0r + ((size_t)((te * HT + t) * 4 + g) * 64 + lane) * 4);
                         out[te] = __builtin_amdgcn_mfma_f32_32x32x2f32(w.x, z.x, out[te], 0, 0, 0);
                         out[te] = __builtin_amdgcn_mfma_f32_32x32x2f32(w.y, z.y, out[te], 0, 0, 0);
                         out[te] = __builtin_amdgcn_mfma_f32_32x32x2f32(w.z, z.z, out[te], 0, 0, 0);
@@ -231,12 +229,7 @@ int launch_bwd_v(Mlp2BwdLaunch L, int64_t n_rows, hipStream_t stream) {
     const int passes = (L.n + L.per_pass - 1) / L.per_pass;
     L.per_pass = (L.n + passes - 1) / passes;
     const size_t lds = (size_t)L.per_pass * img;
-    static size_t lds_set = 0;
-    if (lds > lds_set) {
-        PEA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&mlp2_bwd_kernel<HT, OT, NQ, SAGE>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        lds_set = lds;
-    }
+    PEA_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(&mlp2_bwd_kernel<HT, OT, NQ, SAGE>), lds));
     int n_cu = 0;
     PEA_TRY(device_cu_count(&n_cu));
     const int64_t n_tiles = (n_rows + 31) / 32;

@@ -1,6 +1,7 @@
-// Device helpers shared by the scoring kernels of fuse_score.hip and ablate.hip: the fc2(relu(fc1([u || i]))) scorer of
-// graph_recsys_benchmark/models/base.py:208-214 in ONE order of operations, so that every kernel that scores a pair gives
-// the same bits for it, and the per-device error flag the id-range checks report through.
+// Device helpers shared by the scoring kernels of fuse_score.hip, ablate.hip and dot_score.hip, each defined ONCE so that
+// every kernel that uses one gives the same bits: the fc2(relu(fc1([u || i]))) scorer of graph_recsys_benchmark/models/
+// base.py:208-214, the online-softmax step and channel logit of the fusion, the ranking of one user by one wave
+// (solvers.py:85-96), and the per-device error flag the id-range checks report through.
 #ifndef PEA_SCORE_COMMON_H_
 #define PEA_SCORE_COMMON_H_
 
@@ -21,8 +22,6 @@ inline int lanes_for_r(int R) {
 }
 
 namespace {
-
-__device__ __forceinline__ float4 ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
 
 // fc2(relu(fc1([u || i])))  with fc1_w [R, 2R] staged in LDS by the caller
 __device__ __forceinline__ float mlp_score(const float *__restrict__ ur, const float *__restrict__ ir, int R,
@@ -90,6 +89,94 @@ __device__ __forceinline__ void stage_mlp(int R, const float *fc1_w, const float
 __device__ __forceinline__ float log_sigmoid_ref(float d) {
     // the reference takes sigmoid then log in fp32 with no clamp (may give -inf); keep that
     return logf(1.0f / (1.0f + expf(-d)));
+}
+
+// The MLP scorer of one user for rank_one_user: stage_mlp's weights in LDS and, at the reference's repr_dim R == 16, the
+// user's row in registers (same arithmetic, same order as mlp_score).
+struct MlpScorer {
+    const float *repr, *w1, *b1, *w2;
+    float b2;
+    int R;
+    int64_t u;
+    float4 ur[4];
+    __device__ __forceinline__ MlpScorer(const float *repr_, int64_t u_, int R_, float b2_)
+        : repr(repr_), w1(smem), b1(smem + 2 * R_ * R_), w2(smem + 2 * R_ * R_ + R_), b2(b2_), R(R_), u(u_) {
+        if (R == 16) load_row<4>(repr + u * R, ur);
+    }
+    __device__ __forceinline__ float operator()(int64_t i) const {
+        if (R == 16) {
+            float4 ir[4];
+            load_row<4>(repr + i * R, ir);
+            return mlp_score_reg<4>(ur, ir, w1, b1, w2, b2);
+        }
+        return mlp_score(repr + u * R, repr + i * R, R, w1, b1, w2, b2);
+    }
+};
+
+// One wave ranks one user: lanes score the C candidates 64 per pass (candidate 0 is the positive), then rank / auc / loss
+// by wave reductions in a fixed order.  score(i) is the user's score of node i; ids(base, c) is the id of candidate c in
+// the pass that starts at `base`; `orow` is the user's row in the outputs (each optional).
+template <class Scorer, class Ids>
+__device__ __forceinline__ void rank_one_user(const Scorer &score, const Ids &ids, int C, int64_t N, int lane, int64_t orow,
+                                              float *scores, int32_t *rank, float *auc, float *loss, int *err) {
+    float pos = 0.f;
+    int higher = 0, gt = 0;
+    float lsum = 0.f;
+    for (int base = 0; base < C; base += kWave) {
+        const int c = base + lane;
+        float sc = 0.f;
+        bool ok = c < C;
+        if (ok) {
+            const int64_t i = ids(base, c);
+            if (i < 0 || i >= N) {
+                atomicOr(err, 1);
+                ok = false;
+            } else {
+                sc = score(i);
+                if (scores) scores[orow * C + c] = sc;
+            }
+        }
+        if (base == 0) pos = __shfl(sc, 0);
+        if (ok && c > 0) {
+            // torch.sort(descending) places a negative ahead of the positive only if it scores strictly
+            // higher (stable order keeps index 0 first among ties)
+            higher += sc > pos ? 1 : 0;
+            gt += pos > sc ? 1 : 0;
+            lsum += log_sigmoid_ref(pos - sc);
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        higher += __shfl_xor(higher, off);
+        gt += __shfl_xor(gt, off);
+        lsum += __shfl_xor(lsum, off);
+    }
+    if (lane == 0) {
+        if (rank) rank[orow] = higher;
+        if (auc) auc[orow] = (float)gt / (float)(C - 1);
+        if (loss) loss[orow] = -lsum;
+    }
+}
+
+// One online-softmax step of the channel fusion (channel order).
+__device__ __forceinline__ void softmax_step(float sc, const float4 &x, float &m, float &s, float4 &acc) {
+    const float mn = fmaxf(m, sc);
+    const float f = expf(m - mn), w = expf(sc - mn);
+    s = s * f + w;
+    acc.x = acc.x * f + w * x.x;
+    acc.y = acc.y * f + w * x.y;
+    acc.z = acc.z * f + w * x.z;
+    acc.w = acc.w * f + w * x.w;
+    m = mn;
+}
+
+// the channel logit x_p . att_p of the fusion: per-lane partial, then the G-lane butterfly
+template <int G>
+__device__ __forceinline__ float chan_logit(const float4 &x, const float4 &a, bool in_row) {
+    float sc = in_row ? (x.x * a.x + x.y * a.y) + (x.z * a.z + x.w * a.w) : 0.f;
+#pragma unroll
+    for (int off = 1; off < G; off <<= 1) sc += __shfl_xor(sc, off);
+    return sc;
 }
 
 }  // namespace

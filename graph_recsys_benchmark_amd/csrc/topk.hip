@@ -8,16 +8,13 @@
 // it is computed (top-K scan, rank scan, the exclusion walk of rank_full, any U / K / item split).  No float atomics.
 #include <algorithm>
 
-#include "common.h"
+#include "score_common.h"
 #include "topk_select.h"
 
 namespace pea {
 namespace {
 
 constexpr int kTileFloats = 2048;   // LDS tile of item rows: 8 KB = 128 rows at R = 16
-constexpr int kMaxSplits = 64;
-
-__device__ __forceinline__ float4 ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
 
 // rows are padded to RP in {16, 32, 64} columns with zeros (A, B and fc2_w alike): a padded column adds
 // fma(max(0 + 0, 0), 0, o) = o, so the padding changes no bit of the score
@@ -29,24 +26,13 @@ struct Layout {
     size_t off_w2 = 0, off_a = 0, off_p = 0, off_b = 0, off_part = 0, bytes = 0;
 };
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // How a call is cut: NT users per workgroup (one per lane), the catalogue in S item ranges of `span` items so that few
 // users still fill the machine.  Depends on (U, n_items, K, R) only, so the workspace query and the call agree.
 Layout make_layout(int64_t U, int64_t n_items, int K, int R) {
     Layout L;
     L.RP = padded_r(R);
     L.NT = K <= 32 ? 128 : 64;      // a lane's K-entry list is an LDS column of 8 K bytes
-    const int tile_items = kTileFloats / L.RP;
-    const int64_t user_blocks = std::max<int64_t>((U + L.NT - 1) / L.NT, 1);
-    int64_t s = (1024 + user_blocks - 1) / user_blocks;                       // ~4 workgroups per CU
-    s = std::min<int64_t>(s, std::max<int64_t>(n_items / 512, 1));           // an item range is worth >= 512 items
-    s = std::min<int64_t>(s, std::min<int64_t>(kMaxSplits, kMaxMerge / std::max(K, 1)));
-    s = std::max<int64_t>(s, 1);
-    int64_t span = (std::max<int64_t>(n_items, 1) + s - 1) / s;
-    span = (span + tile_items - 1) / tile_items * tile_items;
-    L.span = span;
-    L.S = (int)std::max<int64_t>((n_items + span - 1) / span, 1);
+    catalogue_split(std::max<int64_t>((U + L.NT - 1) / L.NT, 1), n_items, std::max(K, 1), kTileFloats / L.RP, &L.S, &L.span);
     size_t o = 256;                                                           // error flag
     L.off_w2 = o; o = align256(o + (size_t)L.RP * 4);
     L.off_a = o;  o = align256(o + (size_t)std::max<int64_t>(U, 1) * L.RP * 4);
@@ -164,10 +150,9 @@ extern __shared__ float topk_smem[];
 
 // A lane owns one user (its half A[q] in RP registers); the workgroup streams its item range through an LDS tile and all
 // lanes read the same item row at once (identical addresses: broadcast).
-//   RANK = false: the lane keeps its K best (score, index) as a column of LDS, unordered, and knows the worst of them
-//     (lowest score, highest index among equals).  Items arrive in ascending id, so only a strictly higher score can
-//     displace the worst; only such a score is looked up in the exclusion list, replaces the worst entry, and the column
-//     is rescanned for the new worst.  The (user, range) column goes to the workspace for topk_merge.
+//   RANK = false: the lane keeps its K best (score, index) in the list of topk_select.h.  Only a score above the list's
+//     threshold is looked up in the exclusion list and inserted.  The (user, range) column goes to the workspace for
+//     topk_merge.
 //   RANK = true: two counters, s > pos and s < pos, over every item of the range (exclusions are taken out afterwards by
 //     rank_full_kernel, exact because a pair's score has the same bits there).
 template <int RP, bool RANK, int NT>
@@ -190,6 +175,9 @@ __global__ __launch_bounds__(NT) void topk_scan_kernel(const ScanArgs g) {
     if (RANK) {
         pos = pair_score<RP>(a, g.P + qr * RP, g.w2, b2);
     } else {
+        // list_init of topk_select.h, written out: with the call inlined here the compiler lowers the control flow of the
+        // scan loop below differently (same registers and occupancy, 2.8 % slower on the all-users shape;
+        // profiles/r08/scoring_refactor.md, section 3)
         for (int j = 0; j < K; ++j) {
             ls[j * NT + tid] = -INFINITY;
             li[j * NT + tid] = kEmpty;
@@ -222,21 +210,7 @@ __global__ __launch_bounds__(NT) void topk_scan_kernel(const ScanArgs g) {
                 } else if (s > thr) {
                     const int idx = (int)(t0 + j0 + jj);
                     if (ex_lo < ex_hi && in_sorted(g.excl_items, ex_lo, ex_hi, g.item_lo + idx)) continue;
-                    ls[wslot * NT + tid] = s;
-                    li[wslot * NT + tid] = idx;
-                    float w = ls[tid];
-                    int wi = li[tid];
-                    wslot = 0;
-                    for (int m = 1; m < K; ++m) {
-                        const float sc = ls[m * NT + tid];
-                        const int id = li[m * NT + tid];
-                        if (sc < w || (sc == w && id > wi)) {
-                            w = sc;
-                            wi = id;
-                            wslot = m;
-                        }
-                    }
-                    thr = w;
+                    list_insert(ls, li, NT, tid, K, s, idx, wslot, thr);
                 }
             }
         }
@@ -246,18 +220,13 @@ __global__ __launch_bounds__(NT) void topk_scan_kernel(const ScanArgs g) {
         g.part_i[((int64_t)blockIdx.y * 2) * g.U + q] = hi;
         g.part_i[((int64_t)blockIdx.y * 2 + 1) * g.U + q] = lo;
     } else {
-        for (int j = 0; j < K; ++j) {
-            const int64_t o = ((int64_t)blockIdx.y * K + j) * g.U + q;
-            g.part_s[o] = ls[j * NT + tid];
-            g.part_i[o] = li[j * NT + tid];
-        }
+        list_store(ls, li, NT, tid, K, blockIdx.y, g.U, q, g.part_s, g.part_i);
     }
 }
 
 // (the per-range columns are ordered by topk_merge_kernel of topk_select.h)
 
-// One thread per user: sums the ranges' counters, then walks the user's exclusion list once and takes out what those
-// items contributed (same pair_score on the same rows: the same bits the scan compared).
+// One thread per user: rank_finish of topk_select.h with pair_score on the same rows the scan compared (the same bits).
 template <int RP>
 __global__ __launch_bounds__(64) void rank_full_kernel(int64_t U, int S, int64_t n_items, int64_t item_lo,
                                                        const float *__restrict__ A, const float *__restrict__ B,
@@ -272,42 +241,14 @@ __global__ __launch_bounds__(64) void rank_full_kernel(int64_t U, int S, int64_t
     load_half<RP>(A + q * RP, a);
     const float b2 = fc2_b[0];
     const float pos = pair_score<RP>(a, P + q * RP, w2, b2);
-    int64_t hi = 0, lo = 0;
-    for (int s = 0; s < S; ++s) {
-        hi += part[((int64_t)s * 2) * U + q];
-        lo += part[((int64_t)s * 2 + 1) * U + q];
-    }
-    const int64_t pn = pos_items[q];
-    int64_t others = n_items - ((pn >= item_lo && pn < item_lo + n_items) ? 1 : 0);
-    if (excl_rowptr) {
-        for (int64_t e = excl_rowptr[q]; e < excl_rowptr[q + 1]; ++e) {
-            const int64_t node = excl_items[e];
-            if (node < item_lo || node >= item_lo + n_items || node == pn) continue;
-            const float s = pair_score<RP>(a, B + (node - item_lo) * RP, w2, b2);
-            hi -= s > pos ? 1 : 0;
-            lo -= s < pos ? 1 : 0;
-            --others;
-        }
-    }
-    if (rank) rank[q] = (int32_t)hi;
-    if (auc) auc[q] = others > 0 ? (float)lo / (float)others : 0.f;
-    if (pos_score) pos_score[q] = pos;
-}
-
-int read_err(int *err_dev, hipStream_t stream, const char *what) {
-    int h = 0;
-    PEA_HIP(hipMemcpyAsync(&h, err_dev, sizeof(int), hipMemcpyDeviceToHost, stream));
-    PEA_HIP(hipStreamSynchronize(stream));
-    PEA_REQUIRE(h == 0, PEA_ERR_RANGE, "%s: node id outside [0, num_nodes)", what);
-    return PEA_OK;
+    rank_finish(q, U, S, n_items, item_lo, pos, pos_items[q], excl_rowptr, excl_items, part,
+                [&](int64_t node) { return pair_score<RP>(a, B + (node - item_lo) * RP, w2, b2); }, rank, auc, pos_score);
 }
 
 template <int RP, bool RANK, int NT>
 int launch_scan_nt(const Layout &L, const ScanArgs &g, hipStream_t stream) {
     const size_t lds = (size_t)kTileFloats * 4 + (RANK ? 0 : (size_t)g.K * NT * 8);
-    if (lds > 64 * 1024)
-        PEA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&topk_scan_kernel<RP, RANK, NT>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    PEA_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(&topk_scan_kernel<RP, RANK, NT>), lds));
     const dim3 grid((unsigned)((g.U + NT - 1) / NT), (unsigned)L.S);
     PEA_LAUNCH((topk_scan_kernel<RP, RANK, NT>), grid, dim3(NT), lds, stream, g);
     PEA_HIP(hipGetLastError());
@@ -326,13 +267,8 @@ int launch_scan(const Layout &L, const ScanArgs &g, hipStream_t stream) {
     return launch_scan_nt<64, false, 64>(L, g, stream);
 }
 
-int check_common(const char *what, int64_t U, int R, int64_t num_nodes, int64_t item_lo, int64_t n_items) {
+int check_r(const char *what, int R) {
     PEA_REQUIRE(R > 0 && R % 4 == 0 && R <= 64, PEA_ERR_ARG, "%s: repr_dim %d must be a multiple of 4, <= 64", what, R);
-    PEA_REQUIRE(U >= 0 && num_nodes > 0 && n_items >= 0 && n_items < ((int64_t)1 << 31) - 1, PEA_ERR_ARG,
-                "%s: U=%lld n_items=%lld", what, (long long)U, (long long)n_items);
-    PEA_REQUIRE(item_lo >= 0 && item_lo + n_items <= num_nodes, PEA_ERR_RANGE,
-                "%s: catalogue [%lld, %lld) outside [0, num_nodes = %lld)", what, (long long)item_lo,
-                (long long)(item_lo + n_items), (long long)num_nodes);
     return PEA_OK;
 }
 
@@ -365,7 +301,8 @@ extern "C" int pea_recommend_topk(int64_t U, int K, int R, int64_t num_nodes, co
     using namespace pea;
     hipStream_t stream = (hipStream_t)stream_;
     PEA_REQUIRE(K >= 1 && K <= 128, PEA_ERR_ARG, "recommend_topk: K=%d (1..128)", K);
-    PEA_TRY(check_common("recommend_topk", U, R, num_nodes, item_lo, n_items));
+    PEA_TRY(check_r("recommend_topk", R));
+    PEA_TRY(check_catalogue("recommend_topk", U, num_nodes, item_lo, n_items));
     PEA_REQUIRE(repr && unids && fc1_w && fc1_b && fc2_w && fc2_b && out_items && out_scores && workspace, PEA_ERR_ARG,
                 "recommend_topk: null pointer");
     PEA_REQUIRE(!excl_rowptr || excl_items, PEA_ERR_ARG, "recommend_topk: excl_rowptr without excl_items");
@@ -395,7 +332,7 @@ extern "C" int pea_recommend_topk(int64_t U, int K, int R, int64_t num_nodes, co
                    (const float *)g.part_s, (const int *)g.part_i, out_items, out_scores);
         PEA_HIP(hipGetLastError());
     }
-    return read_err((int *)ws, stream, "recommend_topk");
+    return read_err_flag((int *)ws, stream, "recommend_topk");
 }
 
 extern "C" int pea_rank_full(int64_t U, int R, int64_t num_nodes, const float *repr, const int64_t *unids,
@@ -405,7 +342,8 @@ extern "C" int pea_rank_full(int64_t U, int R, int64_t num_nodes, const float *r
                              size_t workspace_bytes, void *stream_) {
     using namespace pea;
     hipStream_t stream = (hipStream_t)stream_;
-    PEA_TRY(check_common("rank_full", U, R, num_nodes, item_lo, n_items));
+    PEA_TRY(check_r("rank_full", R));
+    PEA_TRY(check_catalogue("rank_full", U, num_nodes, item_lo, n_items));
     PEA_REQUIRE(repr && unids && pos_items && fc1_w && fc1_b && fc2_w && fc2_b && workspace, PEA_ERR_ARG,
                 "rank_full: null pointer");
     PEA_REQUIRE(!excl_rowptr || excl_items, PEA_ERR_ARG, "rank_full: excl_rowptr without excl_items");
@@ -434,5 +372,5 @@ extern "C" int pea_rank_full(int64_t U, int R, int64_t num_nodes, const float *r
 #undef PEA_RANK_FINISH
         PEA_HIP(hipGetLastError());
     }
-    return read_err((int *)ws, stream, "rank_full");
+    return read_err_flag((int *)ws, stream, "rank_full");
 }

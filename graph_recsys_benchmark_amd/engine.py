@@ -814,6 +814,26 @@ def entity_reg(x, batch9):
     return _entity_launch(x, batch9, want_grad=False)[0]
 
 
+def _check_scored(rc):
+    """The return code of a scoring entry point: a node id outside [0, num_nodes) is the reference's IndexError."""
+    if rc == -2:
+        raise IndexError(_lib.last_error())
+    _lib.check(rc)
+
+
+def _rank_io(unids, cand, dev, variants=()):
+    """unids / cand as contiguous int64 and the outputs of an evaluator of cand's [U, C] (its last two dimensions) over
+    `variants` tables: (scores [*variants, U, C], rank int32 / auc / loss [*variants, U]).  For the three candidate
+    evaluators (rank_eval, rank_eval_multi, dot_rank_eval); the catalogue and pair wrappers have other outputs."""
+    unids = unids.to(torch.int64).contiguous()
+    cand = cand.to(torch.int64).contiguous()
+    u, c = cand.shape[-2:]
+    lead = tuple(variants) + (u,)
+    outs = (torch.empty(lead + (c,), dtype=torch.float32, device=dev), torch.empty(lead, dtype=torch.int32, device=dev),
+            torch.empty(lead, dtype=torch.float32, device=dev), torch.empty(lead, dtype=torch.float32, device=dev))
+    return unids, cand, outs
+
+
 def predict(repr_, unids, inids, fc1_w, fc1_b, fc2_w, fc2_b):
     """fc2(relu(fc1([repr[u] || repr[i]]))) -> [B, 1]  (reference models/base.py:208-214)."""
     lib = _lib.require_device()
@@ -828,9 +848,7 @@ def predict(repr_, unids, inids, fc1_w, fc1_b, fc2_w, fc2_b):
     rc = lib.pea_predict(b, repr_.shape[1], repr_.shape[0], _lib.ptr(args[0]), _lib.ptr(unids), _lib.ptr(inids),
                          _lib.ptr(args[1]), _lib.ptr(args[2]), _lib.ptr(args[3]), _lib.ptr(args[4]), _lib.ptr(out),
                          _lib.current_stream())
-    if rc == -2:
-        raise IndexError(_lib.last_error())
-    _lib.check(rc)
+    _check_scored(rc)
     return out.view(-1, 1)
 
 
@@ -839,21 +857,13 @@ def rank_eval(repr_, unids, cand, fc1_w, fc1_b, fc2_w, fc2_b):
     Returns scores [U, C], rank of the positive [U] (int32), auc [U], eval loss [U]."""
     lib = _lib.require_device()
     check_pending_errors()
-    unids = unids.to(torch.int64).contiguous()
-    cand = cand.to(torch.int64).contiguous()
+    unids, cand, (scores, rank, auc, loss) = _rank_io(unids, cand, repr_.device)
     u, c = cand.shape
-    dev = repr_.device
-    scores = torch.empty((u, c), dtype=torch.float32, device=dev)
-    rank = torch.empty(u, dtype=torch.int32, device=dev)
-    auc = torch.empty(u, dtype=torch.float32, device=dev)
-    loss = torch.empty(u, dtype=torch.float32, device=dev)
     args = [t.detach().contiguous() for t in (repr_, fc1_w, fc1_b, fc2_w, fc2_b)]
     rc = lib.pea_rank_eval(u, c, repr_.shape[1], repr_.shape[0], _lib.ptr(args[0]), _lib.ptr(unids), _lib.ptr(cand),
                            _lib.ptr(args[1]), _lib.ptr(args[2]), _lib.ptr(args[3]), _lib.ptr(args[4]),
                            _lib.ptr(scores), _lib.ptr(rank), _lib.ptr(auc), _lib.ptr(loss), _lib.current_stream())
-    if rc == -2:
-        raise IndexError(_lib.last_error())
-    _lib.check(rc)
+    _check_scored(rc)
     return scores, rank, auc, loss
 
 
@@ -894,8 +904,6 @@ def rank_eval_multi(tables, unids, cand, fc1_w, fc1_b, fc2_w, fc2_b):
         raise ValueError('tables must be float32 [V, N, R]')
     tables = tables.detach().contiguous()
     v, n, r = tables.shape
-    unids = unids.to(torch.int64).contiguous()
-    cand = cand.to(torch.int64).contiguous()
     u = unids.shape[0]
     if cand.dim() == 2 and cand.shape[0] == u:
         c, stride = cand.shape[1], 0
@@ -903,18 +911,12 @@ def rank_eval_multi(tables, unids, cand, fc1_w, fc1_b, fc2_w, fc2_b):
         c, stride = cand.shape[2], u * cand.shape[2]
     else:
         raise ValueError('cand must be [U, C] (shared by all variants) or [V, U, C]')
-    dev = tables.device
-    scores = torch.empty((v, u, c), dtype=torch.float32, device=dev)
-    rank = torch.empty((v, u), dtype=torch.int32, device=dev)
-    auc = torch.empty((v, u), dtype=torch.float32, device=dev)
-    loss = torch.empty((v, u), dtype=torch.float32, device=dev)
+    unids, cand, (scores, rank, auc, loss) = _rank_io(unids, cand, tables.device, variants=(v,))
     args = [t.detach().contiguous() for t in (fc1_w, fc1_b, fc2_w, fc2_b)]
     rc = lib.pea_rank_eval_multi(v, u, c, r, n, _lib.ptr(tables), _lib.ptr(unids), _lib.ptr(cand), stride, _lib.ptr(args[0]),
                                  _lib.ptr(args[1]), _lib.ptr(args[2]), _lib.ptr(args[3]), _lib.ptr(scores), _lib.ptr(rank),
                                  _lib.ptr(auc), _lib.ptr(loss), _lib.current_stream())
-    if rc == -2:
-        raise IndexError(_lib.last_error())
-    _lib.check(rc)
+    _check_scored(rc)
     return scores, rank, auc, loss
 
 
@@ -959,9 +961,7 @@ def recommend_topk(repr_, unids, k, item_range, fc1_w, fc1_b, fc2_w, fc2_b, excl
                                 _lib.ptr(rowptr), _lib.ptr(items), _lib.ptr(args[1]), _lib.ptr(args[2]), _lib.ptr(args[3]),
                                 _lib.ptr(args[4]), _lib.ptr(out_items), _lib.ptr(out_scores), _lib.ptr(ws), ws_bytes,
                                 _lib.current_stream())
-    if rc == -2:
-        raise IndexError(_lib.last_error())
-    _lib.check(rc)
+    _check_scored(rc)
     return out_items, out_scores
 
 
@@ -988,9 +988,7 @@ def rank_full(repr_, unids, pos_items, item_range, fc1_w, fc1_b, fc2_w, fc2_b, e
                            _lib.ptr(rowptr), _lib.ptr(items), _lib.ptr(args[1]), _lib.ptr(args[2]), _lib.ptr(args[3]),
                            _lib.ptr(args[4]), _lib.ptr(rank), _lib.ptr(auc), _lib.ptr(pos_score), _lib.ptr(ws), ws_bytes,
                            _lib.current_stream())
-    if rc == -2:
-        raise IndexError(_lib.last_error())
-    _lib.check(rc)
+    _check_scored(rc)
     return rank, auc, pos_score
 
 
@@ -1021,9 +1019,7 @@ def dot_predict(repr_, unids, inids):
     out = torch.empty(b, dtype=torch.float32, device=table.device)
     rc = lib.pea_dot_predict(b, table.shape[1], table.shape[0], _lib.ptr(table), _lib.ptr(unids), _lib.ptr(inids),
                              _lib.ptr(out), _lib.current_stream())
-    if rc == -2:
-        raise IndexError(_lib.last_error())
-    _lib.check(rc)
+    _check_scored(rc)
     return out
 
 
@@ -1033,21 +1029,13 @@ def dot_rank_eval(repr_, unids, cand):
     lib = _lib.require_device()
     check_pending_errors()
     table = _dot_table(repr_)
-    unids = unids.to(torch.int64).contiguous()
-    cand = cand.to(torch.int64).contiguous()
     if cand.dim() != 2 or unids.dim() != 1 or cand.shape[0] != unids.shape[0]:
         raise ValueError('cand must be [U, C] with one row per user of unids')
+    unids, cand, (scores, rank, auc, loss) = _rank_io(unids, cand, table.device)
     u, c = cand.shape
-    dev = table.device
-    scores = torch.empty((u, c), dtype=torch.float32, device=dev)
-    rank = torch.empty(u, dtype=torch.int32, device=dev)
-    auc = torch.empty(u, dtype=torch.float32, device=dev)
-    loss = torch.empty(u, dtype=torch.float32, device=dev)
     rc = lib.pea_dot_rank_eval(u, c, table.shape[1], table.shape[0], _lib.ptr(table), _lib.ptr(unids), _lib.ptr(cand),
                                _lib.ptr(scores), _lib.ptr(rank), _lib.ptr(auc), _lib.ptr(loss), _lib.current_stream())
-    if rc == -2:
-        raise IndexError(_lib.last_error())
-    _lib.check(rc)
+    _check_scored(rc)
     return scores, rank, auc, loss
 
 
@@ -1070,9 +1058,7 @@ def dot_recommend_topk(repr_, unids, k, item_range, exclude=None):
     rc = lib.pea_dot_recommend_topk(u, k, d, table.shape[0], _lib.ptr(table), _lib.ptr(unids), item_lo, n_items,
                                     _lib.ptr(rowptr), _lib.ptr(items), _lib.ptr(out_items), _lib.ptr(out_scores),
                                     _lib.ptr(ws), ws_bytes, _lib.current_stream())
-    if rc == -2:
-        raise IndexError(_lib.last_error())
-    _lib.check(rc)
+    _check_scored(rc)
     return out_items, out_scores
 
 
@@ -1097,9 +1083,7 @@ def dot_rank_full(repr_, unids, pos_items, item_range, exclude=None):
     rc = lib.pea_dot_rank_full(u, d, table.shape[0], _lib.ptr(table), _lib.ptr(unids), _lib.ptr(pos_items), item_lo, n_items,
                                _lib.ptr(rowptr), _lib.ptr(items), _lib.ptr(rank), _lib.ptr(auc), _lib.ptr(pos_score),
                                _lib.ptr(ws), ws_bytes, _lib.current_stream())
-    if rc == -2:
-        raise IndexError(_lib.last_error())
-    _lib.check(rc)
+    _check_scored(rc)
     return rank, auc, pos_score
 
 

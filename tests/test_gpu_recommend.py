@@ -520,6 +520,85 @@ def test_scores_agree_with_predict(R):
     assert bool(((pred.double() - scores.double()).abs() <= 2.0 * tol(s64)).all())
 
 
+# ------------------------------------------------------------------------------------------------ 7b. sampled evaluator
+def rank_eval_case(C, R, integer):
+    """N = 700 nodes, U = 37 users (the last four-user workgroup is partial), per user C distinct candidates (column 0 the
+    positive; distinct, so that no negative IS the positive), and the float64 scores of the header's formula."""
+    N, U = 700, 37
+    rng = np.random.default_rng(1000 * C + R)
+    tb = Tables(61, N, R, integer=integer)
+    unids = torch.from_numpy(rng.integers(0, N, size=U)).to(DEV)
+    cand = torch.from_numpy(np.stack([rng.permutation(N)[:C] for _ in range(U)])).to(DEV)
+    A = tb.repr[unids].double() @ tb.w1[:, :R].double().T + tb.b1.double()
+    B = tb.repr[cand].double() @ tb.w1[:, R:].double().T
+    s64 = torch.relu(A[:, None, :] + B) @ tb.w2.double().reshape(-1) + tb.b2.double().reshape(())
+    return tb, unids, cand, s64
+
+
+def rank_intervals(s64):
+    """what tol allows: a negative can change sides of the positive only inside w = tol(negative) + tol(positive)"""
+    b = tol(s64)
+    w = b[:, 1:] + b[:, :1]
+    d = s64[:, 1:] - s64[:, :1]
+    return (d > w).sum(1), (d >= -w).sum(1), (d < -w).sum(1), (d <= w).sum(1)
+
+
+def per_user_loop(s64_rows):
+    """The reference's per-user evaluation (solvers.py:72, 85-95) on float64 scores [U, C], column 0 the positive: stable
+    descending sort, auc = share of negatives the positive beats, loss = -sum log sigmoid(pos - neg)."""
+    ranks, aucs, losses = [], [], []
+    for row in s64_rows:
+        ranks.append(int(np.argmax(np.argsort(-row, kind='stable') == 0)))
+        aucs.append(float((row[0] > row[1:]).mean()))
+        losses.append(float(-np.log(1.0 / (1.0 + np.exp(-(row[0] - row[1:])))).sum()))
+    return np.asarray(ranks), np.asarray(aucs), np.asarray(losses)
+
+
+# C: one negative; the reference's 1 + 99 (two wave passes); past the two register-cached id passes of the evaluator.
+# R: 16 is the register path, 8 and 64 the generic one.
+@pytest.mark.parametrize('C,R,integer', [(C, R, False) for C in (2, 100, 201) for R in (16, 8, 64)] + [(100, 16, True)])
+def test_rank_eval_against_per_user_loop(C, R, integer):
+    """engine.rank_eval against the reference's loop over users on float64 scores.  pea_rank_eval runs the multi-table
+    evaluator with one table, so rank_eval_multi == rank_eval (test_gpu_ablation.py) compares the kernel with itself; this
+    is the independent check of the MLP evaluator."""
+    tb, unids, cand, s64 = rank_eval_case(C, R, integer)
+    U = unids.shape[0]
+    rank64, auc64, loss64 = per_user_loop(s64.cpu().numpy())
+    scores, rank, auc, loss = engine.rank_eval(tb.repr, unids, cand, *tb.weights)
+    assert scores.shape == (U, C) and rank.dtype == torch.int32
+    err = (scores.double() - s64).abs()
+    print('C=%d R=%d: max score error %.3g, max error / tol %.3g' % (C, R, float(err.max()), float((err / tol(s64)).max())))
+    assert bool((err <= tol(s64)).all()), 'score outside tol'
+    rank_c, auc_c = rank.cpu().numpy(), auc.double().cpu().numpy()
+    if integer:
+        assert bool((s64 == s64.round()).all()) and float(s64.abs().max()) < 2 ** 20
+        assert torch.equal(scores.double(), s64)
+        np.testing.assert_array_equal(rank_c, rank64)
+        assert (np.round(auc_c * (C - 1)) == np.round(auc64 * (C - 1))).all(), 'auc count differs'
+        np.testing.assert_allclose(auc_c, auc64, rtol=0, atol=2.0 ** -23)
+    else:
+        r_lo, r_hi, g_lo, g_hi = (t.cpu().numpy() for t in rank_intervals(s64))
+        single = r_lo == r_hi
+        print('users with a single-valued rank interval: %d of %d' % (single.sum(), U))
+        assert single.mean() >= 0.9, 'the float64 scores leave too many ranks open: pick another seed'
+        assert ((rank_c >= r_lo) & (rank_c <= r_hi)).all(), 'rank outside its float64 interval'
+        np.testing.assert_array_equal(rank_c[single], rank64[single])
+        assert ((auc_c >= g_lo / (C - 1) - 1e-6) & (auc_c <= g_hi / (C - 1) + 1e-6)).all(), 'auc outside its interval'
+        np.testing.assert_allclose(auc_c[g_lo == g_hi], auc64[g_lo == g_hi], rtol=0, atol=2.0 ** -23)
+    # loss: the fp32 torch formula on the kernel's own scores is the fp32 peer, float64 the truth.  sigmoid then log in
+    # fp32 with no clamp: exp(-gap) overflows past 88.72, so a row with a gap <= -89 has loss +inf (integer scores reach
+    # that); a row whose gaps are all >= -87 is finite.  A gap of -88 lands among the denormals and is left to neither.
+    gap = scores[:, :1] - scores[:, 1:]
+    peer = -gap.sigmoid().log().sum(1).cpu().numpy()
+    loss_c = loss.cpu().numpy()
+    worst = gap.min(1).values.cpu().numpy()
+    finite, inf = worst >= -87, worst <= -89
+    assert finite.all() or integer
+    assert np.isposinf(loss_c[inf]).all(), 'a clamp crept in: log(sigmoid) of a gap <= -89 is -inf in fp32'
+    assert finite.any() and np.isfinite(loss_c[finite]).all() and np.isfinite(loss64[finite]).all()
+    helpers.assert_fp32_close(loss_c[finite], peer[finite], loss64[finite], what='eval loss')
+
+
 # ------------------------------------------------------------------------------------------------ 8. errors
 def test_errors():
     U, n = 8, 100
