@@ -331,3 +331,299 @@ def dense_route_rows(entries):
     """[(profile name, kernel as the tables above spell it, [source job of each batch entry])] of _lib.dense_route's records"""
     return [(e.name.decode(), _DENSE_KERNELS[e.family] % e.variant if e.family < 4 else 'fallback', list(e.job[:e.n_jobs]))
             for e in entries]
+
+
+# ------------------------------------------------------------------------------------------------------------
+# the aggregation backward's matrix (csrc/agg_bwd.hip): tests/test_gpu_agg_bwd_matrix.py runs every case on the GPU,
+# tests/test_agg_bwd_matrix_cpu.py checks the graph and measures each case's float32 headroom without one
+# ------------------------------------------------------------------------------------------------------------
+# degrees that sit on a boundary of the backward's row forms: 4 edges per short-row step, 32 = the longest short row, 64 edges per
+# long-row batch, 512 = the longest unchunked row; one row of two full chunks and more
+AGG_DEGREES = (0, 1, 3, 4, 5, 31, 32, 33, 63, 64, 65, 127, 128, 129, 200, 511, 512, 513, 1100)
+_DEGREE_GRAPH = {}
+
+
+def degree_graph(seed=5, n_fill=2000):
+    """COO [2, E] int64 graph in which every degree of AGG_DEGREES occurs as an in-degree AND as an out-degree (so a relation
+    and its reverse both hold every row form), built from stars between four blocks of special nodes and `n_fill` filler nodes:
+
+        dst_lone[q]  in-degree d_q, no out-edge          src_lone[q]  out-degree d_q, no in-edge (the S pass's `lone` rows)
+        dst[q]       in-degree d_q, 2 out-edges          src[q]       out-degree d_q, 2 in-edges
+        isolated     no edge at all
+
+    d_q runs over the non-zero degrees.  One of the two rows of every degree >= 5 carries a duplicated edge; the filler nodes
+    carry random edges among themselves (some duplicated) and a few self loops, and stay far below 1100 edges on either side.
+    Self loops sit on filler nodes only, so the special rows keep their degree whether a plan drops the loops (GAT, GCN) or
+    keeps them (SAGE).  Edges are shuffled.  Returns a dict: n, edge_index, blocks (name -> node ids), degrees (d_q)."""
+    key = (seed, n_fill)
+    if key in _DEGREE_GRAPH:
+        return _DEGREE_GRAPH[key]
+    rng = np.random.default_rng(seed)
+    degs = [d for d in AGG_DEGREES if d > 0]
+    blocks, at = {'fill': np.arange(n_fill)}, n_fill
+    for name in ('dst_lone', 'dst', 'src_lone', 'src'):
+        blocks[name] = np.arange(at, at + len(degs))
+        at += len(degs)
+    blocks['isolated'] = np.arange(at, at + 4)
+    n = at + 4
+    src, dst = [], []
+
+    def star(node, d, duplicate, incoming):
+        distinct = d - 1 if duplicate and d >= 5 else d
+        other = rng.choice(n_fill, size=distinct, replace=False)
+        other = np.concatenate([other, other[:d - distinct]])
+        me = np.full(d, node)
+        src.append(other if incoming else me)
+        dst.append(me if incoming else other)
+
+    for q, d in enumerate(degs):
+        star(blocks['dst_lone'][q], d, q % 2 == 0, True)
+        star(blocks['dst'][q], d, q % 2 == 1, True)
+        star(blocks['src_lone'][q], d, q % 2 == 0, False)
+        star(blocks['src'][q], d, q % 2 == 1, False)
+        star(blocks['dst'][q], 2, False, False)
+        star(blocks['src'][q], 2, False, True)
+    bs, bd = rng.integers(0, n_fill, 1500), rng.integers(0, n_fill, 1500)
+    bd = np.where(bs == bd, (bd + 1) % n_fill, bd)
+    loops = rng.choice(n_fill, size=40, replace=False)
+    src += [bs, bs[:200], loops]
+    dst += [bd, bd[:200], loops]
+    ei = np.stack([np.concatenate(src), np.concatenate(dst)]).astype(np.int64)
+    ei = np.ascontiguousarray(ei[:, rng.permutation(ei.shape[1])])
+    _DEGREE_GRAPH[key] = dict(n=n, edge_index=ei, blocks=blocks, degrees=degs)
+    return _DEGREE_GRAPH[key]
+
+
+def kept_degrees(ei, n, drop_loops):
+    """(in-degree, out-degree) per node of the edges a plan keeps (duplicates count; GAT / GCN plans drop self loops)."""
+    if drop_loops:
+        ei = ei[:, ei[0] != ei[1]]
+    return np.bincount(ei[1], minlength=n), np.bincount(ei[0], minlength=n)
+
+
+def agg_lanes(width):
+    """lanes per row chunk (csrc/agg_common.h: lanes_for), written down by hand"""
+    return next(g for g in (4, 8, 16, 32, 64) if 4 * g >= width)
+
+
+def agg_head_class(heads, out_channels):
+    """the head class launch_bwd_mode picks: 'full' (F / 4 == G), 'four' (F / 4 == 4), 'generic' (any other head width)"""
+    f4 = out_channels // 4
+    return 'full' if f4 == agg_lanes(heads * out_channels) else 'four' if f4 == 4 else 'generic'
+
+
+# section "single conv": (heads, out_channels) per lane width; every (G, head class) pair the dispatcher can form
+AGG_GAT_WIDTHS = {4: [(1, 4), (1, 12), (1, 16), (4, 4)],
+                  8: [(1, 20), (2, 12), (1, 32), (2, 16)],
+                  16: [(1, 64), (4, 16), (2, 24), (1, 40)],
+                  32: [(1, 128), (4, 24), (8, 16), (2, 64)],
+                  64: [(1, 256), (4, 40), (4, 64), (16, 16)]}
+AGG_GAT_SLOPE_WIDTHS = {4: (1, 12), 8: (2, 16), 16: (1, 64), 32: (4, 24), 64: (16, 16)}     # also run with slopes 0.0 and 1.0
+AGG_PLAIN_WIDTHS = (4, 12, 32, 64, 96, 256)        # GCN, SAGE: width of the aggregated rows, one per G (and 12)
+
+
+def _conv_cases():
+    cases, k = [], 0
+    for G, widths in AGG_GAT_WIDTHS.items():
+        for heads, out in widths:
+            slopes = (0.2, 0.0, 1.0) if AGG_GAT_SLOPE_WIDTHS[G] == (heads, out) else (0.2,)
+            for slope in slopes:
+                assert agg_lanes(heads * out) == G
+                in_ch = (8, 36)[k % 2]
+                cases.append(dict(kind='gat', heads=heads, out=out, in_ch=in_ch, slope=slope, deg='row', seed=100 + k, scale=0.3,
+                                  id='gat-G%d-%s-h%dx%d-in%d-slope%g' % (G, agg_head_class(heads, out), heads, out, in_ch, slope)))
+                k += 1
+    # GCN aggregates its transformed rows (the output width); SAGE aggregates its INPUT rows and transforms afterwards, so the
+    # listed width is in_channels there and the output takes the 8 / 36
+    for q, w in enumerate(AGG_PLAIN_WIDTHS):
+        for deg in ('row', 'col'):
+            cases.append(dict(kind='gcn', heads=1, out=w, in_ch=(8, 36)[q % 2], slope=0.2, deg=deg, seed=100 + k, scale=0.3,
+                              id='gcn-G%d-w%d-in%d-deg_%s' % (agg_lanes(w), w, (8, 36)[q % 2], deg)))
+            k += 1
+    for q, w in enumerate(AGG_PLAIN_WIDTHS):
+        cases.append(dict(kind='sage', heads=1, out=(36, 8)[q % 2], in_ch=w, slope=0.2, deg='row', seed=100 + k, scale=0.3,
+                          id='sage-G%d-w%d-out%d' % (agg_lanes(w), w, (36, 8)[q % 2])))
+        k += 1
+    return cases
+
+
+AGG_CONV_CASES = _conv_cases()
+CONV_PARAM_NAMES = {'gat': ('lin.weight', 'att_i', 'att_j', 'bias'), 'gcn': ('weight', 'bias'),
+                    'sage': ('lin_rel.weight', 'lin_rel.bias', 'lin_root.weight')}
+
+
+def conv_case_tensors(case, n):
+    """float32 CPU tensors of one single-conv case: x [n, in], the conv's parameters by name, the dense output gradient"""
+    import torch
+    g = torch.Generator().manual_seed(case['seed'])
+    rand = lambda *shape: torch.randn(shape, generator=g)
+    i, h, f, s = case['in_ch'], case['heads'], case['out'], case['scale']
+    x = rand(n, i) * 0.5
+    if case['kind'] == 'gat':
+        params = {'lin.weight': rand(h * f, i) * s, 'att_i': rand(1, h, f) * s, 'att_j': rand(1, h, f) * s, 'bias': rand(h * f) * 0.1}
+    elif case['kind'] == 'gcn':
+        params = {'weight': rand(i, f) * s, 'bias': rand(f) * 0.1}
+    else:
+        params = {'lin_rel.weight': rand(f, i) * s, 'lin_rel.bias': rand(f) * 0.1, 'lin_root.weight': rand(f, i) * s}
+    return x, params, rand(n, h * f)
+
+
+def restated_conv(kind, in_w, params, heads=1, negative_slope=0.2, gcn_deg_from='row'):
+    """A conv of oracle/pyg_restatement.py whose parameters ARE the given tensors (name -> tensor that may require grad, of
+    any float dtype), so torch autograd differentiates the restatement with respect to them."""
+    from oracle import pyg_restatement as R
+    if kind == 'gat':
+        conv = R.GATConv(in_w, params['lin.weight'].shape[0] // heads, heads=heads, negative_slope=negative_slope)
+        del conv._parameters['att_i'], conv._parameters['att_j'], conv._parameters['bias'], conv.lin._parameters['weight']
+        conv.lin.weight = params['lin.weight']
+        conv.att_i, conv.att_j, conv.bias = params['att_i'], params['att_j'], params['bias']
+    elif kind == 'gcn':
+        conv = R.GCNConv(in_w, params['weight'].shape[1], gcn_deg_from=gcn_deg_from)
+        del conv._parameters['weight'], conv._parameters['bias']
+        conv.weight, conv.bias = params['weight'], params['bias']
+    else:
+        conv = R.SAGEConv(in_w, params['lin_rel.weight'].shape[0])
+        del conv.lin_rel._parameters['weight'], conv.lin_rel._parameters['bias'], conv.lin_root._parameters['weight']
+        conv.lin_rel.weight, conv.lin_rel.bias = params['lin_rel.weight'], params['lin_rel.bias']
+        conv.lin_root.weight = params['lin_root.weight']
+    return conv
+
+
+def conv_reference(case, graph, dtype):
+    """(out, {'x': dx, parameter name: gradient}) of L = sum(conv(x, edge_index) * Gout) by torch autograd on the restatement in
+    `dtype` (float64: the truth; float32: the same operation at the kernels' precision)."""
+    import torch
+    x, params, gout = conv_case_tensors(case, graph['n'])
+    x = x.to(dtype).requires_grad_(True)
+    params = {k: v.to(dtype).requires_grad_(True) for k, v in params.items()}
+    conv = restated_conv(case['kind'], case['in_ch'], params, case['heads'], case['slope'], case['deg'])
+    out = conv(x, torch.from_numpy(graph['edge_index']))
+    (out * gout.to(dtype)).sum().backward()
+    grads = {'x': x.grad.numpy().astype(np.float64)}
+    grads.update({k: v.grad.numpy().astype(np.float64) for k, v in params.items()})
+    return out.detach().numpy(), grads
+
+
+def restated_loss_and_grads(kind, sd, edges, steps, heads, aggr, batch, gcn_deg_from='row', dtype=None):
+    """(loss, {parameter: gradient}) of the whole model's BPR loss by torch autograd on the restatement, assembled like the
+    reference's models/base.py, in `dtype` (default float64).  A second statement of tests/test_gpu_backward.py:
+    f64_loss_and_grads with the dtype left open; the two must stay in step (tests/test_agg_bwd_matrix_cpu.py compares them)."""
+    import torch
+    dtype = dtype or torch.float64
+    params = {k: torch.from_numpy(np.asarray(v)).to(dtype).requires_grad_(True) for k, v in sd.items()}
+    outs = []
+    for p, S in enumerate(steps):
+        h = params['x']
+        for s in range(S):
+            pre = 'pea_channels.%d.gnn_layers.%d.' % (p, s)
+            lp = {k[len(pre):]: v for k, v in params.items() if k.startswith(pre)}
+            last = s == S - 1
+            conv = restated_conv(kind, h.shape[1], lp, heads=1 if (kind != 'gat' or (S > 1 and last)) else heads,
+                                 gcn_deg_from=gcn_deg_from)
+            h = conv(h, torch.from_numpy(np.ascontiguousarray(edges[p][s])))
+            if not last:
+                h = torch.relu(h)
+        outs.append(h)
+    stack = torch.stack(outs, dim=1)
+    if aggr == 'att':
+        fused = (stack * torch.softmax((stack * params['att']).sum(-1), dim=-1).unsqueeze(-1)).sum(1)
+    else:
+        fused = stack.mean(1)
+    b = torch.from_numpy(np.asarray(batch))
+
+    def pred(u, i):
+        hdn = torch.relu(torch.cat([fused[u], fused[i]], dim=-1) @ params['fc1.weight'].t() + params['fc1.bias'])
+        return hdn @ params['fc2.weight'].t() + params['fc2.bias']
+
+    loss = -(pred(b[:, 0], b[:, 1]) - pred(b[:, 0], b[:, 2])).sigmoid().log().sum()
+    loss.backward()
+    return float(loss.detach()), {k: v.grad.numpy().astype(np.float64) for k, v in params.items() if v.grad is not None}
+
+
+def grad_rule_fraction(got, want):
+    """The project's gradient rule (tests/test_gpu_backward.py, two-step schedule test), as the largest used fraction of it:
+    per tensor  err <= 2e-4 max|want| + 1e-6 (largest gradient of the case) + 1e-9.  Returns (fraction, tensor name); every
+    tensor of `want` must be in `got`.  A tensor with a NaN or an infinity gives (nan, its name), which no `<=` accepts."""
+    g_max = max(float(np.abs(w).max()) for w in want.values())
+    worst = (0.0, None)
+    for name, w in want.items():
+        g = np.asarray(got[name], np.float64).reshape(w.shape)
+        if not (np.isfinite(g).all() and np.isfinite(w).all()):
+            return float('nan'), name           # a non-finite gradient ends the comparison: nothing may replace it
+        bound = 2e-4 * float(np.abs(w).max()) + 1e-6 * g_max + 1e-9
+        frac = float(np.abs(g - w).max()) / bound
+        if frac > worst[0]:
+            worst = (frac, name)
+    return worst
+
+
+# section "row flags": (kind, heads, hidden, repr_dim, channels) x the set of live rows a batch produces
+AGG_MODELS = [('gat', 1, 24, 16, 1), ('gat', 1, 96, 12, 2), ('gat', 2, 24, 12, 2),
+              ('gcn', 1, 24, 12, 1), ('gcn', 1, 96, 16, 2), ('sage', 1, 96, 16, 1), ('sage', 1, 24, 12, 2)]
+AGG_DENSITIES = ('one_triple', 'two_percent', 'every_second', 'every_node', 'hubs_only', 'all_but_hubs')
+# the last layer is repr_dim wide, so the models above run the flagged kernels at G = 4 only; these widen it to G = 8 ... 64
+# (repr_dim > 32 also takes model.loss through PEAStackFunction with read_ids instead of PEALossFunction)
+AGG_WIDE_MODELS = [(kind, 1, 24, r, 1) for kind in ('gat', 'gcn') for r in (32, 64, 128, 256)]
+AGG_MODEL_CASES = ([m + (dn,) for m in AGG_MODELS for dn in AGG_DENSITIES] +
+                   [m + (dn,) for m in AGG_WIDE_MODELS for dn in ('two_percent', 'every_node')])
+AGG_MODEL_IDS = ['%s-h%d-hid%d-r%d-P%d-%s' % c for c in AGG_MODEL_CASES]
+AGG_EMB = 16
+
+
+def hub_nodes(graph):
+    """nodes with more than 512 in- or out-edges: the hub rows of the relation or of its reverse"""
+    deg_in, deg_out = kept_degrees(graph['edge_index'], graph['n'], True)
+    return np.flatnonzero((deg_in > 512) | (deg_out > 512))
+
+
+def density_batch(name, graph):
+    """int64 [B, 3] BPR triples whose node ids are exactly the wanted set of live rows: every member once in the user column, a
+    permutation of the set as positives and a few fixed members as negatives.  (Positives and negatives drawn alike make every
+    gradient of the scorer a sum that cancels to nothing, which leaves float32 -- the restatement's as much as the kernels' --
+    no room under a rule relative to the gradient's size: tests/test_agg_bwd_matrix_cpu.py measures the room.)"""
+    n, rng = graph['n'], np.random.default_rng(17)
+    hubs = hub_nodes(graph)
+    if name == 'one_triple':
+        return np.array([[graph['blocks']['src'][9], graph['blocks']['dst'][12], 3]], np.int64)
+    ids = {'two_percent': np.sort(rng.choice(n, size=n // 50, replace=False)), 'every_second': np.arange(0, n, 2),
+           'every_node': np.arange(n), 'hubs_only': hubs, 'all_but_hubs': np.setdiff1d(np.arange(n), hubs)}[name]
+    anchors = ids[np.linspace(0, ids.size - 1, min(8, ids.size // 2)).astype(np.int64)]
+    return np.stack([ids, rng.permutation(ids), anchors[np.arange(ids.size) % anchors.size]], axis=1).astype(np.int64)
+
+
+def agg_model_edges(graph, channels):
+    """metapaths of 2 steps over the degree graph and its reverse: channel 0 ends on the reversed relation, channel 1 on the graph"""
+    ei = graph['edge_index']
+    flip = np.ascontiguousarray(ei[::-1])
+    return [[ei, flip], [flip, ei]][:channels]
+
+
+def agg_model_state(kind, heads, hidden, repr_dim, channels, graph, scale=None, seed=31, emb=AGG_EMB, device='cpu'):
+    """(model, state dict as numpy) of a section "row flags" model; the parameters depend on the arguments only.  Parameter scale
+    0.25, 0.1 for a last layer wider than 32 (at 0.25 the scores of a 128-wide GCN overflow log(sigmoid) in float32: the loss
+    of the float32 restatement itself is inf)"""
+    scale = scale or (0.25 if repr_dim <= 32 else 0.1)
+    model = build_model(kind, graph['n'], agg_model_edges(graph, channels), [2] * channels, emb, hidden, repr_dim, heads=heads,
+                        device=device)
+    model.load_state_dict(random_state_dict(model, seed, scale=scale))
+    return model, {k: v.detach().cpu().numpy() for k, v in model.state_dict().items()}
+
+
+# the colsum cases: (kind, heads, hidden per head, repr_dim, channels) on a small graph with 40 hot destinations.  9 channels
+# x 128 columns: a level 1152 columns wide (colsum_stage1 loops over column blocks of 1024); 3 heads x 4 columns: per-head scales
+AGG_COLSUM_CASES = [('gat', 1, 128, 16, 9), ('gat', 3, 4, 16, 3)]
+AGG_COLSUM_IDS = ['9x128', '3x3headsx4']
+AGG_COLSUM_EMB = 32
+
+
+def colsum_case(kind, heads, hidden, repr_dim, channels, device='cpu', scale=0.2):
+    """(model, state dict as numpy, n, edges, batch) of a colsum case"""
+    rng = np.random.default_rng(3)
+    n = 300
+    a = np.stack([rng.integers(0, n, 4000), rng.integers(0, 40, 4000)]).astype(np.int64)
+    b = np.ascontiguousarray(a[::-1])
+    edges = [[[a, b], [b, a]][p % 2] for p in range(channels)]
+    batch = rng.integers(0, n, size=(64, 3)).astype(np.int64)
+    model = build_model(kind, n, edges, [2] * channels, AGG_COLSUM_EMB, hidden, repr_dim, heads=heads, device=device)
+    model.load_state_dict(random_state_dict(model, 33, scale=scale))
+    return model, {k: v.detach().cpu().numpy() for k, v in model.state_dict().items()}, n, edges, batch
