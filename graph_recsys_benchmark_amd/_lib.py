@@ -192,6 +192,10 @@ SIGNATURES = {
     'pea_dot_bpr_train_workspace_bytes': (_sz, [_i64]),
     'pea_dot_bpr_train': (_int, [_i64, _int, C.POINTER(_vp), C.POINTER(_i64), C.POINTER(_int), _i64, _vp, _i64, _vp, _vp, _vp,
                                  _sz, _vp]),
+    'pea_transr_supported': (_int, [_int]),
+    'pea_transr_train_workspace_bytes': (_sz, [_i64, _int]),
+    'pea_transr_train': (_int, [_i64, _int, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                _sz, _vp]),
 }
 
 KGU_KGAT, KGU_KGCN, KGU_NGCF = 0, 1, 2     # include/peahip.h PEA_KGU_*

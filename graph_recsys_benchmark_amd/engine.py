@@ -1245,3 +1245,98 @@ def dot_bpr_loss(blocks, batch):
         raise ValueError('dot_bpr_loss: block widths (multiples of 4, sum <= 256, at most %d blocks) or batch size (3 B <= %d) '
                          'not supported' % (DOT_TRAIN_MAX_BLOCKS, ROWS_SCATTER_MAX))
     return _DotBprLoss.apply(batch, *blocks)
+
+
+def transr_supported(emb, batch_size):
+    """Whether transr_loss takes this width (a multiple of 4 in 4..128, csrc/transr_train.hip) and this batch (its 3 B node
+    positions go back through rows_scatter_sum); needs no device.  Else the caller stays on autograd."""
+    return bool(_lib.load().pea_transr_supported(int(emb))) and 3 * int(batch_size) <= ROWS_SCATTER_MAX
+
+
+def _block16(t):
+    """t as transr_train reads it: rows with a stride that is a multiple of 4 floats and a 16-byte aligned start (a column
+    block of a wider buffer qualifies); anything else is copied."""
+    t = _rows2d(t.detach())
+    if t.stride(0) % 4 or t.stride(0) < t.shape[1] or t.data_ptr() % 16:
+        t = t.contiguous()
+    return t
+
+
+def transr_train_raw(x, proj, r, batch, need_grad=True):
+    """One launch of csrc/transr_train.hip (+ its fixed-order reduction): (loss, pos [B], neg [B], grad_rows [3B, E],
+    grad_rel_rows [B, E], dproj [E, E], error flag) of the TransR-style kg_loss for x [N, E], proj [E, E], r [R, E] and the
+    int64 [B, >= 4] rows (h, t+, t-, rel) of `batch`.  need_grad=False is the forward-only form: the three gradients are
+    None and no backward work is done."""
+    lib = _lib.require_device()
+    if batch.dtype != torch.int64 or batch.dim() != 2 or batch.shape[1] < 4:
+        raise ValueError('batch must be int64 [B, >=4]')
+    if batch.stride(1) != 1:
+        batch = batch.contiguous()
+    x, r = _block16(x), _block16(r)
+    proj = _rows2d(proj.detach()).contiguous()
+    e = x.shape[1]
+    if not lib.pea_transr_supported(e):
+        raise ValueError('transr_train: width %d not supported (a multiple of 4 in 4..128)' % e)
+    if tuple(proj.shape) != (e, e) or r.shape[1] != e or r.shape[0] < 1 or x.shape[0] < 1:
+        raise ValueError('transr_train: x [N, E], proj [E, E] and r [R, E] expected')
+    b, dev = batch.shape[0], x.device
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    pos = torch.empty(b, dtype=torch.float32, device=dev)
+    neg = torch.empty(b, dtype=torch.float32, device=dev)
+    grad_rows = grad_rel = dproj = None
+    if need_grad:
+        grad_rows = torch.empty((3 * b, e), dtype=torch.float32, device=dev)
+        grad_rel = torch.empty((b, e), dtype=torch.float32, device=dev)
+        dproj = torch.empty((e, e), dtype=torch.float32, device=dev)
+    ws_bytes = int(lib.pea_transr_train_workspace_bytes(b, e))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    _lib.check(lib.pea_transr_train(b, e, _lib.ptr(x), x.stride(0), x.shape[0], _lib.ptr(proj), _lib.ptr(r), r.stride(0),
+                                    r.shape[0], _lib.ptr(batch), batch.stride(0), _lib.ptr(loss), _lib.ptr(pos), _lib.ptr(neg),
+                                    _lib.ptr(grad_rows), _lib.ptr(grad_rel), _lib.ptr(dproj), _lib.ptr(ws), ws_bytes,
+                                    _lib.current_stream()))
+    return loss, pos, neg, grad_rows, grad_rel, dproj, ws[:4].view(torch.int32)[0]
+
+
+class _TransrLoss(torch.autograd.Function):
+    """loss = -sum_b log sigmoid(pos_b - neg_b) of the TransR-style KG phase with its whole backward from the same launch
+    (csrc/transr_train.hip); backward scatters the batch's gradient rows into dense x and r gradients with
+    pea_rows_scatter_sum (fixed order).  Reference: experiments/kgat_solver_bpr.py:110-124 under loss.backward()."""
+
+    @staticmethod
+    def forward(ctx, batch, need_grad, x, proj, r):
+        loss, _, _, grad_rows, grad_rel, dproj, flag = transr_train_raw(x, proj, r, batch, need_grad)
+        if len(_pending_err) >= 64:
+            check_pending_errors()
+        _pending_err.append(flag)
+        if need_grad:
+            ctx.node_ids = batch[:, :3].reshape(-1).contiguous()
+            ctx.rel_ids = batch[:, 3].contiguous()
+            ctx.grads = (grad_rows, grad_rel, dproj)
+            ctx.shapes = (tuple(x.shape), tuple(r.shape))
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        grad_rows, grad_rel, dproj = ctx.grads
+        (n, e), (n_rel, _) = ctx.shapes
+        dx = dp = dr = None
+        if ctx.needs_input_grad[2]:
+            dx = torch.zeros((n, e), dtype=torch.float32, device=g.device)
+            rows_scatter_sum(ctx.node_ids, grad_rows * g, 1, e, [0], dx)
+        if ctx.needs_input_grad[3]:
+            dp = dproj * g
+        if ctx.needs_input_grad[4]:
+            dr = torch.zeros((n_rel, e), dtype=torch.float32, device=g.device)
+            rows_scatter_sum(ctx.rel_ids, grad_rel * g, 1, e, [0], dr)
+        return None, None, dx, dp, dr
+
+
+def transr_loss(x, proj_mat, r, batch):
+    """Differentiable TransR-style kg_loss (models/kg_base.py) of the int64 [B, >= 4] rows (h, t+, t-, rel) of `batch`, forward
+    and backward in HIP; backward() gives dense gradients for x [N, E], proj_mat [E, E] and r [R, E].  With grad disabled,
+    or when no input requires grad, only the forward runs.  A row with an id out of range contributes nothing and raises
+    IndexError at the next check_pending_errors().  transr_supported(E, B) must hold."""
+    if x.dim() != 2 or not transr_supported(x.shape[1], batch.shape[0]):
+        raise ValueError('transr_loss: width (a multiple of 4 in 4..128) or batch size (3 B <= %d) not supported' % ROWS_SCATTER_MAX)
+    need_grad = torch.is_grad_enabled() and any(t.requires_grad for t in (x, proj_mat, r))
+    return _TransrLoss.apply(batch, need_grad, x, proj_mat, r)

@@ -11,6 +11,12 @@ un-normalised conv outputs (engine.dot_bpr_loss).  The dropout masks are then dr
 the random stream of F.dropout: with dropout > 0 the two paths see different masks of the same distribution.  In this
 mode no table is built while training: cached_repr is None and predict() raises until cf_eval() / eval() has run.  Widths
 the kernels refuse, an att_map that requires grad and batches of more than 5461 triples take the autograd path silently.
+
+native_kg=True (constructor kwarg of KGAT / KGCN, default off, independent of native_train) sends the KG phase through HIP
+as well: kg_loss(batch) becomes one launch of csrc/transr_train.hip (engine.transr_loss: the three projections, the loss
+and the whole backward), with the index backward into x and r on the existing deterministic scatter.  It works in training
+and in eval mode.  kg_loss stays the torch composition on a CPU tensor, for a batch that is not int64 [B, >= 4], for an
+emb_dim that is no multiple of 4 in 4..128 and for batches of more than 5461 rows.
 """
 import torch
 import torch.nn.functional as F
@@ -28,6 +34,7 @@ class DotRecsysModel(GraphRecsysModel):
     entity_aware_coff = 0.0
 
     native_train = False
+    native_kg = False
 
     def _convs(self):
         return (self.conv1, self.conv2, self.conv3)
@@ -79,6 +86,7 @@ class KGBaseRecsysModel(DotRecsysModel):
     def _init(self, **kwargs):
         self.dropout = kwargs['dropout']
         self.native_train = bool(kwargs.get('native_train', False))
+        self.native_kg = bool(kwargs.get('native_kg', False))
         emb, hidden = kwargs['emb_dim'], kwargs['hidden_size']
         self.x = Parameter(torch.Tensor(kwargs['dataset']['num_nodes'], emb))
         self.r = Parameter(torch.Tensor(kwargs['dataset'].num_edge_types, emb))
@@ -123,7 +131,11 @@ class KGBaseRecsysModel(DotRecsysModel):
         return -(pos_pred - neg_pred).sigmoid().log().sum()
 
     def kg_loss(self, batch):
-        """TransR-style loss over (head, tail+, tail-, relation) rows (experiments/kgat_solver_bpr.py:110-124); plain torch."""
+        """TransR-style loss over (head, tail+, tail-, relation) rows (experiments/kgat_solver_bpr.py:110-124): one HIP
+        launch with native_kg=True (engine.transr_loss, csrc/transr_train.hip), else the torch composition below."""
+        if (self.native_kg and self.x.is_cuda and batch.dtype == torch.int64 and batch.dim() == 2 and batch.shape[1] >= 4
+                and _engine.transr_supported(self.x.shape[1], batch.shape[0])):
+            return _engine.transr_loss(self.x, self.proj_mat, self.r, batch)
         head = torch.mm(self.x[batch[:, 0]], self.proj_mat) + self.r[batch[:, 3]]
         pos_diff = head - torch.mm(self.x[batch[:, 1]], self.proj_mat)
         neg_diff = head - torch.mm(self.x[batch[:, 2]], self.proj_mat)

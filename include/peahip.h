@@ -661,6 +661,38 @@ int pea_dot_bpr_train(int64_t B, int n_blocks, const float *const *blocks_host, 
                       float *out_loss, float *grad_rows, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * KG phase of KGAT / KGCN (csrc/transr_train.hip): the TransR-style kg_loss of experiments/kgat_solver_bpr.py:110-124 over B
+ * quadruples (int64 rows (h, t+, t-, rel), row stride quad_stride >= 4) and its whole gradient, in one launch.
+ * x [num_nodes, emb] (row stride ldx), proj [emb, emb] contiguous, r [num_rel, emb] (row stride ldr):
+ *     hp = x[h] proj + r[rel],  dpos = hp - x[t+] proj,  dneg = hp - x[t-] proj,
+ *     pos = sum_c dpos_c^2,  neg = sum_c dneg_c^2   (eight fma chains in ascending column order, column c in chain c % 8,
+ *                                                    added pairwise),
+ *     *out_loss = -sum_b log sigmoid(pos_b - neg_b)  (sigmoid then log in fp32; the sign and form are the reference's),
+ *   and with g = -(1 - sigmoid(pos - neg)), G+ = 2 g dpos, G- = -2 g dneg, GH = G+ + G-:
+ *     grad_rows [3B, emb] (rows 3b, 3b + 1, 3b + 2 = h, t+, t-): GH proj^T, -(G+) proj^T, -(G-) proj^T,
+ *     grad_rel_rows [B, emb]: GH,   dproj [emb, emb] = x[h]^T GH - x[t+]^T G+ - x[t-]^T G-.
+ *   The caller scatters grad_rows into a zero-filled [num_nodes, emb] gradient and grad_rel_rows into a zero-filled
+ *   [num_rel, emb] one with pea_rows_scatter_sum (P = 1, R = emb; 3B <= 16384).
+ * pea_transr_supported: emb a multiple of 4 in 4..128; pure, needs no device.
+ * pos_pred / neg_pred [B] are optional: both given or both NULL.  grad_rows, grad_rel_rows and dproj are all given, or all
+ * NULL: forward only, no backward work is done.  x may be a column block of a wider buffer: ldx and ldr are multiples of 4
+ * and at least emb; x, r, proj (and the two gradient row outputs) start on 16-byte boundaries.
+ * Every product runs on v_mfma_f32_16x16x4_f32 (k ascending from a zero accumulator; the three products x[.] proj stay
+ * separate, as the reference has them); dproj is one partial per workgroup added in workgroup order, the loss one sum per
+ * workgroup added in index order: no float atomics, bitwise reproducible, 64-bit row indexing.
+ * Stays asynchronous: a quadruple with a node id outside [0, num_nodes) or a relation id outside [0, num_rel) contributes
+ *   nothing (zero gradient rows, pos = neg = 0), reads nothing out of range and sets the int at workspace[0] to 1.
+ * Argument errors return PEA_ERR_ARG (a short workspace PEA_ERR_NOMEM) before anything is launched.
+ * workspace: pea_transr_train_workspace_bytes(B, emb) (0 = unsupported).
+ * ---------------------------------------------------------------------------------------------- */
+int pea_transr_supported(int emb);
+size_t pea_transr_train_workspace_bytes(int64_t B, int emb);
+int pea_transr_train(int64_t B, int emb, const float *x, int64_t ldx, int64_t num_nodes, const float *proj, const float *r,
+                     int64_t ldr, int64_t num_rel, const int64_t *quads, int64_t quad_stride, float *out_loss, float *pos_pred,
+                     float *neg_pred, float *grad_rows, float *grad_rel_rows, float *dproj, void *workspace,
+                     size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Entity-aware regulariser of the loss (models/base.py:50-73, only with --entity_aware=true):
  *   reg = -sum_b log sigmoid((|x[i]-x[e+]|^2 - |x[i]-x[e-]|^2) * m_i) - sum_b log sigmoid((|x[u]-x[f+]|^2 - |x[u]-x[f-]|^2) * m_u)
  * over the B rows (u, i+, i-, e+, e-, m_i, f+, f-, m_u) of `batch` (int64, row stride >= 9).  One launch gathers the six
