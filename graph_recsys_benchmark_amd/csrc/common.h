@@ -88,6 +88,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float4 ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
 __device__ __forceinline__ void st4(float *p, float4 v) { *reinterpret_cast<float4 *>(p) = v; }
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 constexpr int kWave = 64;          // gfx950 wavefront
 constexpr int kShortDeg = 32;      // rows with <= this many kept edges go to the row-per-subgroup kernel
@@ -431,6 +432,9 @@ int launch_mlp2(const Mlp2Launch &L, const int *rows, int64_t n_rows, hipStream_
 
 // ---------------------------------------------------------------- fusion / scoring (fuse_score.hip)
 constexpr int kMaxChannels = 64;
+// widest batch row pea_rows_scatter_sum moves (rows_scatter.hip: one wave per node, 4 float4 columns per lane): P * R
+// floats.  The training head is offered only where its gradient rows can go back that way (pea_bpr_train_supported)
+constexpr int kScatterMaxCols = 1024;
 struct ChanCols {
     int c[kMaxChannels];
 };

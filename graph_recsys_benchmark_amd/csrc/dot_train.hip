@@ -5,10 +5,11 @@
 //   pos = sum_k n_k(u) . n_k(i),  neg = sum_k n_k(u) . n_k(j),  loss = -sum_b log sigmoid(pos_b - neg_b)
 //   grad_rows [3B, D]: d loss / d X_k[r] for r = u, i, j (rows 3b, 3b + 1, 3b + 2), THROUGH the normalisation:
 //     inv (dn - n (n . dn)) with inv = 1 / ||X||, and dn / 1e-12 where the norm is below 1e-12 (the clamp's branch)
-// One thread owns a triple, as in bpr_train.hip: three passes over its rows (norms, dots, gradients); the rows come from
-// the cache after the first.  The loss is summed per block in thread order and the blocks in index order: no atomics on
-// floats.  The host scatters grad_rows into the per-block gradient tables with pea_rows_scatter_sum.
-#include "score_common.h"
+// One thread owns a triple: three passes over its rows (norms, dots, gradients); the rows come from the cache after the
+// first.  The loss tail is train_common.h's: bpr_term, the block sum in thread order and the blocks in index order: no
+// atomics on floats.  The host scatters grad_rows into the per-block gradient tables with pea_rows_scatter_sum
+// (rows_scatter.hip).
+#include "train_common.h"
 
 namespace pea {
 namespace {
@@ -27,7 +28,6 @@ struct DotBlocks {
 __global__ __launch_bounds__(kTB) void dot_bpr_train_kernel(int64_t B, const DotBlocks blk, int D, int64_t N,
                                                             const int64_t *__restrict__ triples, int64_t stride,
                                                             float *__restrict__ grad_rows, float *block_sums, int *err) {
-    __shared__ float red[kTB];
     const int64_t b = (int64_t)blockIdx.x * kTB + threadIdx.x;
     float term = 0.f;
     if (b < B) {
@@ -75,8 +75,8 @@ __global__ __launch_bounds__(kTB) void dot_bpr_train_kernel(int64_t B, const Dot
                 neg += dn;
             }
             const float d = pos - neg;
-            term = log_sigmoid_ref(d);
-            const float gp = -(1.0f - 1.0f / (1.0f + expf(-d)));      // d loss / d pos;  d loss / d neg = -gp
+            float gp;      // d loss / d pos;  d loss / d neg = -gp
+            bpr_term(d, term, gp);
             int col = 0;
 #pragma unroll
             for (int k = 0; k < kMaxBlocks; ++k) {
@@ -107,20 +107,11 @@ __global__ __launch_bounds__(kTB) void dot_bpr_train_kernel(int64_t B, const Dot
             }
         }
     }
-    red[threadIdx.x] = term;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float a = 0.f;
-        for (int k = 0; k < kTB; ++k) a += red[k];      // triple order inside the block
-        block_sums[blockIdx.x] = a;
-    }
+    block_sum_in_order<kTB>(term, block_sums + blockIdx.x);      // triple order inside the block
 }
 
 __global__ __launch_bounds__(64) void dot_bpr_final_kernel(int n_blocks, const float *block_sums, float *loss) {
-    if (threadIdx.x != 0) return;
-    float s = 0.f;
-    for (int i = 0; i < n_blocks; ++i) s += block_sums[i];      // blocks in index order
-    loss[0] = -s;
+    if (threadIdx.x == 0) store_loss(block_sums, n_blocks, loss);      // blocks in index order
 }
 
 }  // namespace
@@ -129,7 +120,7 @@ __global__ __launch_bounds__(64) void dot_bpr_final_kernel(int n_blocks, const f
 using namespace pea;
 
 extern "C" size_t pea_dot_bpr_train_workspace_bytes(int64_t B) {
-    return B < 0 ? 0 : 256 + (size_t)((B + kTB - 1) / kTB + 4) * sizeof(float);
+    return B < 0 ? 0 : kWsSumsOffset + (size_t)((B + kTB - 1) / kTB + 4) * sizeof(float);
 }
 
 extern "C" int pea_dot_bpr_train(int64_t B, int n_blocks, const float *const *blocks_host, const int64_t *ld_host,
@@ -144,7 +135,7 @@ extern "C" int pea_dot_bpr_train(int64_t B, int n_blocks, const float *const *bl
     for (int k = 0; k < n_blocks; ++k) {
         const int w = widths_host[k];
         PEA_REQUIRE(w >= 4 && w % 4 == 0 && w <= 256, PEA_ERR_ARG, "dot_bpr_train: block %d width %d (a multiple of 4)", k, w);
-        PEA_REQUIRE(blocks_host[k] && (reinterpret_cast<uintptr_t>(blocks_host[k]) & 15) == 0 && ld_host[k] >= w && ld_host[k] % 4 == 0,
+        PEA_REQUIRE(blocks_host[k] && aligned16(blocks_host[k]) && ld_host[k] >= w && ld_host[k] % 4 == 0,
                     PEA_ERR_ARG, "dot_bpr_train: block %d pointer / stride %lld", k, (long long)ld_host[k]);
         blk.x[k] = blocks_host[k];
         blk.ld[k] = ld_host[k];
@@ -155,8 +146,8 @@ extern "C" int pea_dot_bpr_train(int64_t B, int n_blocks, const float *const *bl
     PEA_REQUIRE(num_nodes > 0 && triples && triple_stride >= 3 && out_loss && grad_rows && workspace, PEA_ERR_ARG,
                 "dot_bpr_train: bad argument");
     PEA_REQUIRE(workspace_bytes >= pea_dot_bpr_train_workspace_bytes(B), PEA_ERR_NOMEM, "dot_bpr_train: workspace too small");
-    int *err = (int *)workspace;
-    float *sums = (float *)((char *)workspace + 256);
+    int *err = ws_err_flag(workspace);
+    float *sums = ws_sums(workspace);
     PEA_MEMSET_ASYNC(err, 0, sizeof(int), stream);
     const int blocks = (int)((B + kTB - 1) / kTB);
     ProfScope ps("dot_bpr_train", stream, (double)B * 3.0 * D * 8.0);

@@ -6,33 +6,30 @@
 //   PEA_KGU_NGCF   y = lrelu(A1 W1 + A2 W2)       the reference writes x W_1 + s W_1 + (x * s) W_2; the first two products
 //                                                 are merged here (one GEMM over x + s), which changes the rounding only
 //   out = y * keep * keep_scale                   keep: optional [N, out] byte mask of the dropout that follows the conv
-// One workgroup = 4 waves walks its 16-row tiles in a fixed order (tile blockIdx.x, + gridDim.x, ...).  The weights sit in
-// LDS once per workgroup (row stride + 4 floats); the tile's A1 / A2 rows are staged in LDS with 16-byte loads.  Every
-// product runs on v_mfma_f32_16x16x4_f32 from a zero accumulator with k ascending (lane (n, g) = (lane & 15, lane >> 4)
-// holds k = 4 t + g in step t), in the TRANSPOSED orientation of mlp2.hip: the weights are the A operand and the data rows
-// the B operand, so lane (n, g) ends up with columns 16 u + 4 g .. + 3 of ROW n: one float4 per lane for bias, mask,
-// output gradient and store.
+// Built from the tile toolkit of tile16.h: one workgroup = 4 waves walks its 16-row tiles in a fixed order (tile blockIdx.x,
+// + gridDim.x, ...).  The weights sit in LDS once per workgroup (stage_weight); the tile's A1 / A2 rows are staged in LDS
+// with 16-byte loads.  Every product runs from a zero accumulator with k ascending, in the TRANSPOSED orientation of
+// mlp2.hip: the weights are the A operand and the data rows the B operand (rows_times_w), so lane (n, g) ends up with
+// columns 16 u + 4 g .. + 3 of ROW n: one float4 per lane for bias, mask, output gradient and store.
 // Backward: recomputes the pre-activations with the forward's code (nothing is saved between the calls), then
 //   dZ = g * (z > 0 ? 1 : slope)  (0 for relu; z == 0 takes the slope, torch's rule),   g = g_out * keep * keep_scale
 //   dA1 = dZ1 W1^T, dA2 = dZ2 W2^T,  dx = dA1 + dA2 * s,  ds = dA1 + dA2 * x
 //   dW1 = A1^T dZ1, dW2 = A2^T dZ2,  dbias = column sum of g (KGAT) / of dZ1 (KGCN)
-// dZ goes through LDS once (it is the B operand of dA with the row on the lane and of dW with the row as k).  The dW tiles
-// are dealt out to the four waves and stay in their accumulators over all tiles of the workgroup: one partial per
-// workgroup, added in workgroup order by kg_update_dw_kernel.  No float atomics, grid = f(N), bitwise reproducible.
+// dZ goes through LDS once (it is the B operand of dA with the row on the lane, rows_times_wt, and of dW with the row as
+// k).  The dW tiles are dealt out to the four waves and stay in their accumulators over all tiles of the
+// workgroup: one partial per workgroup (dw_store), added in workgroup order by kg_update_dw_kernel (ordered_sum).  No float
+// atomics, grid = f(N), bitwise reproducible.
 // Shapes whose two weight images and tiles exceed the CU's LDS (both widths > 112 with two weights) are cut into output
 // column chunks: masks, dW and dbias are per output column, dA is the sum of the chunks' parts added in chunk order.
 #include <algorithm>
 
-#include "common.h"
+#include "tile16.h"
+#include "train_common.h"
 
 namespace pea {
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / kWave;
-constexpr int kTR = 16;                       // rows of one tile: one MFMA operand
 constexpr int kMaxWg = 512;                   // partials of the backward: two workgroups per CU
-constexpr size_t kLdsBudget = 156 * 1024;     // of the CU's 160 KB
 
 struct Cfg {
     int IP = 0, OC = 0, LDA = 0, LDW = 0, LDZ = 0, nw = 1, nz = 0, NT = 1;
@@ -43,8 +40,6 @@ bool supported(int kind, int in, int out) {
     return kind >= PEA_KGU_KGAT && kind <= PEA_KGU_NGCF && in >= 4 && in <= 128 && in % 4 == 0 && out >= 4 && out <= 128 &&
            out % 4 == 0;
 }
-
-int ceil16(int v) { return (v + 15) / 16 * 16; }
 
 Cfg make_cfg(int kind, int in, int out, bool bwd) {
     Cfg c;
@@ -58,9 +53,7 @@ Cfg make_cfg(int kind, int in, int out, bool bwd) {
         c.LDW = c.LDZ = c.OC + 4;
         c.lds = sizeof(float) * ((size_t)c.nw * c.IP * c.LDW + (size_t)c.nw * kTR * c.LDA + (size_t)c.nz * kTR * c.LDZ);
         // the backward also keeps its dW tiles in registers: at most 8 per wave and weight with two weights, 16 with one
-        const int per_wave = ((c.IP / 16) * (c.OC / 16) + kWaves - 1) / kWaves;
-        c.NT = 1;
-        while (c.NT < per_wave) c.NT <<= 1;
+        c.NT = tiles_per_wave((c.IP / 16) * (c.OC / 16));
         if ((c.lds <= kLdsBudget && (!bwd || c.NT <= (c.nw == 2 ? 8 : 16))) || c.OC == 16) break;
     }
     return c;
@@ -88,14 +81,6 @@ struct KguArgs {
 
 extern __shared__ __attribute__((aligned(16))) float kgu_smem[];
 
-// columns [c0, c0 + OC) of a [in, out] weight into its LDS image [IP][LDW]; rows >= in and columns >= out are zero
-__device__ __forceinline__ void stage_weight(const KguArgs &a, const float *w, float *img, int c0) {
-    for (int i = threadIdx.x; i < a.IP * a.OC; i += kThreads) {
-        const int k = i / a.OC, c = i - k * a.OC;
-        img[k * a.LDW + c] = (k < a.in && c0 + c < a.out) ? w[(size_t)k * a.out + c0 + c] : 0.f;
-    }
-}
-
 // A1 = x + s (and A2 = x * s) of the tile's 16 rows into LDS; rows >= N are zero rows
 template <bool TWO>
 __device__ __forceinline__ void stage_rows(const KguArgs &a, int64_t row0, float *A1t, float *A2t) {
@@ -110,20 +95,6 @@ __device__ __forceinline__ void stage_rows(const KguArgs &a, int64_t row0, float
         }
         st4(A1t + r * a.LDA + c, make_float4(xv.x + sv.x, xv.y + sv.y, xv.z + sv.z, xv.w + sv.w));
         if (TWO) st4(A2t + r * a.LDA + c, make_float4(xv.x * sv.x, xv.y * sv.y, xv.z * sv.z, xv.w * sv.w));
-    }
-}
-
-// pre-activations of output tile u of the chunk: register r of lane (n, g) = Z[row n][column 16 u + 4 g + r]
-template <bool TWO>
-__device__ __forceinline__ void z_tile(const KguArgs &a, const float *W1s, const float *W2s, const float *A1t, const float *A2t,
-                                       int u, int n, int g, f32x4 &z1, f32x4 &z2) {
-    z1 = (f32x4){0.f, 0.f, 0.f, 0.f};
-    z2 = (f32x4){0.f, 0.f, 0.f, 0.f};
-    const int wo = g * a.LDW + 16 * u + n, ao = n * a.LDA + g;
-    const int in4 = a.in / 4;
-    for (int t = 0; t < in4; ++t) {
-        z1 = __builtin_amdgcn_mfma_f32_16x16x4f32(W1s[wo + 4 * t * a.LDW], A1t[ao + 4 * t], z1, 0, 0, 0);
-        if (TWO) z2 = __builtin_amdgcn_mfma_f32_16x16x4f32(W2s[wo + 4 * t * a.LDW], A2t[ao + 4 * t], z2, 0, 0, 0);
     }
 }
 
@@ -148,13 +119,14 @@ __global__ __launch_bounds__(kThreads) void kg_update_fwd_kernel(const KguArgs a
     float *W2s = W1s + (TWO ? a.IP * a.LDW : 0);
     float *A1t = W2s + a.IP * a.LDW;
     float *A2t = A1t + (TWO ? kTR * a.LDA : 0);
+    constexpr int NC = TWO ? 2 : 1;      // weights = MFMA chains per product; without the second (KGCN) z2 / e2 are never read
     const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave, n = lane & 15, g = lane >> 4;
     const int64_t n_tiles = (a.N + kTR - 1) / kTR;
     for (int i = threadIdx.x; i < (TWO ? 2 : 1) * kTR * a.LDA; i += kThreads) A1t[i] = 0.f;      // the pad columns stay zero
     for (int c0 = 0; c0 < a.out; c0 += a.OC) {
         __syncthreads();
-        stage_weight(a, a.w1, W1s, c0);
-        if (TWO) stage_weight(a, a.w2, W2s, c0);
+        stage_weight<1>(a.w1, a.in, a.out, c0, W1s, a.IP, a.OC, a.LDW);      // one float at a time: the weights need no alignment
+        if (TWO) stage_weight<1>(a.w2, a.in, a.out, c0, W2s, a.IP, a.OC, a.LDW);
         const int oc = a.out - c0 < a.OC ? a.out - c0 : a.OC;
         const int n_ut = (oc + 15) / 16;
         for (int64_t T = blockIdx.x; T < n_tiles; T += gridDim.x) {
@@ -163,8 +135,9 @@ __global__ __launch_bounds__(kThreads) void kg_update_fwd_kernel(const KguArgs a
             __syncthreads();
             const int64_t row = T * kTR + n;
             for (int u = wave; u < n_ut; u += kWaves) {
-                f32x4 z1, z2;
-                z_tile<TWO>(a, W1s, W2s, A1t, A2t, u, n, g, z1, z2);
+                f32x4 z[NC] = {};
+                rows_times_w<NC, NC>(W1s, a.IP, a.LDW, A1t, a.LDA, a.in / 4, u, n, g, z);
+                const f32x4 &z1 = z[0], &z2 = z[NC - 1];
                 const int col = c0 + 16 * u + 4 * g;
                 if (row >= a.N || col >= a.out) continue;
                 float b[4] = {0.f, 0.f, 0.f, 0.f}, k[4], scale, y[4];
@@ -199,6 +172,7 @@ __global__ __launch_bounds__(kThreads) void kg_update_bwd_kernel(const KguArgs a
     float *Z1t = A2t + kTR * a.LDA;
     float *Z2t = Z1t + (TWO ? kTR * a.LDZ : 0);
     float *Gt = Z2t + kTR * a.LDZ;                 // KGAT only: g itself, for dbias
+    constexpr int NC = TWO ? 2 : 1;      // weights = MFMA chains per product; without the second (KGCN) z2 / e2 are never read
     const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave, n = lane & 15, g = lane >> 4;
     const int64_t n_tiles = (a.N + kTR - 1) / kTR;
     const int IT = a.IP / 16;
@@ -208,13 +182,11 @@ __global__ __launch_bounds__(kThreads) void kg_update_bwd_kernel(const KguArgs a
     for (int i = threadIdx.x; i < (TWO ? 2 : 1) * kTR * a.LDA; i += kThreads) A1t[i] = 0.f;
     for (int c0 = 0; c0 < a.out; c0 += a.OC) {
         __syncthreads();
-        stage_weight(a, a.w1, W1s, c0);
-        if (TWO) stage_weight(a, a.w2, W2s, c0);
+        stage_weight<1>(a.w1, a.in, a.out, c0, W1s, a.IP, a.OC, a.LDW);      // one float at a time: the weights need no alignment
+        if (TWO) stage_weight<1>(a.w2, a.in, a.out, c0, W2s, a.IP, a.OC, a.LDW);
         const int oc = a.out - c0 < a.OC ? a.out - c0 : a.OC;
         const int n_ut = (oc + 15) / 16;
-        f32x4 dw1[NT], dw2[NT];
-#pragma unroll
-        for (int q = 0; q < NT; ++q) dw1[q] = dw2[q] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        f32x4 dw[NC][NT] = {};
         float db = 0.f;
         for (int64_t T = blockIdx.x; T < n_tiles; T += gridDim.x) {
             __syncthreads();
@@ -223,8 +195,9 @@ __global__ __launch_bounds__(kThreads) void kg_update_bwd_kernel(const KguArgs a
             const int64_t row = T * kTR + n;
             // ---- pre-activations -> dZ tiles in LDS (zero for rows >= N and columns >= out)
             for (int u = wave; u < n_ut; u += kWaves) {
-                f32x4 z1, z2;
-                z_tile<TWO>(a, W1s, W2s, A1t, A2t, u, n, g, z1, z2);
+                f32x4 z[NC] = {};
+                rows_times_w<NC, NC>(W1s, a.IP, a.LDW, A1t, a.LDA, a.in / 4, u, n, g, z);
+                const f32x4 &z1 = z[0], &z2 = z[NC - 1];
                 const int lc = 16 * u + 4 * g, col = c0 + lc;
                 float gv[4] = {0.f, 0.f, 0.f, 0.f}, d1[4], d2[4];
                 float b[4] = {0.f, 0.f, 0.f, 0.f};
@@ -260,14 +233,10 @@ __global__ __launch_bounds__(kThreads) void kg_update_bwd_kernel(const KguArgs a
             }
             __syncthreads();
             // ---- dA^T = W dZ^T per input tile v: register r of lane (n, g) = dA[row n][input 16 v + 4 g + r]
-            const int oc4 = oc / 4;
             for (int v = wave; v < IT; v += kWaves) {
-                f32x4 e1 = {0.f, 0.f, 0.f, 0.f}, e2 = {0.f, 0.f, 0.f, 0.f};
-                const int wo = (16 * v + n) * a.LDW + g, zo = n * a.LDZ + g;
-                for (int t = 0; t < oc4; ++t) {
-                    e1 = __builtin_amdgcn_mfma_f32_16x16x4f32(W1s[wo + 4 * t], Z1t[zo + 4 * t], e1, 0, 0, 0);
-                    if (TWO) e2 = __builtin_amdgcn_mfma_f32_16x16x4f32(W2s[wo + 4 * t], Z2t[zo + 4 * t], e2, 0, 0, 0);
-                }
+                f32x4 e[NC] = {};
+                rows_times_wt<NC, NC>(W1s, a.IP, a.LDW, Z1t, a.LDZ, oc / 4, v, n, g, e);
+                const f32x4 &e1 = e[0], &e2 = e[NC - 1];
                 const int col = 16 * v + 4 * g;
                 if (row >= a.N || col >= a.in) continue;
                 float4 rx = make_float4(e1[0], e1[1], e1[2], e1[3]), rs = rx;
@@ -286,6 +255,7 @@ __global__ __launch_bounds__(kThreads) void kg_update_bwd_kernel(const KguArgs a
                 st4(ps, rs);
             }
             // ---- dW += A^T dZ over the tile's 16 rows (4 k-steps): register r of lane (n, g) = dW[16 v + 4 g + r][16 u + n]
+            //      (written out here and in transr_train.hip, tile16.h says why)
 #pragma unroll
             for (int q = 0; q < NT; ++q) {
                 const int id = wave + kWaves * q;
@@ -294,9 +264,9 @@ __global__ __launch_bounds__(kThreads) void kg_update_bwd_kernel(const KguArgs a
                 const int ao = g * a.LDA + 16 * v + n, zo = g * a.LDZ + 16 * u + n;
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
-                    dw1[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(A1t[ao + 4 * t * a.LDA], Z1t[zo + 4 * t * a.LDZ], dw1[q], 0, 0, 0);
+                    dw[0][q] = __builtin_amdgcn_mfma_f32_16x16x4f32(A1t[ao + 4 * t * a.LDA], Z1t[zo + 4 * t * a.LDZ], dw[0][q], 0, 0, 0);
                     if (TWO)
-                        dw2[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(A2t[ao + 4 * t * a.LDA], Z2t[zo + 4 * t * a.LDZ], dw2[q], 0, 0, 0);
+                        dw[NC - 1][q] = __builtin_amdgcn_mfma_f32_16x16x4f32(A2t[ao + 4 * t * a.LDA], Z2t[zo + 4 * t * a.LDZ], dw[NC - 1][q], 0, 0, 0);
                 }
             }
             if (a.want_dbias && (int)threadIdx.x < oc) {
@@ -304,21 +274,7 @@ __global__ __launch_bounds__(kThreads) void kg_update_bwd_kernel(const KguArgs a
             }
         }
         // ---- this workgroup's partial of the chunk's columns
-#pragma unroll
-        for (int q = 0; q < NT; ++q) {
-            const int id = wave + kWaves * q;
-            if (id >= IT * n_ut) continue;
-            const int v = id / n_ut, u = id - v * n_ut;
-            const int col = c0 + 16 * u + n;
-            if (col >= a.out) continue;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int i = 16 * v + 4 * g + r;
-                if (i >= a.in) continue;
-                part[(size_t)i * a.out + col] = dw1[q][r];
-                if (TWO) part[wsz + (size_t)i * a.out + col] = dw2[q][r];
-            }
-        }
+        dw_store<NT, NC>(dw, part, wsz, a.in, a.out, c0, IT, n_ut, wave, n, g);
         if (a.want_dbias && (int)threadIdx.x < oc) part[2 * wsz + c0 + threadIdx.x] = db;
     }
 }
@@ -331,15 +287,8 @@ __global__ __launch_bounds__(256) void kg_update_dw_kernel(int n_wg, int in, int
     if (e >= stride) return;
     float *dst = e < wsz ? (dw1 ? dw1 + e : nullptr) : e < 2 * wsz ? (dw2 ? dw2 + (e - wsz) : nullptr) : (dbias ? dbias + (e - 2 * wsz) : nullptr);
     if (!dst) return;
-    float acc = 0.f;
-    for (int w = 0; w < n_wg; ++w) acc += part[(size_t)w * stride + e];
-    *dst = acc;
+    *dst = ordered_sum(part + e, stride, n_wg);
 }
-
-// what a kernel's dynamic-LDS limit is raised to: once, to the most any configuration asks for
-size_t lds_limit(const Cfg &c) { return c.lds > 64 * 1024 ? kLdsBudget : 0; }
-
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 int check_args(const char *who, int64_t N, int kind, int in, int out, const float *x, int64_t ldx, const float *s, int64_t lds,
                const float *w1, const float *w2, const float *bias, const float *o, int64_t ldo) {
@@ -379,10 +328,10 @@ extern "C" int pea_kg_update_forward(int64_t N, int kind, int in_width, int out_
     const double flop_bytes = (double)N * 4.0 * (2.0 * in_width + out_width) + (keep ? (double)N * out_width : 0.0);
     ProfScope ps("kg_update_fwd", stream, flop_bytes);
     if (c.nw == 2) {
-        PEA_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(&kg_update_fwd_kernel<true>), lds_limit(c)));
+        PEA_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(&kg_update_fwd_kernel<true>), lds_limit(c.lds)));
         PEA_LAUNCH(kg_update_fwd_kernel<true>, grid, dim3(kThreads), c.lds, stream, a);
     } else {
-        PEA_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(&kg_update_fwd_kernel<false>), lds_limit(c)));
+        PEA_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(&kg_update_fwd_kernel<false>), lds_limit(c.lds)));
         PEA_LAUNCH(kg_update_fwd_kernel<false>, grid, dim3(kThreads), c.lds, stream, a);
     }
     PEA_HIP(hipGetLastError());
@@ -401,10 +350,10 @@ int launch_bwd(const Cfg &c, const KguArgs &a, dim3 grid, hipStream_t stream) {
     if (c.nw == 2) {
         constexpr int NT2 = NT > 8 ? 8 : NT;      // make_cfg never asks for more with two weights
         PEA_REQUIRE(c.NT <= 8, PEA_ERR_ARG, "kg_update_backward: %d dW tiles per wave", c.NT);
-        PEA_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(&kg_update_bwd_kernel<NT2, true>), lds_limit(c)));
+        PEA_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(&kg_update_bwd_kernel<NT2, true>), lds_limit(c.lds)));
         PEA_LAUNCH((kg_update_bwd_kernel<NT2, true>), grid, dim3(kThreads), c.lds, stream, a);
     } else {
-        PEA_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(&kg_update_bwd_kernel<NT, false>), lds_limit(c)));
+        PEA_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(&kg_update_bwd_kernel<NT, false>), lds_limit(c.lds)));
         PEA_LAUNCH((kg_update_bwd_kernel<NT, false>), grid, dim3(kThreads), c.lds, stream, a);
     }
     PEA_HIP(hipGetLastError());

@@ -4,45 +4,33 @@
 //   loss = -sum_b log sigmoid(pos_b - neg_b)                       (sign and form as the reference has them)
 //   g = -(1 - sigmoid(pos - neg)),  G+ = 2 g dpos,  G- = -2 g dneg,  GH = G+ + G-
 //   d x[h] = GH P^T,  d x[t+] = -(G+) P^T,  d x[t-] = -(G-) P^T,  d r[rel] = GH,  dP = x[h]^T GH - x[t+]^T G+ - x[t-]^T G-
-// Built like kg_update.hip: one workgroup = 4 waves walks its tiles of 16 quadruples in a fixed order (tile blockIdx.x,
-// + gridDim.x, ...).  P sits in LDS once per workgroup (zero rows / columns up to ceil16(E), row stride + 4 floats); the tile's
-// three operands [H; T+; T-] are staged in LDS with 16-byte loads.  Every product runs on v_mfma_f32_16x16x4_f32 from a zero
-// accumulator with k ascending, in the transposed orientation (P is the A operand, the data rows the B operand): lane
-// (n, g) = (lane & 15, lane >> 4) ends up with columns 16 u + 4 g .. + 3 of ROW n.  The three forward products stay separate,
-// as the reference has them.  dpos / dneg go through LDS; pos and neg are fma chains in ascending column order, eight of
+// Built from the tile toolkit of tile16.h: one workgroup = 4 waves walks its tiles of 16 quadruples in a fixed order (tile
+// blockIdx.x, + gridDim.x, ...).  P sits in LDS once per workgroup (stage_weight: zero rows / columns up to ceil16(E)); the
+// tile's three operands [H; T+; T-] are staged in LDS with 16-byte loads.  Every product runs from a zero accumulator with k
+// ascending, in the transposed orientation (P is the A operand, the data rows the B operand, rows_times_w): lane (n, g) ends
+// up with columns 16 u + 4 g .. + 3 of ROW n.  The three forward products stay separate, as the reference has them (three
+// chains in one k-loop).  dpos / dneg go through LDS; pos and neg are fma chains in ascending column order, eight of
 // them (column c in chain c % 8, added pairwise at the end): one chain over 128 squares that sum to ~16 leaves an error of
 // ~8e-6 in pos - neg, four times that of torch's tree sum, and g = d loss / d pos carries it into every gradient (dP at
-// E = 128 then misses the fp32 criterion of the tests); with eight the error is torch's.  The loss term is
-// log_sigmoid_ref.  Backward: [GH; G+; G-] pass through LDS once: they are the B operand of the three row products with
-// P^T (row on the lane) and of dP = [H; T+; T-]^T [GH; -G+; -G-] (the tile's 48 rows as k; the sign rides on the A operand).
-// The dP tiles are dealt out to the four waves and stay in their accumulators over all tiles of the workgroup: one partial
-// per workgroup, added in workgroup order by transr_final_kernel, which also adds the workgroups' loss sums in index order.
+// E = 128 then misses the fp32 criterion of the tests); with eight the error is torch's.  The loss term and g are
+// bpr_term (train_common.h).  Backward: [GH; G+; G-] pass through LDS once: they are the B operand of the three row
+// products with P^T (rows_times_wt) and of dP = [H; T+; T-]^T [GH; -G+; -G-] (the tile's 48 rows as k; the sign rides on
+// the A operand).  The dP tiles are dealt out to the four waves and stay in their accumulators over all
+// tiles of the workgroup: one partial per workgroup (dw_store), added in workgroup order by transr_final_kernel
+// (ordered_sum), which also adds the workgroups' loss sums in index order (store_loss).
 // No float atomics, grid = f(B), bitwise reproducible, 64-bit row indexing.  A quadruple with an id out of range is staged
 // as zero rows (nothing is read through it), contributes nothing, gets zero gradient rows and sets the error flag.
 #include <algorithm>
 
-#include "score_common.h"
+#include "tile16.h"
+#include "train_common.h"
 
 namespace pea {
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / kWave;
-constexpr int kTR = 16;                       // quadruples of one tile: one MFMA operand
 constexpr int kMaxWg = 256;                   // partials of dP: one workgroup per CU
-constexpr size_t kLdsBudget = 156 * 1024;     // of the CU's 160 KB
 
 bool supported(int emb) { return emb >= 4 && emb <= 128 && emb % 4 == 0; }
-
-int ceil16(int v) { return (v + 15) / 16 * 16; }
-
-// dP tiles per wave, rounded up to a power of two (the kernel's NT): 1, 4, 8 or 16 for the widths taken
-int tiles_per_wave(int emb) {
-    const int it = ceil16(emb) / 16, per_wave = (it * it + kWaves - 1) / kWaves;
-    int nt = 1;
-    while (nt < per_wave) nt <<= 1;
-    return nt;
-}
 
 // floats behind the tiles: g and the loss term per row, the row's validity, its four ids (as int64)
 constexpr int kSmallFloats = 16 + 16 + 16 + 2 * 4 * kTR;
@@ -83,13 +71,8 @@ __global__ __launch_bounds__(kThreads) void transr_train_kernel(const TrArgs a) 
     const int64_t n_tiles = (a.B + kTR - 1) / kTR;
     const int IT = a.IP / 16, in4 = a.E / 4, ip4 = a.IP / 4;
     for (int i = threadIdx.x; i < 3 * kTR * LD; i += kThreads) Xt[i] = 0.f;      // the pad columns stay zero
-    for (int i = threadIdx.x; i < a.IP * ip4; i += kThreads) {                   // rows >= E and columns >= E of P are zero
-        const int k = i / ip4, c = 4 * (i - k * ip4);
-        st4(Ps + k * LD + c, (k < a.E && c < a.E) ? ld4(a.proj + (size_t)k * a.E + c) : make_float4(0.f, 0.f, 0.f, 0.f));
-    }
-    f32x4 dp[NT];
-#pragma unroll
-    for (int q = 0; q < NT; ++q) dp[q] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    stage_weight<4>(a.proj, a.E, a.E, 0, Ps, a.IP, a.IP, LD);
+    f32x4 dp[1][NT] = {};
     float wg_loss = 0.f;
     for (int64_t T = blockIdx.x; T < n_tiles; T += gridDim.x) {
         __syncthreads();
@@ -118,14 +101,9 @@ __global__ __launch_bounds__(kThreads) void transr_train_kernel(const TrArgs a) 
         __syncthreads();
         // ---- x[.] P per output tile u: register r of lane (n, g) = row n, column 16 u + 4 g + r; then dpos / dneg
         for (int u = wave; u < IT; u += kWaves) {
-            f32x4 zh = {0.f, 0.f, 0.f, 0.f}, zp = {0.f, 0.f, 0.f, 0.f}, zn = {0.f, 0.f, 0.f, 0.f};
-            const int wo = g * LD + 16 * u + n, ao = n * LD + g;
-            for (int t = 0; t < in4; ++t) {
-                const float w = Ps[wo + 4 * t * LD];
-                zh = __builtin_amdgcn_mfma_f32_16x16x4f32(w, Xt[ao + 4 * t], zh, 0, 0, 0);
-                zp = __builtin_amdgcn_mfma_f32_16x16x4f32(w, Xt[kTR * LD + ao + 4 * t], zp, 0, 0, 0);
-                zn = __builtin_amdgcn_mfma_f32_16x16x4f32(w, Xt[2 * kTR * LD + ao + 4 * t], zn, 0, 0, 0);
-            }
+            f32x4 z[3] = {};
+            rows_times_w<1, 3>(Ps, a.IP, LD, Xt, LD, in4, u, n, g, z);
+            const f32x4 &zh = z[0], &zp = z[1], &zn = z[2];
             const int lc = 16 * u + 4 * g;
             float4 rv = make_float4(0.f, 0.f, 0.f, 0.f);
             if (valid[n] && lc < a.E) rv = ld4(a.r + ids[3 * kTR + n] * a.ldr + lc);
@@ -154,8 +132,8 @@ __global__ __launch_bounds__(kThreads) void transr_train_kernel(const TrArgs a) 
             if (lane < kTR) {
                 const bool ok = valid[lane] != 0;
                 const float pos = ok ? s : 0.f, neg = ok ? other : 0.f, d = pos - neg;
-                term[lane] = ok ? log_sigmoid_ref(d) : 0.f;
-                gco[lane] = ok ? -(1.0f - 1.0f / (1.0f + expf(-d))) : 0.f;      // d loss / d pos;  d loss / d neg = -g
+                bpr_term(d, term[lane], gco[lane]);      // gco: d loss / d pos;  d loss / d neg = -g
+                if (!ok) term[lane] = gco[lane] = 0.f;
                 const int64_t b = T * kTR + lane;
                 if (a.pos && b < a.B) {
                     a.pos[b] = pos;
@@ -190,14 +168,9 @@ __global__ __launch_bounds__(kThreads) void transr_train_kernel(const TrArgs a) 
         __syncthreads();
         // ---- G P^T per input tile v: register r of lane (n, g) = row n, input 16 v + 4 g + r
         for (int v = wave; v < IT; v += kWaves) {
-            f32x4 e0 = {0.f, 0.f, 0.f, 0.f}, e1 = {0.f, 0.f, 0.f, 0.f}, e2 = {0.f, 0.f, 0.f, 0.f};
-            const int wo = (16 * v + n) * LD + g, zo = n * LD + g;
-            for (int t = 0; t < in4; ++t) {
-                const float w = Ps[wo + 4 * t];
-                e0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w, Gt[zo + 4 * t], e0, 0, 0, 0);
-                e1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w, Gt[kTR * LD + zo + 4 * t], e1, 0, 0, 0);
-                e2 = __builtin_amdgcn_mfma_f32_16x16x4f32(w, Gt[2 * kTR * LD + zo + 4 * t], e2, 0, 0, 0);
-            }
+            f32x4 e[3] = {};
+            rows_times_wt<1, 3>(Ps, a.IP, LD, Gt, LD, in4, v, n, g, e);
+            const f32x4 &e0 = e[0], &e1 = e[1], &e2 = e[2];
             const int col = 16 * v + 4 * g;
             const int64_t b = T * kTR + n;
             if (b >= a.B || col >= a.E) continue;
@@ -210,7 +183,7 @@ __global__ __launch_bounds__(kThreads) void transr_train_kernel(const TrArgs a) 
             st4(gr + 2 * a.E, r2);
         }
         // ---- dP += [H; T+; T-]^T [GH; -G+; -G-] over the tile's 48 rows (12 k-steps): register r of lane (n, g) =
-        //      dP[16 v + 4 g + r][16 u + n]
+        //      dP[16 v + 4 g + r][16 u + n]  (written out here and in kg_update.hip, tile16.h says why)
 #pragma unroll
         for (int q = 0; q < NT; ++q) {
             const int id = wave + kWaves * q;
@@ -220,41 +193,13 @@ __global__ __launch_bounds__(kThreads) void transr_train_kernel(const TrArgs a) 
 #pragma unroll
             for (int t = 0; t < 12; ++t) {
                 const float xv = Xt[ao + 4 * t * LD];
-                dp[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(t < 4 ? xv : -xv, Gt[zo + 4 * t * LD], dp[q], 0, 0, 0);
+                dp[0][q] = __builtin_amdgcn_mfma_f32_16x16x4f32(t < 4 ? xv : -xv, Gt[zo + 4 * t * LD], dp[0][q], 0, 0, 0);
             }
         }
     }
     if (threadIdx.x == 0) a.sums[blockIdx.x] = wg_loss;
     if (!BWD) return;
-    float *part = a.part + (size_t)blockIdx.x * a.E * a.E;
-#pragma unroll
-    for (int q = 0; q < NT; ++q) {
-        const int id = wave + kWaves * q;
-        if (id >= IT * IT) continue;
-        const int v = id / IT, u = id - v * IT;
-        const int col = 16 * u + n;
-        if (col >= a.E) continue;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int i = 16 * v + 4 * g + r;
-            if (i < a.E) part[(size_t)i * a.E + col] = dp[q][r];
-        }
-    }
-}
-
-// p[0] + p[stride] + ... (n terms) added in index order; the loads go out eight at a time, the order of the additions stays
-__device__ __forceinline__ float ordered_sum(const float *__restrict__ p, size_t stride, int n) {
-    float acc = 0.f;
-    int w = 0;
-    for (; w + 8 <= n; w += 8) {
-        float v[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = p[(size_t)(w + j) * stride];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc += v[j];
-    }
-    for (; w < n; ++w) acc += p[(size_t)w * stride];
-    return acc;
+    dw_store<NT, 1>(dp, a.part + (size_t)blockIdx.x * a.E * a.E, 0, a.E, a.E, 0, IT, IT, wave, n, g);
 }
 
 // element e of dP = the workgroups' partials added in workgroup order; the loss = minus the workgroups' sums in index order
@@ -262,20 +207,17 @@ __global__ __launch_bounds__(256) void transr_final_kernel(int n_wg, int emb, co
                                                           const float *__restrict__ sums, float *dproj, float *loss) {
     const size_t wsz = (size_t)emb * emb, e = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (dproj && e < wsz) dproj[e] = ordered_sum(part + e, wsz, n_wg);
-    if (e == 0) loss[0] = -ordered_sum(sums, 1, n_wg);
+    if (e == 0) store_loss(sums, n_wg, loss);
 }
-
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 int n_workgroups(int64_t B) { return (int)std::min<int64_t>((B + kTR - 1) / kTR, kMaxWg); }
 
-constexpr size_t kSumsOffset = 256;      // the error flag is the int at workspace[0]
-size_t part_offset() { return kSumsOffset + align256((size_t)kMaxWg * sizeof(float)); }
+size_t part_offset() { return kWsSumsOffset + align256((size_t)kMaxWg * sizeof(float)); }
 
 template <int NT, bool BWD>
 int launch_main(const TrArgs &a, int n_wg, hipStream_t stream) {
     const size_t lds = lds_bytes(a.E, BWD);
-    PEA_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(&transr_train_kernel<NT, BWD>), lds > 64 * 1024 ? kLdsBudget : 0));
+    PEA_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(&transr_train_kernel<NT, BWD>), lds_limit(lds)));
     PEA_LAUNCH((transr_train_kernel<NT, BWD>), dim3(n_wg), dim3(kThreads), lds, stream, a);
     PEA_HIP(hipGetLastError());
     return PEA_OK;
@@ -316,8 +258,8 @@ extern "C" int pea_transr_train(int64_t B, int emb, const float *x, int64_t ldx,
     a.B = B; a.N = num_nodes; a.R = num_rel; a.E = emb; a.IP = ceil16(emb); a.LD = a.IP + 4;
     a.x = x; a.proj = proj; a.r = r; a.ldx = ldx; a.ldr = ldr; a.quads = quads; a.qs = quad_stride;
     a.pos = pos_pred; a.neg = neg_pred; a.grad_rows = grad_rows; a.grad_rel = grad_rel_rows;
-    a.err = (int *)workspace;
-    a.sums = (float *)((char *)workspace + kSumsOffset);
+    a.err = ws_err_flag(workspace);
+    a.sums = ws_sums(workspace);
     a.part = (float *)((char *)workspace + part_offset());
     PEA_MEMSET_ASYNC(a.err, 0, sizeof(int), stream);
     const int n_wg = n_workgroups(B);
@@ -327,7 +269,7 @@ extern "C" int pea_transr_train(int64_t B, int emb, const float *x, int64_t ldx,
         if (!bwd) {
             PEA_TRY((launch_main<1, false>(a, n_wg, stream)));
         } else {
-            switch (tiles_per_wave(emb)) {
+            switch (tiles_per_wave((a.IP / 16) * (a.IP / 16))) {      // dP tiles per wave: 1, 4, 8 or 16 for the widths taken
                 case 1: PEA_TRY((launch_main<1, true>(a, n_wg, stream))); break;
                 case 4: PEA_TRY((launch_main<4, true>(a, n_wg, stream))); break;
                 case 8: PEA_TRY((launch_main<8, true>(a, n_wg, stream))); break;

@@ -733,6 +733,20 @@ def check_pending_errors():
         raise IndexError('index out of range in BPR triples')
 
 
+def _defer_error(flag):
+    """Queue the int32 error flag of a launch for the next check_pending_errors()."""
+    if len(_pending_err) >= 64:          # bounded: a long async loop never grows the list
+        check_pending_errors()
+    _pending_err.append(flag)
+
+
+def _int64_batch(batch, min_cols):
+    """batch as the loss kernels read it: int64 [B, >= min_cols] with unit column stride (else copied)."""
+    if batch.dtype != torch.int64 or batch.dim() != 2 or batch.shape[1] < min_cols:
+        raise ValueError('batch must be int64 [B, >=%d]' % min_cols)
+    return batch if batch.stride(1) == 1 else batch.contiguous()
+
+
 def bpr_score(repr_, triples, fc1_w, fc1_b, fc2_w, fc2_b, want_preds=False, validate=False):
     """loss = -sum(log(sigmoid(pos - neg))) over rows (u, i+, i-) of `triples` (reference models/base.py:46-48,
     208-214).  Returns a 0-dim tensor (and pos, neg [B] when asked).  A triple with a node id out of range makes the
@@ -755,9 +769,7 @@ def bpr_score(repr_, triples, fc1_w, fc1_b, fc2_w, fc2_b, want_preds=False, vali
                                  _lib.ptr(args[1]), _lib.ptr(args[2]), _lib.ptr(args[3]), _lib.ptr(args[4]),
                                  _lib.ptr(pos), _lib.ptr(neg), _lib.ptr(loss), _lib.ptr(ws), ws_bytes,
                                  _lib.current_stream()))
-    if len(_pending_err) >= 64:          # bounded: a long async loop never grows the list
-        check_pending_errors()
-    _pending_err.append(ws[:4].view(torch.int32)[0])
+    _defer_error(ws[:4].view(torch.int32)[0])
     if validate:
         check_pending_errors()
     return (loss, pos, neg) if want_preds else loss
@@ -800,9 +812,7 @@ def _entity_launch(x, batch9, want_grad):
     rows = torch.empty((6 * b, f), dtype=torch.float32, device=xd.device) if want_grad else None
     _lib.check(lib.pea_entity_reg(b, f, xd.shape[0], _lib.ptr(xd), xd.stride(0), _lib.ptr(batch9), batch9.stride(0),
                                   _lib.ptr(reg), _lib.ptr(rows), _lib.ptr(ws), ws_bytes, _lib.current_stream()))
-    if len(_pending_err) >= 64:
-        check_pending_errors()
-    _pending_err.append(ws[:4].view(torch.int32)[0])
+    _defer_error(ws[:4].view(torch.int32)[0])
     return reg, rows
 
 
@@ -1134,6 +1144,13 @@ def rows_scatter_sum(ids, src, num_channels, repr_dim, col_of_channel, dst):
 ROWS_SCATTER_MAX = 16384      # positions pea_rows_scatter_sum sorts in LDS (a BPR batch of up to 5461 triples)
 
 
+def _scatter_dense(ids, rows, n, w):
+    """The dense [n, w] gradient of a table from the gradient rows [len(ids), w] of the positions that read it."""
+    dst = torch.zeros((n, w), dtype=torch.float32, device=rows.device)
+    rows_scatter_sum(ids, rows, 1, w, [0], dst)
+    return dst
+
+
 class _BprTrainLoss(torch.autograd.Function):
     """loss = -sum_b log sigmoid(score(u_b, i+_b) - score(u_b, i-_b)) over the fused rows of the batch's stack rows, and its
     whole backward, in one HIP launch (csrc/bpr_train.hip) + two fixed-order reductions for the parameter gradients
@@ -1169,18 +1186,10 @@ def dot_bpr_train_raw(blocks, batch):
     """One launch of csrc/dot_train.hip: (loss, grad_rows [3B, D], error flag) for the raw conv outputs `blocks` (a list of
     [N, w_k] tensors whose normalised concatenation is the models' table) and the int64 [B, >= 3] triples `batch`."""
     lib = _lib.require_device()
-    if batch.dtype != torch.int64 or batch.dim() != 2 or batch.shape[1] < 3:
-        raise ValueError('batch must be int64 [B, >=3]')
+    batch = _int64_batch(batch, 3)
     if not 1 <= len(blocks) <= DOT_TRAIN_MAX_BLOCKS:
         raise ValueError('1..%d column blocks expected' % DOT_TRAIN_MAX_BLOCKS)
-    if batch.stride(1) != 1:
-        batch = batch.contiguous()
-    rows = []
-    for t in blocks:
-        t = _rows2d(t.detach())
-        if t.stride(0) % 4 or t.data_ptr() % 16:
-            t = t.contiguous()
-        rows.append(t)
+    rows = [_block16(t) for t in blocks]
     n, b, dev = rows[0].shape[0], batch.shape[0], rows[0].device
     if any(t.shape[0] != n for t in rows):
         raise ValueError('the blocks must have the same number of rows')
@@ -1207,9 +1216,7 @@ class _DotBprLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, batch, *blocks):
         loss, grad_rows, flag = dot_bpr_train_raw(blocks, batch)
-        if len(_pending_err) >= 64:
-            check_pending_errors()
-        _pending_err.append(flag)
+        _defer_error(flag)
         ctx.ids = batch[:, :3].reshape(-1).contiguous()
         ctx.grad_rows = grad_rows
         ctx.shapes = [tuple(t.shape) for t in blocks]
@@ -1220,12 +1227,7 @@ class _DotBprLoss(torch.autograd.Function):
         rows = ctx.grad_rows * g
         grads, off = [], 0
         for i, (n, w) in enumerate(ctx.shapes):
-            if ctx.needs_input_grad[1 + i]:
-                dst = torch.zeros((n, w), dtype=torch.float32, device=rows.device)
-                rows_scatter_sum(ctx.ids, rows[:, off:off + w], 1, w, [0], dst)
-                grads.append(dst)
-            else:
-                grads.append(None)
+            grads.append(_scatter_dense(ctx.ids, rows[:, off:off + w], n, w) if ctx.needs_input_grad[1 + i] else None)
             off += w
         return (None,) + tuple(grads)
 
@@ -1254,7 +1256,7 @@ def transr_supported(emb, batch_size):
 
 
 def _block16(t):
-    """t as transr_train reads it: rows with a stride that is a multiple of 4 floats and a 16-byte aligned start (a column
+    """t as dot_bpr_train / transr_train read it: rows with a stride that is a multiple of 4 floats and a 16-byte aligned start (a column
     block of a wider buffer qualifies); anything else is copied."""
     t = _rows2d(t.detach())
     if t.stride(0) % 4 or t.stride(0) < t.shape[1] or t.data_ptr() % 16:
@@ -1268,10 +1270,7 @@ def transr_train_raw(x, proj, r, batch, need_grad=True):
     int64 [B, >= 4] rows (h, t+, t-, rel) of `batch`.  need_grad=False is the forward-only form: the three gradients are
     None and no backward work is done."""
     lib = _lib.require_device()
-    if batch.dtype != torch.int64 or batch.dim() != 2 or batch.shape[1] < 4:
-        raise ValueError('batch must be int64 [B, >=4]')
-    if batch.stride(1) != 1:
-        batch = batch.contiguous()
+    batch = _int64_batch(batch, 4)
     x, r = _block16(x), _block16(r)
     proj = _rows2d(proj.detach()).contiguous()
     e = x.shape[1]
@@ -1305,9 +1304,7 @@ class _TransrLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, batch, need_grad, x, proj, r):
         loss, _, _, grad_rows, grad_rel, dproj, flag = transr_train_raw(x, proj, r, batch, need_grad)
-        if len(_pending_err) >= 64:
-            check_pending_errors()
-        _pending_err.append(flag)
+        _defer_error(flag)
         if need_grad:
             ctx.node_ids = batch[:, :3].reshape(-1).contiguous()
             ctx.rel_ids = batch[:, 3].contiguous()
@@ -1321,13 +1318,11 @@ class _TransrLoss(torch.autograd.Function):
         (n, e), (n_rel, _) = ctx.shapes
         dx = dp = dr = None
         if ctx.needs_input_grad[2]:
-            dx = torch.zeros((n, e), dtype=torch.float32, device=g.device)
-            rows_scatter_sum(ctx.node_ids, grad_rows * g, 1, e, [0], dx)
+            dx = _scatter_dense(ctx.node_ids, grad_rows * g, n, e)
         if ctx.needs_input_grad[3]:
             dp = dproj * g
         if ctx.needs_input_grad[4]:
-            dr = torch.zeros((n_rel, e), dtype=torch.float32, device=g.device)
-            rows_scatter_sum(ctx.rel_ids, grad_rel * g, 1, e, [0], dr)
+            dr = _scatter_dense(ctx.rel_ids, grad_rel * g, n_rel, e)
         return None, None, dx, dp, dr
 
 
