@@ -8,24 +8,10 @@
 // Stream: Philox4x32-10 (Salmon et al. 2011), key = seed, counter = (row index lo, hi, attempt, offset); the first
 // 32-bit output word w maps to an item as floor(w * num_items / 2^32).  oracle/philox.py restates it in numpy.
 #include "common.h"
+#include "philox.h"
 
 namespace pea {
 namespace {
-
-struct U4 {
-    unsigned x, y, z, w;
-};
-
-__device__ __forceinline__ U4 philox4x32_10(U4 c, unsigned k0, unsigned k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned long long p0 = 0xD2511F53ull * c.x, p1 = 0xCD9E8D57ull * c.z;
-        c = U4{(unsigned)(p1 >> 32) ^ c.y ^ k0, (unsigned)p1, (unsigned)(p0 >> 32) ^ c.w ^ k1, (unsigned)p0};
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return c;
-}
 
 // first index with keys[idx] >= key
 __device__ __forceinline__ bool contains(const long long *__restrict__ keys, long long n, long long key) {

@@ -5,7 +5,9 @@ from .peasage import PEASageChannel, PEASageRecsysModel
 from .kgat import KGATRecsysModel
 from .kgcn import KGCNRecsysModel
 from .ngcf import NGCFRecsysModel
+from .metapath2vec import MetaPath2Vec
+from .walk import WalkBasedRecsysModel
 
 __all__ = ['GraphRecsysModel', 'PEABaseChannel', 'PEABaseRecsysModel', 'PEAGATChannel', 'PEAGATRecsysModel',
            'PEAGCNChannel', 'PEAGCNRecsysModel', 'PEASageChannel', 'PEASageRecsysModel', 'KGATRecsysModel', 'KGCNRecsysModel',
-           'NGCFRecsysModel']
+           'NGCFRecsysModel', 'MetaPath2Vec', 'WalkBasedRecsysModel']

@@ -44,7 +44,9 @@ def metrics(model, dataset, num_neg_candidates=99):
         cand[idx, 1:] = neg_i_nids
     dev = model.cached_repr.device
     u_t = torch.as_tensor(np.asarray(u_nids, dtype=np.int64), device=dev)
-    if getattr(model, 'scorer', 'mlp') == 'dot':      # KGAT / KGCN (after model.cf_eval(att_map)) / NGCF
+    if hasattr(model, 'rank_eval'):                   # a model that picks its own evaluator (models/walk.py: HIP or torch by width)
+        scores, rank, auc, loss = model.rank_eval(u_t, torch.from_numpy(cand).to(dev))
+    elif getattr(model, 'scorer', 'mlp') == 'dot':    # KGAT / KGCN (after model.cf_eval(att_map)) / NGCF
         scores, rank, auc, loss = engine.dot_rank_eval(model.cached_repr, u_t, torch.from_numpy(cand).to(dev))
     else:
         scores, rank, auc, loss = engine.rank_eval(model.cached_repr, u_t, torch.from_numpy(cand).to(dev), model.fc1.weight,
@@ -131,7 +133,9 @@ def metrics_full(model, u_nids, pos_items, item_range, exclude=None):
     dev = model.cached_repr.device
     u_t = torch.as_tensor(np.asarray(u_nids, dtype=np.int64), device=dev)
     pos_t = torch.as_tensor(np.asarray(pos_items, dtype=np.int64), device=dev)
-    if getattr(model, 'scorer', 'mlp') == 'dot':
+    if hasattr(model, 'rank_full'):
+        rank, auc, _ = model.rank_full(u_t, pos_t, item_range, exclude=exclude)
+    elif getattr(model, 'scorer', 'mlp') == 'dot':
         rank, auc, _ = engine.dot_rank_full(model.cached_repr, u_t, pos_t, item_range, exclude=exclude)
     else:
         rank, auc, _ = engine.rank_full(model.cached_repr, u_t, pos_t, item_range, model.fc1.weight, model.fc1.bias,

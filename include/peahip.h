@@ -38,6 +38,8 @@
  *   pea_sample_negatives     datasets/movielens.py:920-940 (an on-GPU sampler NEXT TO the bit-exact host mirror)
  *   pea_entity_reg           models/base.py:50-73 (entity-aware regulariser of the loss, value + gradient rows)
  *   pea_bpr_train            models/base.py:193-214 + 46-48 under autograd (fusion + scorer + BPR loss, forward + backward)
+ *   pea_metapath_walks, pea_uniform_walks, pea_skipgram_train
+ *                            models/metapath2vec.py:101-172 (walk sampling on the GPU; skip-gram loss + backward over whole walks)
  *   pea_fuse_ablate, pea_model_forward_ablate, pea_rank_eval_multi
  *                            solvers.py:224-241 (the --metapath_test sweep: eval(metapath_idx) + metrics() per metapath)
  *   pea_recommend_topk, pea_rank_full   models/base.py:208-214 over the WHOLE item catalogue: the K best unseen items per
@@ -691,6 +693,55 @@ int pea_transr_train(int64_t B, int emb, const float *x, int64_t ldx, int64_t nu
                      int64_t ldr, int64_t num_rel, const int64_t *quads, int64_t quad_stride, float *out_loss, float *pos_pred,
                      float *neg_pred, float *grad_rows, float *grad_rel_rows, float *dproj, void *workspace,
                      size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * metapath2vec (csrc/walk.hip, csrc/skipgram.hip): reference models/metapath2vec.py, whose walks are drawn on the CPU
+ * (:101-121, one torch_sparse adj.sample per step) and whose loss gathers [windows, C - 1, D] rows of the table (:147-172).
+ *
+ * Both walk kinds write walks [n_walks, ld] (int64, ld >= walk_length + 1; column 0 = starts[row]) and draw column t >= 1 from
+ *   w = first output word of Philox4x32-10, key = seed (lo, hi), counter = (row lo, row hi, t, offset)
+ * (the stream of pea_sample_negatives); s = (t - 1) % cycle_len.  One walk per thread; the calls stay asynchronous.
+ * pea_metapath_walks: with cur = the node at column t - 1, r = relation_of_step_host[s] and deg = the CSR slots of row cur in
+ *   relation r of the plan:  walks[row, t] = col_r[rowptr_r[cur] + ((w * deg) >> 32)].  The CSR row of a node holds the SOURCES
+ *   of its in-edges: a step goes from a node to one it aggregates from (hand over the flipped COO to walk along the edges).
+ *   Multi-edges stay, so a doubled edge is drawn twice as often.  deg == 0: that column and every later one of the row are -1
+ *   and status[0] (device int32 [2], cleared by the call) counts the walk; a start outside [0, num_nodes) makes the whole row
+ *   -1 and is counted in status[1].  The plan must be unsharded and built without PEA_PLAN_SELF_LOOPS (such a plan drops the
+ *   i -> i edges); cycle_len in 1..16; a relation outside the plan gives PEA_ERR_ARG.
+ * pea_uniform_walks (the negative walks of :123-140): walks[row, t] = block_lo_host[s] + ((w * block_n_host[s]) >> 32), the
+ *   node-id block of the step's target type; 0 < block_n < 2^32.
+ *
+ * pea_skipgram_train: loss and d loss / d table of n_pos positive and n_neg negative rows of T ids each (row strides
+ *   pos_stride / neg_stride >= T) against table [num_nodes, D] (row stride ld), context size C.  A row holds the T - C + 1
+ *   windows j .. j + C - 1; the first id of a window is its start and with each of the other C - 1 it forms a pair,
+ *   out = table[start] . table[other]  (a [M, C] array in the reference's own window layout is the case T == C).
+ *   A pair with an id < 0 or >= num_nodes is skipped (an id >= num_nodes also sets *err_flag, a device int32 that the call
+ *   clears first, to 1).
+ *     pos = -mean log(sigmoid(out) + 1e-15) over the valid pairs of the positive rows,
+ *     neg = -mean log(1 - sigmoid(out) + 1e-15) over those of the negative rows (a side without a valid pair gives 0),
+ *   loss [3] = {pos + neg, pos, neg};  n_valid [2] (int64) = the valid pairs per side;
+ *   grad [num_nodes, D] contiguous = d loss / d table, EVERY row written (zeros where the step touched nothing);
+ *   touched (int32, room for min((n_pos + n_neg) T, num_nodes) entries) = the node ids that sit at a position with an id in
+ *   range, ascending and unique, and *touched_count their number (both on the device): the rows of grad outside it are zero.
+ *   A table row is read once per walk position, by the workgroup that owns the walk (rows staged in LDS); the per-position
+ *   gradient rows go through the workspace and are summed per node in position order after a rocprim radix sort of the
+ *   (id, position) keys -- any number of positions, runs of any length.  No float atomics: identical calls give identical
+ *   bytes.  Not recordable on a launch tape (PEA_ERR_ARG while one records).
+ * pea_skipgram_supported: D a multiple of 4 in 4..128, 2 <= C <= 16, C <= T <= 128; pure.  (n_pos + n_neg) * T < 2^31.
+ * workspace: pea_skipgram_workspace_bytes (0 = unsupported); a short one gives PEA_ERR_NOMEM.
+ * ---------------------------------------------------------------------------------------------- */
+int pea_metapath_walks(const pea_plan *plan, int cycle_len, const int *relation_of_step_host, int walk_length, int64_t n_walks,
+                       const int64_t *starts, uint64_t seed, uint32_t offset, int64_t *walks, int64_t ld, int32_t *status,
+                       void *stream);
+int pea_uniform_walks(int cycle_len, const int64_t *block_lo_host, const int64_t *block_n_host, int walk_length,
+                      int64_t n_walks, const int64_t *starts, uint64_t seed, uint32_t offset, int64_t *walks, int64_t ld,
+                      void *stream);
+int pea_skipgram_supported(int D, int T, int C);
+size_t pea_skipgram_workspace_bytes(int64_t n_pos, int64_t n_neg, int T, int C, int D);
+int pea_skipgram_train(int64_t n_pos, int64_t n_neg, int T, int C, int D, const float *table, int64_t ld, int64_t num_nodes,
+                       const int64_t *pos_walks, int64_t pos_stride, const int64_t *neg_walks, int64_t neg_stride, float *loss,
+                       int64_t *n_valid, float *grad, int32_t *touched, int32_t *touched_count, int32_t *err_flag,
+                       void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Entity-aware regulariser of the loss (models/base.py:50-73, only with --entity_aware=true):
