@@ -22,7 +22,7 @@ namespace {
 // mean's divisor, as in the reference).  out_att [N, P] (optional): softmax weights of variant 0, 1 / P under 'mean'.
 template <int G, int PREG>
 __global__ __launch_bounds__(256) void fuse_ablate_kernel(int64_t N, int P, int R, const float *__restrict__ stack,
-                                                          int64_t ld, const ChanCols col_of_channel,
+                                                          int64_t ld, const ChanCols col_of_channel, const ChanCopy copy,
                                                           const float *__restrict__ att, int mode,
                                                           float *__restrict__ out, float *__restrict__ out_att) {
     const int64_t item = (int64_t)blockIdx.x * (256 / G) + threadIdx.x / G;
@@ -32,11 +32,13 @@ __global__ __launch_bounds__(256) void fuse_ablate_kernel(int64_t N, int P, int 
     const bool in_row = sl * 4 < R;
     const bool active = valid && in_row;
     const int c4 = in_row ? sl * 4 : 0;
-    const float *row = stack + n * ld + c4;
+    const float *row0 = stack + n * ld;
     const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
     const bool mean = mode == PEA_FUSE_MEAN;
     float *dst = out + n * R + c4;
     const int64_t variant_stride = N * (int64_t)R;
+    const unsigned long long lone = copy_row_bits(copy, P, n);
+    stage_copy_rows(copy, P, R, smem);
 
     if constexpr (PREG > 0) {
         float4 x[PREG];
@@ -46,7 +48,7 @@ __global__ __launch_bounds__(256) void fuse_ablate_kernel(int64_t N, int P, int 
             x[p] = zero;
             lg[p] = 0.f;
             if (p < P) {
-                x[p] = ld4(row + col_of_channel.c[p]);
+                x[p] = chan_value(row0 + col_of_channel.c[p], copy.c[p], copy, smem + 3 * p * R, R, (lone >> p) & 1, n, c4, sl);
                 if (!mean) lg[p] = chan_logit<G>(x[p], ld4(att + p * R + c4), in_row);
             }
         }
@@ -82,7 +84,7 @@ __global__ __launch_bounds__(256) void fuse_ablate_kernel(int64_t N, int P, int 
             float m = -3.0e38f, s = 0.f;
             float4 acc = zero;
             for (int p = 0; p < P; ++p) {
-                float4 xv = ld4(row + col_of_channel.c[p]);
+                float4 xv = chan_value(row0 + col_of_channel.c[p], copy.c[p], copy, smem + 3 * p * R, R, (lone >> p) & 1, n, c4, sl);
                 if (p == masked) xv = zero;
                 if (mean) {
                     acc.x += xv.x; acc.y += xv.y; acc.z += xv.z; acc.w += xv.w;
@@ -97,7 +99,7 @@ __global__ __launch_bounds__(256) void fuse_ablate_kernel(int64_t N, int P, int 
             if (v == 0 && out_att) {
                 for (int p = 0; p < P; ++p) {      // uniform trip count: the butterfly inside needs every lane
                     float w = inv;
-                    if (!mean) w = expf(chan_logit<G>(ld4(row + col_of_channel.c[p]), ld4(att + p * R + c4), in_row) - m) * inv;
+                    if (!mean) w = expf(chan_logit<G>(chan_value(row0 + col_of_channel.c[p], copy.c[p], copy, smem + 3 * p * R, R, (lone >> p) & 1, n, c4, sl), ld4(att + p * R + c4), in_row) - m) * inv;
                     if (valid && p % G == sl) out_att[n * P + p] = w;
                 }
             }
@@ -108,18 +110,18 @@ __global__ __launch_bounds__(256) void fuse_ablate_kernel(int64_t N, int P, int 
 constexpr int kRegSmall = 4, kRegChannels = 16;   // register-resident paths: P <= 4, P <= 16; above: re-read the row
 
 template <int G>
-int launch_fuse_ablate_g(int64_t N, int P, int R, const float *stack, int64_t ld, const ChanCols &cols, const float *att,
+int launch_fuse_ablate_g(int64_t N, int P, int R, const float *stack, int64_t ld, const ChanCols &cols, const ChanCopy &copy, const float *att,
                          int mode, float *out, float *out_att, hipStream_t stream) {
     const unsigned blocks = (unsigned)((N + (256 / G) - 1) / (256 / G));
     if (P <= kRegSmall)
-        PEA_LAUNCH((fuse_ablate_kernel<G, kRegSmall>), dim3(blocks), dim3(256), 0, stream, N, P, R, stack, ld, cols, att, mode,
-                   out, out_att);
+        PEA_LAUNCH((fuse_ablate_kernel<G, kRegSmall>), dim3(blocks), dim3(256), copy_lds_bytes(copy, P, R), stream, N, P, R, stack, ld, cols, copy, att,
+                   mode, out, out_att);
     else if (P <= kRegChannels)
-        PEA_LAUNCH((fuse_ablate_kernel<G, kRegChannels>), dim3(blocks), dim3(256), 0, stream, N, P, R, stack, ld, cols, att,
+        PEA_LAUNCH((fuse_ablate_kernel<G, kRegChannels>), dim3(blocks), dim3(256), copy_lds_bytes(copy, P, R), stream, N, P, R, stack, ld, cols, copy, att,
                    mode, out, out_att);
     else
-        PEA_LAUNCH((fuse_ablate_kernel<G, 0>), dim3(blocks), dim3(256), 0, stream, N, P, R, stack, ld, cols, att, mode, out,
-                   out_att);
+        PEA_LAUNCH((fuse_ablate_kernel<G, 0>), dim3(blocks), dim3(256), copy_lds_bytes(copy, P, R), stream, N, P, R, stack, ld, cols, copy, att, mode,
+                   out, out_att);
     PEA_HIP(hipGetLastError());
     return PEA_OK;
 }
@@ -127,23 +129,24 @@ int launch_fuse_ablate_g(int64_t N, int P, int R, const float *stack, int64_t ld
 }  // namespace
 
 int launch_fuse_ablate(int64_t N, int P, int R, const float *stack, int64_t ld, const ChanCols &col_of_channel,
-                       const float *att, int mode, float *out_tables, float *out_att, hipStream_t stream) {
+                       const ChanCopy &copy, const float *att, int mode, float *out_tables, float *out_att, hipStream_t stream) {
     PEA_REQUIRE(N > 0 && stack && out_tables, PEA_ERR_ARG, "fuse_ablate: null argument");
     PEA_REQUIRE(P > 0 && P <= kMaxChannels && R > 0 && R % 4 == 0 && R <= 256, PEA_ERR_ARG,
                 "fuse_ablate: P=%d R=%d (P <= 64, R a multiple of 4 and <= 256)", P, R);
     PEA_REQUIRE(mode == PEA_FUSE_ATT || mode == PEA_FUSE_MEAN, PEA_ERR_ARG, "fuse_ablate: mode %d", mode);
     PEA_REQUIRE(mode == PEA_FUSE_MEAN || att != nullptr, PEA_ERR_ARG, "fuse_ablate: att is required for 'att' fusion");
     PEA_REQUIRE(ld % 4 == 0, PEA_ERR_ARG, "fuse_ablate: stack row stride must be a multiple of 4");
+    PEA_REQUIRE(copy_lds_bytes(copy, P, R) <= kCopyLdsMax, PEA_ERR_ARG, "fuse_ablate: copy rows of a %d x %d stack", P, R);
     // bytes: the stack once, P + 1 tables out
     ProfScope ps("fuse_ablate", stream, 4.0 * (double)N * R * (2.0 * P + 1.0));
     switch (lanes_for_r(R)) {
-        case 1: return launch_fuse_ablate_g<1>(N, P, R, stack, ld, col_of_channel, att, mode, out_tables, out_att, stream);
-        case 2: return launch_fuse_ablate_g<2>(N, P, R, stack, ld, col_of_channel, att, mode, out_tables, out_att, stream);
-        case 4: return launch_fuse_ablate_g<4>(N, P, R, stack, ld, col_of_channel, att, mode, out_tables, out_att, stream);
-        case 8: return launch_fuse_ablate_g<8>(N, P, R, stack, ld, col_of_channel, att, mode, out_tables, out_att, stream);
-        case 16: return launch_fuse_ablate_g<16>(N, P, R, stack, ld, col_of_channel, att, mode, out_tables, out_att, stream);
-        case 32: return launch_fuse_ablate_g<32>(N, P, R, stack, ld, col_of_channel, att, mode, out_tables, out_att, stream);
-        default: return launch_fuse_ablate_g<64>(N, P, R, stack, ld, col_of_channel, att, mode, out_tables, out_att, stream);
+        case 1: return launch_fuse_ablate_g<1>(N, P, R, stack, ld, col_of_channel, copy, att, mode, out_tables, out_att, stream);
+        case 2: return launch_fuse_ablate_g<2>(N, P, R, stack, ld, col_of_channel, copy, att, mode, out_tables, out_att, stream);
+        case 4: return launch_fuse_ablate_g<4>(N, P, R, stack, ld, col_of_channel, copy, att, mode, out_tables, out_att, stream);
+        case 8: return launch_fuse_ablate_g<8>(N, P, R, stack, ld, col_of_channel, copy, att, mode, out_tables, out_att, stream);
+        case 16: return launch_fuse_ablate_g<16>(N, P, R, stack, ld, col_of_channel, copy, att, mode, out_tables, out_att, stream);
+        case 32: return launch_fuse_ablate_g<32>(N, P, R, stack, ld, col_of_channel, copy, att, mode, out_tables, out_att, stream);
+        default: return launch_fuse_ablate_g<64>(N, P, R, stack, ld, col_of_channel, copy, att, mode, out_tables, out_att, stream);
     }
 }
 
@@ -163,7 +166,7 @@ extern "C" int pea_fuse_ablate(int64_t num_nodes, int P, int R, const float *sta
                     PEA_ERR_ARG, "fuse_ablate: channel %d column %d outside the stack row", p, col_of_channel_host[p]);
         cols.c[p] = col_of_channel_host[p];
     }
-    return launch_fuse_ablate(num_nodes, P, R, stack, ld_stack, cols, att, fuse_mode, out_tables, out_att, (hipStream_t)stream);
+    return launch_fuse_ablate(num_nodes, P, R, stack, ld_stack, cols, ChanCopy{}, att, fuse_mode, out_tables, out_att, (hipStream_t)stream);
 }
 
 extern "C" int pea_model_forward_ablate(pea_model *model, const float *const *params_host, const float *x, const float *att,

@@ -438,6 +438,28 @@ constexpr int kScatterMaxCols = 1024;
 struct ChanCols {
     int c[kMaxChannels];
 };
+// Inference forward of GAT / GCN: the last layer's aggregation leaves out the rows without an incoming edge under the
+// channel's last relation (model.hip: aggregate_level), and the fusion kernels finish such a row when they load it: the
+// convolution over the self loop alone of h = the row of T of the channel's last level, with the arithmetic of the
+// aggregation kernels (the same bits).  deg0 null: every row of the channel is in the stack.  (chan_value, score_common.h)
+struct CopyRows {
+    const unsigned char *deg0;   // [N] 1 = the stack row of the channel was not written
+    const float *t;              // T of the channel's last level at the channel's column
+    const float *bias;           // the channel's packed bias
+    const float *dinv;           // GCN: deg^-1/2 of the last relation (node-indexed), else null
+    int ld;                      // row stride of t
+    int F;                       // GAT: columns per attention head
+    int att_src_at, att_dst_at;  // GAT: the channel's packed att_j / att_i rows, in floats from `bias`
+};
+struct ChanCopy {
+    int on = 0;                  // some channel has copy rows
+    int relu = 0;                // the destination applies a relu (single-conv callers; the model's X does not)
+    float neg_slope = 0.f;       // GAT: leaky_relu slope of the logits
+    CopyRows c[kMaxChannels] = {};
+};
+// dynamic LDS of a fusion launch: the packed rows of the copy-row branch, [P][bias | att_j | att_i][R] (stage_copy_rows)
+inline size_t copy_lds_bytes(const ChanCopy &cc, int P, int R) { return cc.on ? (size_t)3 * P * R * sizeof(float) : 0; }
+constexpr size_t kCopyLdsMax = 48 * 1024;   // wider stacks keep the last layer's visits (model.hip: Fwd::copy_at_fuse)
 // optional batch-row selection riding in the fusion launch of a sharded rank: sel_out[k] = the fused row of node
 // ids[k * id_stride] when this rank owns it (row / tile % world == rank), zeros otherwise -- what the loss all-reduce sums
 struct FuseSelect {
@@ -447,14 +469,14 @@ struct FuseSelect {
     int *err = nullptr;        // |= 1 when an id is outside [0, N)
     int rank = 0, world = 1, tile = 1;
 };
-int launch_fuse(int64_t N, int P, int R, const float *stack, int64_t ld, const ChanCols &col_of_channel,
+int launch_fuse(int64_t N, int P, int R, const float *stack, int64_t ld, const ChanCols &col_of_channel, const ChanCopy &copy,
                 const float *att, int masked, int mode, const int *rows, int64_t n_rows, float *out,
                 float *out_stack, hipStream_t stream, const FuseSelect *sel = nullptr);
 
 // metapath ablation (ablate.hip): all P + 1 fused variants of the stack in one pass.  out_tables [P + 1, N, R]: variant 0
 // unmasked, variant 1 + p = channel p zeroed, each bitwise launch_fuse with that mask; out_att [N, P] optional.
 int launch_fuse_ablate(int64_t N, int P, int R, const float *stack, int64_t ld, const ChanCols &col_of_channel,
-                       const float *att, int mode, float *out_tables, float *out_att, hipStream_t stream);
+                       const ChanCopy &copy, const float *att, int mode, float *out_tables, float *out_att, hipStream_t stream);
 struct AblateOut {
     float *tables = nullptr;   // [P + 1, N, R]
     float *att = nullptr;      // [N, P] or null

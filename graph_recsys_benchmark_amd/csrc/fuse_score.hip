@@ -19,7 +19,7 @@ namespace {
 template <int G>
 __global__ __launch_bounds__(256) void fuse_kernel(int64_t n_rows, const int *__restrict__ rows, int P, int R,
                                                    const float *__restrict__ stack, int64_t ld,
-                                                   const ChanCols col_of_channel,
+                                                   const ChanCols col_of_channel, const ChanCopy copy,
                                                    const float *__restrict__ att, int masked, int mode,
                                                    float *__restrict__ out, float *__restrict__ out_stack,
                                                    unsigned fuse_blocks, const FuseSelect sel, int64_t N) {
@@ -45,8 +45,10 @@ __global__ __launch_bounds__(256) void fuse_kernel(int64_t n_rows, const int *__
     const int c4 = sl * 4 < R ? sl * 4 : 0;
     float m = -3.0e38f, s = 0.f;
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    const unsigned long long lone = copy_row_bits(copy, P, n);
+    stage_copy_rows(copy, P, R, smem);
     for (int p = 0; p < P; ++p) {
-        float4 x = ld4(stack + n * ld + col_of_channel.c[p] + c4);
+        float4 x = chan_value(stack + n * ld + col_of_channel.c[p], copy.c[p], copy, smem + 3 * p * R, R, (lone >> p) & 1, n, c4, sl);
         if (p == masked) x = make_float4(0.f, 0.f, 0.f, 0.f);
         if (out_stack && active) *reinterpret_cast<float4 *>(out_stack + (n * P + p) * R + c4) = x;
         if (mode == PEA_FUSE_MEAN) {
@@ -178,7 +180,7 @@ __global__ __launch_bounds__(256) void rank_multi_kernel(int V, int64_t U, int C
 
 }  // namespace
 
-int launch_fuse(int64_t N, int P, int R, const float *stack, int64_t ld, const ChanCols &col_of_channel,
+int launch_fuse(int64_t N, int P, int R, const float *stack, int64_t ld, const ChanCols &col_of_channel, const ChanCopy &copy,
                 const float *att, int masked, int mode, const int *rows, int64_t n_rows, float *out,
                 float *out_stack, hipStream_t stream, const FuseSelect *sel_in) {
     PEA_REQUIRE(P > 0 && P <= kMaxChannels && R > 0 && R % 4 == 0 && R <= 256, PEA_ERR_ARG,
@@ -195,13 +197,15 @@ int launch_fuse(int64_t N, int P, int R, const float *stack, int64_t ld, const C
     }
     if (n_rows <= 0 && sel.n <= 0) return PEA_OK;
     const int G = lanes_for_r(R);
+    const size_t lds = copy_lds_bytes(copy, P, R);
+    PEA_REQUIRE(lds <= kCopyLdsMax, PEA_ERR_ARG, "fuse: copy rows of a %d x %d stack", P, R);
     ProfScope ps("fuse", stream, 4.0 * (double)(n_rows + sel.n) * R * (P + 1));
     const unsigned fuse_blocks = (unsigned)((std::max<int64_t>(n_rows, 0) + (256 / G) - 1) / (256 / G));
     const unsigned blocks = fuse_blocks + (unsigned)((sel.n + (256 / G) - 1) / (256 / G));
 #define PEA_FUSE_CASE(g)                                                                                       \
     case g:                                                                                                    \
-        PEA_LAUNCH(fuse_kernel<g>, dim3(blocks), dim3(256), 0, stream, n_rows, rows, P, R, stack, ld, \
-                           col_of_channel, att, masked, mode, out, out_stack, fuse_blocks, sel, N);            \
+        PEA_LAUNCH(fuse_kernel<g>, dim3(blocks), dim3(256), lds, stream, n_rows, rows, P, R, stack, ld, \
+                           col_of_channel, copy, att, masked, mode, out, out_stack, fuse_blocks, sel, N);            \
         break;
     switch (G) {
         PEA_FUSE_CASE(1)
@@ -211,8 +215,8 @@ int launch_fuse(int64_t N, int P, int R, const float *stack, int64_t ld, const C
         PEA_FUSE_CASE(16)
         PEA_FUSE_CASE(32)
         default:
-            PEA_LAUNCH(fuse_kernel<64>, dim3(blocks), dim3(256), 0, stream, n_rows, rows, P, R, stack, ld,
-                               col_of_channel, att, masked, mode, out, out_stack, fuse_blocks, sel, N);
+            PEA_LAUNCH(fuse_kernel<64>, dim3(blocks), dim3(256), lds, stream, n_rows, rows, P, R, stack, ld,
+                               col_of_channel, copy, att, masked, mode, out, out_stack, fuse_blocks, sel, N);
     }
 #undef PEA_FUSE_CASE
     PEA_HIP(hipGetLastError());
@@ -359,6 +363,6 @@ extern "C" int pea_fuse(int64_t num_nodes, int P, int R, const float *stack, int
                     PEA_ERR_ARG, "fuse: channel %d column %d outside the stack row", p, col_of_channel_host[p]);
         cols.c[p] = col_of_channel_host[p];
     }
-    return pea::launch_fuse(num_nodes, P, R, stack, ld_stack, cols, att, masked_channel, fuse_mode, nullptr, num_nodes, out,
+    return pea::launch_fuse(num_nodes, P, R, stack, ld_stack, cols, pea::ChanCopy{}, att, masked_channel, fuse_mode, nullptr, num_nodes, out,
                             nullptr, (hipStream_t)stream);
 }

@@ -95,13 +95,28 @@ __global__ __launch_bounds__(256) void mlp2_pack_kernel(const Mlp2Launch L) {
         }
     }
     if (gat) {
-        // logits of the first layer from x itself: (W x) . att = x . (W^T att), natural units
+        // logits of the first layer from x itself: (W x) . att = x . (W^T att), natural units.  One fmaf chain over i
+        // ascending per k; the operands of kPackTerms terms are loaded before their part of the chain runs (a column of
+        // W0 is one cache line per term: loaded inside the chain, every term waited for its own line)
+        constexpr int kPackTerms = 16;
         for (int k = (int)threadIdx.x * kPackSplit + part; k < EMB; k += ts) {
             float s = 0.f, d = 0.f;
-            for (int i = 0; i < HID; ++i) {
-                const float w = C.w0[(size_t)i * EMB + k];
-                s = fmaf(C.att_src0[i], w, s);
-                d = fmaf(C.att_dst0[i], w, d);
+            for (int i0 = 0; i0 < HID; i0 += kPackTerms) {
+                float w[kPackTerms], as[kPackTerms], ad[kPackTerms];
+#pragma unroll
+                for (int u = 0; u < kPackTerms; ++u) {
+                    const int i = min(i0 + u, HID - 1);
+                    w[u] = C.w0[(size_t)i * EMB + k];
+                    as[u] = C.att_src0[i];
+                    ad[u] = C.att_dst0[i];
+                }
+#pragma unroll
+                for (int u = 0; u < kPackTerms; ++u) {
+                    if (i0 + u < HID) {
+                        s = fmaf(as[u], w[u], s);
+                        d = fmaf(ad[u], w[u], d);
+                    }
+                }
             }
             C.ws[k] = s;
             C.wd[k] = d;

@@ -425,6 +425,12 @@ struct Fwd {
     const int *own_rows;   // rows this rank owns (null: all N)
     int64_t n_own;
     bool hot_on;           // PEA_HOT, read per forward: tests and A/B runs flip it inside one process
+    // The last layers leave out the rows without incoming edges and the fusion launch finishes them from T (CopyRows):
+    // GAT / GCN inference calls whose last-layer outputs are read by a fusion launch only -- not a training call (batch-row
+    // picks and the backward read X), not a single conv (the caller reads out_x).  A staged caller hands every stage the
+    // outputs it hands the last one.  PEA_LAST_COPY_ROWS=1 (read per forward, for A/B runs and tests) restores the visits;
+    // a stack whose bias / attention rows exceed the fusion launch's LDS block (kCopyLdsMax) keeps them too.
+    bool copy_at_fuse;
 
     explicit Fwd(const ForwardCall &call)
         : c(call), m(call.model), plan(const_cast<pea_plan *>(call.model->plan)), pack(call.wsf),
@@ -433,6 +439,10 @@ struct Fwd {
           own_rows(sharded ? plan->owned_rows : nullptr), n_own(sharded ? plan->n_owned : plan->N) {
         const char *hot_env = getenv("PEA_HOT");
         hot_on = hot_env && atoi(hot_env) != 0;
+        const char *visit_env = getenv("PEA_LAST_COPY_ROWS");
+        copy_at_fuse = !call.training && !call.out_x && (call.abl || call.out_repr || call.out_stack) &&
+                       m->d.kind != PEA_KIND_SAGE && self_loops() && !(visit_env && atoi(visit_env) != 0) &&
+                       (size_t)12 * m->d.num_channels * m->d.repr_dim <= kCopyLdsMax;
     }
     const float *param(const Unit &u, int slot) const {
         return c.params[(size_t)(m->chan_first[(size_t)u.p] + u.s) * (size_t)m->n_slots_per_layer + (size_t)slot];
@@ -551,7 +561,8 @@ int aggregate_level(const Fwd &f, int s, AggMode mode) {
         AggGroup a = agg_over(R);
         // rows without incoming edges of a layer that feeds another layer are not aggregated at all: the next
         // transform reads T_s for them (GemmJob::a1_mask)
-        const bool skip0 = mode != AGG_MEAN && !g.last && f.self_loops() && !training;
+        // ... and of a last layer where the fusion launch reads T_s for them (Fwd::copy_at_fuse)
+        const bool skip0 = mode != AGG_MEAN && f.self_loops() && !training && (!g.last || f.copy_at_fuse);
         // ... and under mean2 such rows already hold their final value up to the relu (mean = 0): they are skipped too,
         // and the next level's transforms apply the relu when they load them (GemmJob::a1_mask)
         const bool skip0_mean = mean2 && !g.last && !training;
@@ -748,6 +759,38 @@ int transform_units(const Fwd &f, int s) {
     return launch_gemm_batch(jobs.data(), (int)jobs.size(), f.own_rows, f.n_own, f.c.stream);
 }
 
+// what the fusion launch needs to finish the rows the last layers left out (Fwd::copy_at_fuse): per channel, what
+// conv_on_load gives a transform job, taken from the channel's last unit, and for GAT the attention rows of the self-loop
+// logit (chan_value reproduces the visit's bits)
+int copy_rows_of(const Fwd &f, ChanCopy &cc) {
+    cc = ChanCopy{};
+    if (!f.copy_at_fuse) return PEA_OK;
+    cc.on = 1;
+    cc.relu = f.c.relu_last;
+    cc.neg_slope = f.m->d.negative_slope;
+    for (const Level &L : f.m->levels) {
+        for (const Unit &u : L.units) {
+            if (!u.last) continue;
+            Relation &R = f.plan->rels[(size_t)u.rel];
+            CopyRows &S = cc.c[u.p];
+            S.deg0 = R.deg0;
+            S.t = f.c.wsf + L.off_t + u.t_col;
+            S.ld = L.ld_t;
+            S.bias = f.pack + L.bias_off + u.t_col;
+            if (f.m->d.kind == PEA_KIND_GAT) {
+                S.F = u.F;
+                S.att_src_at = (int)(L.att_src_off - L.bias_off);
+                S.att_dst_at = (int)(L.att_dst_off - L.bias_off);
+            } else {
+                const bool fc = f.m->d.gcn_deg_from_col != 0;
+                PEA_TRY(ensure_dinv(f.plan, u.rel, fc, f.c.stream));
+                S.dinv = fc ? R.dinv_col : R.dinv_row;
+            }
+        }
+    }
+    return PEA_OK;
+}
+
 int transform_level(const Fwd &f, int s) {
     if (f.m->d.kind == PEA_KIND_SAGE && !f.m->sage2) return transform_mean_first(f, s);
     if (!f.m->levels[(size_t)s].shared_input) return transform_units(f, s);
@@ -942,12 +985,14 @@ int model_forward(const ForwardCall &c) {
             else if (k + 1 < n_levels) PEA_TRY(transform_level(f, k + 1));
         }
         if (k != n_levels - 1) continue;
+        ChanCopy copy;
+        PEA_TRY(copy_rows_of(f, copy));
         if (c.abl)
-            PEA_TRY(launch_fuse_ablate(f.plan->N, d.num_channels, d.repr_dim, f.X, f.ldX, m->x_col, c.att, d.fuse_mode, c.abl->tables,
-                                       c.abl->att, c.stream));
+            PEA_TRY(launch_fuse_ablate(f.plan->N, d.num_channels, d.repr_dim, f.X, f.ldX, m->x_col, copy, c.att, d.fuse_mode,
+                                       c.abl->tables, c.abl->att, c.stream));
         else if (c.out_repr || c.out_stack)
-            PEA_TRY(launch_fuse(f.plan->N, d.num_channels, d.repr_dim, f.X, f.ldX, m->x_col, c.att, c.masked, d.fuse_mode, f.own_rows,
-                                f.n_own, c.out_repr, c.out_stack, c.stream, c.sel));
+            PEA_TRY(launch_fuse(f.plan->N, d.num_channels, d.repr_dim, f.X, f.ldX, m->x_col, copy, c.att, c.masked, d.fuse_mode,
+                                f.own_rows, f.n_own, c.out_repr, c.out_stack, c.stream, c.sel));
     }
     return PEA_OK;
 }

@@ -5,7 +5,7 @@
 #ifndef PEA_SCORE_COMMON_H_
 #define PEA_SCORE_COMMON_H_
 
-#include "common.h"
+#include "agg_common.h"
 
 namespace pea {
 
@@ -84,6 +84,67 @@ __device__ __forceinline__ void stage_mlp(int R, const float *fc1_w, const float
         smem[2 * R * R + R + i] = fc2_w[i];
     }
     __syncthreads();
+}
+
+// bit p: node n is a copy row of channel p.  All flags are fetched before the channel loop of a fusion kernel, several loads
+// in flight, so that no row load of the loop waits for its flag first.
+__device__ __forceinline__ unsigned long long copy_row_bits(const ChanCopy &cc, int P, int64_t n) {
+    unsigned long long bits = 0;
+    if (!cc.on) return bits;
+#pragma unroll 8
+    for (int p = 0; p < P; ++p) {
+        const unsigned char *flag = cc.c[p].deg0;
+        bits |= (unsigned long long)(flag != nullptr && flag[n] != 0) << p;
+    }
+    return bits;
+}
+
+// The packed rows the copy-row branch of chan_value reads, staged once per workgroup: [P][bias | att_j | att_i][R] floats of
+// dynamic LDS (copy_lds_bytes; att rows zero for GCN), so that the branch, which starts when the row's own load has
+// arrived, does not wait for a second memory latency.  (What the branch costs the fusion launch on the 25m-shaped graph,
+// 0.044 -> 0.061 ms, is its arithmetic: the measured gain of the staging is within noise)
+__device__ __forceinline__ void stage_copy_rows(const ChanCopy &cc, int P, int R, float *lds) {
+    if (!cc.on) return;
+    for (int i = threadIdx.x; i < 3 * P * R; i += blockDim.x) {
+        const int c = i % R, k = (i / R) % 3;
+        const CopyRows &S = cc.c[i / (3 * R)];
+        float v = 0.f;
+        if (S.deg0 && (k == 0 || S.att_src_at)) v = S.bias[(k == 0 ? 0 : k == 1 ? S.att_src_at : S.att_dst_at) + c];
+        lds[i] = v;
+    }
+    __syncthreads();
+}
+
+// Channel value of node n at columns c4 .. c4 + 3, as every fusion kernel reads it (sl: the lane's place among the lanes of
+// the node, 4 columns each; c4 = 4 sl, or 0 past the row's end): the stack entry (`row` = the node's stack row at the
+// channel's column), or, where the last layer's aggregation left the row out (CopyRows), what short_rows + finish_row of
+// agg.hip give a row whose only message is its self loop, operation for operation, so that the bits do not depend on who
+// finishes the row.  GCN: fmaf(di * di, h, 0) + b.  GAT: (p h) (1 / (p + 1e-16)) + b with p = 2^(e log2(e) - round(e log2(e)))
+// of the self-loop logit e.  p is 1 only for |e| < ~0.2, else 1 +- an ulp or two, so h + b would differ from the visit's
+// value by up to 2 ulp OF h, which the bias can cancel down to any number of ulp of the sum.  Then the destination's relu.
+// The lanes of a node take the branch together (head_sum is cross-lane).  The unwritten stack entry is never loaded.
+// lone: bit p of copy_row_bits; rows: the channel's [bias | att_j | att_i][R] block of stage_copy_rows.
+__device__ __forceinline__ float4 chan_value(const float *row, const CopyRows &S, const ChanCopy &cc, const float *rows, int R,
+                                             bool lone, int64_t n, int c4, int sl) {
+    float4 v = ld4(lone ? S.t + n * S.ld + c4 : row + c4);
+    if (lone) {
+        if (S.dinv) {
+            const float di = S.dinv[n];
+            v = fma4(di * di, v, make_float4(0.f, 0.f, 0.f, 0.f));
+        } else if (S.att_src_at) {
+            const int lane = (int)threadIdx.x % kWave, F4 = S.F / 4, pos = sl % F4;
+            const bool pow2 = (F4 & (F4 - 1)) == 0;
+            const float a_d = head_sum<0>(dot4(v, ld4(rows + 2 * R + c4)), lane, pos, F4, pow2);
+            const float a = head_sum<0>(dot4(v, ld4(rows + R + c4)), lane, pos, F4, pow2);
+            Soft st;
+            st.init();
+            st.push(leaky(a + a_d, cc.neg_slope), v);
+            v = scale4(st.acc, 1.0f / (st.s + 1e-16f));
+        }
+        v = add4(v, ld4(rows + c4));
+        if (cc.relu) v = make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f));
+    }
+    return v;
 }
 
 __device__ __forceinline__ float log_sigmoid_ref(float d) {
