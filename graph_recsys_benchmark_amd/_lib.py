@@ -196,6 +196,12 @@ SIGNATURES = {
     'pea_transr_train_workspace_bytes': (_sz, [_i64, _int]),
     'pea_transr_train': (_int, [_i64, _int, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                 _sz, _vp]),
+    'pea_herec_supported': (_int, [_int, _int]),
+    'pea_herec_train_workspace_bytes': (_sz, [_i64, _int, _int]),
+    'pea_herec_train': (_int, [_i64, _int, _int, C.POINTER(_vp), C.POINTER(_i64), _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64,
+                               _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'pea_herec_table': (_int, [_int, _int, C.POINTER(_vp), C.POINTER(_i64), _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
+                               _vp, _vp]),
     'pea_metapath_walks': (_int, [_vp, _int, C.POINTER(_int), _int, _i64, _vp, C.c_uint64, C.c_uint32, _vp, _i64, _vp, _vp]),
     'pea_uniform_walks': (_int, [_int, C.POINTER(_i64), C.POINTER(_i64), _int, _i64, _vp, C.c_uint64, C.c_uint32, _vp, _i64, _vp]),
     'pea_skipgram_supported': (_int, [_int, _int, _int]),

@@ -1348,6 +1348,143 @@ def transr_loss(x, proj_mat, r, batch):
 
 
 # ------------------------------------------------------------------------------------------------------------
+# HeRec (csrc/herec.hip; reference models/herec.py, experiments/herec_solver_bpr.py:108-121)
+# ------------------------------------------------------------------------------------------------------------
+HEREC_MAX_TABLES = 4      # PEA_HEREC_MAX_TABLES (include/peahip.h)
+
+
+def herec_supported(dim, num_tables, batch_size=0):
+    """Whether herec_mse_loss / herec_table take this width and number of metapath tables (include/peahip.h,
+    pea_herec_supported) and this batch (its B positions go back through rows_scatter_sum); needs no device."""
+    return bool(_lib.load().pea_herec_supported(int(dim), int(num_tables))) and int(batch_size) <= ROWS_SCATTER_MAX
+
+
+def _herec_args(tables, emb_trans_w, emb_trans_b, user_emb, item_emb, user_rk_bias, item_rk_bias):
+    """The tensors as pea_herec_* read them: (tables, ctypes pointer and stride arrays, w [M, D, D], b [M, D], the four
+    embedding tables), detached, float32, 16-byte aligned."""
+    tables = [_block16(t) for t in tables]
+    m = len(tables)
+    if m < 1 or any(t.shape != tables[0].shape or t.dtype != torch.float32 for t in tables):
+        raise ValueError('herec: a non-empty list of float32 [N, D] tables of one shape expected')
+    d = tables[0].shape[1]
+    if not _lib.load().pea_herec_supported(d, m):
+        raise ValueError('herec: width %d with %d tables is not supported (engine.herec_supported)' % (d, m))
+    w = emb_trans_w if torch.is_tensor(emb_trans_w) else torch.stack([t.detach() for t in emb_trans_w])
+    b = emb_trans_b if torch.is_tensor(emb_trans_b) else torch.stack([t.detach() for t in emb_trans_b])
+    w, b = w.detach().contiguous(), b.detach().contiguous()
+    embs = [t.detach().contiguous() for t in (user_emb, item_emb, user_rk_bias, item_rk_bias)]
+    if (tuple(w.shape) != (m, d, d) or tuple(b.shape) != (m, d) or any(t.dim() != 2 or t.shape[1] != d for t in embs)
+            or embs[0].shape != embs[2].shape or embs[1].shape != embs[3].shape):
+        raise ValueError('herec: w [M, D, D], b [M, D], user tables [num_uids, D] and item tables [num_iids, D] expected')
+    ptrs = (C.c_void_p * m)(*[t.data_ptr() for t in tables])
+    lds = (C.c_int64 * m)(*[t.stride(0) for t in tables])
+    return tables, ptrs, lds, w, b, embs
+
+
+def herec_train_raw(tables, emb_trans_w, emb_trans_b, user_emb, item_emb, user_rk_bias, item_rk_bias, acc_uids, acc_iids,
+                    unids, inids, labels, need_grad=True):
+    """One launch of csrc/herec.hip (+ its fixed-order reduction): (loss, pred [B], dW [M, D, D], db [M, D], g_user [B, 2D],
+    g_item [B, 2D], error flag) for the M frozen tables, the emb_trans weights (a [M, D, D] tensor or a list of [D, D]) and
+    biases, the four embedding tables and B labelled pairs.  need_grad=False: forward only, the four gradients are None."""
+    lib = _lib.require_device()
+    tables, ptrs, lds, w, b, embs = _herec_args(tables, emb_trans_w, emb_trans_b, user_emb, item_emb, user_rk_bias, item_rk_bias)
+    m, (n, d), dev = len(tables), tables[0].shape, tables[0].device
+    unids = unids.to(torch.int64).contiguous()
+    inids = inids.to(torch.int64).contiguous()
+    labels = labels.to(torch.float32).contiguous()
+    if unids.dim() != 1 or unids.shape != inids.shape or unids.shape != labels.shape:
+        raise ValueError('herec: unids, inids and labels must be 1-d of equal length')
+    bsz = unids.shape[0]
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    pred = torch.empty(bsz, dtype=torch.float32, device=dev)
+    dw = db = g_user = g_item = None
+    if need_grad:
+        dw = torch.empty((m, d, d), dtype=torch.float32, device=dev)
+        db = torch.empty((m, d), dtype=torch.float32, device=dev)
+        g_user = torch.empty((bsz, 2 * d), dtype=torch.float32, device=dev)
+        g_item = torch.empty((bsz, 2 * d), dtype=torch.float32, device=dev)
+    ws_bytes = int(lib.pea_herec_train_workspace_bytes(bsz, d, m))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    _lib.check(lib.pea_herec_train(bsz, d, m, ptrs, lds, _lib.ptr(w), _lib.ptr(b), _lib.ptr(embs[0]), _lib.ptr(embs[1]),
+                                   _lib.ptr(embs[2]), _lib.ptr(embs[3]), int(acc_uids), embs[0].shape[0], int(acc_iids),
+                                   embs[1].shape[0], n, _lib.ptr(unids), _lib.ptr(inids), _lib.ptr(labels), _lib.ptr(loss),
+                                   _lib.ptr(pred), _lib.ptr(dw), _lib.ptr(db), _lib.ptr(g_user), _lib.ptr(g_item), _lib.ptr(ws),
+                                   ws_bytes, _lib.current_stream()))
+    return loss, pred, dw, db, g_user, g_item, ws[:4].view(torch.int32)[0].clone()
+
+
+class _HerecLoss(torch.autograd.Function):
+    """loss = mean_b (pred_b - label_b)^2 of the HeRec score with its whole backward from the same launch (csrc/herec.hip);
+    backward scatters the pairs' gradient rows into dense gradients of the four embedding tables with pea_rows_scatter_sum
+    (fixed order; the two user-indexed tables share their ids, the two item-indexed ones likewise).  Reference:
+    models/herec.py:36-46 + experiments/herec_solver_bpr.py:108-121 under loss.backward()."""
+
+    @staticmethod
+    def forward(ctx, tables, acc, ids, need_grad, w, b, user_emb, item_emb, user_rk_bias, item_rk_bias):
+        unids, inids, labels = ids
+        loss, _, dw, db, g_user, g_item, flag = herec_train_raw(tables, w, b, user_emb, item_emb, user_rk_bias, item_rk_bias,
+                                                                acc[0], acc[1], unids, inids, labels, need_grad)
+        _defer_error(flag, 'index out of range in HeRec pairs (a user id outside the user block or an item id outside the '
+                           'item block)')
+        if need_grad:
+            # an id out of range has zero gradient rows; -1 makes the scatter skip it
+            nu, ni = user_emb.shape[0], item_emb.shape[0]
+            lu, li = unids.to(torch.int64) - acc[0], inids.to(torch.int64) - acc[1]
+            ctx.lu = torch.where((lu >= 0) & (lu < nu), lu, torch.full_like(lu, -1)).contiguous()
+            ctx.li = torch.where((li >= 0) & (li < ni), li, torch.full_like(li, -1)).contiguous()
+            ctx.grads = (dw, db, g_user, g_item)
+            ctx.nums = (nu, ni)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        dw, db, g_user, g_item = ctx.grads
+        nu, ni = ctx.nums
+        d = db.shape[1]
+        need = ctx.needs_input_grad
+        gu = g_user * g if need[6] or need[8] else None
+        gi = g_item * g if need[7] or need[9] else None
+        return (None, None, None, None,
+                dw * g if need[4] else None,
+                db * g if need[5] else None,
+                _scatter_dense(ctx.lu, gu[:, :d], nu, d) if need[6] else None,
+                _scatter_dense(ctx.li, gi[:, :d], ni, d) if need[7] else None,
+                _scatter_dense(ctx.lu, gu[:, d:], nu, d) if need[8] else None,
+                _scatter_dense(ctx.li, gi[:, d:], ni, d) if need[9] else None)
+
+
+def herec_mse_loss(tables, emb_trans_w, emb_trans_b, user_emb, item_emb, user_rk_bias, item_rk_bias, acc_uids, acc_iids, unids,
+                   inids, labels):
+    """Differentiable HeRec training loss mean((pred - label)^2) of B labelled pairs, forward and backward in HIP:
+    tables = the M frozen [N, D] metapath2vec tables, emb_trans_w [M, D, D] / emb_trans_b [M, D] the stacked emb_trans
+    parameters (torch Linear layout), the four embedding tables [num_uids | num_iids, D].  backward() gives dense gradients
+    for the six parameter tensors.  With grad disabled, or when no input requires grad, only the forward runs.  A pair with an
+    id outside its block contributes nothing and raises IndexError at the next check_pending_errors().
+    herec_supported(D, M, B) must hold."""
+    tables = list(tables)
+    if not tables or tables[0].dim() != 2 or not herec_supported(tables[0].shape[1], len(tables), unids.shape[0]):
+        raise ValueError('herec_mse_loss: width / number of tables (engine.herec_supported) or batch size (B <= %d) not supported'
+                         % ROWS_SCATTER_MAX)
+    params = (emb_trans_w, emb_trans_b, user_emb, item_emb, user_rk_bias, item_rk_bias)
+    need_grad = torch.is_grad_enabled() and any(t.requires_grad for t in params)
+    return _HerecLoss.apply(tables, (int(acc_uids), int(acc_iids)), (unids, inids, labels), need_grad, *params)
+
+
+def herec_table(tables, emb_trans_w, emb_trans_b, user_emb, item_emb, user_rk_bias, item_rk_bias, acc_uids, acc_iids):
+    """The [N, D + 4] table whose plain row dots are the HeRec scores (include/peahip.h, pea_herec_table): user row
+    [user_emb, 1, c_u, 0, 0], item row [item_emb, beta_i, 1, 0, 0], zeros elsewhere.  One launch; feeds dot_predict,
+    dot_rank_eval, dot_recommend_topk and dot_rank_full."""
+    lib = _lib.require_device()
+    tables, ptrs, lds, w, b, embs = _herec_args(tables, emb_trans_w, emb_trans_b, user_emb, item_emb, user_rk_bias, item_rk_bias)
+    n, d = tables[0].shape
+    out = torch.empty((n, d + 4), dtype=torch.float32, device=tables[0].device)
+    _lib.check(lib.pea_herec_table(d, len(tables), ptrs, lds, _lib.ptr(w), _lib.ptr(b), _lib.ptr(embs[0]), _lib.ptr(embs[1]),
+                                   _lib.ptr(embs[2]), _lib.ptr(embs[3]), int(acc_uids), embs[0].shape[0], int(acc_iids),
+                                   embs[1].shape[0], n, _lib.ptr(out), _lib.current_stream()))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------
 # metapath2vec (csrc/walk.hip, csrc/skipgram.hip; reference models/metapath2vec.py)
 # ------------------------------------------------------------------------------------------------------------
 def _walk_starts(starts, device):

@@ -7,7 +7,8 @@ from .kgcn import KGCNRecsysModel
 from .ngcf import NGCFRecsysModel
 from .metapath2vec import MetaPath2Vec
 from .walk import WalkBasedRecsysModel
+from .herec import HeRecRecsysModel
 
 __all__ = ['GraphRecsysModel', 'PEABaseChannel', 'PEABaseRecsysModel', 'PEAGATChannel', 'PEAGATRecsysModel',
            'PEAGCNChannel', 'PEAGCNRecsysModel', 'PEASageChannel', 'PEASageRecsysModel', 'KGATRecsysModel', 'KGCNRecsysModel',
-           'NGCFRecsysModel', 'MetaPath2Vec', 'WalkBasedRecsysModel']
+           'NGCFRecsysModel', 'MetaPath2Vec', 'WalkBasedRecsysModel', 'HeRecRecsysModel']

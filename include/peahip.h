@@ -695,6 +695,54 @@ int pea_transr_train(int64_t B, int emb, const float *x, int64_t ldx, int64_t nu
                      size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * HeRec (csrc/herec.hip): reference models/herec.py:36-46 with the MSE loss of experiments/herec_solver_bpr.py:108-121.
+ * M frozen metapath2vec tables E_m [num_nodes, D] (host array tables_host of M device pointers, row strides ld_host: multiples
+ * of 4, at least D), w [M, D, D] (torch Linear layout, out x in) and b [M, D] contiguous, the four embedding tables
+ * user_emb / user_rk_bias [num_uids, D] and item_emb / item_rk_bias [num_iids, D] contiguous; everything 16-byte aligned.
+ *     S(n)       = sum_m sigmoid(E_m[n] w_m^T + b_m)            sigmoid(z) = 1 / (1 + expf(-z)), m ascending
+ *     pred(u, i) = <user_emb[u'], item_emb[i']> + <S(u), user_rk_bias[u']> + <S(i), item_rk_bias[i']>
+ *                  u' = u - acc_uids, i' = i - acc_iids
+ * pea_herec_supported(D, M): pure, needs no device.  D a multiple of 4 in 4..128, 1 <= M <= PEA_HEREC_MAX_TABLES, M D <= 256,
+ *   at most 16 dW accumulator tiles per wave and all M weight images plus one tile's rows inside the LDS budget: M <= 4 up to
+ *   D = 64, M <= 2 up to D = 80, M = 1 up to D = 128.  (128, 2) does not fit with both images resident and is refused.
+ * pea_herec_train: B labelled pairs (unids, inids int64 [B], labels float32 [B]), one launch + a fixed-order reduction:
+ *     *out_loss = sum_b (pred_b - label_b)^2 / B,   pred [B] optional,   g_b = 2 (pred_b - label_b) / B
+ *     dw [M, D, D] = dZ_m^T E_m[rows], db [M, D] = colsum dZ_m,  dZ_m = dS (.) s_m (1 - s_m),
+ *                    dS(u) = g user_rk_bias[u'], dS(i) = g item_rk_bias[i']
+ *     g_user [B, 2 D] = [g item_emb[i'], g S(u)]   (gradient rows of user_emb | user_rk_bias at u')
+ *     g_item [B, 2 D] = [g user_emb[u'], g S(i)]   (gradient rows of item_emb | item_rk_bias at i')
+ *   dw, db, g_user, g_item are all given, or all NULL: forward only.  The caller scatters g_user / g_item into zero-filled
+ *   dense gradients with pea_rows_scatter_sum (B <= 16384).
+ *   Every product runs on v_mfma_f32_16x16x4_f32 (k ascending from a zero accumulator); each of the three terms of pred is
+ *   eight fma chains in ascending column order (column c in chain c % 8) added pairwise; dw / db are one partial per
+ *   workgroup added in workgroup order, the loss one sum per workgroup added in index order: no float atomics, the grid is a
+ *   function of B only, bitwise reproducible, 64-bit row indexing.
+ *   Stays asynchronous: a pair whose user id is outside [acc_uids, acc_uids + num_uids) or [0, num_nodes) (items likewise)
+ *   contributes nothing (pred 0, zero gradient rows), reads nothing out of range and sets the int at workspace[0] to 1;
+ *   the mean still divides by B.
+ *   workspace: pea_herec_train_workspace_bytes(B, D, M) (0 = unsupported).
+ * pea_herec_table: out [num_nodes, D + 4], every row written: user row u = [user_emb[u'], 1, c_u, 0, 0], item row i =
+ *   [item_emb[i'], beta_i, 1, 0, 0], every other row zeros, with c_u = <S(u), user_rk_bias[u']> and beta_i = <S(i),
+ *   item_rk_bias[i']> as one fma chain in ascending column order: the plain dot product of a user row and an item row is
+ *   pred(u, i), so the pea_dot_* entry points score, rank and recommend from it.  The two blocks must not overlap.  One
+ *   launch, no library call inside: it can be recorded on a launch tape.
+ * Argument errors return PEA_ERR_ARG (a short workspace PEA_ERR_NOMEM) before anything is launched.
+ * ---------------------------------------------------------------------------------------------- */
+#define PEA_HEREC_MAX_TABLES 4
+int pea_herec_supported(int D, int M);
+size_t pea_herec_train_workspace_bytes(int64_t B, int D, int M);
+int pea_herec_train(int64_t B, int D, int M, const float *const *tables_host, const int64_t *ld_host, const float *w,
+                    const float *b, const float *user_emb, const float *item_emb, const float *user_rk_bias,
+                    const float *item_rk_bias, int64_t acc_uids, int64_t num_uids, int64_t acc_iids, int64_t num_iids,
+                    int64_t num_nodes, const int64_t *unids, const int64_t *inids, const float *labels, float *out_loss,
+                    float *pred, float *dw, float *db, float *g_user, float *g_item, void *workspace, size_t workspace_bytes,
+                    void *stream);
+int pea_herec_table(int D, int M, const float *const *tables_host, const int64_t *ld_host, const float *w, const float *b,
+                    const float *user_emb, const float *item_emb, const float *user_rk_bias, const float *item_rk_bias,
+                    int64_t acc_uids, int64_t num_uids, int64_t acc_iids, int64_t num_iids, int64_t num_nodes, float *out,
+                    void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * metapath2vec (csrc/walk.hip, csrc/skipgram.hip): reference models/metapath2vec.py, whose walks are drawn on the CPU
  * (:101-121, one torch_sparse adj.sample per step) and whose loss gathers [windows, C - 1, D] rows of the table (:147-172).
  *
