@@ -627,3 +627,113 @@ def colsum_case(kind, heads, hidden, repr_dim, channels, device='cpu', scale=0.2
     model = build_model(kind, n, edges, [2] * channels, AGG_COLSUM_EMB, hidden, repr_dim, heads=heads, device=device)
     model.load_state_dict(random_state_dict(model, 33, scale=scale))
     return model, {k: v.detach().cpu().numpy() for k, v in model.state_dict().items()}, n, edges, batch
+
+
+# ------------------------------------------------------------------------------------------------------------
+# the tile classes of the training kernels on csrc/tile16.h (transr_train.hip, herec.hip, kg_update.hip), written down by
+# hand: tests/test_train_tiles_cpu.py holds the restatement against the library's predicates and asserts that the shape
+# lists below, with the lists of the kernels' own suites, reach every class; tests/test_gpu_train_tiles_matrix.py runs them
+# ------------------------------------------------------------------------------------------------------------
+TILE_WAVES = 4                       # tile16.h:21  kWaves = kThreads / kWave
+TILE_LDS_BUDGET = 156 * 1024         # tile16.h:23  kLdsBudget
+TILE_ROWS = 16                       # tile16.h:22  kTR
+
+
+def ceil16(v):
+    """tile16.h:25"""
+    return (v + 15) // 16 * 16
+
+
+def tiles_per_wave(tiles):
+    """tile16.h:28-33: `tiles` accumulator tiles dealt to the four waves, rounded up to a power of two (the kernels' NT)"""
+    per_wave = (tiles + TILE_WAVES - 1) // TILE_WAVES
+    nt = 1
+    while nt < per_wave:
+        nt <<= 1
+    return nt
+
+
+def transr_tile_class(e):
+    """(NT, IT) of transr_train.hip at width e, None where supported() refuses (transr_train.hip:33; the switch of
+    pea_transr_train on tiles_per_wave(IT * IT), :272-277)"""
+    if e < 4 or e > 128 or e % 4 != 0:
+        return None
+    it = ceil16(e) // 16
+    return tiles_per_wave(it * it), it
+
+
+def herec_train_lds_bytes(d, m):
+    """herec.hip:45-50: kSmallFloats and train_lds_bytes"""
+    ip = ceil16(d)
+    ld = ip + 4
+    small = 16 + 16 + 16 + 2 * 2 * TILE_ROWS
+    return 4 * (m * ip * ld + (2 * m + 1) * 2 * TILE_ROWS * ld + small)
+
+
+def herec_tile_class(d, m, max_tables=4):
+    """(NT, MT, IT) of herec_train_kernel at width d with m tables, None where supported() refuses (herec.hip:57-62; the
+    switch of pea_herec_train, :465-470, and launch_train_m, :291-303)"""
+    if d < 4 or d > 128 or d % 4 != 0 or m < 1 or m > max_tables or m * d > 256:
+        return None
+    it = ceil16(d) // 16
+    nt = tiles_per_wave(it * it)
+    if m * nt > 16 or herec_train_lds_bytes(d, m) > TILE_LDS_BUDGET:
+        return None
+    return nt, m, it
+
+
+def kg_update_cfg(kind, fin, fout, bwd):
+    """dict(IT, OC, NT, chunks) of kg_update.hip for kind 'kgat' | 'kgcn' | 'ngcf', None where supported() refuses
+    (kg_update.hip:39-42; make_cfg, :44-60).  chunks = the widths of the output-column chunks the kernels walk (`oc` of the
+    loop `for c0 ... += OC`, :126-131 and :183-188); NT is taken at the first chunk's OC, as make_cfg does."""
+    if kind not in ('kgat', 'kgcn', 'ngcf') or fin < 4 or fin > 128 or fin % 4 or fout < 4 or fout > 128 or fout % 4:
+        return None
+    ip = ceil16(fin)
+    lda = ip + 4
+    nw = 1 if kind == 'kgcn' else 2
+    nz = (nw + (1 if kind == 'kgat' else 0)) if bwd else 0
+    outp = ceil16(fout)
+    chunks = 1
+    while True:
+        oc = ceil16((outp + chunks - 1) // chunks)
+        ldw = oc + 4
+        lds = 4 * (nw * ip * ldw + nw * TILE_ROWS * lda + nz * TILE_ROWS * ldw)
+        nt = tiles_per_wave((ip // 16) * (oc // 16))
+        if (lds <= TILE_LDS_BUDGET and (not bwd or nt <= (8 if nw == 2 else 16))) or oc == 16:
+            break
+        chunks += 1
+    return dict(IT=ip // 16, OC=oc, NT=nt, weights=nw, lds=lds, chunks=[min(oc, fout - c0) for c0 in range(0, fout, oc)])
+
+
+def kg_update_tile_counts(cfg):
+    """IT * n_ut per column chunk: the dW tiles dealt to the waves (kg_update.hip:188, :262)"""
+    return [cfg['IT'] * ((oc + 15) // 16) for oc in cfg['chunks']]
+
+
+# the matrix's shapes with the class each is there for, BY HAND: every GPU test asserts that the restatement above gives it
+TILE_BATCHES = (17, 4097)            # two tiles, the second with one row; 257 tiles on 256 workgroups
+TRANSR_TILE_WIDTHS = [(36, 4, 3), (48, 4, 3), (76, 8, 5), (80, 8, 5), (88, 16, 6), (100, 16, 7), (124, 16, 8)]      # (E, NT, IT)
+HEREC_TILE_SHAPES = [(28, 2, 1, 2), (32, 4, 1, 2), (36, 1, 4, 3), (44, 3, 4, 3), (60, 4, 4, 4), (68, 1, 8, 5), (76, 2, 8, 5),
+                     (80, 2, 8, 5), (84, 1, 16, 6), (100, 1, 16, 7), (124, 1, 16, 8)]                             # (D, M, NT, IT)
+HEREC_BIG_TABLE = dict(d=20, m=3, b=64, n_user=9007, n_item=8200, n_other=50, lead=7, gap=5)      # 282 + 257 tiles of 32 rows
+# (in, out): {weights: (NT, chunk widths)} of the backward
+KG_TILE_WIDTHS = [((48, 48), {1: (4, [48]), 2: (4, [48])}),
+                  ((40, 88), {1: (8, [88]), 2: (8, [88])}),
+                  ((80, 80), {1: (8, [80]), 2: (8, [80])}),
+                  ((68, 100), {1: (16, [100]), 2: (8, [64, 36])}),
+                  ((128, 72), {1: (16, [72]), 2: (8, [48, 24])}),
+                  ((100, 124), {1: (16, [124]), 2: (8, [64, 60])}),
+                  ((4, 128), {1: (2, [128]), 2: (2, [128])}),
+                  ((128, 4), {1: (2, [4]), 2: (2, [4])})]
+KG_KINDS = ('kgat', 'kgcn', 'ngcf')
+KG_BIG_ROWS = 8200                   # 513 tiles on 512 workgroups: the per-chunk accumulators live across a workgroup's tiles
+KG_BIG_WIDTHS = [(68, 100), (128, 72)]
+
+
+def kg_tile_cases():
+    """(kind, in, out, NT, chunk widths) of every (width, kind) cell"""
+    return [(kind, fin, fout) + want[1 if kind == 'kgcn' else 2] for (fin, fout), want in KG_TILE_WIDTHS for kind in KG_KINDS]
+
+
+def kg_tile_id(kind, fin, fout, nt, chunks):
+    return '%s-%dx%d-chunks%s-NT%d' % (kind, fin, fout, '+'.join(map(str, chunks)), nt)

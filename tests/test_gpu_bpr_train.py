@@ -23,7 +23,8 @@ def _reference(picked, att, fc1_w, fc1_b, fc2_w, fc2_b):
 
 
 @pytest.mark.parametrize('b,p,r,mode', [(257, 9, 16, 'att'), (64, 5, 8, 'mean'), (130, 3, 12, 'att'), (33, 13, 32, 'att'),
-                                        (1, 9, 16, 'att'), (100, 1, 4, 'att')])
+                                        (1, 9, 16, 'att'), (100, 1, 4, 'att'),
+                                        (130, 4, 20, 'att'), (64, 3, 24, 'mean'), (33, 2, 28, 'att')])      # bpr_train_kernel<5>, <6>, <7>
 def test_bpr_train_matches_float64_autograd(b, p, r, mode):
     from graph_recsys_benchmark_amd import engine
     dev = torch.device('cuda', 0)

@@ -60,22 +60,26 @@ def check(got, peer, truth, keys, what):
         helpers.assert_fp32_close(np.asarray(got[k]).reshape(peer[k].shape), peer[k], truth[k], what='%s %s' % (what, k))
 
 
-@pytest.mark.parametrize('b', BATCHES)
-@pytest.mark.parametrize('d,m', SHAPES)
-def test_exact_case(d, m, b):
+def exact_inputs(d, m, b):
     """E, W, b zero: s_m = 0.5 and S = M / 2 exactly; embedding tables in {-1, 0, 1}: every partial sum of pred is an exact
-    multiple of 0.5, so pred equals the float64 value whatever the order"""
-    inp, _, _ = inputs(d, m, b)
-    g = on_gpu(inp)
+    multiple of 0.5, so pred equals the float64 value whatever the order.  CPU tensors, and pred in float64"""
+    inp = dict(herec_ref.make_inputs(d, m, b))
     gen = torch.Generator().manual_seed(d + m + b)
     for k in ('user_emb', 'item_emb', 'user_rk_bias', 'item_rk_bias'):
-        g[k] = torch.randint(-1, 2, inp[k].shape, generator=gen).float().to(DEV)
-    g['tables'] = [torch.zeros_like(t) for t in g['tables']]
-    g['w'], g['b'] = torch.zeros_like(g['w']), torch.zeros_like(g['b'])
+        inp[k] = torch.randint(-1, 2, inp[k].shape, generator=gen).float()
+    inp['tables'] = [torch.zeros_like(t) for t in inp['tables']]
+    inp['w'], inp['b'] = torch.zeros_like(inp['w']), torch.zeros_like(inp['b'])
+    lu, li = inp['unids'] - inp['acc_uids'], inp['inids'] - inp['acc_iids']
+    want = ((inp['user_emb'][lu].double() * inp['item_emb'][li].double()).sum(-1) + 0.5 * m * inp['user_rk_bias'][lu].double().sum(-1) +
+            0.5 * m * inp['item_rk_bias'][li].double().sum(-1))
+    return inp, want
+
+
+def check_exact(d, m, b):
+    inp, want = exact_inputs(d, m, b)
+    g = on_gpu(inp)
+    want = want.to(DEV)
     engine.check_pending_errors()
-    lu, li = g['unids'] - inp['acc_uids'], g['inids'] - inp['acc_iids']
-    want = ((g['user_emb'][lu].double() * g['item_emb'][li].double()).sum(-1) + 0.5 * m * g['user_rk_bias'][lu].double().sum(-1) +
-            0.5 * m * g['item_rk_bias'][li].double().sum(-1))
     for need_grad in (False, True):
         out = raw(g, need_grad)
         assert torch.equal(out[1].double(), want), need_grad
@@ -86,7 +90,11 @@ def test_exact_case(d, m, b):
 
 @pytest.mark.parametrize('b', BATCHES)
 @pytest.mark.parametrize('d,m', SHAPES)
-def test_loss_and_gradients(d, m, b):
+def test_exact_case(d, m, b):
+    check_exact(d, m, b)
+
+
+def check_loss_and_gradients(d, m, b):
     inp, truth, peer = inputs(d, m, b)
     g = on_gpu(inp)
     engine.check_pending_errors()
@@ -113,6 +121,12 @@ def test_loss_and_gradients(d, m, b):
         assert torch.equal(x, y)
     loss2, grads2 = native(g)
     assert np.array_equal(loss, loss2) and all(np.array_equal(grads[k], grads2[k]) for k in grads)
+
+
+@pytest.mark.parametrize('b', BATCHES)
+@pytest.mark.parametrize('d,m', SHAPES)
+def test_loss_and_gradients(d, m, b):
+    check_loss_and_gradients(d, m, b)
 
 
 def test_forward_only_matches_and_does_no_backward():
@@ -201,18 +215,29 @@ def model_of(inp, native=True):
     return herec_ref.load_model(model, inp).to(DEV)
 
 
-@pytest.mark.parametrize('d,m', SHAPES)
-def test_table_and_scoring(d, m):
-    inp, truth, peer = inputs(d, m, 1000)
-    g = on_gpu(inp)
+def check_table(inp, g):
+    """the catalogue table against the float32 peer and the float64 truth, and its structure; returns it"""
+    d = inp['w'].shape[1]
     table = engine.herec_table(g['tables'], g['w'], g['b'], g['user_emb'], g['item_emb'], g['user_rk_bias'], g['item_rk_bias'],
                                inp['acc_uids'], inp['acc_iids'])
     assert tuple(table.shape) == (inp['num_nodes'], d + 4)
     helpers.assert_fp32_close(table.cpu().numpy(), herec_ref.table_of(inp, torch.float32, DEV), herec_ref.table_of(inp), what='table')
     nu, ni = inp['user_emb'].shape[0], inp['item_emb'].shape[0]
-    assert not table[nu + ni:].any() and not table[:, d + 2:].any()
-    assert bool((table[:nu, d] == 1).all()) and bool((table[nu:nu + ni, d + 1] == 1).all())
-    assert torch.equal(table[:nu, :d], g['user_emb']) and torch.equal(table[nu:nu + ni, :d], g['item_emb'])
+    u0, i0 = inp['acc_uids'], inp['acc_iids']
+    other = torch.ones(inp['num_nodes'], dtype=torch.bool, device=DEV)
+    other[u0:u0 + nu] = False
+    other[i0:i0 + ni] = False
+    assert not table[other].any() and not table[:, d + 2:].any()
+    assert bool((table[u0:u0 + nu, d] == 1).all()) and bool((table[i0:i0 + ni, d + 1] == 1).all())
+    assert torch.equal(table[u0:u0 + nu, :d], g['user_emb']) and torch.equal(table[i0:i0 + ni, :d], g['item_emb'])
+    return table
+
+
+@pytest.mark.parametrize('d,m', SHAPES)
+def test_table_and_scoring(d, m):
+    inp, truth, peer = inputs(d, m, 1000)
+    g = on_gpu(inp)
+    table = check_table(inp, g)
     model = model_of(inp).eval()
     assert torch.equal(model.cached_repr, table) and all(t.is_cuda for t in model.rk_embeddings)
     got = model.predict(g['unids'], g['inids'])

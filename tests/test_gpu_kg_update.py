@@ -53,7 +53,7 @@ def torch_side(kind, t, dtype, merged=True):
     return (out.detach(),) + tuple(None if leaf[k] is None else leaf[k].grad for k in ('x', 's', 'w1', 'w2', 'bias'))
 
 
-def make(kind, n, fin, fout, seed, exact, with_keep=True, with_bias=True):
+def make(kind, n, fin, fout, seed, exact, with_keep=True, with_bias=True, device=DEV):
     g = torch.Generator().manual_seed(seed)
     if exact:
         draw = lambda *shape: torch.randint(-2, 3, shape, generator=g).float()
@@ -67,7 +67,7 @@ def make(kind, n, fin, fout, seed, exact, with_keep=True, with_bias=True):
     t = {'x': draw(n, fin), 's': draw(n, fin), 'w1': weight(), 'w2': None if kind == 'kgcn' else weight(),
          'bias': draw(fout) if kind != 'ngcf' and with_bias else None, 'g': draw(n, fout), 'slope': slope, 'scale': scale,
          'keep': (torch.rand((n, fout), generator=g) >= (0.5 if exact else 0.1)).to(torch.uint8) if with_keep else None}
-    return {k: (v.to(DEV) if torch.is_tensor(v) else v) for k, v in t.items()}
+    return {k: (v.to(device) if torch.is_tensor(v) else v) for k, v in t.items()}
 
 
 def block(t, pad):
@@ -122,16 +122,24 @@ def assert_exact(kind, t, got):
 EXACT = [(n, 64, 64) for n in ROWS] + [(n, fin, fout) for fin, fout in WIDTHS if (fin, fout) != (64, 64) for n in (17, 300)]
 
 
-@pytest.mark.parametrize('kind', KINDS)
-@pytest.mark.parametrize('n,fin,fout', EXACT)
-def test_exact(kind, n, fin, fout):
+def exact_inputs(kind, n, fin, fout, device=DEV):
     # the keep mask is present in every second case, so both pointer states meet every kind and both tile paths
-    t = make(kind, n, fin, fout, seed=n + fin + 3 * fout, exact=True, with_keep=(n + fin // 4) % 2 == 0)
+    return make(kind, n, fin, fout, seed=n + fin + 3 * fout, exact=True, with_keep=(n + fin // 4) % 2 == 0, device=device)
+
+
+def check_exact(kind, n, fin, fout):
+    t = exact_inputs(kind, n, fin, fout)
     got, _ = raw(kind, t)
     want = assert_exact(kind, t, got)
     if n >= 300 and kind == 'kgat':      # the run does land on z == 0 with a non-zero gradient behind it
         z = (t['x'] + t['s']).double() @ t['w1'].double()
         assert int((z == 0).sum()) > 0 and float(want[1].abs().max()) > 0
+
+
+@pytest.mark.parametrize('kind', KINDS)
+@pytest.mark.parametrize('n,fin,fout', EXACT)
+def test_exact(kind, n, fin, fout):
+    check_exact(kind, n, fin, fout)
 
 
 @pytest.mark.parametrize('kind', KINDS)
@@ -148,19 +156,24 @@ def test_exact_kgat_without_bias():
     assert_exact('kgat', t, got)
 
 
-@pytest.mark.parametrize('kind', KINDS)
-def test_exact_column_blocks_of_wider_buffers(kind):
-    t = make(kind, 65, 12, 20, seed=2, exact=True)
+def check_column_blocks(kind, t):
+    fin, fout = t['w1'].shape
     got, bufs = raw(kind, t, pad=12)
     assert_exact(kind, t, got)
-    for buf, width in zip(bufs, (20, 12, 12)):
+    for buf, width in zip(bufs, (fout, fin, fin)):
         outside = torch.cat([buf[:, :4], buf[:, 4 + width:]], dim=1)
         assert bool((outside == SENTINEL).all()), 'columns outside the block were written'
 
 
 @pytest.mark.parametrize('kind', KINDS)
-@pytest.mark.parametrize('n,fin,fout', [(300, 64, 64), (1000, 64, 64), (300, 64, 32), (1000, 32, 16), (300, 128, 128), (300, 12, 20)])
-def test_random_float(kind, n, fin, fout):
+def test_exact_column_blocks_of_wider_buffers(kind):
+    check_column_blocks(kind, make(kind, 65, 12, 20, seed=2, exact=True))
+
+
+RANDOM_FLOAT = [(300, 64, 64), (1000, 64, 64), (300, 64, 32), (1000, 32, 16), (300, 128, 128), (300, 12, 20)]
+
+
+def check_random_float(kind, n, fin, fout):
     t = make(kind, n, fin, fout, seed=n + fout, exact=False)
     got, _ = raw(kind, t)
     want = torch_side(kind, t, torch.float32, merged=False)
@@ -168,6 +181,12 @@ def test_random_float(kind, n, fin, fout):
     for name, a, b, c in zip(NAMES, got, want, truth):
         if a is not None:
             helpers.assert_fp32_close(a.cpu().numpy(), b.cpu().numpy(), c.cpu().numpy(), what='%s %s' % (kind, name))
+
+
+@pytest.mark.parametrize('kind', KINDS)
+@pytest.mark.parametrize('n,fin,fout', RANDOM_FLOAT)
+def test_random_float(kind, n, fin, fout):
+    check_random_float(kind, n, fin, fout)
 
 
 @pytest.mark.parametrize('kind', KINDS)

@@ -22,7 +22,7 @@ WIDTHS = [4, 20, 64, 128]
 BATCHES = [1, 15, 16, 17, 1000, 5461]      # the tile boundary, several tiles per workgroup, the largest batch the scatter takes
 
 
-def make_batch(b, n_rel, seed):
+def make_batch(b, n_rel, seed, device=DEV):
     g = torch.Generator().manual_seed(seed)
     pool = torch.randperm(N, generator=g)[:40]
     batch = torch.stack([pool[torch.randint(0, 40, (b,), generator=g)], torch.randint(0, N, (b,), generator=g),
@@ -30,7 +30,7 @@ def make_batch(b, n_rel, seed):
     fixed = torch.tensor([[7, 7, 9, 0], [3, 50, 50, n_rel - 1], [3, 50, 61, n_rel - 1]])
     k = min(b, 3)
     batch[:k] = fixed[:k]
-    return batch.to(DEV)
+    return batch.to(device)
 
 
 def make_floats(e, n_rel, seed):
@@ -86,20 +86,35 @@ def np_(t):
     return t.detach().cpu().numpy()
 
 
-@pytest.mark.parametrize('b', [1, 15, 16, 17, 1000])
-@pytest.mark.parametrize('e', WIDTHS)
-def test_exact_integer_case(e, b):
+def exact_inputs(e, b, device=DEV):
+    """x, P, r in {-1, 0, 1} and the batch of the exact case (the module's docstring says why every sum is an integer)"""
     g = torch.Generator().manual_seed(e + b)
-    x = torch.randint(-1, 2, (N, e), generator=g).float().to(DEV)
-    r = torch.randint(-1, 2, (R, e), generator=g).float().to(DEV)
-    p = torch.randint(-1, 2, (e, e), generator=g).float().to(DEV)
-    batch = make_batch(b, R, 3 * b + e)
+    x = torch.randint(-1, 2, (N, e), generator=g).float().to(device)
+    r = torch.randint(-1, 2, (R, e), generator=g).float().to(device)
+    p = torch.randint(-1, 2, (e, e), generator=g).float().to(device)
+    return x, p, r, make_batch(b, R, 3 * b + e, device)
+
+
+def exact_pos_neg(x, p, r, batch, dtype):
+    """pos, neg of the composition in `dtype`"""
+    xd, pd, rd = x.to(dtype), p.to(dtype), r.to(dtype)
+    _, pos, neg = compose(xd[batch[:, 0]], xd[batch[:, 1]], xd[batch[:, 2]], rd[batch[:, 3]], pd)
+    return pos, neg
+
+
+def check_exact(e, b):
+    x, p, r, batch = exact_inputs(e, b)
     _, pos, neg, _, _, _, flag = engine.transr_train_raw(x, p, r, batch)
-    xd, pd, rd = x.double(), p.double(), r.double()
-    _, want_pos, want_neg = compose(xd[batch[:, 0]], xd[batch[:, 1]], xd[batch[:, 2]], rd[batch[:, 3]], pd)
+    want_pos, want_neg = exact_pos_neg(x, p, r, batch, torch.float64)
     assert float(want_pos.max()) < 2 ** 24
     assert torch.equal(pos.double(), want_pos) and torch.equal(neg.double(), want_neg)
     assert int(flag) == 0
+
+
+@pytest.mark.parametrize('b', [1, 15, 16, 17, 1000])
+@pytest.mark.parametrize('e', WIDTHS)
+def test_exact_integer_case(e, b):
+    check_exact(e, b)
 
 
 def check_case(c, what):
@@ -126,9 +141,7 @@ def test_one_relation():
     check_case(case(20, 17, 1), 'E=20 B=17 R=1')
 
 
-@pytest.mark.parametrize('b', [17, 1000])
-@pytest.mark.parametrize('e', WIDTHS)
-def test_raw_gradient_rows(e, b):
+def check_raw_rows(e, b):
     c = case(e, b)
     loss, pos, neg, grad_rows, grad_rel, dproj, flag = engine.transr_train_raw(c['x'], c['p'], c['r'], c['batch'])
     assert grad_rows.shape == (3 * b, e) and grad_rel.shape == (b, e) and dproj.shape == (e, e) and int(flag) == 0
@@ -137,6 +150,12 @@ def test_raw_gradient_rows(e, b):
     helpers.assert_fp32_close(np_(grad_rows), np_(c['peer']['grad_rows']), np_(c['truth']['grad_rows']), what='grad_rows')
     helpers.assert_fp32_close(np_(grad_rel), np_(c['peer']['grad_rel']), np_(c['truth']['grad_rel']), what='grad_rel_rows')
     helpers.assert_fp32_close(np_(dproj), np_(c['peer']['dp']), np_(c['truth']['dp']), what='dproj')
+
+
+@pytest.mark.parametrize('b', [17, 1000])
+@pytest.mark.parametrize('e', WIDTHS)
+def test_raw_gradient_rows(e, b):
+    check_raw_rows(e, b)
 
 
 def test_bad_ids():
@@ -167,18 +186,22 @@ def test_bad_ids():
     engine.check_pending_errors()       # the flag was consumed
 
 
+def check_forward_only(e, b):
+    c = case(e, b)
+    x = c['x'].clone().requires_grad_(True)
+    with_grad = engine.transr_loss(x, c['p'], c['r'], c['batch'])
+    assert with_grad.requires_grad
+    with torch.no_grad():
+        without = engine.transr_loss(x, c['p'], c['r'], c['batch'])
+    assert not without.requires_grad and torch.equal(with_grad.detach(), without)
+    assert not engine.transr_loss(c['x'], c['p'], c['r'], c['batch']).requires_grad      # no input requires grad
+    raw = engine.transr_train_raw(c['x'], c['p'], c['r'], c['batch'], need_grad=False)
+    assert raw[3] is None and raw[4] is None and raw[5] is None and torch.equal(raw[0], without)
+
+
 def test_forward_only_gives_the_same_loss():
     for e, b in ((20, 17), (64, 1000), (128, 1000)):
-        c = case(e, b)
-        x = c['x'].clone().requires_grad_(True)
-        with_grad = engine.transr_loss(x, c['p'], c['r'], c['batch'])
-        assert with_grad.requires_grad
-        with torch.no_grad():
-            without = engine.transr_loss(x, c['p'], c['r'], c['batch'])
-        assert not without.requires_grad and torch.equal(with_grad.detach(), without)
-        assert not engine.transr_loss(c['x'], c['p'], c['r'], c['batch']).requires_grad      # no input requires grad
-        raw = engine.transr_train_raw(c['x'], c['p'], c['r'], c['batch'], need_grad=False)
-        assert raw[3] is None and raw[4] is None and raw[5] is None and torch.equal(raw[0], without)
+        check_forward_only(e, b)
 
 
 def test_two_runs_agree_bitwise():
