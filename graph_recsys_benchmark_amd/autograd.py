@@ -21,8 +21,9 @@ from collections import Counter
 import torch
 
 from . import _lib
-from .engine import (PARAM_SLOTS, RowSet, block_sum, dense_batch, grad_weight, mlp2_backward_data, mlp2_backward_data_sage,
-                     rows_scatter_sum)
+from .dense_ops import RowSet, block_sum, dense_batch, grad_weight, mlp2_backward_data, mlp2_backward_data_sage
+from .engine import PARAM_SLOTS
+from .losses import rows_scatter_sum
 
 
 class _Layout:

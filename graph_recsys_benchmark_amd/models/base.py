@@ -43,6 +43,16 @@ class GraphRecsysModel(torch.nn.Module):
     def predict(self, unids, inids):
         raise NotImplementedError
 
+    def scored(self, op, *args, **kwargs):
+        """engine.<op> of this model's scorer on cached_repr, op one of 'predict', 'rank_eval', 'recommend_topk', 'rank_full':
+        engine.dot_<op>(cached_repr, *args) under 'dot', engine.<op>(cached_repr, *args, fc1 / fc2 parameters) under 'mlp'.
+        solvers.py calls it unbound on whatever model object it is handed: one that names no scorer is an 'mlp' model."""
+        scorer = getattr(self, 'scorer', 'mlp')
+        if scorer == 'dot':
+            return getattr(_engine, 'dot_' + op)(self.cached_repr, *args, **kwargs)
+        return getattr(_engine, op)(self.cached_repr, *args, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias,
+                                    **kwargs)
+
     def loss(self, pos_neg_pair_t):
         """-sum(log(sigmoid(pos - neg))) over rows (u, i+, i-[, entity columns]); in training mode the full-graph
         forward is recomputed first, exactly like the reference (models/base.py:44-45)."""
@@ -52,13 +62,13 @@ class GraphRecsysModel(torch.nn.Module):
             pos_pred = self.predict(pos_neg_pair_t[:, 0], pos_neg_pair_t[:, 1])
             neg_pred = self.predict(pos_neg_pair_t[:, 0], pos_neg_pair_t[:, 2])
             cf_loss = -(pos_pred - neg_pred).sigmoid().log().sum()
-        elif self.scorer == 'dot':
-            pos_pred = _engine.dot_predict(self.cached_repr, pos_neg_pair_t[:, 0], pos_neg_pair_t[:, 1])
-            neg_pred = _engine.dot_predict(self.cached_repr, pos_neg_pair_t[:, 0], pos_neg_pair_t[:, 2])
-            cf_loss = -torch.nn.functional.logsigmoid(pos_pred - neg_pred).sum()
-        else:
+        elif self.scorer == 'mlp':              # both scores and the sum in one launch
             cf_loss = _engine.bpr_score(self.cached_repr, pos_neg_pair_t, self.fc1.weight, self.fc1.bias,
                                         self.fc2.weight, self.fc2.bias)
+        else:
+            pos_pred = self.scored('predict', pos_neg_pair_t[:, 0], pos_neg_pair_t[:, 1])
+            neg_pred = self.scored('predict', pos_neg_pair_t[:, 0], pos_neg_pair_t[:, 2])
+            cf_loss = -torch.nn.functional.logsigmoid(pos_pred - neg_pred).sum()
         if self.entity_aware and self.training:
             # entity-aware regulariser (models/base.py:50-73): one HIP launch (csrc/entity.hip)
             x = self.x if self.cached_repr.requires_grad else self.x.detach()
@@ -87,10 +97,7 @@ class GraphRecsysModel(torch.nn.Module):
         cached = getattr(self, 'cached_repr', None)
         if cached is None or self.training or getattr(self, '_repr_partial', False) or cached.requires_grad:
             raise RuntimeError('recommend() reads the eval-mode table: call model.eval() first')
-        if self.scorer == 'dot':
-            return _engine.dot_recommend_topk(cached, unids, k, item_range, exclude=exclude)
-        return _engine.recommend_topk(cached, unids, k, item_range, self.fc1.weight, self.fc1.bias, self.fc2.weight,
-                                      self.fc2.bias, exclude=exclude)
+        return self.scored('recommend_topk', unids, k, item_range, exclude=exclude)
 
 
 class _ShardedRows(torch.autograd.Function):

@@ -87,7 +87,7 @@ class HeRecRecsysModel(GraphRecsysModel):
         # training mode is where gradients are needed: the composition.  Eval mode scores the table eval() built (no grad)
         if self.training or self.cached_repr is None or not self.cached_repr.is_cuda:
             return self.forward(unids, inids)
-        return _engine.dot_predict(self.cached_repr, unids, inids)
+        return self.scored('predict', unids, inids)
 
     @staticmethod
     def _eval_mse(scores):
@@ -147,7 +147,7 @@ class HeRecRecsysModel(GraphRecsysModel):
         if self.training or self.cached_repr is None:
             raise RuntimeError('rank_eval() reads the eval-mode table: call model.eval() first')
         if self.cached_repr.is_cuda:
-            scores, rank, auc, _ = _engine.dot_rank_eval(self.cached_repr, unids, cand)
+            scores, rank, auc, _ = self.scored('rank_eval', unids, cand)
         else:
             t = self.cached_repr
             scores = torch.sum(t[unids.long()].unsqueeze(1) * t[cand.long()], dim=-1)

@@ -75,7 +75,7 @@ class DotRecsysModel(GraphRecsysModel):
             raise RuntimeError('native_train builds no table while training: call cf_eval() / eval() before predict()')
         if self.cached_repr.requires_grad:      # training: the reference's formula, differentiable
             return torch.sum(self.cached_repr[unids] * self.cached_repr[inids], dim=-1)
-        return _engine.dot_predict(self.cached_repr, unids, inids)
+        return self.scored('predict', unids, inids)
 
 
 class KGBaseRecsysModel(DotRecsysModel):

@@ -6,7 +6,6 @@ only fc1 / fc2 train, so the training step is plain autograd over the gathered r
 import torch
 import torch.nn.functional as F
 
-from .. import engine as _engine
 from ..nn.inits import glorot
 from .base import GraphRecsysModel
 
@@ -50,7 +49,7 @@ class WalkBasedRecsysModel(GraphRecsysModel):
         grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
         if self.training or grad or not self._hip_scorer():
             return self.forward(unids, inids)
-        return _engine.predict(self.cached_repr, unids, inids, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias)
+        return self.scored('predict', unids, inids)
 
     def loss(self, batch):
         pos_pred = self.predict(batch[:, 0], batch[:, 1])
@@ -73,7 +72,7 @@ class WalkBasedRecsysModel(GraphRecsysModel):
         if self.training:
             raise RuntimeError('rank_eval() reads the eval-mode table: call model.eval() first')
         if self._hip_scorer():
-            return _engine.rank_eval(self.cached_repr, unids, cand, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias)
+            return self.scored('rank_eval', unids, cand)
         with torch.no_grad():
             scores = self._score_matrix(unids.to(torch.int64), cand.to(torch.int64))
             pos, neg = scores[:, :1], scores[:, 1:]
@@ -89,8 +88,7 @@ class WalkBasedRecsysModel(GraphRecsysModel):
         if self.training:
             raise RuntimeError('rank_full() reads the eval-mode table: call model.eval() first')
         if self._hip_scorer():
-            return _engine.rank_full(self.cached_repr, unids, pos_items, item_range, self.fc1.weight, self.fc1.bias,
-                                     self.fc2.weight, self.fc2.bias, exclude=exclude)
+            return self.scored('rank_full', unids, pos_items, item_range, exclude=exclude)
         with torch.no_grad():
             unids, pos_items = unids.to(torch.int64), pos_items.to(torch.int64)
             items = torch.arange(item_range[0], item_range[1], device=unids.device)

@@ -1,0 +1,321 @@
+"""Scoring and evaluation on a table of node rows: the BPR score of a batch, the entity regulariser, the ablation fusion and
+the four scoring operations (predict, candidate ranking, catalogue top-K, catalogue ranking).  Each has ONE host body for the
+fc1 / fc2 scorer (pea_*) and the inner product (pea_dot_*): `fc` is the four fc tensors or None (_scorer)."""
+import ctypes as C
+
+import torch
+
+from . import _lib
+from .errors import check as check_pending_errors, defer as _defer_error, ws_flag
+from .losses import _int64_batch
+
+
+def bpr_score(repr_, triples, fc1_w, fc1_b, fc2_w, fc2_b, want_preds=False, validate=False):
+    """loss = -sum(log(sigmoid(pos - neg))) over rows (u, i+, i-) of `triples` (reference models/base.py:46-48,
+    208-214).  Returns a 0-dim tensor (and pos, neg [B] when asked).  A triple with a node id out of range makes the
+    loss NaN on the device and IndexError at the next check_pending_errors() (validate=True: at once)."""
+    lib = _lib.require_device()
+    triples = _int64_batch(triples, 3, 'triples must be int64 [B, >=3]')
+    b, r, dev = triples.shape[0], repr_.shape[1], repr_.device
+    ws_bytes = int(lib.pea_bpr_workspace_bytes(b))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    pos, neg = (torch.empty(b, dtype=torch.float32, device=dev) if want_preds else None for _ in range(2))
+    args = [t.detach().contiguous() for t in (repr_, fc1_w, fc1_b, fc2_w, fc2_b)]
+    _lib.check(lib.pea_bpr_score(b, r, repr_.shape[0], _lib.ptr(args[0]), _lib.ptr(triples), triples.stride(0),
+                                 _lib.ptr(args[1]), _lib.ptr(args[2]), _lib.ptr(args[3]), _lib.ptr(args[4]),
+                                 _lib.ptr(pos), _lib.ptr(neg), _lib.ptr(loss), _lib.ptr(ws), ws_bytes,
+                                 _lib.current_stream()))
+    _defer_error(ws_flag(ws))
+    if validate:
+        check_pending_errors()
+    return (loss, pos, neg) if want_preds else loss
+
+
+class _EntityReg(torch.autograd.Function):
+    """reg(x) with the gradient rows of the same launch (csrc/entity.hip); backward = one index_add into dx."""
+
+    @staticmethod
+    def forward(ctx, x, batch9):
+        reg, rows = _entity_launch(x, batch9, want_grad=True)
+        ctx.save_for_backward(rows, batch9)
+        ctx.shape = x.shape
+        return reg
+
+    @staticmethod
+    def backward(ctx, g):
+        rows, t = ctx.saved_tensors
+        ids = t[:, [1, 3, 4, 0, 6, 7]].reshape(-1)            # order of the six gradient rows per batch row
+        dx = torch.zeros(ctx.shape, dtype=rows.dtype, device=rows.device)
+        dx.index_add_(0, ids, rows * g)
+        return dx, None
+
+
+def _entity_launch(x, batch9, want_grad):
+    lib = _lib.require_device()
+    batch9 = _int64_batch(batch9, 9, 'entity-aware batches are int64 [B, 9] (u, i+, i-, 6 entity columns)')
+    xd = x.detach()
+    if xd.stride(1) != 1 or xd.stride(0) % 4:
+        xd = xd.contiguous()
+    b, f = batch9.shape[0], xd.shape[1]
+    ws_bytes = int(lib.pea_entity_reg_workspace_bytes(b, f))
+    if ws_bytes == 0:
+        raise ValueError('entity_reg: emb_dim %d must be a multiple of 4, <= 256' % f)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=xd.device)
+    reg = torch.empty((), dtype=torch.float32, device=xd.device)
+    rows = torch.empty((6 * b, f), dtype=torch.float32, device=xd.device) if want_grad else None
+    _lib.check(lib.pea_entity_reg(b, f, xd.shape[0], _lib.ptr(xd), xd.stride(0), _lib.ptr(batch9), batch9.stride(0),
+                                  _lib.ptr(reg), _lib.ptr(rows), _lib.ptr(ws), ws_bytes, _lib.current_stream()))
+    _defer_error(ws_flag(ws))
+    return reg, rows
+
+
+def entity_reg(x, batch9):
+    """Entity-aware regulariser (reference models/base.py:50-73) in one HIP launch; differentiable with respect to x
+    when x requires grad (gradient rows come out of the same launch)."""
+    if torch.is_grad_enabled() and x.requires_grad:
+        return _EntityReg.apply(x, batch9)
+    return _entity_launch(x, batch9, want_grad=False)[0]
+
+
+def fuse_ablate(stack, att, mode='att', want_att=True):
+    """Every ablation variant of a channel stack [N, P, R] in one pass (include/peahip.h, pea_fuse_ablate): returns tables
+    [P + 1, N, R] -- tables[0] the unmasked fusion (reference models/base.py:196-203), tables[1 + p] with channel p zeroed
+    first (:194-195) -- and the unmasked fusion weights [N, P] (None unless want_att).  att: [P, R] (or [1, P, R]) for
+    mode 'att', ignored for 'mean'."""
+    lib = _lib.require_device()
+    check_pending_errors()
+    if mode not in ('att', 'mean'):
+        raise NotImplementedError('Other aggr methods not implemeted!')
+    if stack.dim() != 3 or stack.dtype != torch.float32 or not stack.is_cuda:
+        raise ValueError('stack must be a CUDA float32 [N, P, R] tensor')
+    stack = stack.detach().contiguous()
+    n, p, r = stack.shape
+    att_t = None
+    if mode == 'att':
+        if att is None:
+            raise ValueError("att is required for mode 'att'")
+        att_t = att.detach().reshape(p, r).contiguous()
+    cols = (C.c_int * p)(*[q * r for q in range(p)])
+    tables = torch.empty((p + 1, n, r), dtype=torch.float32, device=stack.device)
+    weights = torch.empty((n, p), dtype=torch.float32, device=stack.device) if want_att else None
+    _lib.check(lib.pea_fuse_ablate(n, p, r, _lib.ptr(stack), p * r, cols, _lib.ptr(att_t),
+                                   _lib.FUSE_ATT if mode == 'att' else _lib.FUSE_MEAN, _lib.ptr(tables), _lib.ptr(weights),
+                                   _lib.current_stream()))
+    return tables, weights
+
+
+def _check_scored(rc):
+    """The return code of a scoring entry point: a node id outside [0, num_nodes) is the reference's IndexError."""
+    if rc == -2:
+        raise IndexError(_lib.last_error())
+    _lib.check(rc)
+
+
+def _rank_io(unids, cand, dev, variants=()):
+    """unids / cand as contiguous int64 and the outputs of an evaluator of cand's [U, C] (its last two dimensions) over
+    `variants` tables: (scores [*variants, U, C], rank int32 / auc / loss [*variants, U]).  For the candidate evaluators
+    (rank_eval, rank_eval_multi, dot_rank_eval); the catalogue and pair bodies have other outputs."""
+    unids = unids.to(torch.int64).contiguous()
+    cand = cand.to(torch.int64).contiguous()
+    u, c = cand.shape[-2:]
+    lead = tuple(variants) + (u,)
+    outs = (torch.empty(lead + (c,), dtype=torch.float32, device=dev), torch.empty(lead, dtype=torch.int32, device=dev),
+            torch.empty(lead, dtype=torch.float32, device=dev), torch.empty(lead, dtype=torch.float32, device=dev))
+    return unids, cand, outs
+
+
+def rank_eval_multi(tables, unids, cand, fc1_w, fc1_b, fc2_w, fc2_b):
+    """rank_eval over V tables [V, N, R] in one launch (include/peahip.h, pea_rank_eval_multi).  cand [U, C]: every variant
+    ranks the same candidates; cand [V, U, C]: variant v ranks cand[v].  Returns scores [V, U, C], rank [V, U] (int32),
+    auc [V, U], eval loss [V, U]; row v is bitwise rank_eval(tables[v], unids, cand or cand[v], ...)."""
+    lib = _lib.require_device()
+    check_pending_errors()
+    if tables.dim() != 3 or tables.dtype != torch.float32:
+        raise ValueError('tables must be float32 [V, N, R]')
+    tables = tables.detach().contiguous()
+    v, n, r = tables.shape
+    u = unids.shape[0]
+    if cand.dim() == 2 and cand.shape[0] == u:
+        c, stride = cand.shape[1], 0
+    elif cand.dim() == 3 and cand.shape[0] == v and cand.shape[1] == u:
+        c, stride = cand.shape[2], u * cand.shape[2]
+    else:
+        raise ValueError('cand must be [U, C] (shared by all variants) or [V, U, C]')
+    unids, cand, (scores, rank, auc, loss) = _rank_io(unids, cand, tables.device, variants=(v,))
+    args = [t.detach().contiguous() for t in (fc1_w, fc1_b, fc2_w, fc2_b)]
+    rc = lib.pea_rank_eval_multi(v, u, c, r, n, _lib.ptr(tables), _lib.ptr(unids), _lib.ptr(cand), stride, _lib.ptr(args[0]),
+                                 _lib.ptr(args[1]), _lib.ptr(args[2]), _lib.ptr(args[3]), _lib.ptr(scores), _lib.ptr(rank),
+                                 _lib.ptr(auc), _lib.ptr(loss), _lib.current_stream())
+    _check_scored(rc)
+    return scores, rank, auc, loss
+
+
+# ---- the four scoring operations: one body each, two public names each
+def _dot_table(repr_):
+    """Validation shared by the inner-product entry points (include/peahip.h, pea_dot_*): a CUDA float32 [N, D] table, D a
+    multiple of 4 and <= 256; returned detached and contiguous."""
+    if not torch.is_tensor(repr_) or repr_.dim() != 2 or repr_.dtype != torch.float32:
+        raise ValueError('the table must be a float32 [N, D] tensor')
+    if not repr_.is_cuda:
+        raise ValueError('the table must live on the GPU (there is no CPU fallback)')
+    d = repr_.shape[1]
+    if d < 4 or d % 4 != 0 or d > 256:
+        raise ValueError('the table width %d must be a multiple of 4 in 4..256' % d)
+    return repr_.detach().contiguous()
+
+
+def _scorer(op, repr_, fc):
+    """The two forms of scoring operation `op` behind one call.  Returns (table, run, query): run(head, tail) launches
+    pea_dot_<op>(*head, *tail, stream) for fc None (the inner product, over a table that _dot_table has checked), else
+    pea_<op>(*head, the four fc pointers, *tail, stream): the fc pointers sit where include/peahip.h has them.  run raises like
+    _check_scored; query is the form's topk_workspace_bytes entry point."""
+    lib = _lib.require_device()
+    if fc is None:
+        prefix, table, fc = 'pea_dot_', repr_, ()
+    else:
+        prefix, table, fc = 'pea_', repr_.detach().contiguous(), [t.detach().contiguous() for t in fc]
+
+    def run(head, tail):
+        _check_scored(getattr(lib, prefix + op)(*head, *[_lib.ptr(t) for t in fc], *tail, _lib.current_stream()))
+    return table, run, getattr(lib, prefix + 'topk_workspace_bytes')
+
+
+def _catalogue_args(repr_, unids, item_range, exclude):
+    unids = unids.to(torch.int64).contiguous()
+    if unids.dim() != 1:
+        raise ValueError('unids must be 1-d')
+    item_lo, item_hi = int(item_range[0]), int(item_range[1])
+    if item_hi < item_lo:
+        raise ValueError('item_range is (first item node id, one past the last)')
+    rowptr = items = None
+    if exclude is not None:
+        rowptr, items = exclude
+        if rowptr.dtype != torch.int64 or items.dtype != torch.int64 or rowptr.numel() != unids.numel() + 1:
+            raise ValueError('exclude is (rowptr int64 [U + 1], items int64) -- see utils.interactions.seen_items_csr')
+        if rowptr.device != repr_.device or items.device != repr_.device:
+            raise ValueError('the exclusion lists must live on the device of the table')
+        rowptr, items = rowptr.contiguous(), items.contiguous()
+        if items.numel() == 0:                  # a valid pointer for the C side even when nobody has seen anything
+            items = torch.zeros(1, dtype=torch.int64, device=repr_.device)
+    return unids, item_lo, item_hi - item_lo, rowptr, items
+
+
+def _catalogue_ws(query, u, n_items, k, r, dev):
+    """(workspace, its size as the C side wants it) of a catalogue scan keeping k items per user"""
+    ws_bytes = int(query(u, n_items, k, r))
+    return torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev), ws_bytes
+
+
+def _predict(repr_, unids, inids, fc):
+    unids = unids.to(torch.int64).contiguous()
+    inids = inids.to(torch.int64).contiguous()
+    if unids.shape != inids.shape or unids.dim() != 1:
+        raise ValueError('unids / inids must be 1-d of equal length')
+    table, run, _ = _scorer('predict', repr_, fc)
+    out = torch.empty(unids.shape[0], dtype=torch.float32, device=table.device)
+    run((unids.shape[0], table.shape[1], table.shape[0], _lib.ptr(table), _lib.ptr(unids), _lib.ptr(inids)), (_lib.ptr(out),))
+    return out
+
+
+def _rank_eval(repr_, unids, cand, fc):
+    table, run, _ = _scorer('rank_eval', repr_, fc)
+    unids, cand, outs = _rank_io(unids, cand, table.device)
+    run((cand.shape[0], cand.shape[1], table.shape[1], table.shape[0], _lib.ptr(table), _lib.ptr(unids), _lib.ptr(cand)),
+        [_lib.ptr(t) for t in outs])
+    return outs
+
+
+def _recommend_topk(repr_, unids, k, item_range, exclude, fc):
+    table, run, query = _scorer('recommend_topk', repr_, fc)
+    unids, item_lo, n_items, rowptr, items = _catalogue_args(table, unids, item_range, exclude)
+    u, k, r, dev = unids.shape[0], int(k), table.shape[1], table.device
+    out_items = torch.empty((u, max(k, 0)), dtype=torch.int64, device=dev)
+    out_scores = torch.empty((u, max(k, 0)), dtype=torch.float32, device=dev)
+    ws, ws_bytes = _catalogue_ws(query, u, n_items, k, r, dev)
+    run((u, k, r, table.shape[0], _lib.ptr(table), _lib.ptr(unids), item_lo, n_items, _lib.ptr(rowptr), _lib.ptr(items)),
+        (_lib.ptr(out_items), _lib.ptr(out_scores), _lib.ptr(ws), ws_bytes))
+    return out_items, out_scores
+
+
+def _rank_full(repr_, unids, pos_items, item_range, exclude, fc):
+    table, run, query = _scorer('rank_full', repr_, fc)
+    unids, item_lo, n_items, rowptr, items = _catalogue_args(table, unids, item_range, exclude)
+    pos_items = pos_items.to(torch.int64).contiguous()
+    if pos_items.shape != unids.shape:
+        raise ValueError('one positive per requested user')
+    u, r, dev = unids.shape[0], table.shape[1], table.device
+    rank = torch.empty(u, dtype=torch.int32, device=dev)
+    auc, pos_score = torch.empty(u, dtype=torch.float32, device=dev), torch.empty(u, dtype=torch.float32, device=dev)
+    ws, ws_bytes = _catalogue_ws(query, u, n_items, 1, r, dev)
+    run((u, r, table.shape[0], _lib.ptr(table), _lib.ptr(unids), _lib.ptr(pos_items), item_lo, n_items, _lib.ptr(rowptr),
+         _lib.ptr(items)), (_lib.ptr(rank), _lib.ptr(auc), _lib.ptr(pos_score), _lib.ptr(ws), ws_bytes))
+    return rank, auc, pos_score
+
+
+def predict(repr_, unids, inids, fc1_w, fc1_b, fc2_w, fc2_b):
+    """fc2(relu(fc1([repr[u] || repr[i]]))) -> [B, 1]  (reference models/base.py:208-214)."""
+    check_pending_errors()
+    return _predict(repr_, unids, inids, (fc1_w, fc1_b, fc2_w, fc2_b)).view(-1, 1)
+
+
+def dot_predict(repr_, unids, inids):
+    """sum(repr[u] * repr[i]) -> [B]  (reference models/kgat.py, kgcn.py, ngcf.py: predict), as one fma chain over the
+    columns in ascending order (include/peahip.h, pea_dot_predict)."""
+    check_pending_errors()
+    return _predict(_dot_table(repr_), unids, inids, None)
+
+
+def rank_eval(repr_, unids, cand, fc1_w, fc1_b, fc2_w, fc2_b):
+    """Batched evaluator (reference solvers.py:56-96): cand [U, C], column 0 = the held-out positive.
+    Returns scores [U, C], rank of the positive [U] (int32), auc [U], eval loss [U]."""
+    check_pending_errors()
+    return _rank_eval(repr_, unids, cand, (fc1_w, fc1_b, fc2_w, fc2_b))
+
+
+def dot_rank_eval(repr_, unids, cand):
+    """rank_eval with the inner-product scorer: cand [U, C], column 0 = the held-out positive.  Returns scores [U, C], rank
+    of the positive [U] (int32), auc [U], eval loss [U]."""
+    check_pending_errors()
+    table = _dot_table(repr_)
+    if cand.dim() != 2 or unids.dim() != 1 or cand.shape[0] != unids.shape[0]:
+        raise ValueError('cand must be [U, C] with one row per user of unids')
+    return _rank_eval(table, unids, cand, None)
+
+
+def recommend_topk(repr_, unids, k, item_range, fc1_w, fc1_b, fc2_w, fc2_b, exclude=None):
+    """The k best items of the catalogue item_range = (lo, hi) (node ids [lo, hi)) for every user of `unids`, scored
+    like predict (reference models/base.py:208-214) and ordered by (score descending, node id ascending); `exclude`
+    = (rowptr [U + 1], items) names per requested user the items to leave out (utils.interactions.seen_items_csr).
+    Returns (items int64 [U, k], scores float32 [U, k]); a user with fewer than k eligible items gets (-1, -inf) in the
+    tail.  One pass over the catalogue on the device (include/peahip.h, pea_recommend_topk); the [U, items] score matrix
+    is never written."""
+    check_pending_errors()
+    return _recommend_topk(repr_, unids, k, item_range, exclude, (fc1_w, fc1_b, fc2_w, fc2_b))
+
+
+def dot_recommend_topk(repr_, unids, k, item_range, exclude=None):
+    """recommend_topk with the inner-product scorer: the k best items of the catalogue item_range = (lo, hi) for every user
+    of `unids`, ordered by (score descending, node id ascending), `exclude` = (rowptr [U + 1], items) left out.  Returns
+    (items int64 [U, k], scores float32 [U, k]) with a (-1, -inf) tail.  The catalogue scan is an MFMA GEMM whose score
+    tiles are selected from in registers (include/peahip.h, pea_dot_recommend_topk); the [U, items] score matrix is never
+    written."""
+    check_pending_errors()
+    return _recommend_topk(_dot_table(repr_), unids, k, item_range, exclude, None)
+
+
+def rank_full(repr_, unids, pos_items, item_range, fc1_w, fc1_b, fc2_w, fc2_b, exclude=None):
+    """All-item evaluation (the protocol of reference solvers.py:56-96 with EVERY eligible item as a negative instead of
+    99 sampled ones): per user the rank of the held-out positive = number of eligible other items scoring strictly
+    higher, auc = share of them scoring strictly lower, and the positive's score.  Returns (rank int32 [U], auc [U],
+    pos_score [U]).  include/peahip.h, pea_rank_full."""
+    check_pending_errors()
+    return _rank_full(repr_, unids, pos_items, item_range, exclude, (fc1_w, fc1_b, fc2_w, fc2_b))
+
+
+def dot_rank_full(repr_, unids, pos_items, item_range, exclude=None):
+    """rank_full with the inner-product scorer: per user the number of eligible other items scoring strictly higher than
+    the held-out positive, the share scoring strictly lower, and the positive's score.  Returns (rank int32 [U], auc [U],
+    pos_score [U]).  include/peahip.h, pea_dot_rank_full."""
+    check_pending_errors()
+    return _rank_full(_dot_table(repr_), unids, pos_items, item_range, exclude, None)

@@ -20,6 +20,8 @@ On the GPU box the collectives run over RCCL (backend 'nccl').
 import torch
 import torch.distributed as dist
 
+from . import errors
+
 
 def _hip():
     from . import _lib
@@ -374,14 +376,11 @@ class ShardLayout:
             off += t.numel()
 
     def _err_flag(self, device):
-        from . import engine
         key = str(device)
         if key not in self._flags:
             self._flags[key] = torch.zeros(1, dtype=torch.int32, device=device)
-        flag = self._flags[key]
-        if not any(f is flag for f in engine._pending_err):
-            engine._pending_err.append(flag)
-        return flag
+        errors.defer_persistent(self._flags[key])
+        return self._flags[key]
 
     def allgather_rows(self, table, group=None):
         """table [N, ...]: every rank has written the rows it owns; fills in everybody else's (in place).  The rank-major

@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from . import engine
+from .models.base import GraphRecsysModel
 from .utils.interactions import seen_items_csr
 from .utils.sampling import generate_candidates
 
@@ -30,7 +31,7 @@ def metrics_from_ranks(rank):
 def metrics(model, dataset, num_neg_candidates=99):
     """Returns (HR[16], NDCG[16], AUC[1], eval_loss[1]) means over the test users, like BaseSolver.metrics.
     `model` must be in eval() mode (cached_repr refreshed; for KGAT / KGCN: model.cf_eval(att_map), as the reference's
-    solver does).  A model whose scorer is 'dot' is ranked by engine.dot_rank_eval."""
+    solver does).  A model whose scorer is 'dot' is ranked by engine.dot_rank_eval (GraphRecsysModel.scored)."""
     u_nids = list(dataset.test_pos_unid_inid_map.keys())
     cand = np.empty((len(u_nids), 1 + num_neg_candidates), dtype=np.int64)
     for idx, u_nid in enumerate(u_nids):
@@ -46,11 +47,8 @@ def metrics(model, dataset, num_neg_candidates=99):
     u_t = torch.as_tensor(np.asarray(u_nids, dtype=np.int64), device=dev)
     if hasattr(model, 'rank_eval'):                   # a model that picks its own evaluator (models/walk.py: HIP or torch by width)
         scores, rank, auc, loss = model.rank_eval(u_t, torch.from_numpy(cand).to(dev))
-    elif getattr(model, 'scorer', 'mlp') == 'dot':    # KGAT / KGCN (after model.cf_eval(att_map)) / NGCF
-        scores, rank, auc, loss = engine.dot_rank_eval(model.cached_repr, u_t, torch.from_numpy(cand).to(dev))
-    else:
-        scores, rank, auc, loss = engine.rank_eval(model.cached_repr, u_t, torch.from_numpy(cand).to(dev), model.fc1.weight,
-                                                   model.fc1.bias, model.fc2.weight, model.fc2.bias)
+    else:                                             # by its scorer; KGAT / KGCN: after model.cf_eval(att_map)
+        scores, rank, auc, loss = GraphRecsysModel.scored(model, 'rank_eval', u_t, torch.from_numpy(cand).to(dev))
     hr, ndcg = metrics_from_ranks(rank.cpu().numpy())
     return hr.mean(axis=0), ndcg.mean(axis=0), np.array([auc.double().mean().item()]), np.array([loss.double().mean().item()])
 
@@ -135,11 +133,8 @@ def metrics_full(model, u_nids, pos_items, item_range, exclude=None):
     pos_t = torch.as_tensor(np.asarray(pos_items, dtype=np.int64), device=dev)
     if hasattr(model, 'rank_full'):
         rank, auc, _ = model.rank_full(u_t, pos_t, item_range, exclude=exclude)
-    elif getattr(model, 'scorer', 'mlp') == 'dot':
-        rank, auc, _ = engine.dot_rank_full(model.cached_repr, u_t, pos_t, item_range, exclude=exclude)
     else:
-        rank, auc, _ = engine.rank_full(model.cached_repr, u_t, pos_t, item_range, model.fc1.weight, model.fc1.bias,
-                                        model.fc2.weight, model.fc2.bias, exclude=exclude)
+        rank, auc, _ = GraphRecsysModel.scored(model, 'rank_full', u_t, pos_t, item_range, exclude=exclude)
     return metrics_full_from_ranks(rank.cpu().numpy(), auc.double().cpu().numpy())
 
 

@@ -30,6 +30,61 @@ def test_library_exports_every_declared_symbol():
     assert lib.pea_version().startswith(b'peahip')
 
 
+C_WIDTH = {'void': 'void', 'int': 'int', 'int64_t': 'int64', 'size_t': 'uint64', 'uint64_t': 'uint64', 'uint32_t': 'uint32',
+           'float': 'float', 'double': 'double'}
+
+
+def c_width(decl, is_param):
+    """Width class of a C return type or parameter declaration: 'pointer', or the class of its scalar type"""
+    if '*' in decl or '[' in decl:
+        return 'pointer'
+    words = [w for w in decl.split() if w not in ('const', 'struct')]
+    if is_param and len(words) > 1:
+        words = words[:-1]                      # the parameter's name
+    return C_WIDTH.get(' '.join(words), 'unknown C type: %s' % decl.strip())
+
+
+def ctypes_width(t):
+    if t is None:
+        return 'void'
+    if t in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(t, ctypes._Pointer):
+        return 'pointer'
+    # ctypes aliases the fixed-width names to the platform's: size_t and uint64_t are one class here as well
+    table = {ctypes.c_int: 'int', ctypes.c_int64: 'int64', ctypes.c_size_t: 'uint64', ctypes.c_uint64: 'uint64',
+             ctypes.c_uint32: 'uint32', ctypes.c_float: 'float', ctypes.c_double: 'double'}
+    return table.get(t, 'unknown ctypes type: %r' % t)
+
+
+def declared_prototypes():
+    """{name: (return class, [parameter classes])} of every prototype of include/peahip.h"""
+    text = open(os.path.join(ROOT, 'include', 'peahip.h')).read()
+    text = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
+    text = re.sub(r'//[^\n]*', '', text)
+    protos = {}
+    for ret, name, params in re.findall(r'([A-Za-z_][\w \*]*?)\b(pea_[a-z_0-9]+)\s*\(([^)]*)\)\s*;', text):
+        params = [p for p in params.split(',') if p.strip() and p.strip() != 'void']
+        assert name not in protos, 'declared twice: %s' % name
+        protos[name] = (c_width(ret, False), [c_width(p, True) for p in params])
+    return protos
+
+
+def test_every_prototype_matches_its_ctypes_signature_by_width():
+    """Return type, number of arguments and the width class of every argument (pointer / int / int64_t / size_t or uint64_t /
+    uint32_t / float / double) of include/peahip.h against _lib.SIGNATURES: ctypes converts what it is told to, so an int
+    bound where the header says int64_t, or an argument too few, corrupts the call without an error."""
+    from graph_recsys_benchmark_amd import _lib
+    protos = declared_prototypes()
+    assert len(protos) == 112 and len(_lib.SIGNATURES) == 112
+    assert sorted(protos) == sorted(_lib.SIGNATURES)
+    mismatches = []
+    for name, (ret, params) in sorted(protos.items()):
+        restype, argtypes = _lib.SIGNATURES[name]
+        bound = (ctypes_width(restype), [ctypes_width(t) for t in argtypes])
+        if bound != (ret, params):
+            mismatches.append('%s: header %s, ctypes %s' % (name, (ret, params), bound))
+    assert not mismatches, '\n'.join(mismatches)
+
+
 def test_no_device_means_loud_failure():
     """Without a gfx950 device the product path must raise, never fall back to a CPU path."""
     import torch

@@ -238,3 +238,38 @@ def test_refusals():
     x, p, r = make_floats(132, R, 1)
     with pytest.raises(ValueError):
         engine.transr_loss(x, p, r, make_batch(64, R, 1))
+
+
+def test_a_queued_flag_does_not_pin_the_workspace():
+    """the flag a transr_loss call queues stays alive until the next check (a KG phase only checks at eval()): it must not keep
+    the step's workspace -- the [E, E] partials of every workgroup -- alive with it.  E = 64, B = 40 as in test_bad_ids."""
+    from graph_recsys_benchmark_amd import _lib, errors
+    assert int(_lib.load().pea_transr_train_workspace_bytes(40, 64)) > errors.WS_FLAG_VIEW_MAX == 4096
+    c = case(64, 1000)
+    x, p, r, clean = c['x'], c['p'], c['r'], c['batch'][:40].clone()
+    engine.check_pending_errors()
+    engine.transr_loss(x.clone().requires_grad_(True), p, r, clean).backward()
+    assert engine._pending_err[-1].untyped_storage().nbytes() <= 4096
+    bad = clean.clone()
+    bad[5, 1] = N
+    engine.transr_loss(x.clone().requires_grad_(True), p, r, bad).backward()
+    assert engine._pending_err[-1].untyped_storage().nbytes() <= 4096
+    with pytest.raises(IndexError):
+        engine.check_pending_errors()
+    assert not engine._pending_err
+
+
+def test_a_queued_herec_flag_does_not_pin_the_workspace():
+    """the same rule for herec_mse_loss at (D, M) = (64, 2), B = 40"""
+    import herec_ref
+    from graph_recsys_benchmark_amd import _lib, errors
+    assert int(_lib.load().pea_herec_train_workspace_bytes(40, 64, 2)) > errors.WS_FLAG_VIEW_MAX == 4096
+    inp = herec_ref.make_inputs(64, 2, 40)
+    g = {k: (v.to(DEV) if torch.is_tensor(v) else v) for k, v in inp.items()}
+    g['tables'] = [t.to(DEV) for t in inp['tables']]
+    params = [g[k].clone().requires_grad_(True) for k in ('w', 'b', 'user_emb', 'item_emb', 'user_rk_bias', 'item_rk_bias')]
+    engine.check_pending_errors()
+    engine.herec_mse_loss(g['tables'], *params, g['acc_uids'], g['acc_iids'], g['unids'], g['inids'], g['labels']).backward()
+    assert engine._pending_err[-1].untyped_storage().nbytes() <= 4096
+    engine.check_pending_errors()
+    assert not engine._pending_err
