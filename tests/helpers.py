@@ -737,3 +737,187 @@ def kg_tile_cases():
 
 def kg_tile_id(kind, fin, fout, nt, chunks):
     return '%s-%dx%d-chunks%s-NT%d' % (kind, fin, fout, '+'.join(map(str, chunks)), nt)
+
+
+# ------------------------------------------------------------------------------------------------------------
+# the weighted neighbour sum's matrix (pea_weighted_aggregate: AGG_WSUM of csrc/agg.hip, the column-group loop of
+# csrc/model_bwd.hip): tests/test_gpu_wsum_matrix.py runs every case on the GPU, tests/test_wsum_matrix_cpu.py checks the
+# graph, the case list and the comparison itself without one
+# ------------------------------------------------------------------------------------------------------------
+_WSUM = {}
+WSUM_GROUP = 256             # model_bwd.hip: pea_weighted_aggregate cuts the width into groups of 256 columns
+WSUM_MAX_GROUPS = 16         # common.h: kMaxAggGroups, the groups of one launch_aggregate call
+# width: every lane width with full and with idle lanes, two, three (600 = 256 + 256 + 88) and four (772 = 3 x 256 + 4) column groups,
+# and 4100 = 16 x 256 + 4: one group past a launch_aggregate call
+WSUM_WIDTHS = (4, 12, 16, 20, 32, 36, 40, 64, 96, 128, 132, 160, 256, 260, 320, 512, 600, 772, 4100)
+WSUM_CHUNK64_WIDTHS = (12, 32, 40, 96, 160, 260)          # one width per G and a two-group one, run again with PEA_CHUNK=64
+
+
+def wsum_graph():
+    """degree_graph() without its 40 self loops (weighted_aggregate refuses them, as the reference does): 2076 nodes, 15,856
+    edges, 230 of them duplicates; the loops sat on filler nodes, so every degree of AGG_DEGREES still occurs on both sides."""
+    if 'graph' not in _WSUM:
+        g = degree_graph()
+        ei = g['edge_index']
+        _WSUM['graph'] = dict(g, edge_index=np.ascontiguousarray(ei[:, ei[0] != ei[1]]))
+    return _WSUM['graph']
+
+
+def wsum_groups(width):
+    """widths of the column groups pea_weighted_aggregate makes of `width`, written down by hand"""
+    return [min(WSUM_GROUP, width - c) for c in range(0, width, WSUM_GROUP)]
+
+
+def wsum_case_id(width):
+    """G of the first group (and of the last where it differs), the number of column groups, the width"""
+    lanes = [agg_lanes(w) for w in wsum_groups(width)]
+    return 'G%s-groups%d-w%d' % ('+'.join(str(g) for g in dict.fromkeys((lanes[0], lanes[-1]))), len(lanes), width)
+
+
+def wsum_cases(widths=WSUM_WIDTHS):
+    """[(width, id)]"""
+    return [(w, wsum_case_id(w)) for w in widths]
+
+
+def wsum_cells(widths=WSUM_WIDTHS):
+    """the (G of the last column group, number of groups, 'full' | 'idle' lanes in that group) cells the widths fill; every group
+    before the last is 256 columns wide, G = 64 with full lanes"""
+    return {(agg_lanes(wsum_groups(w)[-1]), len(wsum_groups(w)), 'full' if wsum_groups(w)[-1] == 4 * agg_lanes(wsum_groups(w)[-1]) else 'idle')
+            for w in widths}
+
+
+# every G alone, with full lanes and with idle ones; two groups with a last group of G = 4, 16 and 64; three and four groups; one
+# group more than a launch_aggregate call takes.  Widths 4 / 12, 36 / 40 and 132 / 160 share a cell (they differ in how many lanes idle).
+WSUM_CELLS = ([(G, 1, 'full') for G in (4, 8, 16, 32, 64)] + [(G, 1, 'idle') for G in (4, 8, 16, 32, 64)] +
+              [(4, 2, 'idle'), (16, 2, 'full'), (64, 2, 'full'), (32, 3, 'idle'), (4, 4, 'idle'), (4, WSUM_MAX_GROUPS + 1, 'idle')])
+
+
+def check_wsum_cells(widths=WSUM_WIDTHS):
+    """Raises with the name of the first cell of WSUM_CELLS that no width fills"""
+    cells = wsum_cells(widths)
+    for G, groups, lanes in WSUM_CELLS:
+        assert (G, groups, lanes) in cells, 'no width fills the cell (G = %d, groups = %d) with %s lanes' % (G, groups, lanes)
+
+
+def wsum_inputs(width, exact=False):
+    """float32 numpy (x [n, width], w [E] in the graph's COO order, gout [n, width]).  Random: x, gout ~ N(0, 1), w = +-U(0.25, 1.5)
+    per COO edge, so duplicated edges carry different weights and a weight on the wrong edge moves a sum by about 1.  Exact: x, gout
+    integer in [-8, 8], w integer in {-4..4} without 0: every partial sum is an integer below 2^24 (1100 x 32) whatever the order."""
+    key = ('in', width, bool(exact))
+    if key in _WSUM:
+        return _WSUM[key]
+    for k in [k for k in _WSUM if k[0] == 'in' and k[1] > 512 and k[1] != width]:
+        del _WSUM[k]                                       # the widest inputs are 34 MB each: one width of them at a time
+    g = wsum_graph()
+    n, e = g['n'], g['edge_index'].shape[1]
+    rng = np.random.default_rng(7000 + width + (100000 if exact else 0))
+    if exact:
+        x = rng.integers(-8, 9, size=(n, width)).astype(np.float32)
+        gout = rng.integers(-8, 9, size=(n, width)).astype(np.float32)
+        w = (rng.integers(1, 5, size=e) * rng.choice([-1, 1], size=e)).astype(np.float32)
+    else:
+        x = rng.standard_normal((n, width), dtype=np.float32)
+        gout = rng.standard_normal((n, width), dtype=np.float32)
+        w = (rng.uniform(0.25, 1.5, size=e) * rng.choice([-1.0, 1.0], size=e)).astype(np.float32)
+    _WSUM[key] = (x, w, gout)
+    return _WSUM[key]
+
+
+def index_add_wsum(feat, w, gather, scatter, n):
+    """zeros.index_add_(0, scatter, feat[gather] * w[:, None]) in the dtype of `feat` (torch tensors), 512 columns at a time (the
+    products of 4100 columns in float64 would take 0.5 GB); a column's additions keep their order"""
+    import torch
+    out = torch.zeros(n, feat.shape[1], dtype=feat.dtype)
+    for c in range(0, feat.shape[1], 512):
+        out[:, c:c + 512].index_add_(0, scatter, feat[:, c:c + 512][gather] * w[:, None])
+    return out
+
+
+def wsum_reference(width, reverse, dtype, exact=False):
+    """numpy [n, width] in `dtype` (torch.float32 | torch.float64): out_i = sum_{e: j->i} w_e x_j of wsum_inputs(width, exact), or
+    with reverse its backward dx_j = sum_{e: j->i} w_e gout_i, the same sum over the reversed relation.  Cached; do not modify."""
+    import torch
+    key = ('ref', width, bool(reverse), str(dtype), bool(exact))
+    if key in _WSUM:
+        return _WSUM[key]
+    for k in [k for k in _WSUM if k[0] == 'ref' and k[1] > 512 and k[1] != width]:
+        del _WSUM[k]
+    g = wsum_graph()
+    x, w, gout = wsum_inputs(width, exact)
+    src, dst = torch.from_numpy(g['edge_index'][0]), torch.from_numpy(g['edge_index'][1])
+    feat = torch.from_numpy(gout if reverse else x).to(dtype)
+    out = index_add_wsum(feat, torch.from_numpy(w).to(dtype), dst if reverse else src, src if reverse else dst, g['n']).numpy()
+    out.setflags(write=False)
+    _WSUM[key] = out
+    return out
+
+
+def fp32_tier(got, want, truth, rtol=1e-5, atol=1e-6):
+    """Which tier of assert_fp32_close decides about `got` (for reports; it asserts nothing): 'strict' = every element within
+    rtol / atol of `want`; 'per-row' = every row with a missing element is within 2x the oracle's own error + atol + 16 ulp of
+    float64; 'two-sided' = some row is beyond that, and the whole-array test at the end of assert_fp32_close decides"""
+    got, want, truth = np.asarray(got, np.float64), np.asarray(want, np.float64), np.asarray(truth, np.float64)
+    bad = (np.abs(got - want) > atol + rtol * np.abs(want)).reshape(-1, got.shape[-1]).any(axis=1)
+    if not bad.any():
+        return 'strict'
+    g2, w2, t2 = (a.reshape(-1, got.shape[-1])[bad] for a in (got, want, truth))
+    ok = np.abs(g2 - t2).max(axis=1) <= 2.0 * np.abs(w2 - t2).max(axis=1) + atol + 16.0 * EPS32 * np.abs(t2).max(axis=1)
+    return 'per-row' if ok.all() else 'two-sided'
+
+
+def row_ulps(got, truth):
+    """largest row error of `got` against the float64 `truth` in float32 ulps of the row's magnitude (assert_fp32_close's unit)"""
+    got, truth = np.asarray(got, np.float64), np.asarray(truth, np.float64)
+    scale = np.abs(truth).max(axis=-1)
+    err = np.abs(got - truth).max(axis=-1)
+    return float((err[scale > 0] / (EPS32 * scale[scale > 0])).max())
+
+
+# the three baseline convs on the graph above, 36 -> 20 columns (G = 16 with idle lanes into the dense update)
+KG_CONV_IN, KG_CONV_OUT = 36, 20
+KG_CONV_PARAMS = {'kgat': ('weight_add', 'weight_bi', 'bias'), 'kgcn': ('weight', 'bias'), 'ngcf': ('W_1', 'W_2')}
+
+
+def kg_conv_tensors(kind, scale=0.3):
+    """float32 CPU tensors of one conv case: x [n, 36], {parameter: tensor}, att_map [E] (a softmax of random scores over every
+    destination's in-edges, in COO order; NGCF computes its own coefficient), the dense output gradient [n, 20]"""
+    import torch
+    g = wsum_graph()
+    n, ei = g['n'], g['edge_index']
+    gen = torch.Generator().manual_seed(900 + sorted(KG_CONV_PARAMS).index(kind))
+    rand = lambda *shape: torch.randn(shape, generator=gen)
+    x = rand(n, KG_CONV_IN) * 0.5
+    params = {k: rand(KG_CONV_OUT) * 0.1 if k == 'bias' else rand(KG_CONV_IN, KG_CONV_OUT) * scale for k in KG_CONV_PARAMS[kind]}
+    score = rand(ei.shape[1]).double()
+    dst = torch.from_numpy(ei[1])
+    ex = torch.exp(score - score.max())
+    att = (ex / torch.zeros(n, dtype=torch.float64).index_add_(0, dst, ex)[dst]).float()
+    return x, params, att, rand(n, KG_CONV_OUT)
+
+
+def kg_conv_reference(kind, dtype, scale=0.3):
+    """(out, {'x': dx, parameter: gradient}) of L = sum(conv(x) * Gout) by torch autograd on a restatement of the module's
+    arithmetic (nn/kg_conv.py, fused=False) in `dtype`, the aggregate being the index-op sum of wsum_reference"""
+    import torch
+    import torch.nn.functional as F
+    g = wsum_graph()
+    n, ei = g['n'], torch.from_numpy(g['edge_index'])
+    x, params, att, gout = kg_conv_tensors(kind, scale)
+    x = x.to(dtype).requires_grad_(True)
+    p = {k: v.to(dtype).requires_grad_(True) for k, v in params.items()}
+    if kind == 'ngcf':
+        deg = (torch.bincount(ei.reshape(-1), minlength=n) / 2).view(-1, 1)
+        w = (1 / torch.sqrt((deg[ei[1]] * deg[ei[0]]).to(dtype))).view(-1)
+    else:
+        w = att.to(dtype)
+    s = index_add_wsum(x, w, ei[0], ei[1], n)
+    if kind == 'kgat':
+        out = F.leaky_relu((x + s) @ p['weight_add'], 0.2) + F.leaky_relu((x * s) @ p['weight_bi'], 0.2) + p['bias']
+    elif kind == 'kgcn':
+        out = F.relu((s + x) @ p['weight'] + p['bias'])
+    else:
+        out = F.leaky_relu(x @ p['W_1'] + s @ p['W_1'] + (x * s) @ p['W_2'], 0.2)
+    (out * gout.to(dtype)).sum().backward()
+    grads = {'x': x.grad.numpy().astype(np.float64)}
+    grads.update({k: v.grad.numpy().astype(np.float64) for k, v in p.items()})
+    return out.detach().numpy(), grads
