@@ -1,4 +1,4 @@
-"""ctypes binding of libpeahip.so (C ABI: include/peahip.h).
+"""ctypes binding of libpeahip.so (C ABI: include/peahip.h and include/peahip_kge.h).
 
 The product path has NO fallback: if the HIP library is missing or no gfx950 device is visible, every
 compute entry point raises.  (CPU parity checking lives in oracle/, which this package never imports.)
@@ -210,6 +210,14 @@ SIGNATURES = {
                                   _sz, _vp]),
 }
 
+# every symbol include/peahip_kge.h declares (the knowledge-graph-embedding models), typed by load() like the table above
+KGE_SIGNATURES = {
+    'pea_cfkg_supported': (_int, [_int, _int]),
+    'pea_cfkg_train_workspace_bytes': (_sz, [_i64, _int, _int]),
+    'pea_cfkg_train': (_int, [_i64, _int, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+}
+CFKG_MAX_REL = 64     # include/peahip_kge.h PEA_CFKG_MAX_REL
+
 KGU_KGAT, KGU_KGCN, KGU_NGCF = 0, 1, 2     # include/peahip.h PEA_KGU_*
 
 _lib = None
@@ -223,7 +231,7 @@ def load():
             raise ImportError('%s is missing: build it with `python -c "import __graft_entry__ as g; g.build()"` '
                               '(or make -C graph_recsys_benchmark_amd/csrc); there is no CPU fallback' % LIB_PATH)
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(KGE_SIGNATURES.items()):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

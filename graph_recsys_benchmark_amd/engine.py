@@ -17,10 +17,10 @@ from .dense_ops import (  # noqa: F401
     RowSet, _rows2d, block_sum, dense_batch, grad_weight, mlp2_backward_data, mlp2_backward_data_sage)
 from .errors import _pending_err, _pending_what, check as check_pending_errors, defer as _defer_error  # noqa: F401
 from .losses import (  # noqa: F401
-    DOT_TRAIN_MAX_BLOCKS, HEREC_MAX_TABLES, ROWS_SCATTER_MAX, _block16, _BprTrainLoss, _DotBprLoss, _herec_args, _HerecLoss,
-    _int64_batch, _scatter_dense, _TransrLoss, bpr_train_loss, bpr_train_raw, bpr_train_supported, dot_bpr_loss, dot_bpr_supported,
-    dot_bpr_train_raw, herec_mse_loss, herec_supported, herec_table, herec_train_raw, rows_scatter_sum, transr_loss,
-    transr_supported, transr_train_raw)
+    DOT_TRAIN_MAX_BLOCKS, HEREC_MAX_TABLES, ROWS_SCATTER_MAX, _block16, _BprTrainLoss, _CfkgLoss, _DotBprLoss, _herec_args,
+    _HerecLoss, _int64_batch, _scatter_dense, _TransrLoss, bpr_train_loss, bpr_train_raw, bpr_train_supported, cfkg_loss,
+    cfkg_supported, cfkg_train_raw, dot_bpr_loss, dot_bpr_supported, dot_bpr_train_raw, herec_mse_loss, herec_supported,
+    herec_table, herec_train_raw, rows_scatter_sum, transr_loss, transr_supported, transr_train_raw)
 from .scoring import (  # noqa: F401
     _catalogue_args, _check_scored, _dot_table, _entity_launch, _EntityReg, _rank_io, bpr_score, dot_predict, dot_rank_eval,
     dot_rank_full, dot_recommend_topk, entity_reg, fuse_ablate, predict, rank_eval, rank_eval_multi, rank_full, recommend_topk)

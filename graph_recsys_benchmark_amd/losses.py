@@ -251,6 +251,75 @@ def transr_loss(x, proj_mat, r, batch):
     return _TransrLoss.apply(batch, need_grad, x, proj_mat, r)
 
 
+# ---- CFKG (csrc/cfkg.hip, include/peahip_kge.h; reference models/cfkg.py, experiments/cfkg_solver_bpr.py:95-106)
+def cfkg_supported(emb, num_rel, batch_size):
+    """Whether cfkg_loss takes this width and number of relations (pea_cfkg_supported: a multiple of 4 in 4..128, 1..64
+    relations) and this batch (its 3 B node positions go back through rows_scatter_sum); needs no device.  Else the caller
+    stays on autograd."""
+    return bool(_lib.load().pea_cfkg_supported(int(emb), int(num_rel))) and 3 * int(batch_size) <= ROWS_SCATTER_MAX
+
+
+def cfkg_train_raw(x, r, batch, need_grad=True):
+    """One launch of csrc/cfkg.hip (+ its fixed-order reduction): (loss, pos [B], neg [B], grad_rows [3B, E], grad_r [R, E],
+    error flag) of the CFKG kg_loss for x [N, E], r [R, E] and the int64 [B, >= 4] rows (h, t+, t-, rel) of `batch`.  grad_r is
+    the whole relation gradient, summed inside the launch.  need_grad=False is the forward-only form: the two gradients are
+    None and no backward work is done."""
+    lib = _lib.require_device()
+    batch = _int64_batch(batch, 4)
+    x, r = _block16(x), _block16(r)
+    e, n_rel = x.shape[1], r.shape[0]
+    if r.shape[1] != e or x.shape[0] < 1 or not lib.pea_cfkg_supported(e, n_rel):
+        raise ValueError('cfkg_train: x [N, E] and r [R, E] with E a multiple of 4 in 4..128 and 1 <= R <= %d expected, got %s and %s'
+                         % (_lib.CFKG_MAX_REL, tuple(x.shape), tuple(r.shape)))
+    b, dev = batch.shape[0], x.device
+    loss, pos, neg = _outputs(dev, (), (b,), (b,))
+    grad_rows, grad_r = _outputs(dev, (3 * b, e), (n_rel, e), wanted=need_grad)
+    ws, ws_bytes = _workspace(lib.pea_cfkg_train_workspace_bytes, (b, e, n_rel), dev)
+    _lib.check(lib.pea_cfkg_train(b, e, _lib.ptr(x), x.stride(0), x.shape[0], _lib.ptr(r), r.stride(0), n_rel, _lib.ptr(batch),
+                                  batch.stride(0), _lib.ptr(loss), _lib.ptr(pos), _lib.ptr(neg), _lib.ptr(grad_rows),
+                                  _lib.ptr(grad_r), _lib.ptr(ws), ws_bytes, _lib.current_stream()))
+    return loss, pos, neg, grad_rows, grad_r, ws_flag(ws)
+
+
+class _CfkgLoss(torch.autograd.Function):
+    """loss = -(sum_b log sigmoid(pos_b) + sum_b log sigmoid(-neg_b)) of the CFKG KG phase with its whole backward from the same
+    launch (csrc/cfkg.hip); backward scatters the batch's gradient rows into the dense x gradient with pea_rows_scatter_sum
+    (fixed order) and hands the relation gradient out as the launch left it.  Reference: experiments/cfkg_solver_bpr.py:95-106
+    under loss.backward()."""
+
+    @staticmethod
+    def forward(ctx, batch, need_grad, x, r):
+        loss, _, _, grad_rows, grad_r, flag = cfkg_train_raw(x, r, batch, need_grad)
+        _defer_error(flag, 'index out of range in KG quadruples')
+        if need_grad:
+            ctx.node_ids = batch[:, :3].reshape(-1).contiguous()
+            ctx.grads = (grad_rows, grad_r)
+            ctx.shape = tuple(x.shape)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        grad_rows, grad_r = ctx.grads
+        dx = dr = None
+        if ctx.needs_input_grad[2]:
+            dx = _scatter_dense(ctx.node_ids, grad_rows * g, *ctx.shape)
+        if ctx.needs_input_grad[3]:
+            dr = grad_r * g
+        return None, None, dx, dr
+
+
+def cfkg_loss(x, r, batch):
+    """Differentiable CFKG kg_loss (models/cfkg.py) of the int64 [B, >= 4] rows (h, t+, t-, rel) of `batch`, forward and backward
+    in HIP; backward() gives dense gradients for x [N, E] and r [R, E].  With grad disabled, or when no input requires grad,
+    only the forward runs.  A row with an id out of range contributes nothing and raises IndexError at the next
+    check_pending_errors().  cfkg_supported(E, R, B) must hold."""
+    if x.dim() != 2 or r.dim() != 2 or not cfkg_supported(x.shape[1], r.shape[0], batch.shape[0]):
+        raise ValueError('cfkg_loss: width (a multiple of 4 in 4..128), relations (1..%d) or batch size (3 B <= %d) not supported'
+                         % (_lib.CFKG_MAX_REL, ROWS_SCATTER_MAX))
+    need_grad = torch.is_grad_enabled() and any(t.requires_grad for t in (x, r))
+    return _CfkgLoss.apply(batch, need_grad, x, r)
+
+
 # ---- HeRec (csrc/herec.hip; reference models/herec.py, experiments/herec_solver_bpr.py:108-121)
 def herec_supported(dim, num_tables, batch_size=0):
     """Whether herec_mse_loss / herec_table take this width and number of metapath tables (include/peahip.h,

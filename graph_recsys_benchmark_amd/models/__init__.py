@@ -8,7 +8,8 @@ from .ngcf import NGCFRecsysModel
 from .metapath2vec import MetaPath2Vec
 from .walk import WalkBasedRecsysModel
 from .herec import HeRecRecsysModel
+from .cfkg import CFKGRecsysModel
 
 __all__ = ['GraphRecsysModel', 'PEABaseChannel', 'PEABaseRecsysModel', 'PEAGATChannel', 'PEAGATRecsysModel',
            'PEAGCNChannel', 'PEAGCNRecsysModel', 'PEASageChannel', 'PEASageRecsysModel', 'KGATRecsysModel', 'KGCNRecsysModel',
-           'NGCFRecsysModel', 'MetaPath2Vec', 'WalkBasedRecsysModel', 'HeRecRecsysModel']
+           'NGCFRecsysModel', 'MetaPath2Vec', 'WalkBasedRecsysModel', 'HeRecRecsysModel', 'CFKGRecsysModel']

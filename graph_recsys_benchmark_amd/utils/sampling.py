@@ -3,6 +3,7 @@ seeds (`random.seed / np.random.seed / torch.manual_seed`, reference solvers.py:
 
     cf_negative_sampling   graph_recsys_benchmark/datasets/movielens.py:879-997 (BPR branch :920-940, shuffle :994-997)
                            (Yelp twin: datasets/yelp.py:746-760)
+    kg_negative_sampling   graph_recsys_benchmark/datasets/movielens.py:861-877 (the KG quadruples CFKG trains on)
     generate_candidates    graph_recsys_benchmark/solvers.py:21-31
     entity_aware_row       graph_recsys_benchmark/datasets/movielens.py:1147-1181 (the six entity columns of a row)
 
@@ -49,6 +50,27 @@ def cf_negative_sampling(dataset):
         raise NotImplementedError('entity_aware=True needs dataset.iid_feat_nids / uid_feat_nids / nid2e_dict '
                                   '(built by the reference\'s dataset preprocessing); attach them to the dataset')
     train_data_t = torch.from_numpy(train_data_np).long()
+    shuffle_idx = torch.randperm(train_data_t.shape[0])
+    dataset.train_data = train_data_t[shuffle_idx]
+    dataset.train_data_length = train_data_t.shape[0]
+    return dataset.train_data
+
+
+def kg_negative_sampling(dataset):
+    """KG training quadruples: every edge of every relation of dataset.edge_index_nps as (h, t+), one uniformly drawn node as
+    the negative tail (ONE np.random.randint over all edges) and the relation's edge_type_dict id, then a torch.randperm
+    shuffle.  Sets dataset.train_data / train_data_length like the reference and returns the int64 [E, 4] tensor
+    (h, t+, t-, rel).  A dataset without edge_type_dict gets the types the reference's dataset builds: enumerate over the keys
+    of edge_index_nps (datasets/movielens.py:329)."""
+    type_of = getattr(dataset, 'edge_type_dict', None)
+    if type_of is None:
+        type_of = {name: k for k, name in enumerate(dataset.edge_index_nps.keys())}
+    pairs = [(edge_index, np.ones((edge_index.shape[1], 1)) * type_of[edge_type])
+             for edge_type, edge_index in dataset.edge_index_nps.items()]
+    pos_np = np.hstack([p[0] for p in pairs]).T
+    r_np = np.vstack([p[1] for p in pairs])
+    neg_t_np = np.random.randint(low=0, high=dataset.num_nodes, size=(pos_np.shape[0], 1))
+    train_data_t = torch.from_numpy(np.hstack([pos_np, neg_t_np, r_np])).long()
     shuffle_idx = torch.randperm(train_data_t.shape[0])
     dataset.train_data = train_data_t[shuffle_idx]
     dataset.train_data_length = train_data_t.shape[0]
