@@ -343,8 +343,8 @@ AGG_DEGREES = (0, 1, 3, 4, 5, 31, 32, 33, 63, 64, 65, 127, 128, 129, 200, 511, 5
 _DEGREE_GRAPH = {}
 
 
-def degree_graph(seed=5, n_fill=2000):
-    """COO [2, E] int64 graph in which every degree of AGG_DEGREES occurs as an in-degree AND as an out-degree (so a relation
+def degree_graph(seed=5, n_fill=2000, degrees=None):
+    """COO [2, E] int64 graph in which every degree of `degrees` (default AGG_DEGREES) occurs as an in-degree AND as an out-degree (so a relation
     and its reverse both hold every row form), built from stars between four blocks of special nodes and `n_fill` filler nodes:
 
         dst_lone[q]  in-degree d_q, no out-edge          src_lone[q]  out-degree d_q, no in-edge (the S pass's `lone` rows)
@@ -354,16 +354,23 @@ def degree_graph(seed=5, n_fill=2000):
     d_q runs over the non-zero degrees.  One of the two rows of every degree >= 5 carries a duplicated edge; the filler nodes
     carry random edges among themselves (some duplicated) and a few self loops, and stay far below 1100 edges on either side.
     Self loops sit on filler nodes only, so the special rows keep their degree whether a plan drops the loops (GAT, GCN) or
-    keeps them (SAGE).  Edges are shuffled.  Returns a dict: n, edge_index, blocks (name -> node ids), degrees (d_q)."""
-    key = (seed, n_fill)
+    keeps them (SAGE).  Edges are shuffled.  Returns a dict: n, edge_index, blocks (name -> node ids), degrees (d_q).
+
+    `degrees`: another degree list (part of the cache key; the default graph does not depend on it).  A degree that AGG_DEGREES
+    does not hold gets its stars in the `dst` and `src` blocks only: the two `lone` blocks exist for the aggregation backward's
+    S pass and keep the first len(lone) degrees of the list, so blocks['dst_lone'][q] and blocks['dst'][q] still share d_q."""
+    degrees = AGG_DEGREES if degrees is None else tuple(degrees)
+    key = (seed, n_fill) if degrees == AGG_DEGREES else (seed, n_fill, degrees)
     if key in _DEGREE_GRAPH:
         return _DEGREE_GRAPH[key]
     rng = np.random.default_rng(seed)
-    degs = [d for d in AGG_DEGREES if d > 0]
+    degs = [d for d in degrees if d > 0 and d in AGG_DEGREES] + [d for d in degrees if d > 0 and d not in AGG_DEGREES]
+    n_lone = sum(d in AGG_DEGREES for d in degs)
     blocks, at = {'fill': np.arange(n_fill)}, n_fill
     for name in ('dst_lone', 'dst', 'src_lone', 'src'):
-        blocks[name] = np.arange(at, at + len(degs))
-        at += len(degs)
+        size = n_lone if name.endswith('lone') else len(degs)
+        blocks[name] = np.arange(at, at + size)
+        at += size
     blocks['isolated'] = np.arange(at, at + 4)
     n = at + 4
     src, dst = [], []
@@ -377,9 +384,11 @@ def degree_graph(seed=5, n_fill=2000):
         dst.append(me if incoming else other)
 
     for q, d in enumerate(degs):
-        star(blocks['dst_lone'][q], d, q % 2 == 0, True)
+        if q < n_lone:
+            star(blocks['dst_lone'][q], d, q % 2 == 0, True)
         star(blocks['dst'][q], d, q % 2 == 1, True)
-        star(blocks['src_lone'][q], d, q % 2 == 0, False)
+        if q < n_lone:
+            star(blocks['src_lone'][q], d, q % 2 == 0, False)
         star(blocks['src'][q], d, q % 2 == 1, False)
         star(blocks['dst'][q], 2, False, False)
         star(blocks['src'][q], 2, False, True)
@@ -921,3 +930,290 @@ def kg_conv_reference(kind, dtype, scale=0.3):
     grads = {'x': x.grad.numpy().astype(np.float64)}
     grads.update({k: v.grad.numpy().astype(np.float64) for k, v in p.items()})
     return out.detach().numpy(), grads
+
+
+# ------------------------------------------------------------------------------------------------------------
+# the edge softmax's and the KG attention maps' matrix (csrc/kg_attention.hip: es_rows / es_merge / es_finish / kg_types):
+# tests/test_gpu_es_matrix.py runs every case on the GPU, tests/test_es_matrix_cpu.py checks the graph, the cell list, the
+# float32 headroom of every case and the comparison itself without one
+# ------------------------------------------------------------------------------------------------------------
+# a long item runs 4 edges per subgroup per trip: one trip of the scalar modes (G = 1) is 256 edges
+ES_DEGREES = AGG_DEGREES + (255, 256, 257)
+ES_T = 37                                       # rows of the relation table r; edge types in (-(T-1) .. T-1)
+ES_MODES = ('kgat', 'kgcn')
+ES_FULL_WIDTHS = (16, 32, 64, 128, 256)         # emb == 4 G: every lane holds four columns
+ES_IDLE_WIDTHS = (4, 12, 20, 24, 36, 40, 96, 132, 160)      # emb < 4 G: lanes with `active` false (4 and 12: G = 4)
+ES_KNOB_WIDTHS = (12, 32, 40, 96, 160)          # one per G, run again on every other plan shape
+ES_RTOL, ES_ATOL = 2e-5, 1e-9                   # the per-edge rule of tests/test_gpu_kg_attention.py
+ES_LOGITS = {'spread3': (0.0, 3.0), 'spread30': (0.0, 30.0), 'plus1e4_spread3': (1e4, 3.0), 'minus1e4_spread30': (-1e4, 30.0)}
+ES_CELLS = [(mode, G, lanes) for mode in ES_MODES for G in (4, 8, 16, 32, 64) for lanes in ('full', 'idle')]
+_ES = {}
+
+
+def es_graph():
+    """degree_graph(degrees=ES_DEGREES): 2082 nodes, 17,444 edges.  Its 40 self loops and its duplicated edges stay: the KG and
+    softmax plans carry no self-loop flag, so every COO edge takes part."""
+    return degree_graph(degrees=ES_DEGREES)
+
+
+def es_cell(mode, emb):
+    """(mode, G, 'full' | 'idle')"""
+    return mode, agg_lanes(emb), 'full' if emb == 4 * agg_lanes(emb) else 'idle'
+
+
+def es_case_id(mode, emb, n_types=None):
+    return '%s-G%d-%s-emb%d' % (es_cell(mode, emb) + (emb,)) + ('' if n_types is None else '-T%d' % n_types)
+
+
+def check_es_cells(full=ES_FULL_WIDTHS, idle=ES_IDLE_WIDTHS):
+    """Raises with the name of the first cell of ES_CELLS that no width fills (and when a width stands in the wrong list)"""
+    for w in full:
+        assert es_cell('kgat', w)[2] == 'full', 'width %d has idle lanes' % w
+    for w in idle:
+        assert es_cell('kgat', w)[2] == 'idle', 'width %d has no idle lane' % w
+    cells = {es_cell(mode, w) for mode in ES_MODES for w in tuple(full) + tuple(idle)}
+    for mode, G, lanes in ES_CELLS:
+        assert (mode, G, lanes) in cells, 'no width fills the cell (%s, G = %d) with %s lanes' % (mode, G, lanes)
+
+
+def es_csr_order(index):
+    """CSR slot -> COO edge of a plan without source slices (a stable sort by the row the edge belongs to)"""
+    return np.argsort(index, kind='stable')
+
+
+def es_types(n_types):
+    """int64 [E] per COO edge, drawn from (-(T-1) .. T-1); the copies of a duplicated edge get different types (T > 1), so a type
+    read through a wrong `eid` changes the score of one of them"""
+    key = ('types', n_types)
+    if key not in _ES:
+        ei = es_graph()['edge_index']
+        rng = np.random.default_rng(4100 + n_types)
+        t = rng.integers(-(n_types - 1), n_types, size=ei.shape[1]).astype(np.int64)
+        if n_types > 1:
+            t[:4] = (n_types - 1, -(n_types - 1), 0, -1)
+            seen = {}
+            for e in range(ei.shape[1]):
+                used = seen.setdefault((int(ei[0, e]), int(ei[1, e])), set())
+                while int(t[e]) in used:
+                    t[e] = (t[e] + n_types) % (2 * n_types - 1) - (n_types - 1)      # the next type, wrapping inside the range
+                used.add(int(t[e]))
+        t.setflags(write=False)
+        _ES[key] = t
+    return _ES[key]
+
+
+def es_logits(name):
+    """float32 [E] per COO edge: offset + spread * N(0, 1) of ES_LOGITS[name] (drawn per edge: the copies of a duplicate differ)"""
+    key = ('logits', name)
+    if key not in _ES:
+        off, spread = ES_LOGITS[name]
+        e = es_graph()['edge_index'].shape[1]
+        a = (off + spread * np.random.default_rng(4200 + sorted(ES_LOGITS).index(name)).standard_normal(e)).astype(np.float32)
+        a.setflags(write=False)
+        _ES[key] = a
+    return _ES[key]
+
+
+def es_index(side):
+    """the softmax's `index`: 'dst' = the destination of every edge, 'src' = its source (the rows of the reversed relation)"""
+    return es_graph()['edge_index'][1 if side == 'dst' else 0]
+
+
+def es_mask(side):
+    """bool [E]: the edges that get -inf.  Rows of 3 to 199 edges: every third edge in CSR order from the first one on; rows of
+    200 edges and more: their first third in CSR order, which holds whole trips of a lane and, at PEA_CHUNK=64, whole chunks.
+    Never a whole row, nothing in rows below 3 edges."""
+    key = ('mask', side)
+    if key not in _ES:
+        index = es_index(side)
+        order = es_csr_order(index)
+        deg = np.bincount(index, minlength=es_graph()['n'])
+        start = np.concatenate([[0], np.cumsum(deg)[:-1]])
+        k = np.arange(index.size) - start[index[order]]             # position of slot s in its row
+        d = deg[index[order]]
+        m = np.zeros(index.size, bool)
+        m[order] = ((d >= 3) & (d < 200) & (k % 3 == 0)) | ((d >= 200) & (k < d // 3))
+        m.setflags(write=False)
+        _ES[key] = m
+    return _ES[key]
+
+
+def es_masked_logits(side):
+    """es_logits('spread3') with -inf on es_mask(side)"""
+    a = es_logits('spread3').copy()
+    a[es_mask(side)] = -np.inf
+    return a
+
+
+def es_grad_out():
+    """float32 [E]: the output gradient of every softmax backward case"""
+    if 'gout' not in _ES:
+        g = np.random.default_rng(4300).standard_normal(es_graph()['edge_index'].shape[1]).astype(np.float32)
+        g.setflags(write=False)
+        _ES['gout'] = g
+    return _ES['gout']
+
+
+def es_softmax_reference(logits, index, dtype=None):
+    """(y, grad of the logits under es_grad_out()) as float64 numpy: oracle.pyg_restatement.segment_softmax and torch autograd on it
+    in `dtype` (default float64; float32: the same operation at the kernels' precision)"""
+    import torch
+    from oracle.pyg_restatement import segment_softmax
+    dtype = dtype or torch.float64
+    s = torch.from_numpy(np.array(logits)).to(dtype).requires_grad_(True)
+    y = segment_softmax(s, torch.from_numpy(np.ascontiguousarray(index)), es_graph()['n'])
+    y.backward(torch.from_numpy(np.array(es_grad_out())).to(dtype))
+    return y.detach().numpy().astype(np.float64), s.grad.numpy().astype(np.float64)
+
+
+def es_softmax_case(name, side, dtype=None):
+    """es_softmax_reference of es_logits(name) (name 'masked': es_masked_logits(side)) over es_index(side).  Cached; do not modify."""
+    import torch
+    key = ('softmax', name, side, str(dtype or torch.float64))
+    if key not in _ES:
+        logits = es_masked_logits(side) if name == 'masked' else es_logits(name)
+        y, g = es_softmax_reference(logits, es_index(side), dtype)
+        y.setflags(write=False)
+        g.setflags(write=False)
+        _ES[key] = (y, g)
+    return _ES[key]
+
+
+def f64_alpha(mode, x, proj, r, ei, ea, chunk=1 << 21, reversed_zero_sign=1.0, dtype=None):
+    """The reference's alpha (experiments/kgat_solver_bpr.py:313-320, kgcn_solver_bpr.py:313-319) in float64, chunked over edges: a
+    copy of tests/test_gpu_kg_attention.py: f64_alpha with the dtype left open (float32: the torch restatement at the kernels'
+    precision).  reversed_zero_sign=-1 gives the 'fixed' sign rule for the type-0 edges of the second half of the edge list (the
+    flipped half of a KG input), which the reference does NOT apply."""
+    import torch
+    dtype = dtype or torch.float64
+    x64, r64 = x.to(dtype), r.to(dtype)
+    xp = x64 @ proj.to(dtype) if mode == 'kgat' else None
+    t = ea[:, 0]
+    signs = torch.sign(t).to(dtype)
+    signs[signs == 0] = 1
+    if reversed_zero_sign != 1.0:
+        half = ei.shape[1] // 2
+        flip0 = torch.zeros_like(signs, dtype=torch.bool)
+        flip0[half:] = t[half:] == 0
+        signs[flip0] = reversed_zero_sign
+    out = torch.empty(ei.shape[1], dtype=dtype, device=x.device)
+    for b in range(0, ei.shape[1], chunk):
+        sl = slice(b, b + chunk)
+        trans = r64[t[sl].abs()] * signs[sl].view(-1, 1)
+        if mode == 'kgat':
+            out[sl] = (xp[ei[1, sl]] * torch.tanh(xp[ei[0, sl]] + trans)).sum(-1)
+        else:
+            out[sl] = (x64[ei[1, sl]] * trans).sum(-1)
+    return out
+
+
+def es_kg_inputs(emb, n_types):
+    """float32 CPU tensors x [n, emb], proj [emb, emb], r [T, emb] at the scale 0.3 (64 / emb)^0.5 of
+    tests/test_gpu_kg_attention.py::test_kg_map_other_widths (scores of spread ~1 at every width)"""
+    import torch
+    key = ('kg_in', emb, n_types)
+    if key not in _ES:
+        g = torch.Generator().manual_seed(4400 + 10 * emb + n_types)
+        scale = 0.3 * (64.0 / emb) ** 0.5
+        n = es_graph()['n']
+        _ES[key] = (torch.randn(n, emb, generator=g) * scale, torch.randn(emb, emb, generator=g) / emb ** 0.5,
+                    torch.randn(n_types, emb, generator=g) * scale)
+    return _ES[key]
+
+
+def es_kg_reference(mode, emb, n_types, dtype=None, wrong=None):
+    """float64 numpy [E]: segment_softmax(f64_alpha(...)) over the destinations of es_graph() with es_types(n_types), computed in
+    `dtype` (default float64).  wrong = 'slot': the type of CSR slot s is edge_type[s] instead of edge_type[eid[s]]; 'last': the
+    last CSR slot of the first 1100-edge row is left out of its row's sum; 'rev0': -r[0] on the type-0 edges of the second half
+    of the edge list.  Cached; do not modify."""
+    import torch
+    from oracle.pyg_restatement import segment_softmax
+    dtype = dtype or torch.float64
+    key = ('kg_ref', mode, emb, n_types, str(dtype), wrong)
+    if key in _ES:
+        return _ES[key]
+    g = es_graph()
+    n, ei = g['n'], torch.from_numpy(g['edge_index'])
+    x, proj, r = es_kg_inputs(emb, n_types)
+    t = np.array(es_types(n_types))
+    order = es_csr_order(g['edge_index'][1])
+    if wrong == 'slot':
+        t[order] = es_types(n_types)[:order.size]
+    alpha = f64_alpha(mode, x, proj, r, ei, torch.from_numpy(t).view(-1, 1), dtype=dtype,
+                      reversed_zero_sign=-1.0 if wrong == 'rev0' else 1.0)
+    if wrong == 'last':
+        from oracle.pyg_restatement import scatter_add, scatter_max
+        deg = np.bincount(g['edge_index'][1], minlength=n)
+        row = int(np.flatnonzero(deg == 1100)[0])
+        last = int(order[np.cumsum(deg)[row] - 1])
+        ex = (alpha - scatter_max(alpha, ei[1], n)[ei[1]]).exp()
+        den = scatter_add(ex, ei[1], n)
+        den[row] -= ex[last]
+        y = ex / (den[ei[1]] + 1e-16)
+    else:
+        y = segment_softmax(alpha, ei[1], n)
+    y = y.numpy().astype(np.float64)
+    y.setflags(write=False)
+    _ES[key] = y
+    return y
+
+
+def es_rule_fraction(got, want):
+    """largest |got - want| / (2e-5 |want| + 1e-9) over the edges: the per-edge rule as a used fraction (<= 1 passes); nan where
+    either side holds a non-finite value, which no `<=` accepts"""
+    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
+    if not (np.isfinite(got).all() and np.isfinite(want).all()):
+        return float('nan')
+    return float((np.abs(got - want) / (ES_RTOL * np.abs(want) + ES_ATOL)).max())
+
+
+def es_bwd_fraction(got, want, y, g_max):
+    """the same for the softmax backward's bound of tests/test_gpu_kg_attention.py: 2e-5 |g64| + 1e-6 y max|g| + 1e-9"""
+    got, want, y = np.asarray(got, np.float64), np.asarray(want, np.float64), np.asarray(y, np.float64)
+    if not (np.isfinite(got).all() and np.isfinite(want).all()):
+        return float('nan')
+    return float((np.abs(got - want) / (ES_RTOL * np.abs(want) + 1e-6 * y * g_max + ES_ATOL)).max())
+
+
+def es_plan_bins(deg, chunk=512, short_deg=32):
+    """What csrc/plan.hip makes of these degrees without source slices, written down by hand: the six leading fields of
+    pea_plan_relation_info, and `chunks`: {degree of a hub row: [length of each of its chunks]} (nch = ceil(deg / chunk) chunks of
+    ceil(deg / nch) edges, the last one shorter: 513 -> 257 + 256, 1100 -> 367 + 367 + 366)"""
+    deg = np.asarray(deg)
+    hub = (deg > short_deg) & (deg > chunk)
+    chunks = {}
+    for d in sorted(set(int(v) for v in deg[hub])):
+        nch = -(-d // chunk)
+        ln = -(-d // nch)
+        chunks[d] = [min(ln, d - c * ln) for c in range(nch)]
+    slots = int(sum(len(chunks[int(d)]) for d in deg[hub]))
+    return dict(edges=int(deg.sum()), max_degree=int(deg.max()), short_rows=int((deg <= short_deg).sum()),
+                long_items=int(((deg > short_deg) & (deg <= chunk)).sum()) + slots, hub_rows=int(hub.sum()), hub_slots=slots,
+                chunks=chunks)
+
+
+ES_SLICES = 8                # one phase of 8 source slices (plan.hip: S = 8 x phases)
+ES_SLICE_MIN_SEGMENT = 32    # common.h: kSliceMinSegment; rows of >= S x this many edges (and more than `chunk`) are cut per slice
+
+
+def es_sliced_bins(ei, n, chunk=512, short_deg=32, slices=ES_SLICES):
+    """The same for a source-sliced plan of `slices` = 8 slices (one phase): a row of more than `chunk` and at least 8 x 32 edges is
+    cut into its per-slice segments (slice of an edge = (src - min src) * S // span), each segment into equalised chunks; the
+    chunks are laid out four per workgroup and slice, padded with `slot == -2` items to whole rounds of 8 x 4, ahead of every
+    other item.  Also returns `sliced_degrees`, the degrees of the rows that were cut."""
+    src, dst = ei
+    deg = np.bincount(dst, minlength=n)
+    smin, span = int(src.min()), int(src.max()) - int(src.min()) + 1
+    sl = (src - smin) * slices // span
+    cut = (deg > short_deg) & (deg > chunk) & (deg >= slices * ES_SLICE_MIN_SEGMENT)
+    hub = (deg > short_deg) & (deg > chunk) & ~cut
+    plain = es_plan_bins(np.where(cut, 0, deg), chunk, short_deg)
+    per_slice, slots = np.zeros(slices, np.int64), 0
+    for row in np.flatnonzero(cut):
+        seg = np.bincount(sl[dst == row], minlength=slices)
+        per_slice += -(-seg // chunk)
+        slots += int((-(-seg // chunk)).sum())
+    rounds = int((-(-per_slice // 4)).max()) if cut.any() else 0
+    return dict(edges=int(deg.sum()), max_degree=int(deg.max()), short_rows=int((deg <= short_deg).sum()),
+                long_items=plain['long_items'] + rounds * slices * 4, hub_rows=int(hub.sum() + cut.sum()),
+                hub_slots=plain['hub_slots'] + slots, sliced_degrees=sorted(int(d) for d in deg[cut]), pad_items=rounds * slices * 4 - slots)
