@@ -14,6 +14,10 @@
 //                 ids coalesced, the 64/G subgroups take them round-robin, partial states are merged
 //                 with xor shuffles
 //   hub rows    : chunks write (m, s, acc) records; a merge kernel folds them in chunk order
+//
+// Defined once, used by every kernel below: the 4-edge softmax update and the subgroup fold (agg_common.h: SoftV::batch4,
+// SoftV::fold), the masked logit, the accumulate of the other modes and its fold, and the row closure RowEnd (what a lane
+// loads about its destination row, the self loop, the partial record of a hub chunk, finish_row).
 #include <algorithm>
 #include <cstdlib>
 
@@ -46,6 +50,129 @@ __device__ __forceinline__ void finish_row(const AggGroup &P, int row, int c4, i
     st4(P.out + (size_t)row * P.ld_out + c4, o);
 }
 
+// The logit of one edge slot, natural units; a slot without an edge gets -inf.  Computed for every slot, then selected:
+// no branch, 2^(-inf) = 0.
+__device__ __forceinline__ float masked_logit(bool ok, float a, float a_d, float slope) {
+    const float z = leaky(a + a_d, slope);
+    return ok ? z : -INFINITY;
+}
+
+// One edge slot of the modes without a softmax.  a: dinv of the source (GCN) / the edge's weight, 0 for a slot without an
+// edge (WSUM); di: dinv of the row (GCN).
+template <int MODE, int V4>
+__device__ __forceinline__ void accumulate(float4 (&sum)[V4], bool ok, float a, float di, const float4 (&h)[V4]) {
+    if (MODE == AGG_GCN) {
+        const float w = ok ? a * di : 0.f;
+#pragma unroll
+        for (int v = 0; v < V4; ++v) sum[v] = fma4(w, h[v], sum[v]);
+    } else if (MODE == AGG_WSUM) {
+#pragma unroll
+        for (int v = 0; v < V4; ++v) sum[v] = fma4(a, h[v], sum[v]);
+    } else if (ok) {
+#pragma unroll
+        for (int v = 0; v < V4; ++v) sum[v] = add4(sum[v], h[v]);
+    }
+}
+
+// SoftV::fold for those sums
+template <int G, int V4>
+__device__ __forceinline__ void fold_sum(float4 (&sum)[V4]) {
+#pragma unroll
+    for (int off = G; off < kWave; off <<= 1) {
+#pragma unroll
+        for (int v = 0; v < V4; ++v) sum[v] = add4(sum[v], shfl_xor4(sum[v], off));
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// row closure: what a lane keeps of its destination row, and how the row (or its hub chunk) ends
+// ------------------------------------------------------------------------------------------------
+// The lane holds V4 float4 chunks of the row, chunk v at column c0 + cs * v.  Thin lanes (V4 = 1): one chunk, heads of
+// P.F / 4 lanes (HT > 0: that width at compile time).  Fat lanes (V4 > 1): heads of HT lanes, cs = 4 * HT.
+template <int MODE, int HT, int V4>
+struct RowEnd {
+    int lane, pos, F4, c0, cs;
+    bool pow2;
+    float a_d = 0.f, di = 0.f, slope = 0.f;
+    float4 att_s[V4], h_self[V4];
+
+    __device__ __forceinline__ RowEnd(const AggGroup &P, int lane_, int sl, int c0_) : lane(lane_), c0(c0_) {
+        F4 = V4 == 1 ? P.F / 4 : HT;
+        pos = sl % F4;
+        cs = 4 * F4;
+        pow2 = (F4 & (F4 - 1)) == 0;
+    }
+    __device__ __forceinline__ const float *self_row(const AggGroup &P, int row) const {
+        return row_at(P.feat_self + c0, row, P.ld_self);
+    }
+    // h . w summed over the head (fat lanes add their chunks to 0.f first, as their kernel always has)
+    __device__ __forceinline__ float head_dot(const float4 (&h)[V4], const float4 (&w)[V4]) const {
+        float d = V4 == 1 ? dot4(h[0], w[0]) : 0.f + dot4(h[0], w[0]);
+#pragma unroll
+        for (int v = 1; v < V4; ++v) d += dot4(h[v], w[v]);
+        return head_sum<HT>(d, lane, pos, F4, pow2);
+    }
+    // the prologue of a row
+    __device__ __forceinline__ void load(const AggGroup &P, int row) {
+        slope = P.neg_slope;  // kept in a register: read inside the edge loop it became a scalar load + wait per edge
+        if (MODE == AGG_GAT) {
+            float4 att_d[V4];
+#pragma unroll
+            for (int v = 0; v < V4; ++v) {
+                att_s[v] = ld4(P.att_src + c0 + cs * v);
+                h_self[v] = ld4(self_row(P, row) + cs * v);
+                att_d[v] = ld4(P.att_dst + c0 + cs * v);
+            }
+            a_d = head_dot(h_self, att_d);
+        } else if (MODE == AGG_GCN) {
+            di = P.dinv_self[row];
+        }
+    }
+    // hub chunk: the partial record, chunks in plain column order (the merge kernel is layout-agnostic), (m, s) by the
+    // head's first lane
+    __device__ __forceinline__ void partial(const AggGroup &P, int slot, SoftV<V4> &st, const float4 (&sum)[V4]) const {
+        const int nk = P.W / P.F;
+        float *rec = P.partial + (size_t)slot * (size_t)(P.W + 2 * nk);
+#pragma unroll
+        for (int v = 0; v < V4; ++v) st4(rec + c0 + cs * v, MODE == AGG_GAT ? st.chunk(v) : sum[v]);
+        if (MODE == AGG_GAT && c0 % P.F == 0) {
+            const int kk = 2 * (c0 / P.F);
+            rec[P.W + kk] = st.m;
+            rec[P.W + kk + 1] = st.s;
+        }
+    }
+    // the self loop (every lane: the head sum is cross-lane), then finish_row per chunk by the lanes that `store`
+    // (stats are written by the head's first chunk).  LATE: no load() went before, the self loop loads what it needs (the
+    // hub merge: nothing of the row is live across its record loop, nothing is read for a row without a self loop).
+    template <bool LATE = false>
+    __device__ __forceinline__ void close(const AggGroup &P, int row, int deg, SoftV<V4> &st, float4 (&sum)[V4], bool store) {
+        if (P.self_loop) {
+            if (LATE) load(P, row);
+            if (MODE == AGG_GAT) {
+                st.push(leaky(head_dot(h_self, att_s) + a_d, slope), h_self);
+            } else if (MODE == AGG_GCN) {
+#pragma unroll
+                for (int v = 0; v < V4; ++v) sum[v] = fma4(di * di, ld4(self_row(P, row) + cs * v), sum[v]);
+            }
+        }
+        if (!store) return;
+        Soft one;
+        one.m = st.m;
+        one.s = st.s;
+#pragma unroll
+        for (int v = 0; v < V4; ++v) {
+            one.acc = st.chunk(v);
+            finish_row<MODE>(P, row, c0 + cs * v, deg, one, sum[v]);
+        }
+    }
+};
+
+template <int V4>
+__device__ __forceinline__ void zero(float4 (&sum)[V4]) {
+#pragma unroll
+    for (int v = 0; v < V4; ++v) sum[v] = make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
 // ------------------------------------------------------------------------------------------------
 // short rows: one G-lane subgroup per destination row
 // ------------------------------------------------------------------------------------------------
@@ -60,24 +187,13 @@ __device__ __forceinline__ void short_rows(const AggGroup &P, const int blk) {
     const int beg = P.rowptr[row];
     const int end = valid ? P.rowptr[row + 1] : beg;
     const float *feat = P.feat + c4;
-    const float *feat_self = P.feat_self + c4;
 
     Soft st;
     st.init();
-    float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
-    const int lane = (int)threadIdx.x % kWave;
-    const int F4 = P.F / 4, pos = sl % F4;
-    const bool pow2 = (F4 & (F4 - 1)) == 0;
-    float a_d = 0.f, di = 0.f;
-    const float slope = P.neg_slope;  // kept in a register: read inside the edge loop it became a scalar load + wait per edge
-    float4 att_s = make_float4(0.f, 0.f, 0.f, 0.f), h_self = att_s;
-    if (MODE == AGG_GAT) {
-        att_s = ld4(P.att_src + c4);
-        h_self = ld4(row_at(feat_self, row, P.ld_self));
-        a_d = head_sum<F4T>(dot4(h_self, ld4(P.att_dst + c4)), lane, pos, F4, pow2);
-    } else if (MODE == AGG_GCN) {
-        di = P.dinv_self[row];
-    }
+    float4 sum[1];
+    zero(sum);
+    RowEnd<MODE, F4T, 1> R(P, (int)threadIdx.x % kWave, sl, c4);
+    R.load(P, row);
     // the subgroups of a wave walk rows of different length: keep every lane in the loop (the head sums are
     // cross-lane) and mask finished rows instead
     int len = end - beg;
@@ -88,8 +204,8 @@ __device__ __forceinline__ void short_rows(const AggGroup &P, const int blk) {
     for (int t = 0; t < len; t += U) {
         int jj[U];
         bool ok[U];
-        float4 h[U];
-        float a[U];
+        float4 h[U][1];
+        float a[U] = {};
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int e = beg + t + u;
@@ -98,59 +214,45 @@ __device__ __forceinline__ void short_rows(const AggGroup &P, const int blk) {
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            h[u] = ld4(row_at(feat, jj[u], P.ld_feat));
+            h[u][0] = ld4(row_at(feat, jj[u], P.ld_feat));
             if (MODE == AGG_GCN) a[u] = P.dinv[jj[u]];
             if (MODE == AGG_WSUM) a[u] = ok[u] ? P.edge_w[P.eid[beg + t + u]] : 0.f;
         }
         if (MODE == AGG_GAT) {
 #pragma unroll
-            for (int u = 0; u < U; ++u) a[u] = head_sum<F4T>(dot4(h[u], att_s), lane, pos, F4, pow2);
+            for (int u = 0; u < U; ++u) a[u] = R.head_dot(h[u], R.att_s);
             float e[U];
-            float mx = -INFINITY;                                            // largest logit of the batch, natural units
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const float z = leaky(a[u] + a_d, slope);                   // computed for every slot, then selected:
-                e[u] = ok[u] ? z : -INFINITY;                                // no branch, 2^(-inf) = 0
-                mx = fmaxf(mx, e[u]);
-            }
-            const float mn = fmaxf(st.m, mx * kLog2e);                       // running max, log2 domain (finite)
-            const float fs = __builtin_amdgcn_exp2f(st.m - mn);
-            st.m = mn;
-            st.s *= fs;
-            st.acc = scale4(st.acc, fs);
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const float p = __builtin_amdgcn_exp2f(fmaf(e[u], kLog2e, -mn));  // 0 for the masked slots
-                st.s += p;
-                st.acc = fma4(p, h[u], st.acc);
-            }
+            for (int u = 0; u < U; ++u) e[u] = masked_logit(ok[u], a[u], R.a_d, R.slope);
+            st.batch4(e, h);
         } else {
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
-                if (MODE == AGG_GCN) {
-                    sum = fma4(ok[u] ? a[u] * di : 0.f, h[u], sum);
-                } else if (MODE == AGG_WSUM) {
-                    sum = fma4(a[u], h[u], sum);
-                } else {
-                    if (ok[u]) sum = add4(sum, h[u]);
-                }
-            }
+            for (int u = 0; u < U; ++u) accumulate<MODE>(sum, ok[u], a[u], R.di, h[u]);
         }
     }
-    if (P.self_loop) {
-        if (MODE == AGG_GAT) {
-            const float a = head_sum<F4T>(dot4(h_self, att_s), lane, pos, F4, pow2);
-            st.push(leaky(a + a_d, slope), h_self);
-        } else if (MODE == AGG_GCN) {
-            sum = fma4(di * di, ld4(row_at(feat_self, row, P.ld_self)), sum);
-        }
-    }
-    if (active) finish_row<MODE>(P, row, c4, end - beg, st, sum);
+    R.close(P, row, end - beg, st, sum, active);
 }
 
 // ------------------------------------------------------------------------------------------------
 // long rows and hub chunks: one wave per item
 // ------------------------------------------------------------------------------------------------
+// What follows the gather of an item, thin or fat: fold the subgroup states, then the partial record (hub chunk: the
+// merge kernel finishes the row) or the row's end.
+template <int G, int MODE, int HT, int V4>
+__device__ __forceinline__ void end_item(const AggGroup &P, const LongItem it, RowEnd<MODE, HT, V4> &R, SoftV<V4> &st,
+                                         float4 (&sum)[V4], bool store) {
+    if (MODE == AGG_GAT) {
+        st.template fold<G>();
+    } else {
+        fold_sum<G>(sum);
+    }
+    if (it.slot >= 0) {
+        if (store) R.partial(P, it.slot, st, sum);
+        return;
+    }
+    R.close(P, it.row, it.end - it.beg, st, sum, store);
+}
+
 // HOT: the K most frequent sources of the relation sit in the workgroup's LDS image (K rows x W columns, filled once per
 // workgroup); a CSR entry <= -2 names image row -(j + 2), anything >= 0 is read from memory as before.  Same edges, same
 // order, same values: results are bitwise those of the plain kernel.
@@ -162,28 +264,16 @@ __device__ __forceinline__ void long_item(const AggGroup &P, const LongItem it, 
     const bool active = sl * 4 < P.W;
     const int c4 = active ? sl * 4 : 0;
     const float *feat = P.feat + c4;
-    const float *feat_self = P.feat_self + c4;
-    const int row = it.row;
     const int *col = HOT ? P.hot_col : P.col;
     const int W4 = P.W / 4;
     const int lc = active ? sl : 0;   // this lane's float4 column inside an image row
 
     Soft st;
     st.init();
-    float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
-    const int kk = 2 * (c4 / P.F);
-    const int F4 = P.F / 4, pos = sl % F4;
-    const bool pow2 = (F4 & (F4 - 1)) == 0;
-    float a_d = 0.f, di = 0.f;
-    const float slope = P.neg_slope;  // kept in a register: read inside the edge loop it became a scalar load + wait per edge
-    float4 att_s = make_float4(0.f, 0.f, 0.f, 0.f), h_self = att_s;
-    if (MODE == AGG_GAT) {
-        att_s = ld4(P.att_src + c4);
-        h_self = ld4(row_at(feat_self, row, P.ld_self));
-        a_d = head_sum<F4T>(dot4(h_self, ld4(P.att_dst + c4)), lane, pos, F4, pow2);
-    } else if (MODE == AGG_GCN) {
-        di = P.dinv_self[row];
-    }
+    float4 sum[1];
+    zero(sum);
+    RowEnd<MODE, F4T, 1> R(P, lane, sl, c4);
+    R.load(P, it.row);
     // edges in flight per subgroup: U*NSG gathered rows per wave before the first use
     int src = it.beg + lane < it.end ? col[it.beg + lane] : -1;
     for (int base = it.beg; base < it.end; base += kWave) {
@@ -193,8 +283,8 @@ __device__ __forceinline__ void long_item(const AggGroup &P, const LongItem it, 
         for (int t = 0; t < cnt; t += NSG * U) {
             int jj[U];
             bool ok[U];
-            float4 h[U];
-            float a[U];
+            float4 h[U / 4][4][1];
+            float a[U] = {};
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const int idx = t + u * NSG + sub;
@@ -206,94 +296,45 @@ __device__ __forceinline__ void long_item(const AggGroup &P, const LongItem it, 
             for (int u = 0; u < U; ++u) {
                 if (HOT && jj[u] < 0) {  // image row (ds_read_b128), no memory traffic
                     const int r = -(jj[u] + 2);
-                    h[u] = img[r * W4 + lc];
+                    h[u / 4][u % 4][0] = img[r * W4 + lc];
                     if (MODE == AGG_GCN) a[u] = hot_dinv[r];
                 } else {
-                    h[u] = ld4(row_at(feat, jj[u], P.ld_feat));
+                    h[u / 4][u % 4][0] = ld4(row_at(feat, jj[u], P.ld_feat));
                     if (MODE == AGG_GCN) a[u] = P.dinv[jj[u]];
                 }
                 if (MODE == AGG_WSUM) a[u] = ok[u] ? P.edge_w[P.eid[base + t + u * NSG + sub]] : 0.f;
             }
             if (MODE == AGG_GAT) {
 #pragma unroll
-                for (int u = 0; u < U; ++u) a[u] = head_sum<F4T>(dot4(h[u], att_s), lane, pos, F4, pow2);
-            }
-            if (MODE == AGG_GAT) {
-                // softmax updates in batches of 4 edges (the batch size is part of the arithmetic: it stays 4 whatever
-                // U is, so every variant of the kernel produces the same bits): shared new max, one rescale, 4 weights
+                for (int u = 0; u < U; ++u) a[u] = R.head_dot(h[u / 4][u % 4], R.att_s);
+                // softmax updates in batches of 4 edges, whatever U is (SoftV::batch4)
 #pragma unroll
-                for (int u0 = 0; u0 < U; u0 += 4) {
+                for (int b = 0; b < U / 4; ++b) {
                     float e[4];
-                    float mx = -INFINITY;                                        // largest logit of the batch, natural units
 #pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const float z = leaky(a[u0 + u] + a_d, slope);          // computed for every slot, then selected:
-                        e[u] = ok[u0 + u] ? z : -INFINITY;                       // no branch, 2^(-inf) = 0
-                        mx = fmaxf(mx, e[u]);
-                    }
-                    const float mn = fmaxf(st.m, mx * kLog2e);                   // running max, log2 domain (finite)
-                    const float fs = __builtin_amdgcn_exp2f(st.m - mn);
-                    st.m = mn;
-                    st.s *= fs;
-                    st.acc = scale4(st.acc, fs);
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const float p = __builtin_amdgcn_exp2f(fmaf(e[u], kLog2e, -mn));  // 0 for the masked slots
-                        st.s += p;
-                        st.acc = fma4(p, h[u0 + u], st.acc);
-                    }
+                    for (int u = 0; u < 4; ++u) e[u] = masked_logit(ok[4 * b + u], a[4 * b + u], R.a_d, R.slope);
+                    st.batch4(e, h[b]);
                 }
             } else {
 #pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    if (MODE == AGG_GCN) {
-                        sum = fma4(ok[u] ? a[u] * di : 0.f, h[u], sum);
-                    } else if (MODE == AGG_WSUM) {
-                        sum = fma4(a[u], h[u], sum);
-                    } else {
-                        if (ok[u]) sum = add4(sum, h[u]);
-                    }
-                }
+                for (int u = 0; u < U; ++u) accumulate<MODE>(sum, ok[u], a[u], R.di, h[u / 4][u % 4]);
             }
         }
         src = src_next;
     }
-    // fold the NSG subgroup states (xor butterfly: every lane ends with the same value)
-#pragma unroll
-    for (int off = G; off < kWave; off <<= 1) {
-        if (MODE == AGG_GAT) {
-            const float m2 = __shfl_xor(st.m, off), s2 = __shfl_xor(st.s, off);
-            const float4 a2 = shfl_xor4(st.acc, off);
-            st.merge(m2, s2, a2);
-        } else {
-            sum = add4(sum, shfl_xor4(sum, off));
-        }
-    }
-    if (it.slot >= 0) {  // hub chunk: write the partial record, the merge kernel finishes the row
-        if (sub == 0 && active) {
-            const int nk = P.W / P.F;
-            float *rec = P.partial + (size_t)it.slot * (size_t)(P.W + 2 * nk);
-            if (MODE == AGG_GAT) {
-                st4(rec + c4, st.acc);
-                if (c4 % P.F == 0) {
-                    rec[P.W + kk] = st.m;
-                    rec[P.W + kk + 1] = st.s;
-                }
-            } else {
-                st4(rec + c4, sum);
-            }
-        }
-        return;
-    }
-    if (P.self_loop) {
-        if (MODE == AGG_GAT) {
-            const float a = head_sum<F4T>(dot4(h_self, att_s), lane, pos, F4, pow2);
-            st.push(leaky(a + a_d, slope), h_self);
-        } else if (MODE == AGG_GCN) {
-            sum = fma4(di * di, ld4(row_at(feat_self, row, P.ld_self)), sum);
-        }
-    }
-    if (sub == 0 && active) finish_row<MODE>(P, row, c4, it.end - it.beg, st, sum);
+    end_item<G>(P, it, R, st, sum, sub == 0 && active);
+}
+
+// Long item `item` of a group.  slot == -2 means no work: the padding of the XCD-affine item layout (plan.hip), and here
+// also an index past the group's items.  Wave-uniform.
+__device__ __forceinline__ LongItem item_at(const AggGroup &P, int item) {
+    if (item >= P.n_long) return LongItem{0, 0, 0, -2};
+    return P.long_items[item];
+}
+
+// This wave's item number in group gi, the group of its workgroup (find_group): 4 items per workgroup.
+__device__ __forceinline__ int wave_index(const AggLaunch &L, int gi) {
+    return ((int)blockIdx.x - L.blk_start[gi]) * (kBlock / kWave) + (int)threadIdx.x / kWave;
 }
 
 // One launch per (lane width, head class) of a level: workgroups [0, n_long_blocks) take the long rows and hub chunks
@@ -311,13 +352,9 @@ __global__ __launch_bounds__(kBlock) void agg_rows_kernel(const AggLaunch L) {
     }
     const int gi = find_group(L);
     const AggGroup &P = L.g[gi];
-    const int wave = (int)threadIdx.x / kWave;
-    const int lane = (int)threadIdx.x % kWave;
-    const int item = ((int)blockIdx.x - L.blk_start[gi]) * (kBlock / kWave) + wave;
-    if (item >= P.n_long) return;  // wave-uniform
-    const LongItem it = P.long_items[item];
-    if (it.slot == -2) return;  // padding of the XCD-affine item layout (plan.hip)
-    long_item<G, MODE, F4T, 4, false>(P, it, lane, nullptr, nullptr);
+    const LongItem it = item_at(P, wave_index(L, gi));
+    if (it.slot == -2) return;
+    long_item<G, MODE, F4T, 4, false>(P, it, (int)threadIdx.x % kWave, nullptr, nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -338,33 +375,16 @@ __device__ __forceinline__ void long_item_fat(const AggGroup &P, const LongItem 
     // the HL lanes of a head interleave its float4 chunks: lane (head h, position q) holds chunks q, q + HL, q + 2 HL, ...
     // of the head, so ONE load instruction reads HL * 16 contiguous bytes per edge (64+ bytes for HL >= 4); with 16
     // contiguous columns per lane every instruction touched every cache line of the row (measured 2x slower)
-    const int pos = sl % HL;
-    const int c0 = active ? (sl / HL) * P.F + 4 * pos : 0;   // column of chunk 0; chunk v sits at c0 + 4 * HL * v
+    const int c0 = active ? (sl / HL) * P.F + 4 * (sl % HL) : 0;   // column of chunk 0; chunk v sits at c0 + 4 * HL * v
     constexpr int CS = 4 * HL;
     const float *feat = P.feat + c0;
-    const float *feat_self = P.feat_self + c0;
-    const int row = it.row;
-    const int kk = 2 * (c0 / P.F);
 
-    float sm = kNegBig, ss = 0.f;   // running softmax state of this lane's head (GAT)
-    float4 acc[V4];                 // weighted sum (GAT) / plain sum (GCN, MEAN)
-#pragma unroll
-    for (int v = 0; v < V4; ++v) acc[v] = make_float4(0.f, 0.f, 0.f, 0.f);
-    float a_d = 0.f, di = 0.f;
-    const float slope = P.neg_slope;
-    float4 att_s[V4], h_self[V4];
-    if (MODE == AGG_GAT) {
-        float d = 0.f;
-#pragma unroll
-        for (int v = 0; v < V4; ++v) {
-            att_s[v] = ld4(P.att_src + c0 + CS * v);
-            h_self[v] = ld4(row_at(feat_self, row, P.ld_self) + CS * v);
-            d += dot4(h_self[v], ld4(P.att_dst + c0 + CS * v));
-        }
-        a_d = head_sum<HL>(d, lane, pos, HL, true);
-    } else if (MODE == AGG_GCN) {
-        di = P.dinv_self[row];
-    }
+    SoftV<V4> st;   // running softmax state of this lane's head (GAT)
+    st.init();
+    float4 sum[V4];  // plain sum (GCN, MEAN)
+    zero(sum);
+    RowEnd<MODE, HL, V4> R(P, lane, sl, c0);
+    R.load(P, it.row);
     int src = it.beg + lane < it.end ? P.col[it.beg + lane] : -1;
     for (int base = it.beg; base < it.end; base += kWave) {
         const int nxt = base + kWave + lane;
@@ -374,7 +394,7 @@ __device__ __forceinline__ void long_item_fat(const AggGroup &P, const LongItem 
             int jj[U];
             bool ok[U];
             float4 h[U][V4];
-            float a[U];
+            float a[U] = {};
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const int idx = t + u * NSG + sub;
@@ -391,125 +411,31 @@ __device__ __forceinline__ void long_item_fat(const AggGroup &P, const LongItem 
             }
             if (MODE == AGG_GAT) {
 #pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    float d = 0.f;
-#pragma unroll
-                    for (int v = 0; v < V4; ++v) d += dot4(h[u][v], att_s[v]);
-                    a[u] = head_sum<HL>(d, lane, pos, HL, true);
-                }
-                // one softmax update per 4 edges, as in the thin kernel
+                for (int u = 0; u < U; ++u) a[u] = R.head_dot(h[u], R.att_s);
                 float e[U];
-                float mx = -INFINITY;
 #pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const float z = leaky(a[u] + a_d, slope);
-                    e[u] = ok[u] ? z : -INFINITY;
-                    mx = fmaxf(mx, e[u]);
-                }
-                const float mn = fmaxf(sm, mx * kLog2e);    // log2-domain running max, natural logits (agg_common.h: Soft)
-                const float fs = __builtin_amdgcn_exp2f(sm - mn);
-                sm = mn;
-                ss *= fs;
-#pragma unroll
-                for (int v = 0; v < V4; ++v) acc[v] = scale4(acc[v], fs);
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const float p = __builtin_amdgcn_exp2f(fmaf(e[u], kLog2e, -mn));
-                    ss += p;
-#pragma unroll
-                    for (int v = 0; v < V4; ++v) acc[v] = fma4(p, h[u][v], acc[v]);
-                }
+                for (int u = 0; u < U; ++u) e[u] = masked_logit(ok[u], a[u], R.a_d, R.slope);
+                st.batch4(e, h);  // one softmax update per 4 edges, as in the thin kernel
             } else {
+                // no per-edge weights here: WSUM is instantiated (launch_fat_groups' switch) and never launched, and
+                // keeps the plain sum it always had
+                constexpr int SUM = MODE == AGG_WSUM ? (int)AGG_MEAN : MODE;
 #pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    if (MODE == AGG_GCN) {
-                        const float w = ok[u] ? a[u] * di : 0.f;
-#pragma unroll
-                        for (int v = 0; v < V4; ++v) acc[v] = fma4(w, h[u][v], acc[v]);
-                    } else if (ok[u]) {
-#pragma unroll
-                        for (int v = 0; v < V4; ++v) acc[v] = add4(acc[v], h[u][v]);
-                    }
-                }
+                for (int u = 0; u < U; ++u) accumulate<SUM>(sum, ok[u], a[u], R.di, h[u]);
             }
         }
         src = src_next;
     }
-    // fold the NSG subgroup states (xor butterfly: every lane ends with the same value)
-#pragma unroll
-    for (int off = G; off < kWave; off <<= 1) {
-        if (MODE == AGG_GAT) {
-            const float m2 = __shfl_xor(sm, off), s2 = __shfl_xor(ss, off);
-            const float mn = fmaxf(sm, m2);
-            const float f1 = __builtin_amdgcn_exp2f(sm - mn), f2 = __builtin_amdgcn_exp2f(m2 - mn);
-            ss = ss * f1 + s2 * f2;
-#pragma unroll
-            for (int v = 0; v < V4; ++v) acc[v] = add4(scale4(acc[v], f1), scale4(shfl_xor4(acc[v], off), f2));
-            sm = mn;
-        } else {
-#pragma unroll
-            for (int v = 0; v < V4; ++v) acc[v] = add4(acc[v], shfl_xor4(acc[v], off));
-        }
-    }
-    if (it.slot >= 0) {  // hub chunk: partial record in plain column order (the merge kernel is layout-agnostic)
-        if (sub == 0 && active) {
-            const int nk = P.W / P.F;
-            float *rec = P.partial + (size_t)it.slot * (size_t)(P.W + 2 * nk);
-#pragma unroll
-            for (int v = 0; v < V4; ++v) st4(rec + c0 + CS * v, acc[v]);
-            if (MODE == AGG_GAT && pos == 0) {
-                rec[P.W + kk] = sm;
-                rec[P.W + kk + 1] = ss;
-            }
-        }
-        return;
-    }
-    if (P.self_loop) {
-        if (MODE == AGG_GAT) {
-            float d = 0.f;
-#pragma unroll
-            for (int v = 0; v < V4; ++v) d += dot4(h_self[v], att_s[v]);
-            const float e = leaky(head_sum<HL>(d, lane, pos, HL, true) + a_d, slope);
-            // Soft::push
-            const float mn = fmaxf(sm, e * kLog2e);
-            const float fs = __builtin_amdgcn_exp2f(sm - mn), p = __builtin_amdgcn_exp2f(fmaf(e, kLog2e, -mn));
-            sm = mn;
-            ss = fmaf(ss, fs, p);
-#pragma unroll
-            for (int v = 0; v < V4; ++v) {
-                acc[v].x = fmaf(acc[v].x, fs, p * h_self[v].x);
-                acc[v].y = fmaf(acc[v].y, fs, p * h_self[v].y);
-                acc[v].z = fmaf(acc[v].z, fs, p * h_self[v].z);
-                acc[v].w = fmaf(acc[v].w, fs, p * h_self[v].w);
-            }
-        } else if (MODE == AGG_GCN) {
-#pragma unroll
-            for (int v = 0; v < V4; ++v) acc[v] = fma4(di * di, ld4(row_at(feat_self, row, P.ld_self) + CS * v), acc[v]);
-        }
-    }
-    if (sub == 0 && active) {
-        Soft st;
-        st.m = sm;
-        st.s = ss;
-#pragma unroll
-        for (int v = 0; v < V4; ++v) {   // finish_row per float4 chunk (stats are written by the head's first chunk)
-            st.acc = acc[v];
-            finish_row<MODE>(P, row, c0 + CS * v, it.end - it.beg, st, acc[v]);
-        }
-    }
+    end_item<G>(P, it, R, st, sum, sub == 0 && active);
 }
 
 template <int G, int MODE, int HL, int V4>
 __global__ __launch_bounds__(kBlock) void agg_long_fat_kernel(const AggLaunch L) {
     const int gi = find_group(L);
     const AggGroup &P = L.g[gi];
-    const int wave = (int)threadIdx.x / kWave;
-    const int lane = (int)threadIdx.x % kWave;
-    const int item = ((int)blockIdx.x - L.blk_start[gi]) * (kBlock / kWave) + wave;
-    if (item >= P.n_long) return;  // wave-uniform
-    const LongItem it = P.long_items[item];
-    if (it.slot == -2) return;  // padding of the XCD-affine item layout (plan.hip)
-    long_item_fat<G, MODE, HL, V4>(P, it, lane);
+    const LongItem it = item_at(P, wave_index(L, gi));
+    if (it.slot == -2) return;
+    long_item_fat<G, MODE, HL, V4>(P, it, (int)threadIdx.x % kWave);
 }
 
 // One 1024-thread workgroup per CU, persistent: it fills the LDS image once, then its 16 waves walk the item list.  The
@@ -537,9 +463,7 @@ __global__ __launch_bounds__(kHotBlock) void agg_long_hot_kernel(const AggLaunch
     const int n_virtual = (P.n_long + 3) / 4;
     const int stride = (int)gridDim.x * 4;
     for (int v = (int)blockIdx.x % 8 + 8 * (4 * ((int)blockIdx.x / 8) + wave / 4); v < n_virtual; v += stride) {
-        const int item = v * 4 + wave % 4;
-        if (item >= P.n_long) continue;
-        const LongItem it = P.long_items[item];
+        const LongItem it = item_at(P, v * 4 + wave % 4);
         if (it.slot == -2) continue;
         long_item<G, MODE, F4T, kHotU, true>(P, it, lane, hot_img, hot_dinv);
     }
@@ -553,9 +477,8 @@ __global__ __launch_bounds__(kBlock) void agg_merge_kernel(const AggLaunch L) {
     constexpr int NSG = kWave / G;
     const int gi = find_group(L);
     const AggGroup &P = L.g[gi];
-    const int wave = (int)threadIdx.x / kWave;
+    const int item = wave_index(L, gi);
     const int lane = (int)threadIdx.x % kWave;
-    const int item = ((int)blockIdx.x - L.blk_start[gi]) * (kBlock / kWave) + wave;
     if (item >= P.n_hub) return;
     const int row = P.hub_rows[item];
     const int first = P.hub_first[item], count = P.hub_count[item];
@@ -568,29 +491,29 @@ __global__ __launch_bounds__(kBlock) void agg_merge_kernel(const AggLaunch L) {
 
     Soft st;
     st.init();
-    float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 sum[1];
+    zero(sum);
     // a hub row of the 25m-shaped graph has ~300 chunk records: 8 of them are in flight per subgroup before the first
     // merge (folded in the same chunk order as one at a time: the kernel was one dependent load per record, 30 us)
     constexpr int UM = 8;
     for (int c0 = sub; c0 < count; c0 += NSG * UM) {
-        float4 a[UM];
+        float4 a[UM][1];
         float m2[UM], s2[UM];
 #pragma unroll
         for (int u = 0; u < UM; ++u) {
             const int c = c0 + u * NSG;
             const bool ok = c < count;
             const float *rec = P.partial + (size_t)(first + (ok ? c : c0)) * rec_sz;
-            a[u] = ld4(rec + c4);
-            if (MODE == AGG_GAT) {
-                m2[u] = rec[P.W + kk];
-                s2[u] = rec[P.W + kk + 1];
-            }
             // a slot past the end becomes the neutral record (weight 2^(kNegBig - m) = 0, state x 1): the merges below
-            // stay unconditional, so the compiler keeps the UM loads ahead of them instead of sinking each into its branch
-            if (!ok) {
-                a[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-                m2[u] = kNegBig;
-                s2[u] = 0.f;
+            // stay unconditional, so the compiler keeps the UM loads ahead of them instead of sinking each into its branch.
+            // Selects, not `if (!ok)` assignments: with those, whether the loads stayed ahead hung on unrelated code
+            // around the loop (the 8-lane GAT kernel lost them when `st` became SoftV<1>).
+            const float4 r = ld4(rec + c4);
+            a[u][0] = make_float4(ok ? r.x : 0.f, ok ? r.y : 0.f, ok ? r.z : 0.f, ok ? r.w : 0.f);
+            if (MODE == AGG_GAT) {
+                const float mr = rec[P.W + kk], sr = rec[P.W + kk + 1];
+                m2[u] = ok ? mr : kNegBig;
+                s2[u] = ok ? sr : 0.f;
             }
         }
 #pragma unroll
@@ -598,97 +521,96 @@ __global__ __launch_bounds__(kBlock) void agg_merge_kernel(const AggLaunch L) {
             if (MODE == AGG_GAT) {
                 st.merge(m2[u], s2[u], a[u]);
             } else {
-                sum = add4(sum, a[u]);
+                sum[0] = add4(sum[0], a[u][0]);
             }
         }
     }
-#pragma unroll
-    for (int off = G; off < kWave; off <<= 1) {
-        if (MODE == AGG_GAT) {
-            const float m2 = __shfl_xor(st.m, off), s2 = __shfl_xor(st.s, off);
-            const float4 a2 = shfl_xor4(st.acc, off);
-            st.merge(m2, s2, a2);
-        } else {
-            sum = add4(sum, shfl_xor4(sum, off));
-        }
+    if (MODE == AGG_GAT) {
+        st.fold<G>();
+    } else {
+        fold_sum<G>(sum);
     }
-    const float *feat_self = P.feat_self + c4;
-    if (P.self_loop) {
-        const float4 h = ld4(row_at(feat_self, row, P.ld_self));
-        if (MODE == AGG_GAT) {
-            const int F4 = P.F / 4, pos = sl % F4;
-            const bool pow2 = (F4 & (F4 - 1)) == 0;
-            const float a_d = head_sum<F4T>(dot4(h, ld4(P.att_dst + c4)), lane, pos, F4, pow2);
-            const float a = head_sum<F4T>(dot4(h, ld4(P.att_src + c4)), lane, pos, F4, pow2);
-            st.push(leaky(a + a_d, P.neg_slope), h);
-        } else if (MODE == AGG_GCN) {
-            const float di = P.dinv_self[row];
-            sum = fma4(di * di, h, sum);
-        }
-    }
-    const int deg = P.rowptr[row + 1] - P.rowptr[row];
-    if (sub == 0 && active) finish_row<MODE>(P, row, c4, deg, st, sum);
+    RowEnd<MODE, F4T, 1> R(P, lane, sl, c4);
+    R.template close<true>(P, row, P.rowptr[row + 1] - P.rowptr[row], st, sum, sub == 0 && active);
 }
 
-
+// ------------------------------------------------------------------------------------------------
+// host: launch planning per (lane width, head class), byte model, profile names
+// ------------------------------------------------------------------------------------------------
 // profile names, as profiles/summarize.py derives them from rocprofv3's kernel names: agg_rows_g<G>_<mode> = the level
-// launch (long rows, hub chunks and short rows), agg_merge_* / agg_longhot_*
-template <int G, int MODE>
-const char *kname(int which) {
-    static char names[4][32];
-    static bool init = false;
-    if (!init) {
-        const char *w[4] = {"short", "rows", "merge", "longhot"};
-        const char *m = MODE == AGG_GAT ? "gat" : MODE == AGG_GCN ? "gcn" : MODE == AGG_WSUM ? "wsum" : "mean";
-        for (int i = 0; i < 4; ++i) snprintf(names[i], sizeof(names[i]), "agg_%s_g%d_%s", w[i], G, m);
-        init = true;
-    }
-    return names[which];
+// launch (long rows, hub chunks and short rows), agg_merge_* / agg_longhot_* / agg_long_fat_*.  The table is a
+// function-local static: built once, by whichever thread comes first.
+enum LaunchKind { kRows, kMerge, kLongHot, kLongFat, kLaunchKinds };
+template <int MODE>
+const char *launch_name(LaunchKind kind, int G) {
+    struct Names {
+        char s[kLaunchKinds][5][32];
+        Names() {
+            const char *w[kLaunchKinds] = {"rows", "merge", "longhot", "long_fat"};
+            const char *m = MODE == AGG_GAT ? "gat" : MODE == AGG_GCN ? "gcn" : MODE == AGG_WSUM ? "wsum" : "mean";
+            for (int k = 0; k < kLaunchKinds; ++k)
+                for (int i = 0; i < 5; ++i) snprintf(s[k][i], sizeof(s[k][i]), "agg_%s_g%d_%s", w[k], 4 << i, m);
+        }
+    };
+    static const Names names;
+    int i = 0;
+    while ((4 << i) < G) ++i;
+    return names.s[kind][i];
+}
+
+// Per message of a group: `alg`, the algorithmic bytes of SURVEY.md 8(d) (4 B per gathered feature column + 4 B source
+// index + 4 B per attention scalar (GAT) / norm scalar (GCN)), and `pull`, what a launch itself pulls through the memory
+// system (the row chunk + its source index, GCN: + the norm scalar, each once).
+struct MsgBytes {
+    double alg, pull;
+};
+template <int MODE>
+MsgBytes msg_bytes(const AggGroup &g) {
+    return {4.0 * g.W + 4.0 * g.idx_share + (MODE == AGG_GAT ? 4.0 * (g.W / g.F) : MODE == AGG_GCN ? 4.0 * g.idx_share : 0.0),
+            4.0 * g.W + 4.0 + (MODE == AGG_GCN ? 4.0 : 0.0)};
+}
+// the gather footprint of a group (a launch reports the largest among its groups)
+double table_bytes(const AggGroup &g) { return g.table_rows * 4.0 * g.W; }
+
+// Appends g to L with n_long of its long items (4 per workgroup): a group starts on a multiple of 8 workgroups, so that
+// item -> workgroup -> XCD (round-robin) is the plan's placement in the thin and in the fat kernel alike.
+AggGroup &add_group(AggLaunch &L, const AggGroup &g, int n_long, int &blocks) {
+    L.blk_start[L.n_groups] = blocks;
+    AggGroup &c = L.g[L.n_groups++];
+    c = g;
+    c.n_long = n_long;
+    blocks += ((n_long + 3) / 4 + 7) / 8 * 8;
+    return c;
 }
 
 template <int G, int MODE, int F4T>
 int launch_for_g(const AggLaunch &base, const int *sel, int n_sel, hipStream_t stream) {
     AggLaunch L;
-    // algorithmic bytes of SURVEY.md 8(d) attributed to a launch: per message 4 B per gathered feature column
-    // + 4 B source index + 4 B per attention scalar (GAT) / norm scalar (GCN), times the messages it reduces
-    double bytes_short = 0.0;
-    // ... and what the launch itself pulls through the memory system: every message's row chunk + its source index
-    // (GCN: + the norm scalar), each once; `table`: the largest gather footprint among the launch's groups
-    double pull_short = 0.0, table = 0.0;
-    for (int i = 0; i < n_sel; ++i) {
-        const AggGroup &g = base.g[sel[i]];
-        const double per_msg = 4.0 * g.W + 4.0 * g.idx_share + (MODE == AGG_GAT ? 4.0 * (g.W / g.F) : MODE == AGG_GCN ? 4.0 * g.idx_share : 0.0);
-        bytes_short += per_msg * g.msgs_short;
-        const double pull = 4.0 * g.W + 4.0 + (MODE == AGG_GCN ? 4.0 : 0.0);
-        pull_short += pull * g.msgs_short;
-        table = table > g.table_rows * 4.0 * g.W ? table : g.table_rows * 4.0 * g.W;
-    }
     // long rows + hub chunks first, short rows behind them, ONE launch (groups with an LDS image or already served by the
     // fat-lane kernel keep their short rows here, their long items go elsewhere)
     L.n_groups = 0;
     int blocks = 0, sblocks = 0;
-    double pull_plain = 0.0, alg_plain = 0.0;
+    double alg_short = 0.0, pull_short = 0.0, alg_plain = 0.0, pull_plain = 0.0, table = 0.0;
     for (int i = 0; i < n_sel; ++i) {
         const AggGroup &g = base.g[sel[i]];
+        const MsgBytes b = msg_bytes<MODE>(g);
+        alg_short += b.alg * g.msgs_short;
+        pull_short += b.pull * g.msgs_short;
+        table = std::max(table, table_bytes(g));
         const bool long_here = g.n_long > 0 && !g.hot_col && !g.skip_long;
         if (g.n_short <= 0 && !long_here) continue;
-        L.blk_start[L.n_groups] = blocks;
         L.blk_short[L.n_groups] = sblocks;
-        AggGroup &c = L.g[L.n_groups++];
-        c = g;
-        if (!long_here) c.n_long = 0;
+        add_group(L, g, long_here ? g.n_long : 0, blocks);
         if (g.n_short > 0) sblocks += (g.n_short + (kBlock / G) - 1) / (kBlock / G);
         if (!long_here) continue;
-        blocks += ((g.n_long + 3) / 4 + 7) / 8 * 8;  // groups start on a multiple of 8 workgroups (XCD round-robin)
-        const double per_msg = 4.0 * g.W + 4.0 * g.idx_share + (MODE == AGG_GAT ? 4.0 * (g.W / g.F) : MODE == AGG_GCN ? 4.0 * g.idx_share : 0.0);
-        alg_plain += per_msg * g.msgs_long;
-        pull_plain += (4.0 * g.W + 4.0 + (MODE == AGG_GCN ? 4.0 : 0.0)) * g.msgs_long;
+        alg_plain += b.alg * g.msgs_long;
+        pull_plain += b.pull * g.msgs_long;
     }
     L.blk_start[L.n_groups] = blocks;
     L.blk_short[L.n_groups] = sblocks;
     L.n_long_blocks = blocks;
     if (blocks + sblocks > 0) {
-        ProfScope ps(kname<G, MODE>(1), stream, alg_plain + bytes_short, pull_plain + pull_short, table);
+        ProfScope ps(launch_name<MODE>(kRows, G), stream, alg_plain + alg_short, pull_plain + pull_short, table);
         PEA_LAUNCH((agg_rows_kernel<G, MODE, F4T>), dim3(blocks + sblocks), dim3(kBlock), 0, stream, L);
         PEA_HIP(hipGetLastError());
     }
@@ -705,11 +627,10 @@ int launch_for_g(const AggLaunch &base, const int *sel, int n_sel, hipStream_t s
         PEA_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(&agg_long_hot_kernel<G, MODE, F4T>), lds));
         const int n_virtual = (g.n_long + 3) / 4;
         const int grid = std::max(8, std::min(256, (n_virtual + 3) / 4 + 7 & ~7));
-        const double per_msg = 4.0 * g.W + 4.0 * g.idx_share + (MODE == AGG_GAT ? 4.0 * (g.W / g.F) : MODE == AGG_GCN ? 4.0 * g.idx_share : 0.0);
+        const MsgBytes b = msg_bytes<MODE>(g);
         // pulled through the memory system: the cold rows, every index, and one image fill per workgroup
-        const double pull = (4.0 * g.W + (MODE == AGG_GCN ? 4.0 : 0.0)) * g.msgs_long * (1.0 - g.hot_frac) + 4.0 * g.msgs_long +
-                            (double)grid * (double)lds;
-        ProfScope ps(kname<G, MODE>(3), stream, per_msg * g.msgs_long, pull, g.table_rows * 4.0 * g.W);
+        const double pull = (b.pull - 4.0) * g.msgs_long * (1.0 - g.hot_frac) + 4.0 * g.msgs_long + (double)grid * (double)lds;
+        ProfScope ps(launch_name<MODE>(kLongHot, G), stream, b.alg * g.msgs_long, pull, table_bytes(g));
         PEA_LAUNCH((agg_long_hot_kernel<G, MODE, F4T>), dim3(grid), dim3(kHotBlock), lds, stream, L);
         PEA_HIP(hipGetLastError());
     }
@@ -725,7 +646,7 @@ int launch_for_g(const AggLaunch &base, const int *sel, int n_sel, hipStream_t s
     }
     L.blk_start[L.n_groups] = blocks;
     if (blocks > 0) {
-        ProfScope ps(kname<G, MODE>(2), stream, 0.0);
+        ProfScope ps(launch_name<MODE>(kMerge, G), stream, 0.0);
         PEA_LAUNCH((agg_merge_kernel<G, MODE, F4T>), dim3(blocks), dim3(kBlock), 0, stream, L);
         PEA_HIP(hipGetLastError());
     }
@@ -750,17 +671,6 @@ int launch_g(const AggLaunch &base, int cls, const int *sel, int n, hipStream_t 
 // lanes so that one load instruction reads >= 128 contiguous bytes per edge (a whole cache line: with 4 lanes per head,
 // 64-byte pieces, the kernel touched every line twice and lost to the thin kernel): 8 columns per lane for F = 64,
 // 16 for F = 128 / 256.
-template <int MODE>
-const char *fat_name(int G) {
-    static char names[4][32];
-    const int i = G == 8 ? 0 : G == 16 ? 1 : G == 32 ? 2 : 3;
-    if (!names[i][0]) {
-        const char *m = MODE == AGG_GAT ? "gat" : MODE == AGG_GCN ? "gcn" : "mean";
-        snprintf(names[i], sizeof(names[i]), "agg_long_fat_g%d_%s", G, m);
-    }
-    return names[i];
-}
-
 template <int G, int MODE, int HL, int V4>
 int launch_fat(const AggLaunch &base, const int *sel, int n_sel, hipStream_t stream) {
     AggLaunch L;
@@ -769,17 +679,15 @@ int launch_fat(const AggLaunch &base, const int *sel, int n_sel, hipStream_t str
     double alg = 0.0, pull = 0.0, table = 0.0;
     for (int i = 0; i < n_sel; ++i) {
         const AggGroup &g = base.g[sel[i]];
-        L.blk_start[L.n_groups] = blocks;
-        L.g[L.n_groups++] = g;
-        blocks += ((g.n_long + 3) / 4 + 7) / 8 * 8;  // same item -> workgroup -> XCD placement as the thin kernel
-        const double per_msg = 4.0 * g.W + 4.0 * g.idx_share + (MODE == AGG_GAT ? 4.0 * (g.W / g.F) : MODE == AGG_GCN ? 4.0 * g.idx_share : 0.0);
-        alg += per_msg * g.msgs_long;
-        pull += (4.0 * g.W + 4.0 + (MODE == AGG_GCN ? 4.0 : 0.0)) * g.msgs_long;
-        table = std::max(table, g.table_rows * 4.0 * g.W);
+        add_group(L, g, g.n_long, blocks);
+        const MsgBytes b = msg_bytes<MODE>(g);
+        alg += b.alg * g.msgs_long;
+        pull += b.pull * g.msgs_long;
+        table = std::max(table, table_bytes(g));
     }
     L.blk_start[L.n_groups] = blocks;
     if (blocks <= 0) return PEA_OK;
-    ProfScope ps(fat_name<MODE>(G), stream, alg, pull, table);
+    ProfScope ps(launch_name<MODE>(kLongFat, G), stream, alg, pull, table);
     PEA_LAUNCH((agg_long_fat_kernel<G, MODE, HL, V4>), dim3(blocks), dim3(kBlock), 0, stream, L);
     PEA_HIP(hipGetLastError());
     return PEA_OK;

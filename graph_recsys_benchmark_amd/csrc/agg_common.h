@@ -1,5 +1,7 @@
 // Device helpers shared by the forward (agg.hip) and backward (agg_bwd.hip) aggregation kernels.
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 
 namespace pea {
@@ -27,36 +29,89 @@ __device__ __forceinline__ float4 shfl_xor4(float4 v, int m) {
     return make_float4(__shfl_xor(v.x, m), __shfl_xor(v.y, m), __shfl_xor(v.z, m), __shfl_xor(v.w, m));
 }
 
-// Running softmax-weighted sum for one attention group: value = acc / s with weights exp(e - m).
-struct Soft {
+// Running softmax-weighted sum for one attention group over V4 float4 chunks per lane: value = acc / s with weights
+// exp(e - m).  One chunk (Soft) keeps `acc` a plain float4; chunk(v) reads either form.
+template <int V4>
+struct SoftV {
     float m, s;
-    float4 acc;
-    __device__ __forceinline__ void init() { m = kNegBig; s = 0.f; acc = make_float4(0.f, 0.f, 0.f, 0.f); }
+    typename std::conditional<V4 == 1, float4, float4[V4]>::type acc;
+    __device__ __forceinline__ float4 &chunk(int v) {
+        if constexpr (V4 == 1) return acc; else return acc[v];
+    }
+    __device__ __forceinline__ void init() {
+        m = kNegBig;
+        s = 0.f;
+#pragma unroll
+        for (int v = 0; v < V4; ++v) chunk(v) = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
     // The running max m lives in the log2 domain, the logits e in NATURAL units exactly as the reference forms them
     // (leaky_relu(x_i . att_i + x_j . att_j), reference GATConv.message): a weight is 2^(e * log2(e) - m), one v_fma_f32 (the
     // product exact inside it) + one v_exp_f32.  Every weight of a state is relative to the same m, whatever m is, so the
     // rounding of m itself cancels in acc / s; only the small difference e * log2(e) - m is rounded.  (Round 2 folded
     // log2(e) into the packed attention vectors instead: one more rounding per vector component, and the exponent inherited
     // the rounding of the scaled logit -- up to 4x the sequential oracle's error on deep multi-head stacks.)
-    __device__ __forceinline__ void push(float e, float4 h) {
+    __device__ __forceinline__ void push(float e, const float4 (&h)[V4]) {
         const float mn = fmaxf(m, e * kLog2e);
         const float fs = __builtin_amdgcn_exp2f(m - mn);                    // factor on the old state (1 when the max stays)
         const float p = __builtin_amdgcn_exp2f(fmaf(e, kLog2e, -mn));       // weight of the new edge
         m = mn;
         s = fmaf(s, fs, p);
-        acc.x = fmaf(acc.x, fs, p * h.x);
-        acc.y = fmaf(acc.y, fs, p * h.y);
-        acc.z = fmaf(acc.z, fs, p * h.z);
-        acc.w = fmaf(acc.w, fs, p * h.w);
+#pragma unroll
+        for (int v = 0; v < V4; ++v) {
+            float4 &a = chunk(v);
+            a.x = fmaf(a.x, fs, p * h[v].x);
+            a.y = fmaf(a.y, fs, p * h[v].y);
+            a.z = fmaf(a.z, fs, p * h[v].z);
+            a.w = fmaf(a.w, fs, p * h[v].w);
+        }
     }
-    __device__ __forceinline__ void merge(float m2, float s2, float4 a2) {
+    __device__ __forceinline__ void push(float e, float4 h) {  // one chunk, handed over as the float4 it is
+        const float4 one[1] = {h};
+        push(e, one);
+    }
+    __device__ __forceinline__ void merge(float m2, float s2, const float4 (&a2)[V4]) {
         const float mn = fmaxf(m, m2);
         const float f1 = __builtin_amdgcn_exp2f(m - mn), f2 = __builtin_amdgcn_exp2f(m2 - mn);
         s = s * f1 + s2 * f2;
-        acc = add4(scale4(acc, f1), scale4(a2, f2));
+#pragma unroll
+        for (int v = 0; v < V4; ++v) chunk(v) = add4(scale4(chunk(v), f1), scale4(a2[v], f2));
         m = mn;
     }
+    // One update for 4 edges with already-masked logits e (natural units; -inf = no edge, weight 2^(-inf) = 0): shared new
+    // max, one rescale, four weights in slot order.  The batch size is part of the arithmetic: it stays 4 whatever the
+    // caller keeps in flight, so every variant of the gather produces the same bits.
+    __device__ __forceinline__ void batch4(const float (&e)[4], const float4 (&h)[4][V4]) {
+        float mx = -INFINITY;                                                // largest logit of the batch, natural units
+#pragma unroll
+        for (int u = 0; u < 4; ++u) mx = fmaxf(mx, e[u]);
+        const float mn = fmaxf(m, mx * kLog2e);                              // running max, log2 domain (finite)
+        const float fs = __builtin_amdgcn_exp2f(m - mn);
+        m = mn;
+        s *= fs;
+#pragma unroll
+        for (int v = 0; v < V4; ++v) chunk(v) = scale4(chunk(v), fs);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const float p = __builtin_amdgcn_exp2f(fmaf(e[u], kLog2e, -mn));  // 0 for the masked slots
+            s += p;
+#pragma unroll
+            for (int v = 0; v < V4; ++v) chunk(v) = fma4(p, h[u][v], chunk(v));
+        }
+    }
+    // fold the kWave / G subgroup states of a wave (xor butterfly: every lane ends with the same value)
+    template <int G>
+    __device__ __forceinline__ void fold() {
+#pragma unroll
+        for (int off = G; off < kWave; off <<= 1) {
+            const float m2 = __shfl_xor(m, off), s2 = __shfl_xor(s, off);
+            float4 a2[V4];
+#pragma unroll
+            for (int v = 0; v < V4; ++v) a2[v] = shfl_xor4(chunk(v), off);
+            merge(m2, s2, a2);
+        }
+    }
 };
+using Soft = SoftV<1>;
 
 // slope in [0, 1] (checked on the host): leaky_relu(a) = max(a, slope * a)
 __device__ __forceinline__ float leaky(float a, float slope) { return fmaxf(a, a * slope); }
