@@ -1,4 +1,4 @@
-"""ctypes binding of libpeahip.so (C ABI: include/peahip.h and include/peahip_kge.h).
+"""ctypes binding of libpeahip.so (C ABI: include/peahip.h, include/peahip_kge.h and include/peahip_eval.h).
 
 The product path has NO fallback: if the HIP library is missing or no gfx950 device is visible, every
 compute entry point raises.  (CPU parity checking lives in oracle/, which this package never imports.)
@@ -218,6 +218,17 @@ KGE_SIGNATURES = {
 }
 CFKG_MAX_REL = 64     # include/peahip_kge.h PEA_CFKG_MAX_REL
 
+# every symbol include/peahip_eval.h declares (the all-item evaluation with several positives per user)
+EVAL_SIGNATURES = {
+    'pea_rank_multi_workspace_bytes': (_sz, [_i64, _i64, _i64, _int]),
+    'pea_dot_rank_multi_workspace_bytes': (_sz, [_i64, _i64, _i64, _int]),
+    'pea_rank_full_multi': (_int, [_i64, _int, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                   _vp, _vp, _vp, _sz, _vp]),
+    'pea_dot_rank_full_multi': (_int, [_i64, _int, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                       _sz, _vp]),
+}
+RANK_MULTI_CHUNK = 8     # csrc/topk_select.h kPC: thresholds of one (user, chunk) row
+
 KGU_KGAT, KGU_KGCN, KGU_NGCF = 0, 1, 2     # include/peahip.h PEA_KGU_*
 
 _lib = None
@@ -231,7 +242,7 @@ def load():
             raise ImportError('%s is missing: build it with `python -c "import __graft_entry__ as g; g.build()"` '
                               '(or make -C graph_recsys_benchmark_amd/csrc); there is no CPU fallback' % LIB_PATH)
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(KGE_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(KGE_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

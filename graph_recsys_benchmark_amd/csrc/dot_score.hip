@@ -11,6 +11,7 @@
 
 #include "score_common.h"
 #include "topk_select.h"
+#include "../../include/peahip_eval.h"
 
 namespace pea {
 namespace {
@@ -286,6 +287,183 @@ int check_d(const char *what, int D) {
     return PEA_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- several positives per user
+// pea_dot_rank_full_multi (include/peahip_eval.h): the rows, counters and finish of topk_select.h with dot_pair and the
+// MFMA tiles of dot_scan_kernel.
+struct MultiLayout {
+    int DP = 32, S = 1, LD = 8;
+    int64_t span = 0, rows = 0;
+    size_t off_thr = 0, off_part = 0, bytes = 0, lds = 0;
+};
+
+constexpr int kMultiNW = 4;         // waves of one workgroup of the scan: 128 rows share an item tile (<= 34 KB of LDS)
+
+// Depends on (U, Q, n_items, D) only: the rows are the bound multi_rows, not the rows in use.  The four lane groups of a
+// row add their counters up in the wave, so an item range leaves one column.
+MultiLayout make_multi_layout(int64_t U, int64_t Q, int64_t n_items, int D) {
+    MultiLayout L;
+    L.DP = D <= 32 ? 32 : (D <= 64 ? 64 : (D <= 128 ? 128 : 256));
+    L.LD = tile_ld(D);
+    L.lds = (size_t)kTI * L.LD * 4;
+    L.rows = multi_rows(U, Q);
+    const int rows_wg = kUW * kMultiNW;
+    catalogue_split(std::max<int64_t>((L.rows + rows_wg - 1) / rows_wg, 1), n_items, 1, kTI, &L.S, &L.span);
+    size_t o = 256;                                                     // error flag
+    L.off_thr = o;  o = align256(o + (size_t)std::max<int64_t>(Q, 1) * 4);
+    L.off_part = o; o = align256(o + (size_t)L.S * 2 * kPC * std::max<int64_t>(L.rows, 1) * 4);
+    L.bytes = o;
+    return L;
+}
+
+struct MultiArgs {
+    int64_t U, Q, rows, N, n_items, item_lo, span;
+    int S, D, LD;
+    const float *repr;
+    const int64_t *unids, *pos_rowptr, *pos_items, *excl_rowptr, *excl_items;
+    float *thr;      // [Q] the positives' scores
+    int *part;       // [S, 2, kPC, rows] counts of (s > t), (s < t)
+    int *err;
+};
+
+// one wave per user: multi_thresholds with dot_pair; the one place the ids of the call are checked
+__global__ __launch_bounds__(256) void dot_multi_pos_kernel(const MultiArgs g) {
+    const int lane = threadIdx.x % kWave;
+    const int64_t q = (int64_t)blockIdx.x * (256 / kWave) + threadIdx.x / kWave;
+    if (q >= g.U) return;
+    const int64_t u = g.unids[q];
+    const bool u_ok = u >= 0 && u < g.N;
+    if (!u_ok && lane == 0) atomicOr(g.err, 1);
+    multi_thresholds(q, g.Q, g.pos_rowptr, lane,
+                     [&](int64_t j) {
+                         const int64_t p = g.pos_items[j];
+                         if (p < 0 || p >= g.N) {
+                             atomicOr(g.err, 1);
+                             return 0.f;
+                         }
+                         return u_ok ? dot_pair(g.repr + u * g.D, g.repr + p * g.D, g.D) : 0.f;
+                     },
+                     g.thr);
+}
+
+// dot_scan_kernel's RANK tiles with a (user, chunk) row per (lane, half) column and multi_count in place of the two
+// counters: the same MFMA steps in the same order, so the same bits.  A wave whose rows all hold one threshold runs the
+// chain at length 1; a workgroup of idle rows leaves at once.
+template <int DP>
+__global__ __launch_bounds__(256) void dot_multi_scan_kernel(const MultiArgs g) {
+    const int NT = blockDim.x;
+    float *tile = dot_smem;
+    const int tid = threadIdx.x;
+    const int lane = tid % kWave, n = lane & 15, grp = lane >> 4;
+    const int D = g.D, LD = g.LD;
+    const int64_t r0 = ((int64_t)blockIdx.x * (NT / kWave) + tid / kWave) * kUW + n;
+    int64_t r[2];
+    int cnt[2];
+    float ub[2][DP / 4];
+    float thr[2][kPC];
+    int hi[2][kPC], lo[2][kPC];
+    int64_t first[2];
+    int64_t node[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        r[h] = r0 + 16 * h;
+        int64_t q = 0;
+        first[h] = 0;
+        cnt[h] = 0;
+        if (r[h] < g.rows) multi_row(r[h], g.U, g.Q, g.pos_rowptr, q, first[h], cnt[h]);
+        node[h] = g.unids[q];
+        if (node[h] < 0 || node[h] >= g.N) node[h] = 0;        // reported by dot_multi_pos_kernel
+    }
+    if (!__syncthreads_or(cnt[0] > 0 || cnt[1] > 0)) return;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        // an idle column rides along in the MFMA on user 0's row; its counters are never stored
+        const float *row = g.repr + node[h] * D + grp;
+#pragma unroll
+        for (int t = 0; t < DP / 4; ++t) ub[h][t] = 4 * t < D ? row[4 * t] : 0.f;
+#pragma unroll
+        for (int k = 0; k < kPC; ++k) {
+            thr[h][k] = k < cnt[h] ? g.thr[first[h] + k] : 0.f;
+            hi[h][k] = lo[h][k] = 0;
+        }
+    }
+    const bool one = __ballot(cnt[0] > 1 || cnt[1] > 1) == 0;
+    const int64_t i0 = (int64_t)blockIdx.y * g.span;
+    const int64_t i1 = i0 + g.span < g.n_items ? i0 + g.span : g.n_items;
+    const int d4 = D / 4;
+    const float *a_row0 = tile + n * LD + grp, *a_row1 = tile + (16 + n) * LD + grp;
+    for (int64_t t0 = i0; t0 < i1; t0 += kTI) {
+        __syncthreads();
+        // rows past the end of the range are zero rows: they score 0 and are skipped below
+        for (int x = tid; x < kTI * d4; x += NT) {
+            const int rr = x / d4, c4 = x - rr * d4;
+            const float4 v = t0 + rr < i1 ? ld4(g.repr + (g.item_lo + t0 + rr) * D + 4 * c4) : make_float4(0.f, 0.f, 0.f, 0.f);
+            *reinterpret_cast<float4 *>(tile + rr * LD + 4 * c4) = v;
+        }
+        __syncthreads();
+        f32x4 acc[2][2];
+#pragma unroll
+        for (int is = 0; is < 2; ++is)
+#pragma unroll
+            for (int h = 0; h < 2; ++h) acc[is][h] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int t = 0; t < DP / 4; ++t) {
+            if (4 * t >= D) break;
+            const float a0 = a_row0[4 * t], a1 = a_row1[4 * t];
+            acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, ub[0][t], acc[0][0], 0, 0, 0);
+            acc[0][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, ub[1][t], acc[0][1], 0, 0, 0);
+            acc[1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, ub[0][t], acc[1][0], 0, 0, 0);
+            acc[1][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, ub[1][t], acc[1][1], 0, 0, 0);
+        }
+#pragma unroll
+        for (int is = 0; is < 2; ++is) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int64_t it = t0 + 16 * is + 4 * grp + j;
+                if (it >= i1) continue;
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    if (one) multi_count<1>(acc[is][h][j], thr[h], hi[h], lo[h]);
+                    else multi_count<kPC>(acc[is][h][j], thr[h], hi[h], lo[h]);
+                }
+            }
+        }
+    }
+    // the four lane groups of a column each saw a quarter of the items: integer sums, any order gives the same
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+#pragma unroll
+        for (int k = 0; k < kPC; ++k) {
+            hi[h][k] += __shfl_xor(hi[h][k], 16);
+            hi[h][k] += __shfl_xor(hi[h][k], 32);
+            lo[h][k] += __shfl_xor(lo[h][k], 16);
+            lo[h][k] += __shfl_xor(lo[h][k], 32);
+        }
+        if (grp == 0 && cnt[h] > 0) multi_store(g.part, blockIdx.y, g.rows, r[h], cnt[h], hi[h], lo[h]);
+    }
+}
+
+// one wave per user: rank_multi_finish of topk_select.h with dot_pair (the bits the scan compared)
+__global__ __launch_bounds__(256) void dot_multi_finish_kernel(const MultiArgs g, int32_t *above, int32_t *below,
+                                                               float *pos_score, int32_t *n_neg) {
+    const int lane = threadIdx.x % kWave;
+    const int64_t q = (int64_t)blockIdx.x * (256 / kWave) + threadIdx.x / kWave;
+    if (q >= g.U) return;
+    int64_t u = g.unids[q];
+    if (u < 0 || u >= g.N) u = 0;        // reported by dot_multi_pos_kernel
+    rank_multi_finish(q, g.U, g.Q, g.rows, g.S, g.n_items, g.item_lo, g.pos_rowptr, g.pos_items, g.thr, g.excl_rowptr,
+                      g.excl_items, g.part, [&](int64_t node) { return dot_pair(g.repr + u * g.D, g.repr + node * g.D, g.D); },
+                      lane, above, below, pos_score, n_neg);
+}
+
+template <int DP>
+int launch_multi_scan(const MultiLayout &L, const MultiArgs &g, hipStream_t stream) {
+    const int rows_wg = kUW * kMultiNW;
+    const dim3 grid((unsigned)((g.rows + rows_wg - 1) / rows_wg), (unsigned)L.S);
+    PEA_LAUNCH(dot_multi_scan_kernel<DP>, grid, dim3(kWave * kMultiNW), L.lds, stream, g);
+    PEA_HIP(hipGetLastError());
+    return PEA_OK;
+}
+
 }  // namespace
 }  // namespace pea
 
@@ -421,4 +599,58 @@ extern "C" int pea_dot_rank_full(int64_t U, int D, int64_t num_nodes, const floa
         PEA_HIP(hipGetLastError());
     }
     return read_err_flag((int *)ws, stream, "dot_rank_full");
+}
+
+// include/peahip_eval.h
+extern "C" size_t pea_dot_rank_multi_workspace_bytes(int64_t U, int64_t Q, int64_t n_items, int D) {
+    if (U < 0 || Q < 0 || n_items < 0 || n_items >= ((int64_t)1 << 31) - 1 || D < 4 || D > 256 || D % 4 != 0) return 0;
+    return pea::make_multi_layout(U, Q, n_items, D).bytes;
+}
+
+extern "C" int pea_dot_rank_full_multi(int64_t U, int D, int64_t num_nodes, const float *repr, const int64_t *unids,
+                                       const int64_t *pos_rowptr, const int64_t *pos_items, int64_t Q, int64_t item_lo,
+                                       int64_t n_items, const int64_t *excl_rowptr, const int64_t *excl_items, int32_t *above,
+                                       int32_t *below, float *pos_score, int32_t *n_neg, void *workspace,
+                                       size_t workspace_bytes, void *stream_) {
+    using namespace pea;
+    hipStream_t stream = (hipStream_t)stream_;
+    PEA_TRY(check_d("dot_rank_full_multi", D));
+    PEA_TRY(check_catalogue("dot_rank_full_multi", U, num_nodes, item_lo, n_items));
+    PEA_REQUIRE(Q >= 0, PEA_ERR_ARG, "dot_rank_full_multi: Q=%lld", (long long)Q);
+    PEA_REQUIRE(repr && unids && pos_rowptr && pos_items && above && below && pos_score && n_neg && workspace, PEA_ERR_ARG,
+                "dot_rank_full_multi: null pointer");
+    PEA_REQUIRE(!excl_rowptr || excl_items, PEA_ERR_ARG, "dot_rank_full_multi: excl_rowptr without excl_items");
+    const MultiLayout L = make_multi_layout(U, Q, n_items, D);
+    PEA_REQUIRE(workspace_bytes >= L.bytes, PEA_ERR_NOMEM, "dot_rank_full_multi: workspace too small (%zu < %zu)",
+                workspace_bytes, L.bytes);
+    if (U == 0) return PEA_OK;
+    char *ws = (char *)workspace;
+    PEA_MEMSET_ASYNC((int *)ws, 0, sizeof(int), stream);
+    MultiArgs g;
+    g.U = U; g.Q = Q; g.rows = L.rows; g.N = num_nodes; g.n_items = n_items; g.item_lo = item_lo; g.span = L.span;
+    g.S = L.S; g.D = D; g.LD = L.LD;
+    g.repr = repr; g.unids = unids; g.pos_rowptr = pos_rowptr; g.pos_items = pos_items;
+    g.excl_rowptr = excl_rowptr; g.excl_items = excl_items;
+    g.thr = (float *)(ws + L.off_thr);
+    g.part = (int *)(ws + L.off_part);
+    g.err = (int *)ws;
+    const dim3 waves((unsigned)((U + 3) / 4));
+    {
+        ProfScope ps("dot_rank_multi_pos", stream, (double)Q * (8.0 * D + 20.0));
+        PEA_LAUNCH(dot_multi_pos_kernel, waves, dim3(256), 0, stream, g);
+        PEA_HIP(hipGetLastError());
+    }
+    if (Q > 0) {
+        ProfScope ps("dot_rank_multi_scan", stream, (double)L.rows * (double)n_items * (2.0 * D + 4.0 * kPC));
+        if (L.DP == 32) PEA_TRY(launch_multi_scan<32>(L, g, stream));
+        else if (L.DP == 64) PEA_TRY(launch_multi_scan<64>(L, g, stream));
+        else if (L.DP == 128) PEA_TRY(launch_multi_scan<128>(L, g, stream));
+        else PEA_TRY(launch_multi_scan<256>(L, g, stream));
+    }
+    {
+        ProfScope ps("dot_rank_multi_finish", stream, 8.0 * (double)Q * L.S);
+        PEA_LAUNCH(dot_multi_finish_kernel, waves, dim3(256), 0, stream, g, above, below, pos_score, n_neg);
+        PEA_HIP(hipGetLastError());
+    }
+    return read_err_flag((int *)ws, stream, "dot_rank_full_multi");
 }

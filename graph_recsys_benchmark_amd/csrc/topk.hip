@@ -10,6 +10,7 @@
 
 #include "score_common.h"
 #include "topk_select.h"
+#include "../../include/peahip_eval.h"
 
 namespace pea {
 namespace {
@@ -284,6 +285,139 @@ int launch_prep(const Layout &L, int64_t U, int64_t U_pos, int64_t n_items, int 
     return PEA_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- several positives per user
+// pea_rank_full_multi (include/peahip_eval.h): the rows, counters and finish of topk_select.h with pair_score.
+struct MultiLayout {
+    int RP = 16, S = 1;
+    int64_t span = 0, rows = 0;
+    size_t off_w2 = 0, off_a = 0, off_p = 0, off_b = 0, off_thr = 0, off_part = 0, bytes = 0;
+};
+
+constexpr int kMultiNT = 128;       // rows of one workgroup of the scan, one per lane
+
+// Depends on (U, Q, n_items, R) only: the rows are the bound multi_rows, not the rows in use.
+MultiLayout make_multi_layout(int64_t U, int64_t Q, int64_t n_items, int R) {
+    MultiLayout L;
+    L.RP = padded_r(R);
+    L.rows = multi_rows(U, Q);
+    catalogue_split(std::max<int64_t>((L.rows + kMultiNT - 1) / kMultiNT, 1), n_items, 1, kTileFloats / L.RP, &L.S, &L.span);
+    size_t o = 256;                                                           // error flag
+    L.off_w2 = o;   o = align256(o + (size_t)L.RP * 4);
+    L.off_a = o;    o = align256(o + (size_t)std::max<int64_t>(U, 1) * L.RP * 4);
+    L.off_p = o;    o = align256(o + (size_t)std::max<int64_t>(Q, 1) * L.RP * 4);
+    L.off_b = o;    o = align256(o + (size_t)std::max<int64_t>(n_items, 1) * L.RP * 4);
+    L.off_thr = o;  o = align256(o + (size_t)std::max<int64_t>(Q, 1) * 4);
+    L.off_part = o; o = align256(o + (size_t)L.S * 2 * kPC * std::max<int64_t>(L.rows, 1) * 4);
+    L.bytes = o;
+    return L;
+}
+
+struct MultiArgs {
+    int64_t U, Q, rows, n_items, item_lo, span;
+    int S;
+    const float *A, *B, *P, *w2, *fc2_b;
+    const int64_t *pos_rowptr, *pos_items, *excl_rowptr, *excl_items;
+    float *thr;      // [Q] the positives' scores
+    int *part;       // [S, 2, kPC, rows] counts of (s > t), (s < t)
+};
+
+// one wave per user: multi_thresholds with pair_score on the rows topk_prep wrote
+template <int RP>
+__global__ __launch_bounds__(256) void rank_multi_pos_kernel(const MultiArgs g) {
+    const int lane = threadIdx.x % kWave;
+    const int64_t q = (int64_t)blockIdx.x * (256 / kWave) + threadIdx.x / kWave;
+    if (q >= g.U) return;
+    float a[RP];
+    load_half<RP>(g.A + q * RP, a);
+    const float b2 = g.fc2_b[0];
+    multi_thresholds(q, g.Q, g.pos_rowptr, lane, [&](int64_t j) { return pair_score<RP>(a, g.P + j * RP, g.w2, b2); }, g.thr);
+}
+
+// topk_scan_kernel's RANK loop with a (user, chunk) row per lane and multi_count over T thresholds in place of the two
+// counters.  Both instantiations are launched over all the rows: T = 1 takes the workgroups whose rows hold one threshold
+// at the most (with one positive per user that is every workgroup, at the registers and occupancy of the single-positive
+// scan), T = kPC the others; a workgroup that is not this kernel's, or whose rows are all idle, leaves at once.
+template <int RP, int T>
+__global__ __launch_bounds__(kMultiNT) void rank_multi_scan_kernel(const MultiArgs g) {
+    constexpr int NT = kMultiNT, TI = kTileFloats / RP;
+    float *tile = topk_smem;
+    const int tid = threadIdx.x;
+    const int64_t r = (int64_t)blockIdx.x * NT + tid;
+    int64_t q = 0, first = 0;
+    int n = 0;
+    if (r < g.rows) multi_row(r, g.U, g.Q, g.pos_rowptr, q, first, n);
+    const bool many = __syncthreads_or(n > 1) != 0;
+    if (T == 1 ? (many || !__syncthreads_or(n > 0)) : !many) return;
+    float a[RP];
+    load_half<RP>(g.A + q * RP, a);
+    const float b2 = g.fc2_b[0];
+    float thr[T];
+    int hi[T], lo[T];
+#pragma unroll
+    for (int k = 0; k < T; ++k) {
+        thr[k] = k < n ? g.thr[first + k] : 0.f;
+        hi[k] = lo[k] = 0;
+    }
+    const int64_t i0 = (int64_t)blockIdx.y * g.span;
+    const int64_t i1 = i0 + g.span < g.n_items ? i0 + g.span : g.n_items;
+    for (int64_t t0 = i0; t0 < i1; t0 += TI) {
+        const int nt = (int)(i1 - t0 < TI ? i1 - t0 : TI);
+        __syncthreads();
+        for (int x = tid; x < nt * (RP / 4); x += NT)
+            reinterpret_cast<float4 *>(tile)[x] = ld4(g.B + t0 * RP + (int64_t)x * 4);
+        __syncthreads();
+        // rows past nt inside the tile are scored from stale LDS and ignored, as in topk_scan_kernel
+        for (int j0 = 0; j0 < nt; j0 += 4) {
+            float s4[4];
+            pair_score4<RP>(a, tile + j0 * RP, g.w2, b2, s4);
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj) {
+                if (j0 + jj >= nt) break;
+                multi_count<T>(s4[jj], thr, hi, lo);
+            }
+        }
+    }
+    if (n > 0) multi_store(g.part, blockIdx.y, g.rows, r, n, hi, lo);
+}
+
+// one wave per user: rank_multi_finish of topk_select.h with pair_score on the rows the scan compared (the same bits)
+template <int RP>
+__global__ __launch_bounds__(256) void rank_multi_finish_kernel(const MultiArgs g, int32_t *above, int32_t *below,
+                                                                float *pos_score, int32_t *n_neg) {
+    const int lane = threadIdx.x % kWave;
+    const int64_t q = (int64_t)blockIdx.x * (256 / kWave) + threadIdx.x / kWave;
+    if (q >= g.U) return;
+    float a[RP];
+    load_half<RP>(g.A + q * RP, a);
+    const float b2 = g.fc2_b[0];
+    rank_multi_finish(q, g.U, g.Q, g.rows, g.S, g.n_items, g.item_lo, g.pos_rowptr, g.pos_items, g.thr, g.excl_rowptr,
+                      g.excl_items, g.part,
+                      [&](int64_t node) { return pair_score<RP>(a, g.B + (node - g.item_lo) * RP, g.w2, b2); }, lane, above,
+                      below, pos_score, n_neg);
+}
+
+template <int RP>
+int launch_multi(const MultiArgs &g, int R, int32_t *above, int32_t *below, float *pos_score, int32_t *n_neg, hipStream_t stream) {
+    const dim3 waves((unsigned)((g.U + 3) / 4));
+    if (g.Q > 0) {
+        {
+            ProfScope ps("rank_multi_pos", stream, (double)g.Q * (4.0 * RP + 4.0));
+            PEA_LAUNCH(rank_multi_pos_kernel<RP>, waves, dim3(256), 0, stream, g);
+            PEA_HIP(hipGetLastError());
+        }
+        ProfScope ps("rank_multi_scan", stream, (double)g.rows * (double)g.n_items * (3.0 * R + 4.0 * kPC));
+        const size_t lds = (size_t)kTileFloats * 4;
+        const dim3 grid((unsigned)((g.rows + kMultiNT - 1) / kMultiNT), (unsigned)g.S);
+        PEA_LAUNCH((rank_multi_scan_kernel<RP, 1>), grid, dim3(kMultiNT), lds, stream, g);
+        PEA_LAUNCH((rank_multi_scan_kernel<RP, kPC>), grid, dim3(kMultiNT), lds, stream, g);
+        PEA_HIP(hipGetLastError());
+    }
+    ProfScope ps("rank_multi_finish", stream, 8.0 * (double)g.Q * g.S);
+    PEA_LAUNCH(rank_multi_finish_kernel<RP>, waves, dim3(256), 0, stream, g, above, below, pos_score, n_neg);
+    PEA_HIP(hipGetLastError());
+    return PEA_OK;
+}
+
 }  // namespace
 }  // namespace pea
 
@@ -373,4 +507,46 @@ extern "C" int pea_rank_full(int64_t U, int R, int64_t num_nodes, const float *r
         PEA_HIP(hipGetLastError());
     }
     return read_err_flag((int *)ws, stream, "rank_full");
+}
+
+// include/peahip_eval.h
+extern "C" size_t pea_rank_multi_workspace_bytes(int64_t U, int64_t Q, int64_t n_items, int R) {
+    if (U < 0 || Q < 0 || n_items < 0 || n_items >= ((int64_t)1 << 31) - 1 || R <= 0 || R > 64 || R % 4 != 0) return 0;
+    return pea::make_multi_layout(U, Q, n_items, R).bytes;
+}
+
+extern "C" int pea_rank_full_multi(int64_t U, int R, int64_t num_nodes, const float *repr, const int64_t *unids,
+                                   const int64_t *pos_rowptr, const int64_t *pos_items, int64_t Q, int64_t item_lo,
+                                   int64_t n_items, const int64_t *excl_rowptr, const int64_t *excl_items, const float *fc1_w,
+                                   const float *fc1_b, const float *fc2_w, const float *fc2_b, int32_t *above, int32_t *below,
+                                   float *pos_score, int32_t *n_neg, void *workspace, size_t workspace_bytes, void *stream_) {
+    using namespace pea;
+    hipStream_t stream = (hipStream_t)stream_;
+    PEA_TRY(check_r("rank_full_multi", R));
+    PEA_TRY(check_catalogue("rank_full_multi", U, num_nodes, item_lo, n_items));
+    PEA_REQUIRE(Q >= 0, PEA_ERR_ARG, "rank_full_multi: Q=%lld", (long long)Q);
+    PEA_REQUIRE(repr && unids && pos_rowptr && pos_items && fc1_w && fc1_b && fc2_w && fc2_b && above && below && pos_score &&
+                    n_neg && workspace,
+                PEA_ERR_ARG, "rank_full_multi: null pointer");
+    PEA_REQUIRE(!excl_rowptr || excl_items, PEA_ERR_ARG, "rank_full_multi: excl_rowptr without excl_items");
+    const MultiLayout L = make_multi_layout(U, Q, n_items, R);
+    PEA_REQUIRE(workspace_bytes >= L.bytes, PEA_ERR_NOMEM, "rank_full_multi: workspace too small (%zu < %zu)", workspace_bytes,
+                L.bytes);
+    if (U == 0) return PEA_OK;
+    char *ws = (char *)workspace;
+    PEA_MEMSET_ASYNC((int *)ws, 0, sizeof(int), stream);
+    Layout prep;
+    prep.RP = L.RP; prep.off_w2 = L.off_w2; prep.off_a = L.off_a; prep.off_p = L.off_p; prep.off_b = L.off_b;
+    PEA_TRY(launch_prep(prep, U, Q, n_items, R, num_nodes, repr, unids, pos_items, item_lo, fc1_w, fc1_b, fc2_w, ws, stream));
+    MultiArgs g;
+    g.U = U; g.Q = Q; g.rows = L.rows; g.n_items = n_items; g.item_lo = item_lo; g.span = L.span; g.S = L.S;
+    g.A = (const float *)(ws + L.off_a); g.B = (const float *)(ws + L.off_b); g.P = (const float *)(ws + L.off_p);
+    g.w2 = (const float *)(ws + L.off_w2); g.fc2_b = fc2_b;
+    g.pos_rowptr = pos_rowptr; g.pos_items = pos_items; g.excl_rowptr = excl_rowptr; g.excl_items = excl_items;
+    g.thr = (float *)(ws + L.off_thr);
+    g.part = (int *)(ws + L.off_part);
+    if (L.RP == 16) PEA_TRY(launch_multi<16>(g, R, above, below, pos_score, n_neg, stream));
+    else if (L.RP == 32) PEA_TRY(launch_multi<32>(g, R, above, below, pos_score, n_neg, stream));
+    else PEA_TRY(launch_multi<64>(g, R, above, below, pos_score, n_neg, stream));
+    return read_err_flag((int *)ws, stream, "rank_full_multi");
 }

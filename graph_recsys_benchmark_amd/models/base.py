@@ -44,7 +44,8 @@ class GraphRecsysModel(torch.nn.Module):
         raise NotImplementedError
 
     def scored(self, op, *args, **kwargs):
-        """engine.<op> of this model's scorer on cached_repr, op one of 'predict', 'rank_eval', 'recommend_topk', 'rank_full':
+        """engine.<op> of this model's scorer on cached_repr, op one of 'predict', 'rank_eval', 'recommend_topk', 'rank_full',
+        'rank_full_multi':
         engine.dot_<op>(cached_repr, *args) under 'dot', engine.<op>(cached_repr, *args, fc1 / fc2 parameters) under 'mlp'.
         solvers.py calls it unbound on whatever model object it is handed: one that names no scorer is an 'mlp' model."""
         scorer = getattr(self, 'scorer', 'mlp')

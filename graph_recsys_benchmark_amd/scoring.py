@@ -1,6 +1,7 @@
 """Scoring and evaluation on a table of node rows: the BPR score of a batch, the entity regulariser, the ablation fusion and
-the four scoring operations (predict, candidate ranking, catalogue top-K, catalogue ranking).  Each has ONE host body for the
-fc1 / fc2 scorer (pea_*) and the inner product (pea_dot_*): `fc` is the four fc tensors or None (_scorer)."""
+the five scoring operations (predict, candidate ranking, catalogue top-K, catalogue ranking, catalogue ranking with several
+positives per user).  Each has ONE host body for the fc1 / fc2 scorer (pea_*) and the inner product (pea_dot_*): `fc` is the
+four fc tensors or None (_scorer)."""
 import ctypes as C
 
 import torch
@@ -169,7 +170,8 @@ def _scorer(op, repr_, fc):
     """The two forms of scoring operation `op` behind one call.  Returns (table, run, query): run(head, tail) launches
     pea_dot_<op>(*head, *tail, stream) for fc None (the inner product, over a table that _dot_table has checked), else
     pea_<op>(*head, the four fc pointers, *tail, stream): the fc pointers sit where include/peahip.h has them.  run raises like
-    _check_scored; query is the form's topk_workspace_bytes entry point."""
+    _check_scored; query is the form's workspace query for `op`: rank_multi_workspace_bytes for 'rank_full_multi'
+    (include/peahip_eval.h), topk_workspace_bytes for the rest."""
     lib = _lib.require_device()
     if fc is None:
         prefix, table, fc = 'pea_dot_', repr_, ()
@@ -178,7 +180,8 @@ def _scorer(op, repr_, fc):
 
     def run(head, tail):
         _check_scored(getattr(lib, prefix + op)(*head, *[_lib.ptr(t) for t in fc], *tail, _lib.current_stream()))
-    return table, run, getattr(lib, prefix + 'topk_workspace_bytes')
+    query = 'rank_multi_workspace_bytes' if op == 'rank_full_multi' else 'topk_workspace_bytes'
+    return table, run, getattr(lib, prefix + query)
 
 
 def _catalogue_args(repr_, unids, item_range, exclude):
@@ -253,6 +256,35 @@ def _rank_full(repr_, unids, pos_items, item_range, exclude, fc):
     return rank, auc, pos_score
 
 
+def _rank_full_multi(repr_, unids, pos_rowptr, pos_items, item_range, exclude, fc):
+    table, run, query = _scorer('rank_full_multi', repr_, fc)
+    unids, item_lo, n_items, rowptr, items = _catalogue_args(table, unids, item_range, exclude)
+    u, r, dev = unids.shape[0], table.shape[1], table.device
+    for t in (pos_rowptr, pos_items):
+        if not torch.is_tensor(t) or t.dtype != torch.int64 or t.dim() != 1:
+            raise ValueError('positives are (pos_rowptr int64 [U + 1], pos_items int64 [Q]) -- see utils.interactions.positives_csr')
+        if t.device != dev:
+            raise ValueError('the positives must live on the device of the table')
+    if pos_rowptr.numel() != u + 1:
+        raise ValueError('pos_rowptr must have one entry per requested user and one more')
+    pos_rowptr, pos_items = pos_rowptr.contiguous(), pos_items.contiguous()
+    q = pos_items.numel()
+    above, below = (torch.empty(q, dtype=torch.int32, device=dev) for _ in range(2))
+    pos_score = torch.empty(q, dtype=torch.float32, device=dev)
+    n_neg = torch.empty(u, dtype=torch.int32, device=dev)
+    if u == 0:                                  # nobody asked: an empty tensor has no address to hand to the C side
+        return above, below, pos_score, n_neg
+    ws_bytes = int(query(u, q, n_items, r))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    # a valid address for the C side even where there is nothing to read or write
+    spare = torch.zeros(2, dtype=torch.int64, device=dev) if q == 0 else None
+    at = _lib.ptr if q else (lambda t: _lib.ptr(spare))
+    run((u, r, table.shape[0], _lib.ptr(table), _lib.ptr(unids), _lib.ptr(pos_rowptr), at(pos_items), q, item_lo, n_items,
+         _lib.ptr(rowptr), _lib.ptr(items)),
+        (at(above), at(below), at(pos_score), _lib.ptr(n_neg), _lib.ptr(ws), ws_bytes))
+    return above, below, pos_score, n_neg
+
+
 def predict(repr_, unids, inids, fc1_w, fc1_b, fc2_w, fc2_b):
     """fc2(relu(fc1([repr[u] || repr[i]]))) -> [B, 1]  (reference models/base.py:208-214)."""
     check_pending_errors()
@@ -319,3 +351,21 @@ def dot_rank_full(repr_, unids, pos_items, item_range, exclude=None):
     pos_score [U]).  include/peahip.h, pea_dot_rank_full."""
     check_pending_errors()
     return _rank_full(_dot_table(repr_), unids, pos_items, item_range, exclude, None)
+
+
+def rank_full_multi(repr_, unids, pos_rowptr, pos_items, item_range, fc1_w, fc1_b, fc2_w, fc2_b, exclude=None):
+    """rank_full for users with any number of held-out positives, in one catalogue scan (include/peahip_eval.h,
+    pea_rank_full_multi).  The positives are a CSR (pos_rowptr int64 [U + 1], pos_items int64 [Q]) on the table's device,
+    every row strictly ascending (utils.interactions.positives_csr); a user's negatives are the catalogue items in neither
+    its exclusion row nor its positive row.  Returns, in the flat order of pos_items, (above int32 [Q] = negatives scoring
+    strictly higher, below int32 [Q] = negatives scoring strictly lower, pos_score [Q]) and n_neg int32 [U]: the integers
+    rank_full gives for (user, positive j) when the user's other positives are excluded too."""
+    check_pending_errors()
+    return _rank_full_multi(repr_, unids, pos_rowptr, pos_items, item_range, exclude, (fc1_w, fc1_b, fc2_w, fc2_b))
+
+
+def dot_rank_full_multi(repr_, unids, pos_rowptr, pos_items, item_range, exclude=None):
+    """rank_full_multi with the inner-product scorer (include/peahip_eval.h, pea_dot_rank_full_multi): (above int32 [Q],
+    below int32 [Q], pos_score [Q], n_neg int32 [U])."""
+    check_pending_errors()
+    return _rank_full_multi(_dot_table(repr_), unids, pos_rowptr, pos_items, item_range, exclude, None)

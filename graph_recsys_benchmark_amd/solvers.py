@@ -11,7 +11,7 @@ import torch
 
 from . import engine
 from .models.base import GraphRecsysModel
-from .utils.interactions import seen_items_csr
+from .utils.interactions import positives_csr, seen_items_csr
 from .utils.sampling import generate_candidates
 
 NUM_RECS_RANGE = 20   # utils/rec_utils.py:4
@@ -154,3 +154,150 @@ def metrics_full_from_dataset(model, dataset):
     u_t = torch.as_tensor(np.asarray(u_nids, dtype=np.int64), device=dev)
     exclude = seen_items_csr(dataset.edge_index_nps['user2item'], u_t, item_range)
     return metrics_full(model, u_nids, pos, item_range, exclude)
+
+
+# ---- several held-out positives per user (engine.rank_full_multi; include/peahip_eval.h)
+MULTI_METRICS = ('HR', 'NDCG_ref', 'Recall', 'Precision', 'NDCG', 'MRR', 'AP', 'AUC')
+
+
+def multi_metrics_from_counts(above, pos_score, below, pos_rowptr, n_neg):
+    """Per-user metrics of an all-item ranking with any number of positives, in float64 from the integer counts of
+    engine.rank_full_multi: above / below [Q] (negatives scoring strictly higher / lower than flat positive j), pos_score [Q],
+    pos_rowptr [U + 1], n_neg [U].  The 0-based place of positive j in the user's merged descending list is
+        r_j = above_j + #{j' of the same user: s_j' > s_j, or s_j' == s_j and j' < j}
+    (a positive goes ahead of an equal negative, as rank_one_user has it and as the stable sort of reference solvers.py:88 does
+    with the positives first; ties among positives go by row order).  With h_k = #{r_j < k}, r_min = min r_j and P the user's
+    positives, for k = 5 .. NUM_RECS_RANGE (columns) the dict holds
+        'HR' [U, 16]         [r_min < k]                                    utils/rec_utils.py:7 hit()
+        'NDCG_ref' [U, 16]   h_k / log2(r_min + 2) if r_min < k else 0      utils/rec_utils.py:18 ndcg(), exactly: the hits of
+                             the first k places over the discount of the FIRST hit alone, not a normalised DCG
+        'Recall' [U, 16]     h_k / P
+        'Precision' [U, 16]  h_k / k
+        'NDCG' [U, 16]       sum over r_j < k of 1 / log2(r_j + 2), over sum over i < min(P, k) of 1 / log2(i + 2)
+        'MRR' [U]            1 / (r_min + 1)
+        'AP' [U]             mean over the positives in rank order m = 1 .. P of m / (r_(m) + 1)
+        'AUC' [U]            sum of below_j over P n_neg                    utils/rec_utils.py:28 auc()
+    A user without a positive or without a negative has nan rows here; metrics_full_multi refuses such a user."""
+    above = np.asarray(above, dtype=np.int64).reshape(-1)
+    below = np.asarray(below, dtype=np.int64).reshape(-1)
+    score = np.asarray(pos_score).reshape(-1)
+    rowptr = np.asarray(pos_rowptr, dtype=np.int64).reshape(-1)
+    n_neg = np.asarray(n_neg, dtype=np.int64).reshape(-1)
+    u = rowptr.size - 1
+    if above.size != below.size or above.size != score.size or n_neg.size != u or (u >= 0 and rowptr[-1] != above.size):
+        raise ValueError('above, below, pos_score are [Q] with Q = pos_rowptr[U], n_neg is [U]')
+    ks = np.arange(5, NUM_RECS_RANGE + 1)
+    out = {name: np.full((u, ks.size) if name in ('HR', 'NDCG_ref', 'Recall', 'Precision', 'NDCG') else (u,), np.nan)
+           for name in MULTI_METRICS}
+    disc = 1.0 / np.log2(np.arange(NUM_RECS_RANGE, dtype=np.float64) + 2.0)        # of places 0 .. 19
+    ideal = np.cumsum(disc)
+    for q in range(u):
+        b, e = int(rowptr[q]), int(rowptr[q + 1])
+        p = e - b
+        if p == 0:
+            continue
+        s = score[b:e]
+        ahead = (s[None, :] > s[:, None]) | ((s[None, :] == s[:, None]) & (np.arange(p)[None, :] < np.arange(p)[:, None]))
+        r = np.sort(above[b:e] + ahead.sum(axis=1))                # r_(1) <= r_(2) <= ...: distinct places
+        r_min = int(r[0])
+        h = (r[None, :] < ks[:, None]).sum(axis=1).astype(np.float64)
+        out['HR'][q] = (r_min < ks).astype(np.float64)
+        out['NDCG_ref'][q] = np.where(r_min < ks, h / np.log2(r_min + 2.0), 0.0)
+        out['Recall'][q] = h / p
+        out['Precision'][q] = h / ks
+        gain = np.where(r < NUM_RECS_RANGE, disc[np.minimum(r, NUM_RECS_RANGE - 1)], 0.0)
+        dcg = np.array([gain[r < k].sum() for k in ks])
+        out['NDCG'][q] = dcg / ideal[np.minimum(p, ks) - 1]
+        out['MRR'][q] = 1.0 / (r_min + 1.0)
+        out['AP'][q] = np.mean(np.arange(1, p + 1, dtype=np.float64) / (r + 1.0))
+        if n_neg[q] > 0:
+            out['AUC'][q] = float(below[b:e].sum()) / (float(p) * float(n_neg[q]))
+    return out
+
+
+def _exclude_rows(exclude, u):
+    """the exclusion CSR as U numpy rows (empty rows for None)"""
+    if exclude is None:
+        return [np.zeros(0, dtype=np.int64)] * u
+    rowptr, items = (t.detach().cpu().numpy() for t in exclude)
+    return [items[rowptr[q]:rowptr[q + 1]] for q in range(u)]
+
+
+def rank_full_multi_flattened(rank_full, u_nids, pos_rowptr, pos_items, item_range, exclude=None, device=None):
+    """engine.rank_full_multi's outputs from a SINGLE-positive rank_full(unids, pos_items, item_range, exclude=) -> (rank, auc,
+    pos_score): one call over the Q (user, positive) pairs, the user repeated, each pair's exclusion row the sorted,
+    de-duplicated union of the user's exclusion row and its positive row (rank_full skips the positive itself).  Then
+    above = rank, pos_score as is, n_neg = the catalogue items outside that union, below = round(auc n_neg): auc is the
+    float32 quotient below / n_neg, off by at most 2^-24 of itself, so the product is within one half of below for a catalogue
+    of fewer than 2^23 items (a larger one is refused).  Pays the catalogue scan once per positive: the route of a model that has a rank_full of its own only (models/walk.py), and the yardstick the native
+    route is tested and measured against.  Returns numpy (above int64 [Q], below int64 [Q], pos_score float32 [Q], n_neg
+    int64 [U])."""
+    u_nids = np.asarray(u_nids, dtype=np.int64).reshape(-1)
+    rowptr = np.asarray(pos_rowptr, dtype=np.int64).reshape(-1)
+    items = np.asarray(pos_items, dtype=np.int64).reshape(-1)
+    lo, hi = int(item_range[0]), int(item_range[1])
+    if hi - lo >= 1 << 23:
+        raise ValueError('the flattened route recovers `below` from a float32 auc: catalogues of fewer than 2^23 items only')
+    excl = _exclude_rows(exclude, u_nids.size)
+    unions, n_neg = [], np.zeros(u_nids.size, dtype=np.int64)
+    for q in range(u_nids.size):
+        un = np.union1d(excl[q], items[rowptr[q]:rowptr[q + 1]]).astype(np.int64)
+        unions.append(un)
+        n_neg[q] = (hi - lo) - int(((un >= lo) & (un < hi)).sum())
+    counts = np.diff(rowptr)
+    flat_q = np.repeat(np.arange(u_nids.size), counts)
+    if items.size == 0:
+        return np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.float32), n_neg
+    f_rowptr = np.zeros(items.size + 1, dtype=np.int64)
+    np.cumsum([unions[q].size for q in flat_q], out=f_rowptr[1:])
+    f_items = np.concatenate([unions[q] for q in flat_q]) if f_rowptr[-1] else np.zeros(0, dtype=np.int64)
+    to = (lambda a: torch.as_tensor(a, device=device)) if device is not None else torch.as_tensor
+    rank, auc, pos_score = rank_full(to(u_nids[flat_q]), to(items), item_range, exclude=(to(f_rowptr), to(f_items)))
+    above = rank.detach().cpu().numpy().astype(np.int64)
+    below = np.rint(auc.detach().cpu().numpy().astype(np.float64) * n_neg[flat_q]).astype(np.int64)
+    return above, below, pos_score.detach().cpu().numpy(), n_neg
+
+
+def metrics_full_multi(model, u_nids, positives, item_range, exclude=None):
+    """Unsampled evaluation with any number of held-out positives per user (the ratio-split protocol KGAT / NGCF / KGCN were
+    published under): a user's negatives are the catalogue items in neither its exclusion row nor its positives.  positives:
+    what utils.interactions.positives_csr takes (a sequence of U lists, or [2, E] test edges), or its (pos_rowptr, pos_items)
+    result.  Returns the dict of multi_metrics_from_counts reduced to means over the users ([16] for k = 5 .. 20, or a
+    scalar).  Raises ValueError('No pos or neg samples found in evaluation!') for a user with no positive or no negative, as
+    reference solvers.py:60-61.  One catalogue scan through GraphRecsysModel.scored(model, 'rank_full_multi', ...); a model
+    with a rank_full of its own and no rank_full_multi goes through rank_full_multi_flattened on it.  `model` must be in
+    eval() mode; exclude = (rowptr, items) on the model's device."""
+    dev = model.cached_repr.device
+    u_t = torch.as_tensor(np.asarray(u_nids, dtype=np.int64), device=dev)
+    if isinstance(positives, tuple) and len(positives) == 2 and all(torch.is_tensor(t) and t.dim() == 1 for t in positives):
+        pos_rowptr, pos_items = (t.to(dev) for t in positives)
+    else:
+        pos_rowptr, pos_items = positives_csr(positives, u_t)
+    rowptr_np = pos_rowptr.cpu().numpy()
+    if u_t.numel() == 0 or np.any(np.diff(rowptr_np) == 0):
+        raise ValueError("No pos or neg samples found in evaluation!")
+    if hasattr(model, 'rank_full_multi'):
+        above, below, pos_score, n_neg = model.rank_full_multi(u_t, pos_rowptr, pos_items, item_range, exclude=exclude)
+    elif hasattr(model, 'rank_full'):
+        above, below, pos_score, n_neg = rank_full_multi_flattened(model.rank_full, u_t.cpu().numpy(), rowptr_np,
+                                                                   pos_items.cpu().numpy(), item_range, exclude, device=dev)
+    else:
+        above, below, pos_score, n_neg = GraphRecsysModel.scored(model, 'rank_full_multi', u_t, pos_rowptr, pos_items, item_range,
+                                                                 exclude=exclude)
+    above, below, pos_score, n_neg = (t.cpu().numpy() if torch.is_tensor(t) else t for t in (above, below, pos_score, n_neg))
+    if np.any(np.asarray(n_neg) <= 0):
+        raise ValueError("No pos or neg samples found in evaluation!")
+    per_user = multi_metrics_from_counts(above, pos_score, below, rowptr_np, n_neg)
+    return {name: v.mean(axis=0) for name, v in per_user.items()}
+
+
+def metrics_full_multi_from_dataset(model, dataset):
+    """metrics_full_multi with users and positives from dataset.test_pos_unid_inid_map (lists of any length), the item block from
+    dataset.type_accs / num_iids and the exclusion from dataset.edge_index_nps['user2item']."""
+    u_nids = list(dataset.test_pos_unid_inid_map.keys())
+    positives = [dataset.test_pos_unid_inid_map[u_nid] for u_nid in u_nids]
+    item_range = (dataset.type_accs['iid'], dataset.type_accs['iid'] + dataset.num_iids)
+    dev = model.cached_repr.device
+    u_t = torch.as_tensor(np.asarray(u_nids, dtype=np.int64), device=dev)
+    exclude = seen_items_csr(dataset.edge_index_nps['user2item'], u_t, item_range)
+    return metrics_full_multi(model, u_nids, positives, item_range, exclude)
