@@ -21,6 +21,10 @@ code acting on those conv outputs.
 
 Fixtures are numbers only: inputs (x, parameters, edge lists, batches) and
 outputs (per-channel reps, fused cached_repr, predictions, losses).
+
+`python oracle/make_golden.py` rewrites every fixture but the headline ones; `python oracle/make_golden.py headline
+[--out DIR]` writes only tests/golden/headline_*.npz and headline_*.grad.npz (the reference's default widths, with the
+gradients of its own loss.backward(); see make_headline_case).
 """
 import importlib
 import json
@@ -508,7 +512,188 @@ def make_graph_input_tables():
     print('graph_input_tables.json', {k: len(v) for k, v in out.items()})
 
 
+# ------------------------------------------------------------------------------------------------------------
+# the headline cases: the reference's default widths (experiments/pea*_solver_bpr.py: emb 64, hidden 64, repr 16, one head,
+# nine 2-step metapaths), where the two-step schedules (csrc/mlp2.hip, csrc/mlp2_bwd.hip) engage, with the gradients of
+# the reference's own loss.backward().    python oracle/make_golden.py headline [--out DIR]
+# ------------------------------------------------------------------------------------------------------------
+HEADLINE_BLOCKS = (('user', 40), ('item', 56), ('year', 6), ('actor', 9), ('director', 5), ('writer', 5), ('genre', 4), ('tag', 8))
+HEADLINE_SIZE_CAP = 406774      # bytes of the largest file the repository carried before (tests/golden/checkpoints/PEASage_ea0.pt)
+HEADLINE_CASES = (              # name, kind, emb == hidden, metapaths (1-based, of the reference's nine), seed
+    ('headline_gat_att', 'gat', 64, (1, 2, 3, 4, 5, 6, 7, 8, 9), 3030),
+    ('headline_gcn_att', 'gcn', 64, (1, 2, 3, 4, 5, 6, 7, 8, 9), 3031),
+    ('headline_sage_att', 'sage', 64, (1, 2, 3, 8, 9), 3032),       # two matrices per layer: nine channels would break the cap
+    ('headline_gcn_att_w128', 'gcn', 128, (1, 2, 9), 3033))
+
+
+def headline_hin(seed, e_u2i=1400, e_attr=70):
+    """A small HIN in the reference's id layout with the eight relations of the Movielens latest-small branch of
+    update_pea_graph_input: N = 136 (3 isolated trailing nodes); user2item with Zipf item popularity (item 1 takes several
+    hundred in-edges: a long row, and a hub row under PEA_CHUNK=64), every user -> item 0, multi-edges, and no in-edge at
+    any node that is not an item; tag2item with repeated pairs; tag2user with a few explicit self loops (dropped by GAT / GCN,
+    kept by SAGE), as tiny_hin has.  Returns (n, {block: (first, one past last)}, edge_index_nps as the reference keeps them)."""
+    rng = np.random.default_rng(seed)
+    blocks, at = {}, 0
+    for name, size in HEADLINE_BLOCKS:
+        blocks[name] = (at, at + size)
+        at += size
+    n = at + 3
+    (u0, u1), (i0, i1) = blocks['user'], blocks['item']
+    users = rng.integers(u0, u1, size=e_u2i)
+    items = i0 + rng.zipf(1.3, size=e_u2i) % (i1 - i0)
+    hub = np.stack([np.arange(u0, u1), np.full(u1 - u0, i0)])
+    rel = {'user2item': np.concatenate([np.stack([users, items]), hub], axis=1)}
+    for name in ('year', 'actor', 'director', 'writer', 'genre', 'tag'):
+        a = np.stack([rng.integers(*blocks[name], size=e_attr), rng.integers(i0, i1, size=e_attr)])
+        if name == 'tag':
+            a = np.concatenate([a, a[:, :20]], axis=1)                       # repeated pairs
+        rel[name + '2item'] = a
+    t2u = np.stack([rng.integers(*blocks['tag'], size=60), rng.integers(u0, u1, size=60)])
+    loops = np.concatenate([np.arange(i0, i0 + 5), np.arange(u0 + 2, u0 + 4)])
+    rel['tag2user'] = np.concatenate([t2u, np.stack([loops, loops])], axis=1)   # explicit self loops
+    return n, blocks, {k: v.astype(np.float64) for k, v in rel.items()}
+
+
+def load_reference_graph_input():
+    """utils/general_utils.py:update_pea_graph_input, loaded the way make_graph_input_tables loads it."""
+    ds_stub = types.ModuleType('graph_recsys_benchmark.datasets')
+    ds_stub.MovieLens, ds_stub.Yelp = type('MovieLens', (), {}), type('Yelp', (), {})
+    sys.modules['graph_recsys_benchmark.datasets'] = ds_stub
+    return importlib.import_module('graph_recsys_benchmark.utils.general_utils').update_pea_graph_input
+
+
+def make_headline_case(mods, graph_input, name, kind, width, picked, seed, out_dir):
+    """<name>.npz in the key layout of make_case (the reference model run in float32) and <name>.grad.npz: the gradients of
+    the reference's own model.loss(batch).backward() in training mode, run on a .double() copy of the same model and rounded
+    to float32 for storage.  Returns the two file sizes and the measured fraction of the gradient rule
+    (tests/helpers.py: grad_rule_fraction) that the reference's float32 run uses against its float64 run."""
+    import copy
+    import helpers as H             # tests/helpers.py: the gradient rule is written down once
+    torch.manual_seed(seed)
+    np.random.seed(seed)
+    random.seed(seed)
+    n, blocks, rel = headline_hin(seed)
+    fake = types.SimpleNamespace(edge_index_nps=rel)
+    full = graph_input({'dataset': 'Movielens', 'name': 'latest-small'}, {'device': 'cpu'}, fake)
+    assert len(full) == 9
+    mpl = [full[q - 1] for q in picked]
+    steps = [len(eil) for eil in mpl]
+    ModelBase = {'gat': mods['peagat'].PEAGATRecsysModel, 'gcn': mods['peagcn'].PEAGCNRecsysModel,
+                 'sage': mods['peasage'].PEASageRecsysModel}[kind]
+
+    class PEAModel(ModelBase):
+        def update_graph_input(self, dataset):
+            return mpl
+
+    model = PEAModel(entity_aware=False, entity_aware_coff=0.1, meta_path_steps=steps, if_use_features=False, channel_aggr='att',
+                     dataset={'num_nodes': n}, num_nodes=n, emb_dim=width, hidden_size=width, repr_dim=16, num_heads=1, dropout=0)
+    with torch.no_grad():                       # trained-like magnitudes and non-zero biases, as make_case does
+        for pname, p in model.named_parameters():
+            if pname.endswith('bias'):
+                p.copy_(torch.randn_like(p) * 0.1)
+            elif pname != 'x':
+                p.mul_(1.5)
+    model64 = copy.deepcopy(model).double()     # before the first backward: cached_repr is not a leaf afterwards
+
+    fx = {'param/' + k: v.detach().numpy().copy() for k, v in model.state_dict().items()}
+    for p, eil in enumerate(mpl):
+        for s, ei in enumerate(eil):
+            fx['edge/%d/%d' % (p, s)] = ei.numpy()
+    for k, v in rel.items():                    # the relations by name: tests hold edge/p/s against graph_input_tables.json
+        fx['rel/' + k] = v.astype(np.int64)
+    meta = dict(kind=kind, heads=1, channel_aggr='att', steps=steps, num_nodes=n, emb_dim=width, hidden_size=width, repr_dim=16,
+                entity_aware=False, gcn_deg_from='row', seed=seed, metapaths=list(picked), blocks={k: list(v) for k, v in blocks.items()})
+
+    rng = np.random.default_rng(seed + 1)
+    B = 96
+    # negatives cycle over six fixed items: drawn like the positives, the scorer's gradients cancel and float32 has no room
+    # under a rule relative to the gradient's size (tests/helpers.py: density_batch)
+    anchors = blocks['item'][0] + np.array([2, 9, 17, 30, 41, 50])
+    batch = np.stack([rng.integers(*blocks['user'], size=B), rng.integers(*blocks['item'], size=B),
+                      anchors[np.arange(B) % 6]], axis=1).astype(np.int64)
+    bt = torch.from_numpy(batch)
+    fx['in/batch'] = batch
+    with torch.no_grad():
+        for p, ch in enumerate(model.pea_channels):
+            fx['out/channel/%d' % p] = ch(model.x, mpl[p]).numpy()
+        model.eval()
+        fx['out/repr'] = model.cached_repr.numpy().copy()
+        for masked in (1, 6):                   # channel 1 ends in user2item; channel 6 sits inside the flip(user2item) group
+            if masked < len(mpl):
+                model.eval(masked)
+                fx['out/repr_mask%d' % masked] = model.cached_repr.numpy().copy()
+        model.eval()
+        fx['out/pos'] = model.predict(bt[:, 0], bt[:, 1]).numpy().reshape(-1)
+        fx['out/neg'] = model.predict(bt[:, 0], bt[:, 2]).numpy().reshape(-1)
+        fx['out/loss_eval'] = np.float32(model.loss(bt).item())
+        model.train()
+        fx['out/loss_train'] = np.float32(model.loss(bt).item())
+    bt9 = None
+    if name == 'headline_gat_att':              # the entity-aware pass: six entity columns and two 0/1 mask columns
+        ent = rng.integers(0, n, size=(B, 6))
+        mask = rng.integers(0, 2, size=(B, 2))
+        batch9 = np.concatenate([batch, ent[:, 0:2], mask[:, 0:1], ent[:, 2:4], mask[:, 1:2]], axis=1).astype(np.int64)
+        assert all(set(np.unique(batch9[:, c])) == {0, 1} for c in (5, 8))
+        fx['in/batch9'] = batch9
+        bt9 = torch.from_numpy(batch9)
+        model.entity_aware = True
+        with torch.no_grad():
+            fx['out/loss_train_ea'] = np.float32(model.loss(bt9).item())
+        model.entity_aware = False
+
+    def loss_and_grads(m, b):
+        m.train()
+        m.zero_grad()
+        loss = m.loss(b)
+        loss.backward()
+        return float(loss.detach()), {k: p.grad.detach().double().numpy().copy() for k, p in m.named_parameters()}
+
+    loss32, g32 = loss_and_grads(model, bt)
+    loss64, g64 = loss_and_grads(model64, bt)
+    assert np.float32(loss32) == fx['out/loss_train']
+    frac, worst = H.grad_rule_fraction(g32, g64)
+    if not frac <= 0.5:
+        raise RuntimeError('%s: the reference\'s float32 run uses %.3f of the gradient rule (%s): take another batch or seed, '
+                           'not another rule' % (name, frac, worst))
+    gx = {'grad/' + k: v.astype(np.float32) for k, v in g64.items()}
+    gx['loss64'] = np.float64(loss64)
+    if bt9 is not None:
+        model64.entity_aware = True
+        loss64_ea, g64_ea = loss_and_grads(model64, bt9)
+        for k in g64:                           # the regulariser depends on x only
+            assert k == 'x' or np.array_equal(g64_ea[k], g64[k]), k
+        gx['grad_ea/x'] = g64_ea['x'].astype(np.float32)
+        gx['loss64_ea'] = np.float64(loss64_ea)
+    gmeta = dict(ref_fp32_rule_fraction=frac, ref_fp32_rule_tensor=worst, loss32=loss32, stored_as='float32')
+    fx['meta'] = np.frombuffer(json.dumps(meta).encode(), dtype=np.uint8)
+    gx['meta'] = np.frombuffer(json.dumps(gmeta).encode(), dtype=np.uint8)
+    os.makedirs(out_dir, exist_ok=True)
+    sizes = []
+    for path, arrays in ((os.path.join(out_dir, name + '.npz'), fx), (os.path.join(out_dir, name + '.grad.npz'), gx)):
+        np.savez_compressed(path, **arrays)
+        sizes.append(os.path.getsize(path))
+        if sizes[-1] > HEADLINE_SIZE_CAP:
+            os.remove(path)
+            raise RuntimeError('%s: %d bytes, over the cap of %d: shrink the graph' % (path, sizes[-1], HEADLINE_SIZE_CAP))
+    deg = np.bincount(rel['user2item'][1].astype(np.int64), minlength=n)
+    print('%s N=%d P=%d loss32=%.6f loss64=%.6f ref_fp32_rule_fraction=%.4f (%s) bytes %d + %d; user2item: longest row %d, '
+          'rows without in-edge %d' % (name, n, len(mpl), loss32, loss64, frac, worst, sizes[0], sizes[1], deg.max(), (deg == 0).sum()))
+    return sizes, frac
+
+
+def make_headline(out_dir):
+    sys.path.insert(0, os.path.join(os.path.dirname(HERE), 'tests'))
+    sys.path.insert(0, os.path.dirname(HERE))
+    mods = load_reference_models()
+    graph_input = load_reference_graph_input()
+    for name, kind, width, picked, seed in HEADLINE_CASES:
+        make_headline_case(mods, graph_input, name, kind, width, picked, seed, out_dir)
+
+
 if __name__ == '__main__':
+    if len(sys.argv) > 1 and sys.argv[1] == 'headline':        # the new files only; everything else stays byte-identical
+        make_headline(sys.argv[sys.argv.index('--out') + 1] if '--out' in sys.argv else OUT)
+        sys.exit(0)
     os.makedirs(OUT, exist_ok=True)
     mods = load_reference_models()
     make_case(mods, 'pea_gat_p5s2_h1_att', 'gat', 'p5s2', 1, 'att', 2020)

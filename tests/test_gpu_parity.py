@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import (GoldenCase, assert_fp32_close, build_model, f64_forward, golden_cases, model_from_golden,
+from helpers import (GoldenCase, agg_lanes, assert_fp32_close, build_model, f64_forward, golden_cases, model_from_golden,
                      random_hin, random_state_dict)
 from oracle import oracle as orc
 
@@ -187,7 +187,7 @@ def test_entity_aware_kernel_value_and_gradient():
     """A11 as one HIP launch (csrc/entity.hip) on the batch of the reference-generated fixture pea_gat_p5s2_h1_att_ea:
     value against the C oracle and the reference's formula in float64 (models/base.py:50-73), gradient with respect to x
     against float64 autograd of that formula; a batch row with masks 0 contributes log(1/2) twice and no gradient."""
-    from graph_recsys_benchmark_amd import engine
+    from graph_recsys_benchmark_amd import engine, scoring
     g = GoldenCase('pea_gat_p5s2_h1_att_ea')
     assert g.batch9 is not None and g.batch9.shape[1] == 9
     x = torch.from_numpy(g.state_dict['x']).cuda().requires_grad_(True)
@@ -207,7 +207,22 @@ def test_entity_aware_kernel_value_and_gradient():
     np.testing.assert_allclose(float(reg), orc.entity_reg(g.state_dict['x'], g.batch9), rtol=1e-5)
     gw = xd.grad.numpy()
     np.testing.assert_allclose(_np(x.grad), gw, rtol=1e-4, atol=1e-6 * float(np.abs(gw).max()))
-    assert (g.batch9[:, 5] == 0).any() or (g.batch9[:, 8] == 0).any() or True
+    b = g.batch9
+    assert (b[:, 5] == 0).any() and (b[:, 8] == 0).any()
+    # a batch row with both masks 0: six gradient rows of exact zeros out of the launch itself, and 2 log 2 in the value
+    dead = (b[:, 5] == 0) & (b[:, 8] == 0)
+    live = (b[:, 5] == 1) & (b[:, 8] == 1)
+    assert dead.any() and live.any()
+    with torch.no_grad():
+        _, rows = scoring._entity_launch(x.detach(), t, want_grad=True)
+        rows = _np(rows).reshape(b.shape[0], 6, -1)
+        assert (rows[dead] == 0).all() and np.isfinite(rows).all()
+        assert (np.abs(rows[live]).max(axis=(1, 2)) > 0).all()
+        k_dead, k_live = int(np.flatnonzero(dead)[0]), int(np.flatnonzero(live)[0])
+        alone = float(engine.entity_reg(x.detach(), t[[k_live]]))
+        pair = float(engine.entity_reg(x.detach(), t[[k_dead, k_live]]))
+        np.testing.assert_allclose(pair - alone, 2.0 * np.log(2.0), rtol=1e-5)
+        np.testing.assert_allclose(float(engine.entity_reg(x.detach(), t[[k_dead]])), 2.0 * np.log(2.0), rtol=1e-6)
     with torch.no_grad():                                   # no-grad path: same value, no gradient rows
         np.testing.assert_allclose(float(engine.entity_reg(x.detach(), t)), float(reg), rtol=0, atol=0)
     bad = t.clone()
@@ -216,3 +231,35 @@ def test_entity_aware_kernel_value_and_gradient():
         assert bool(torch.isnan(engine.entity_reg(x.detach(), bad)))
     with pytest.raises(IndexError):
         engine.check_pending_errors()
+
+
+@pytest.mark.parametrize('emb', [4, 16, 20, 128, 256])
+def test_entity_aware_kernel_at_every_lane_group(emb):
+    """csrc/entity.hip has five lane-group instantiations; the fixtures run G = 8 (emb 32) and G = 16 (emb 64).  Here emb 4 and
+    16 (G = 4, one and four active lanes), 20 (G = 8 with idle lanes), 128 (G = 32) and 256 (G = 64) on random rows, B = 67 so
+    that the last workgroup is partial at every rows-per-workgroup (64 ... 4): value and gradient against the float64 formula
+    (reference models/base.py:50-73) and float64 autograd, at the tolerances of the test above."""
+    from graph_recsys_benchmark_amd import engine
+    rng = np.random.default_rng(100 + emb)
+    n, B = 50, 67
+    xs = (rng.normal(size=(n, emb)) * 0.5 / np.sqrt(emb)).astype(np.float32)       # squared distances of about 0.5
+    ids, masks = rng.integers(0, n, size=(B, 7)), rng.integers(0, 2, size=(B, 2))
+    b9 = np.concatenate([ids[:, :5], masks[:, :1], ids[:, 5:], masks[:, 1:]], axis=1).astype(np.int64)
+    assert all(set(np.unique(b9[:, c])) == {0, 1} for c in (5, 8)) and B % (256 // agg_lanes(emb)) != 0
+    x = torch.from_numpy(xs).cuda().requires_grad_(True)
+    reg = engine.entity_reg(x, torch.from_numpy(b9).cuda())
+    reg.backward()
+    engine.check_pending_errors()
+    xd = torch.from_numpy(xs).double().requires_grad_(True)
+    td = torch.from_numpy(b9)
+
+    def sq(a, b):
+        d = xd[td[:, a]] - xd[td[:, b]]
+        return (d * d).sum(-1)
+
+    want = -(((sq(1, 3) - sq(1, 4)) * td[:, 5]).sigmoid().log().sum()) - (((sq(0, 6) - sq(0, 7)) * td[:, 8]).sigmoid().log().sum())
+    want.backward()
+    np.testing.assert_allclose(float(reg), float(want), rtol=1e-5)
+    gw = xd.grad.numpy()
+    assert np.abs(gw).max() > 0
+    np.testing.assert_allclose(_np(x.grad), gw, rtol=1e-4, atol=1e-6 * float(np.abs(gw).max()))
