@@ -1,4 +1,5 @@
-"""ctypes binding of libpeahip.so (C ABI: include/peahip.h, include/peahip_kge.h and include/peahip_eval.h).
+"""ctypes binding of libpeahip.so (C ABI: include/peahip.h, include/peahip_kge.h, include/peahip_eval.h and
+include/peahip_sample.h).
 
 The product path has NO fallback: if the HIP library is missing or no gfx950 device is visible, every
 compute entry point raises.  (CPU parity checking lives in oracle/, which this package never imports.)
@@ -229,6 +230,14 @@ EVAL_SIGNATURES = {
 }
 RANK_MULTI_CHUNK = 8     # csrc/topk_select.h kPC: thresholds of one (user, chunk) row
 
+# every symbol include/peahip_sample.h declares (the on-device KG triple sampler and row shuffle)
+SAMPLE_SIGNATURES = {
+    'pea_kg_sample': (_int, [_i64, _vp, _vp, _int, _vp, _vp, _vp, _vp, _i64, _vp, _i64, C.c_uint64, C.c_uint32, _int, _vp, _i64, _vp,
+                             _vp]),
+    'pea_permute_rows': (_int, [_i64, _int, _vp, _i64, _vp, _i64, C.c_uint64, C.c_uint32, _vp]),
+}
+KG_MAX_SEGMENTS, PERMUTE_MAX_WIDTH = 1024, 16     # include/peahip_sample.h PEA_KG_MAX_SEGMENTS, PEA_PERMUTE_MAX_WIDTH
+
 KGU_KGAT, KGU_KGCN, KGU_NGCF = 0, 1, 2     # include/peahip.h PEA_KGU_*
 
 _lib = None
@@ -242,7 +251,8 @@ def load():
             raise ImportError('%s is missing: build it with `python -c "import __graft_entry__ as g; g.build()"` '
                               '(or make -C graph_recsys_benchmark_amd/csrc); there is no CPU fallback' % LIB_PATH)
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(KGE_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()):
+        for name, (res, args) in (list(SIGNATURES.items()) + list(KGE_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) +
+                                  list(SAMPLE_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

@@ -5,6 +5,8 @@ one (candidate draw, pandas merge, 4 H2D copies, 3 MLP launches, a sort and 3 D2
 candidate ids are drawn on the host with the very same np.random.choice call per user (bit-exact ids, same stream
 position afterwards), then ALL users are scored by one launch of pea_rank_eval; HR@5..20 / NDCG@5..20 / AUC / eval
 loss follow graph_recsys_benchmark/utils/rec_utils.py:7-30 (hit :7, ndcg :18, auc :28) and solvers.py:72,93-96.
+
+kg_epoch is the KG-phase training loop of the KGAT / KGCN / CFKG drivers over a table that already lives on the device.
 """
 import numpy as np
 import torch
@@ -15,6 +17,34 @@ from .utils.interactions import positives_csr, seen_items_csr
 from .utils.sampling import generate_candidates
 
 NUM_RECS_RANGE = 20   # utils/rec_utils.py:4
+
+
+def kg_epoch(model, optimizer, train_data, batch_size, max_steps=None):
+    """The KG-phase loop of the reference's drivers (experiments/cfkg_solver_bpr.py:227 ff., kgat_solver_bpr.py:289-306) over a
+    table that is already on the model's device (utils.device_kg_negative_sampling): batches are views of consecutive rows,
+    the last short one included as DataLoader includes it; every step runs zero_grad, kg_loss, backward, step.  The
+    per-batch losses stay in one device tensor and are read ONCE: the return value is their float64 mean, the reference's
+    np.mean(kg_loss_per_batch), where its loop reads every step's loss with .item().  max_steps caps the number of steps.
+    Pending id errors of the epoch's launches raise here (engine.check_pending_errors)."""
+    n, batch_size = int(train_data.shape[0]), int(batch_size)
+    if batch_size < 1:
+        raise ValueError('kg_epoch: batch_size %d' % batch_size)
+    steps = (n + batch_size - 1) // batch_size
+    if max_steps is not None:
+        steps = min(steps, int(max_steps))
+    if steps <= 0:
+        return float('nan')
+    losses = torch.zeros(steps, dtype=torch.float32, device=train_data.device)
+    for k in range(steps):
+        batch = train_data[k * batch_size:(k + 1) * batch_size]
+        optimizer.zero_grad()
+        loss = model.kg_loss(batch)
+        loss.backward()
+        optimizer.step()
+        losses[k] = loss.detach()
+    mean = float(losses.double().mean().item())
+    engine.check_pending_errors()
+    return mean
 
 
 def metrics_from_ranks(rank):

@@ -13,6 +13,9 @@ device-side Philox stream would not reproduce the reference's ids (SURVEY.md 5.8
     device_negative_sampling   the ADDITIONAL device-side sampler: same strategies and output
                                layout, its own Philox4x32-10 stream (csrc/sampler.hip); never a replacement for the
                                bit-exact path above.
+    device_kg_negative_sampling   its KG twin (csrc/kg_sampler.hip): the (h, t+, t-, rel) table of kg_negative_sampling from
+                               one launch over a kg_triple_store, the epoch shuffle a keyed bijection inside that launch;
+                               device_shuffle_rows applies the same bijection to any int64 table.
 """
 import random as rd
 
@@ -144,4 +147,172 @@ def device_negative_sampling(dataset, seed, epoch=0, device='cuda', shuffle=True
     if shuffle:
         out = out[torch.randperm(out.shape[0], device=device)]
     dataset.train_data, dataset.train_data_length = out, out.shape[0]
+    return out
+
+
+# ---- the KG twin: on-device triple sampler with the epoch shuffle inside the launch (csrc/kg_sampler.hip,
+# ---- include/peahip_sample.h).  An addition next to kg_negative_sampling above, never its replacement: its ids are its own.
+class KGTripleStore:
+    """Every KG triple of a dataset, laid out for pea_kg_sample: heads / tails int64 [E] in the order kg_negative_sampling
+    stacks them (relation by relation, in the order of dataset.edge_index_nps), and one segment per relation: seg_ptr
+    [S + 1], seg_rel [S] (the relation's edge_type_dict id), and the node block (seg_lo, seg_n) [S] its typed negatives are
+    drawn from.  `host` holds the numpy copies of the four tables."""
+
+    def __init__(self, heads, tails, seg_ptr, seg_rel, seg_lo, seg_n, num_nodes, device):
+        self.num_nodes, self.device = int(num_nodes), torch.device(device)
+        self.host = {'seg_ptr': seg_ptr, 'seg_rel': seg_rel, 'seg_lo': seg_lo, 'seg_n': seg_n}
+        to = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.int64)).to(self.device)
+        self.heads, self.tails = to(heads), to(tails)
+        self.device = self.heads.device                                # with its index: 'cuda' became 'cuda:0'
+        self.seg_ptr, self.seg_rel, self.seg_lo, self.seg_n = to(seg_ptr), to(seg_rel), to(seg_lo), to(seg_n)
+        s = len(seg_rel)
+        self.any_lo, self.any_n = to(np.zeros(s)), to(np.full(s, self.num_nodes))       # strategy 'random': any node
+        self._keys = None
+
+    @property
+    def num_triples(self):
+        return int(self.heads.numel())
+
+    @property
+    def num_segments(self):
+        return int(self.seg_rel.numel())
+
+    def segment_of_rows(self):
+        """int64 [E]: the segment index of every store row"""
+        counts = self.seg_ptr[1:] - self.seg_ptr[:-1]
+        return torch.repeat_interleave(torch.arange(self.num_segments, device=self.device), counts)
+
+    def rows(self):
+        """int64 [E, 3]: (h, t+, relation id) of every store row, in store order"""
+        return torch.stack([self.heads, self.tails, self.seg_rel[self.segment_of_rows()]], dim=1)
+
+    def keys(self):
+        """The sorted table of known triples, ((s N) + h) N + t, built once (torch.unique on the store's device)"""
+        if self._keys is None:
+            n = self.num_nodes
+            self._keys = torch.unique((self.segment_of_rows() * n + self.heads) * n + self.tails)
+        return self._keys
+
+
+def _default_tail_blocks(dataset, names, tails_of):
+    """{relation: (lo, n)}: the node-type block of dataset.type_accs that holds the relation's tails; a block ends where the
+    next one starts (the last at num_nodes).  A relation without triples draws from every node."""
+    starts = np.asarray(sorted(set(int(v) for v in dataset.type_accs.values())) + [int(dataset.num_nodes)], dtype=np.int64)
+    blocks = {}
+    for name in names:
+        t = tails_of[name]
+        if t.size == 0:
+            blocks[name] = (0, int(dataset.num_nodes))
+            continue
+        k = int(np.searchsorted(starts, int(t.min()), side='right')) - 1
+        if k < 0 or k >= starts.size - 1:
+            raise ValueError('kg_triple_store: tails of %r lie outside every node-type block' % name)
+        blocks[name] = (int(starts[k]), int(starts[k + 1] - starts[k]))
+    return blocks
+
+
+def kg_triple_store(dataset, device='cuda', tail_blocks=None):
+    """The KGTripleStore of a dataset, built once per dataset: relations in the order of dataset.edge_index_nps, relation ids
+    from edge_type_dict (or enumerated, as kg_negative_sampling does).  tail_blocks = {relation: (lo, n)} names the node block
+    a relation's typed negatives come from; by default the dataset.type_accs block its tails lie in.  A relation whose tails
+    leave their block raises ValueError, as do more than 1024 relations and ids outside [0, num_nodes)."""
+    from .. import _lib
+    type_of = getattr(dataset, 'edge_type_dict', None)
+    if type_of is None:
+        type_of = {name: k for k, name in enumerate(dataset.edge_index_nps.keys())}
+    names = list(dataset.edge_index_nps.keys())
+    n = int(dataset.num_nodes)
+    if not 1 <= len(names) <= _lib.KG_MAX_SEGMENTS:
+        raise ValueError('kg_triple_store: %d relations (1..%d)' % (len(names), _lib.KG_MAX_SEGMENTS))
+    if not 1 <= n < 2 ** 32:
+        raise ValueError('kg_triple_store: num_nodes %d outside [1, 2^32)' % n)
+    edges = {name: np.asarray(dataset.edge_index_nps[name]).astype(np.int64).reshape(2, -1) for name in names}
+    tails_of = {name: edges[name][1] for name in names}
+    if tail_blocks is None:
+        tail_blocks = _default_tail_blocks(dataset, names, tails_of)
+    seg_ptr = np.zeros(len(names) + 1, dtype=np.int64)
+    seg_rel, seg_lo, seg_n = (np.zeros(len(names), dtype=np.int64) for _ in range(3))
+    for s, name in enumerate(names):
+        lo, cnt = (int(v) for v in tail_blocks[name])
+        e = edges[name]
+        if not (0 <= lo and 1 <= cnt and lo + cnt <= n):
+            raise ValueError('kg_triple_store: tail block (%d, %d) of %r is not inside [0, %d)' % (lo, cnt, name, n))
+        if e.size and (e.min() < 0 or e.max() >= n):
+            raise ValueError('kg_triple_store: a node id of %r is outside [0, %d)' % (name, n))
+        if e.size and (e[1].min() < lo or e[1].max() >= lo + cnt):
+            raise ValueError('kg_triple_store: tails of %r leave their block [%d, %d)' % (name, lo, lo + cnt))
+        seg_ptr[s + 1] = seg_ptr[s] + e.shape[1]
+        seg_rel[s], seg_lo[s], seg_n[s] = int(type_of[name]), lo, cnt
+    heads = np.concatenate([edges[name][0] for name in names])
+    tails = np.concatenate([edges[name][1] for name in names])
+    return KGTripleStore(heads, tails, seg_ptr, seg_rel, seg_lo, seg_n, n, device)
+
+
+def _store_of(dataset_or_store, device):
+    if isinstance(dataset_or_store, KGTripleStore):
+        return dataset_or_store
+    store = getattr(dataset_or_store, 'kg_store', None)
+    if not isinstance(store, KGTripleStore) or store.device != torch.empty(0, device=device).device:
+        store = kg_triple_store(dataset_or_store, device)
+        dataset_or_store.kg_store = store
+    return store
+
+
+def device_kg_negative_sampling(dataset_or_store, seed, epoch=0, device='cuda', strategy='random', filtered=False, shuffle=True):
+    """KG quadruples sampled ON THE GPU: int64 [E, 4] CUDA tensor (h, t+, t-, relation id), the columns kg_loss of CFKG, KGAT
+    and KGCN reads, from one launch of csrc/kg_sampler.hip -- the epoch shuffle included (a keyed bijection of the row index:
+    no randperm, no second table).  strategy 'random': t- uniform over all nodes, the reference's distribution
+    (datasets/movielens.py:861-877); 'typed': uniform over the node block of the relation's tails.  filtered: a draw equal to
+    t+ or completing a known triple of the relation is redrawn (up to 64 times; the store caches the key table).  `epoch`
+    is the Philox counter's fourth word: an independent draw and shuffle per epoch.  Takes a dataset (its store is built
+    on first use and kept at dataset.kg_store) or a kg_triple_store; sets train_data, train_data_length and
+    negatives_exhausted on it."""
+    from .. import _lib
+    if strategy not in ('random', 'typed'):
+        raise NotImplementedError('strategy %r (random or typed)' % (strategy,))
+    if not isinstance(dataset_or_store, KGTripleStore):
+        _lib.require_device()
+    store = _store_of(dataset_or_store, device)
+    # what the launch cannot check for itself (the tables are device memory): the host copies answer for them
+    host = store.host
+    if (np.diff(host['seg_ptr']) < 0).any() or host['seg_ptr'][0] != 0 or host['seg_ptr'][-1] != store.num_triples:
+        raise ValueError('kg triple store: seg_ptr must rise from 0 to the number of triples')
+    if (host['seg_n'] < 1).any() or (host['seg_n'] >= 2 ** 32).any():
+        raise ValueError('kg triple store: a seg_n is outside [1, 2^32)')
+    lib = _lib.require_device()
+    lo, cnt = (store.seg_lo, store.seg_n) if strategy == 'typed' else (store.any_lo, store.any_n)
+    keys = store.keys() if filtered and store.num_triples else None
+    out = torch.empty((store.num_triples, 4), dtype=torch.int64, device=store.device)
+    exhausted = torch.zeros(1, dtype=torch.int32, device=store.device)
+    _lib.check(lib.pea_kg_sample(store.num_triples, _lib.ptr(store.heads), _lib.ptr(store.tails), store.num_segments,
+                                 _lib.ptr(store.seg_ptr), _lib.ptr(store.seg_rel), _lib.ptr(lo), _lib.ptr(cnt), store.num_nodes,
+                                 _lib.ptr(keys), 0 if keys is None else keys.numel(), int(seed) & (2 ** 64 - 1),
+                                 int(epoch) & 0xFFFFFFFF, int(bool(shuffle)), _lib.ptr(out),
+                                 out.stride(0), _lib.ptr(exhausted), _lib.current_stream()))
+    n_exhausted = int(exhausted.item())
+    if n_exhausted:
+        # 64 rejection attempts all hit known triples (a head linked to nearly its whole block): the row keeps a known tail
+        # as its negative.  Loud, because such a row is a false negative.
+        import warnings
+        warnings.warn('device_kg_negative_sampling: %d of %d negatives are known triples (rejection sampling exhausted)'
+                      % (n_exhausted, out.shape[0]), RuntimeWarning)
+    for target in {id(dataset_or_store): dataset_or_store, id(store): store}.values():
+        target.negatives_exhausted = n_exhausted
+        target.train_data, target.train_data_length = out, out.shape[0]
+    return out
+
+
+def device_shuffle_rows(rows, seed, epoch=0):
+    """A shuffled copy of a contiguous int64 [n, w] CUDA tensor (w in 1..16): out[perm(i)] = rows[i] with the keyed bijection
+    of csrc/kg_sampler.hip, one launch, no randperm and no index tensor.  The shuffle the device BPR triples
+    (device_negative_sampling(..., shuffle=False)) and HeRec's labelled rows can opt into."""
+    from .. import _lib
+    lib = _lib.require_device()
+    if not (torch.is_tensor(rows) and rows.is_cuda and rows.dtype == torch.int64 and rows.dim() == 2 and rows.is_contiguous()):
+        raise ValueError('device_shuffle_rows: a contiguous int64 [n, w] CUDA tensor expected')
+    if not 1 <= rows.shape[1] <= _lib.PERMUTE_MAX_WIDTH:
+        raise ValueError('device_shuffle_rows: %d columns (1..%d)' % (rows.shape[1], _lib.PERMUTE_MAX_WIDTH))
+    out = torch.empty_like(rows)
+    _lib.check(lib.pea_permute_rows(rows.shape[0], rows.shape[1], _lib.ptr(rows), rows.stride(0), _lib.ptr(out), out.stride(0),
+                                    int(seed) & (2 ** 64 - 1), int(epoch) & 0xFFFFFFFF, _lib.current_stream()))
     return out
