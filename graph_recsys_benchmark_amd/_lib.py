@@ -1,5 +1,5 @@
-"""ctypes binding of libpeahip.so (C ABI: include/peahip.h, include/peahip_kge.h, include/peahip_eval.h and
-include/peahip_sample.h).
+"""ctypes binding of libpeahip.so (C ABI: include/peahip.h, include/peahip_kge.h, include/peahip_eval.h,
+include/peahip_sample.h and include/peahip_fm.h).
 
 The product path has NO fallback: if the HIP library is missing or no gfx950 device is visible, every
 compute entry point raises.  (CPU parity checking lives in oracle/, which this package never imports.)
@@ -238,6 +238,19 @@ SAMPLE_SIGNATURES = {
 }
 KG_MAX_SEGMENTS, PERMUTE_MAX_WIDTH = 1024, 16     # include/peahip_sample.h PEA_KG_MAX_SEGMENTS, PEA_PERMUTE_MAX_WIDTH
 
+# every symbol include/peahip_fm.h declares (the factorisation-machine models: NFM)
+_f = C.c_float
+FM_SIGNATURES = {
+    'pea_nfm_supported': (_int, [_int, _int]),
+    'pea_nfm_train_workspace_bytes': (_sz, [_i64, _int, _int]),
+    'pea_nfm_train': (_int, [_i64, _int, _int, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                             _vp, _f, _f, _int, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'pea_nfm_fold': (_int, [_int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp]),
+    'pea_nfm_score': (_int, [_int, _i64, _i64, _i64, _int, _int, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                             _vp, _vp, _vp, _vp]),
+}
+NFM_PAIRS, NFM_ROWS, NFM_RANGE, NFM_MAX_BATCH = 0, 1, 2, 8192     # include/peahip_fm.h PEA_NFM_*
+
 KGU_KGAT, KGU_KGCN, KGU_NGCF = 0, 1, 2     # include/peahip.h PEA_KGU_*
 
 _lib = None
@@ -252,7 +265,7 @@ def load():
                               '(or make -C graph_recsys_benchmark_amd/csrc); there is no CPU fallback' % LIB_PATH)
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(KGE_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) +
-                                  list(SAMPLE_SIGNATURES.items())):
+                                  list(SAMPLE_SIGNATURES.items()) + list(FM_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

@@ -20,11 +20,12 @@ from .losses import (  # noqa: F401
     DOT_TRAIN_MAX_BLOCKS, HEREC_MAX_TABLES, ROWS_SCATTER_MAX, _block16, _BprTrainLoss, _CfkgLoss, _DotBprLoss, _herec_args,
     _HerecLoss, _int64_batch, _scatter_dense, _TransrLoss, bpr_train_loss, bpr_train_raw, bpr_train_supported, cfkg_loss,
     cfkg_supported, cfkg_train_raw, dot_bpr_loss, dot_bpr_supported, dot_bpr_train_raw, herec_mse_loss, herec_supported,
-    herec_table, herec_train_raw, rows_scatter_sum, transr_loss, transr_supported, transr_train_raw)
+    herec_table, herec_train_raw, nfm_mse_loss, nfm_position_ids, nfm_supported, nfm_train_raw, rows_scatter_sum, transr_loss,
+    transr_supported, transr_train_raw)
 from .scoring import (  # noqa: F401
     _catalogue_args, _check_scored, _dot_table, _entity_launch, _EntityReg, _rank_io, bpr_score, dot_predict, dot_rank_eval,
     dot_rank_full, dot_rank_full_multi, dot_recommend_topk, entity_reg, fuse_ablate, predict, rank_eval, rank_eval_multi, rank_full,
-    rank_full_multi, recommend_topk)
+    rank_full_multi, recommend_topk, NfmFolded, nfm_fold, nfm_fold_torch, nfm_predict, nfm_rank_eval, nfm_score_block)
 from .sharding import ShardLayout
 from .walk_ops import (  # noqa: F401
     _SkipgramLoss, _walk_rows, _walk_starts, metapath_walks, skipgram_loss, skipgram_supported, skipgram_train_raw, uniform_walks)

@@ -441,3 +441,154 @@ def herec_table(tables, emb_trans_w, emb_trans_b, user_emb, item_emb, user_rk_bi
                                    _lib.ptr(embs[2]), _lib.ptr(embs[3]), int(acc_uids), embs[0].shape[0], int(acc_iids),
                                    embs[1].shape[0], n, _lib.ptr(out), _lib.current_stream()))
     return out
+
+
+# ---- NFM (csrc/nfm.hip, include/peahip_fm.h; reference models/nfm.py over torchfm's NeuralFactorizationMachineModel)
+NFM_DENSE = ('w1', 'b1', 'w2', 'b2', 'bias0', 'bn1_w', 'bn1_b', 'bn2_w', 'bn2_b')      # the dense gradients of nfm_train_raw
+
+
+def nfm_supported(emb_dim, hidden_size, batch_size=2):
+    """Whether nfm_mse_loss / nfm_fold / the nfm scorers take these widths (include/peahip_fm.h, pea_nfm_supported: multiples
+    of 4 in 4..128) and this batch (2 <= B, torch's BatchNorm refuses one row; its 2 B positions go back through
+    rows_scatter_sum); needs no device."""
+    return (bool(_lib.load().pea_nfm_supported(int(emb_dim), int(hidden_size))) and 2 <= int(batch_size)
+            and 2 * int(batch_size) <= ROWS_SCATTER_MAX)
+
+
+def _nfm_dense(emb, lin, bias0, bn1, w1, b1, bn2, w2, b2):
+    """The NFM tensors as pea_nfm_* read them: emb as a 16-byte aligned block with a row stride that is a multiple of 4, the
+    rest detached and contiguous; bn = (weight, bias, running_mean, running_var), the running buffers as they are (the launch
+    updates them in place)."""
+    emb = _block16(emb)
+    e, n = emb.shape[1], emb.shape[0]
+    flat = [t.detach().contiguous() for t in (lin, bias0, bn1[0], bn1[1], w1, b1, bn2[0], bn2[1], w2, b2)]
+    h = flat[4].shape[0]
+    if (flat[0].numel() != n or flat[1].numel() != 1 or tuple(flat[4].shape) != (h, e) or flat[5].numel() != h or flat[8].numel() != h
+            or flat[9].numel() != 1 or any(t.numel() != e for t in (flat[2], flat[3], bn1[2], bn1[3]))
+            or any(t.numel() != h for t in (flat[6], flat[7], bn2[2], bn2[3]))):
+        raise ValueError('nfm: emb [U + I, E], lin [U + I, 1], W1 [H, E], w2 [1, H] and batch normalisations of E and H columns expected')
+    if any(t.dtype != torch.float32 for t in [emb] + flat + list(bn1[2:]) + list(bn2[2:])):
+        raise ValueError('nfm: float32 tensors expected')
+    if not all(t.is_contiguous() for t in list(bn1[2:]) + list(bn2[2:])):
+        raise ValueError('nfm: the running buffers must be contiguous')
+    return emb, flat, e, h
+
+
+def nfm_train_raw(emb, lin, bias0, bn1, w1, b1, bn2, w2, b2, num_users, uids, iids, labels, keep=None, keep_scale=1.0,
+                  need_grad=True, update_running=True, eps=1e-5, momentum=0.1):
+    """The training step of csrc/nfm.hip for B labelled pairs of LOCAL ids: a dict with loss, pred [B], batch_stats (mean1,
+    var1 [E], mean2, var2 [H]: the batch's means and biased variances), grads {name: tensor} over NFM_DENSE, grad_rows
+    [2B, E + 4] (row b the user position of pair b, row B + b the item position: [d emb row | d lin, 0, 0, 0]), pos_ids [2B]
+    (the table rows of those positions, -1 for a pair with an id out of range: what rows_scatter_sum takes), dense (the buffer
+    grads views) and the error flag.  bn1 / bn2 = (weight, bias, running_mean, running_var); with update_running the running buffers are updated in
+    place as torch's BatchNorm1d does in training mode.  keep = (keep1 [B, E], keep2 [B, H]) uint8 / bool dropout masks with
+    keep_scale = 1 / (1 - p), or None.  need_grad=False: forward only, grads and grad_rows are None."""
+    lib = _lib.require_device()
+    emb, flat, e, h = _nfm_dense(emb, lin, bias0, bn1, w1, b1, bn2, w2, b2)
+    dev, n = emb.device, emb.shape[0]
+    uids, iids = uids.to(torch.int64).contiguous(), iids.to(torch.int64).contiguous()
+    labels = labels.to(torch.float32).contiguous()
+    if uids.dim() != 1 or uids.shape != iids.shape or uids.shape != labels.shape:
+        raise ValueError('nfm: uids, iids and labels must be 1-d of equal length')
+    bsz = uids.shape[0]
+    if not nfm_supported(e, h, bsz):
+        raise ValueError('nfm_train: widths (%d, %d) or batch size %d not supported (engine.nfm_supported)' % (e, h, bsz))
+    k1 = k2 = None
+    if keep is not None:
+        k1, k2 = ((k.view(torch.uint8) if k.dtype == torch.bool else k.to(torch.uint8)).contiguous() for k in keep)
+        if tuple(k1.shape) != (bsz, e) or tuple(k2.shape) != (bsz, h):
+            raise ValueError('nfm: keep masks [B, E] and [B, H] expected')
+    loss, pred, stats = _outputs(dev, (), (bsz,), (2 * e + 2 * h,))
+    dense, rows = _outputs(dev, (h * e + 2 * h + 4 + 2 * e + 2 * h,), (2 * bsz, e + 4), wanted=need_grad)
+    pos = torch.empty(2 * bsz, dtype=torch.int64, device=dev) if need_grad else None
+    ws, ws_bytes = _workspace(lib.pea_nfm_train_workspace_bytes, (bsz, e, h), dev)
+    _lib.check(lib.pea_nfm_train(bsz, e, h, int(num_users), n - int(num_users), _lib.ptr(emb), emb.stride(0), _lib.ptr(flat[0]),
+                                 _lib.ptr(flat[1]), _lib.ptr(flat[2]), _lib.ptr(flat[3]), _lib.ptr(bn1[2]), _lib.ptr(bn1[3]),
+                                 _lib.ptr(flat[4]), _lib.ptr(flat[5]), _lib.ptr(flat[6]), _lib.ptr(flat[7]), _lib.ptr(bn2[2]),
+                                 _lib.ptr(bn2[3]), _lib.ptr(flat[8]), _lib.ptr(flat[9]), float(eps), float(momentum),
+                                 int(bool(update_running)), _lib.ptr(uids), _lib.ptr(iids), _lib.ptr(labels), _lib.ptr(k1), _lib.ptr(k2),
+                                 float(keep_scale), _lib.ptr(loss), _lib.ptr(pred), _lib.ptr(stats), _lib.ptr(dense), _lib.ptr(rows),
+                                 _lib.ptr(pos), _lib.ptr(ws), ws_bytes, _lib.current_stream()))
+    return {'loss': loss, 'pred': pred, 'dense': dense, 'grads': _nfm_dense_views(dense, e, h) if need_grad else None,
+            'grad_rows': rows, 'pos_ids': pos, 'flag': ws_flag(ws),
+            'batch_stats': (stats[:e], stats[e:2 * e], stats[2 * e:2 * e + h], stats[2 * e + h:])}
+
+
+def _nfm_dense_views(dense, e, h):
+    """{name: view} over NFM_DENSE of the d_dense buffer of pea_nfm_train (include/peahip_fm.h)"""
+    o = h * e + 2 * h + 4
+    return {'w1': dense[:h * e].view(h, e), 'b1': dense[h * e:h * e + h], 'w2': dense[h * e + h:h * e + 2 * h].view(1, h),
+            'b2': dense[h * e + 2 * h:h * e + 2 * h + 1], 'bias0': dense[h * e + 2 * h + 1:h * e + 2 * h + 2],
+            'bn1_w': dense[o:o + e], 'bn1_b': dense[o + e:o + 2 * e], 'bn2_w': dense[o + 2 * e:o + 2 * e + h],
+            'bn2_b': dense[o + 2 * e + h:o + 2 * e + 2 * h]}
+
+
+def nfm_position_ids(num_users, num_items, uids, iids):
+    """The 2 B rows of the [U + I] tables that B pairs of local ids read, users first; -1 (skipped by rows_scatter_sum) for
+    both positions of a pair with an id out of range."""
+    u, i = uids.to(torch.int64), iids.to(torch.int64)
+    ok = (u >= 0) & (u < num_users) & (i >= 0) & (i < num_items)
+    bad = torch.full_like(u, -1)
+    return torch.cat([torch.where(ok, u, bad), torch.where(ok, i + num_users, bad)]).contiguous()
+
+
+class _NfmLoss(torch.autograd.Function):
+    """loss = mean_b (sigmoid(y_b) - label_b)^2 of the NFM score with its whole backward from the same chain of launches
+    (csrc/nfm.hip); backward scatters the 2 B position rows into ONE dense [U + I, E + 4] buffer with pea_rows_scatter_sum
+    (fixed order): its first E columns are emb's gradient, column E is lin's.  Reference: models/nfm.py:16-33 under
+    loss.backward()."""
+
+    @staticmethod
+    def forward(ctx, ids, opts, emb, lin, bias0, bn1_w, bn1_b, w1, b1, bn2_w, bn2_b, w2, b2):
+        uids, iids, labels = ids
+        num_users = int(opts['num_users'])
+        out = nfm_train_raw(emb, lin, bias0, (bn1_w, bn1_b) + tuple(opts['bn1_running']), w1, b1,
+                            (bn2_w, bn2_b) + tuple(opts['bn2_running']), w2, b2, num_users, uids, iids, labels, keep=opts.get('keep'),
+                            keep_scale=opts.get('keep_scale', 1.0), need_grad=opts['need_grad'],
+                            update_running=opts.get('update_running', True), eps=opts.get('eps', 1e-5),
+                            momentum=opts.get('momentum', 0.1))
+        _defer_error(out['flag'], 'index out of range in NFM pairs (a user id outside [0, num_users) or an item id outside '
+                                  '[0, num_items))')
+        if opts['need_grad']:
+            ctx.out = out
+            ctx.shapes = (tuple(emb.shape), tuple(lin.shape), w1.shape[0])
+        opts['pred'] = out['pred']
+        return out['loss']
+
+    @staticmethod
+    def backward(ctx, g):
+        (n, e), lin_shape, h = ctx.shapes
+        need = ctx.needs_input_grad
+        d_emb = d_lin = None
+        if need[2] or need[3]:
+            table = _scatter_dense(ctx.out['pos_ids'], ctx.out['grad_rows'] * g, n, e + 4)
+            d_emb = table[:, :e] if need[2] else None
+            d_lin = table[:, e].reshape(lin_shape) if need[3] else None
+        grads = _nfm_dense_views(ctx.out['dense'] * g, e, h)        # one multiply for the nine dense gradients
+
+        def dense(k, name):
+            return grads[name] if need[k] else None
+        return (None, None, d_emb, d_lin, dense(4, 'bias0'), dense(5, 'bn1_w'), dense(6, 'bn1_b'), dense(7, 'w1'), dense(8, 'b1'),
+                dense(9, 'bn2_w'), dense(10, 'bn2_b'), dense(11, 'w2'), dense(12, 'b2'))
+
+
+def nfm_mse_loss(emb, lin, bias0, bn1, w1, b1, bn2, w2, b2, num_users, uids, iids, labels, keep=None, keep_scale=1.0,
+                 update_running=True, eps=1e-5, momentum=0.1, info=None):
+    """Differentiable NFM training loss mean((sigmoid(y) - label)^2) of B labelled pairs of LOCAL ids, forward and backward in
+    HIP.  bn1 / bn2 = (weight, bias, running_mean, running_var) of the two BatchNorm1d: the running buffers are updated in place
+    (update_running), the caller counts num_batches_tracked.  keep = (keep1 [B, E], keep2 [B, H]) dropout masks with keep_scale
+    = 1 / (1 - p), or None: nothing is drawn here.  backward() gives dense gradients for the eleven parameter tensors.  With
+    grad disabled, or when no input requires grad, only the forward runs (the running buffers are still updated, as torch
+    does).  A pair with an id out of range raises IndexError at the next check_pending_errors().  info: a dict that receives
+    'pred' [B].  nfm_supported(E, H, B) must hold."""
+    if emb.dim() != 2 or w1.dim() != 2 or not nfm_supported(emb.shape[1], w1.shape[0], uids.shape[0]):
+        raise ValueError('nfm_mse_loss: widths (multiples of 4 in 4..128) or batch size (2 <= B, 2 B <= %d) not supported'
+                         % ROWS_SCATTER_MAX)
+    params = (emb, lin, bias0, bn1[0], bn1[1], w1, b1, bn2[0], bn2[1], w2, b2)
+    opts = {'num_users': num_users, 'bn1_running': bn1[2:], 'bn2_running': bn2[2:], 'keep': keep, 'keep_scale': keep_scale,
+            'update_running': update_running, 'eps': eps, 'momentum': momentum,
+            'need_grad': torch.is_grad_enabled() and any(t.requires_grad for t in params)}
+    loss = _NfmLoss.apply((uids, iids, labels), opts, *params)
+    if info is not None:
+        info['pred'] = opts['pred']
+    return loss

@@ -1,4 +1,4 @@
-from .base import GraphRecsysModel, PEABaseChannel, PEABaseRecsysModel
+from .base import GraphRecsysModel, MFRecsysModel, PEABaseChannel, PEABaseRecsysModel
 from .peagat import PEAGATChannel, PEAGATRecsysModel
 from .peagcn import PEAGCNChannel, PEAGCNRecsysModel
 from .peasage import PEASageChannel, PEASageRecsysModel
@@ -9,7 +9,9 @@ from .metapath2vec import MetaPath2Vec
 from .walk import WalkBasedRecsysModel
 from .herec import HeRecRecsysModel
 from .cfkg import CFKGRecsysModel
+from .nfm import NFMRecsysModel
 
 __all__ = ['GraphRecsysModel', 'PEABaseChannel', 'PEABaseRecsysModel', 'PEAGATChannel', 'PEAGATRecsysModel',
            'PEAGCNChannel', 'PEAGCNRecsysModel', 'PEASageChannel', 'PEASageRecsysModel', 'KGATRecsysModel', 'KGCNRecsysModel',
-           'NGCFRecsysModel', 'MetaPath2Vec', 'WalkBasedRecsysModel', 'HeRecRecsysModel', 'CFKGRecsysModel']
+           'NGCFRecsysModel', 'MetaPath2Vec', 'WalkBasedRecsysModel', 'HeRecRecsysModel', 'CFKGRecsysModel',
+           'MFRecsysModel', 'NFMRecsysModel']

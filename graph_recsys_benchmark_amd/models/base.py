@@ -4,6 +4,7 @@ Mirrors (names, kwargs, attributes, error behaviour) graph_recsys_benchmark/mode
     GraphRecsysModel      :29-96   loss() / eval() contract (BPR term :43-48, eval cache :88-96)
     PEABaseChannel        :129-140 relu between steps, none after the last
     PEABaseRecsysModel    :143-214 kwargs read at :148-152,156,167-179; forward / predict
+    MFRecsysModel         :98-126  BCE-with-logits loss over local ids (plain torch; models/nfm.py builds on it)
 Differences, all on purpose:
   * forward() hands ALL channels and steps to one schedule (engine.PEAEngine) instead of looping in Python;
   * graph tensors must be on the GPU; there is no CPU fallback (parity checks use oracle/ from the tests);
@@ -396,3 +397,35 @@ class PEABaseRecsysModel(GraphRecsysModel):
             return self.fc2(torch.relu(self.fc1(z)))
         return _engine.predict(self.cached_repr, unids, inids, self.fc1.weight, self.fc1.bias, self.fc2.weight,
                                self.fc2.bias)
+
+
+class MFRecsysModel(torch.nn.Module):
+    """The reference's base class of the matrix-factorisation family (models/base.py:98-126): forward(uid, iid) scores pairs of
+    LOCAL ids with logits, loss() is BCE-with-logits over labelled rows (u, i, .., label) in training mode and over a
+    (u, pos, neg..) block with labels [1, 0, ..] in eval mode, predict = forward."""
+
+    def __init__(self, **kwargs):
+        super().__init__()
+        self._init(**kwargs)
+        self.reset_parameters()
+
+    def _init(self, **kwargs):
+        raise NotImplementedError
+
+    def reset_parameters(self):
+        raise NotImplementedError
+
+    def loss(self, pos_neg_pair_t):
+        loss_func = torch.nn.BCEWithLogitsLoss()
+        if self.training:
+            pred = self.predict(pos_neg_pair_t[:, 0], pos_neg_pair_t[:, 1])
+            label = pos_neg_pair_t[:, -1].float()
+        else:
+            pos_pred = self.predict(pos_neg_pair_t[:, 0], pos_neg_pair_t[:, 1])[:1]
+            neg_pred = self.predict(pos_neg_pair_t[:, 0], pos_neg_pair_t[:, 2])
+            pred = torch.cat([pos_pred, neg_pred])
+            label = torch.cat([torch.ones_like(pos_pred), torch.zeros_like(neg_pred)]).float()
+        return loss_func(pred, label)
+
+    def predict(self, unids, inids):
+        return self.forward(unids, inids)

@@ -369,3 +369,99 @@ def dot_rank_full_multi(repr_, unids, pos_rowptr, pos_items, item_range, exclude
     below int32 [Q], pos_score [Q], n_neg int32 [U])."""
     check_pending_errors()
     return _rank_full_multi(_dot_table(repr_), unids, pos_rowptr, pos_items, item_range, exclude, None)
+
+
+# ---- NFM (csrc/nfm.hip, include/peahip_fm.h): the eval-mode fold and the pair scorer over it
+NFM_ID_MESSAGE = 'index out of range in NFM pairs (a user id outside [0, num_users) or an item id outside [0, num_items))'
+
+
+class NfmFolded:
+    """The eval-mode NFM as the scorer reads it: emb [U + I, E] (a 16-byte aligned block), lin [U + I], the folded first
+    layer w [H, E] / b [H], w2 [H], the scalar bias [1], and the block sizes."""
+
+    def __init__(self, emb, lin, w, b, w2, bias, num_users):
+        self.emb, self.lin, self.w, self.b, self.w2, self.bias = emb, lin, w, b, w2, bias
+        self.num_users, self.num_items = int(num_users), int(emb.shape[0]) - int(num_users)
+
+    @property
+    def device(self):
+        return self.emb.device
+
+
+def nfm_fold_torch(emb, lin, bias0, bn1, w1, b1, bn2, w2, b2, num_users, eps=1e-5):
+    """nfm_fold in torch ops, on any device and in the tensors' dtype: the same three products in the same association."""
+    s1 = bn1[0] / torch.sqrt(bn1[3] + eps)
+    t1 = bn1[1] - bn1[2] * s1
+    s2 = bn2[0] / torch.sqrt(bn2[3] + eps)
+    t2 = bn2[1] - bn2[2] * s2
+    w = (s2[:, None] * w1) * s1[None, :]
+    b = s2 * (w1 @ t1 + b1) + t2
+    return NfmFolded(emb.detach(), lin.detach().reshape(-1), w.detach(), b.detach(), w2.detach().reshape(-1),
+                     (bias0 + b2).detach().reshape(1), num_users)
+
+
+def nfm_fold(emb, lin, bias0, bn1, w1, b1, bn2, w2, b2, num_users, eps=1e-5):
+    """The eval-mode MLP of NFM folded into one affine map and a relu (include/peahip_fm.h, pea_nfm_fold), one launch:
+    bn = (weight, bias, running_mean, running_var).  Returns the NfmFolded the nfm scorers take."""
+    from .losses import _nfm_dense
+    lib = _lib.require_device()
+    emb, flat, e, h = _nfm_dense(emb, lin, bias0, bn1, w1, b1, bn2, w2, b2)
+    dev = emb.device
+    w, b, bias = (torch.empty(s, dtype=torch.float32, device=dev) for s in ((h, e), (h,), (1,)))
+    _lib.check(lib.pea_nfm_fold(e, h, _lib.ptr(flat[4]), _lib.ptr(flat[5]), _lib.ptr(flat[2]), _lib.ptr(flat[3]), _lib.ptr(bn1[2]),
+                                _lib.ptr(bn1[3]), _lib.ptr(flat[6]), _lib.ptr(flat[7]), _lib.ptr(bn2[2]), _lib.ptr(bn2[3]),
+                                _lib.ptr(flat[1]), _lib.ptr(flat[9]), float(eps), _lib.ptr(w), _lib.ptr(b), _lib.ptr(bias),
+                                _lib.current_stream()))
+    return NfmFolded(emb, flat[0].reshape(-1), w, b, flat[8].reshape(-1), bias, num_users)
+
+
+def _nfm_score(fold, mode, uids, iids, n_users, c, lo, want_logits, want_pred, want_rank):
+    lib = _lib.require_device()
+    dev = fold.device
+    e, h = fold.emb.shape[1], fold.w.shape[0]
+    if not lib.pea_nfm_supported(e, h):
+        raise ValueError('nfm scorer: widths (%d, %d) not supported (engine.nfm_supported)' % (e, h))
+    shape = (n_users,) if mode == _lib.NFM_PAIRS else (n_users, c)
+    logits = torch.empty(shape, dtype=torch.float32, device=dev) if want_logits or want_rank else None
+    pred = torch.empty(shape, dtype=torch.float32, device=dev) if want_pred else None
+    rank = torch.empty(n_users, dtype=torch.int32, device=dev) if want_rank else None
+    auc = torch.empty(n_users, dtype=torch.float32, device=dev) if want_rank else None
+    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    _lib.check(lib.pea_nfm_score(mode, n_users, c, lo, e, h, fold.num_users, fold.num_items, _lib.ptr(fold.emb), fold.emb.stride(0),
+                                 _lib.ptr(fold.lin), _lib.ptr(fold.w), _lib.ptr(fold.b), _lib.ptr(fold.w2), _lib.ptr(fold.bias),
+                                 _lib.ptr(uids), _lib.ptr(iids), _lib.ptr(logits), _lib.ptr(pred), _lib.ptr(rank), _lib.ptr(auc),
+                                 _lib.ptr(flag), _lib.current_stream()))
+    _defer_error(flag, NFM_ID_MESSAGE)
+    return logits, pred, rank, auc
+
+
+def nfm_predict(fold, uids, iids, logits=False):
+    """pred [B] = sigmoid(y) of B pairs of LOCAL ids over the folded weights (what the reference's predict returns in eval
+    mode); logits=True: (y, pred).  An id out of range scores y = 0 and raises IndexError at the next
+    check_pending_errors()."""
+    check_pending_errors()
+    uids, iids = uids.to(torch.int64).contiguous().view(-1), iids.to(torch.int64).contiguous().view(-1)
+    if uids.shape != iids.shape:
+        raise ValueError('uids and iids must have the same length')
+    y, pred, _, _ = _nfm_score(fold, _lib.NFM_PAIRS, uids, iids, uids.numel(), 1, 0, logits, True, False)
+    return (y, pred) if logits else pred
+
+
+def nfm_rank_eval(fold, uids, cand):
+    """The contract of dot_rank_eval on the NFM scorer: cand [U', C] of LOCAL item ids, column 0 the held-out positive.
+    Returns (logits [U', C], pred [U', C], rank [U'] int32, auc [U']): rank counts the negatives whose logit is strictly
+    higher, auc is the share strictly lower; both read the logits, which order as pred does until the sigmoid saturates."""
+    check_pending_errors()
+    uids, cand = uids.to(torch.int64).contiguous(), cand.to(torch.int64).contiguous()
+    if cand.dim() != 2 or uids.dim() != 1 or cand.shape[0] != uids.shape[0] or cand.shape[1] < 1:
+        raise ValueError('cand must be [U, C >= 1] with one row per user of uids')
+    return _nfm_score(fold, _lib.NFM_ROWS, uids, cand, uids.numel(), cand.shape[1], 0, True, True, True)
+
+
+def nfm_score_block(fold, uids, item_lo, n_items):
+    """logits [U', n_items] of every user of uids against the LOCAL items item_lo .. item_lo + n_items - 1."""
+    check_pending_errors()
+    uids = uids.to(torch.int64).contiguous()
+    if not (0 <= int(item_lo) and int(n_items) >= 1 and int(item_lo) + int(n_items) <= fold.num_items):
+        raise ValueError('the item range must lie inside the %d items' % fold.num_items)
+    return _nfm_score(fold, _lib.NFM_RANGE, uids, None, uids.numel(), int(n_items), int(item_lo), True, False, False)[0]

@@ -1,7 +1,7 @@
 """Host-side samplers with the reference's exact RNG call sequence, so sampled ids are BIT-EXACT given the same
 seeds (`random.seed / np.random.seed / torch.manual_seed`, reference solvers.py:123-127) and the same call order.
 
-    cf_negative_sampling   graph_recsys_benchmark/datasets/movielens.py:879-997 (BPR branch :920-940, shuffle :994-997)
+    cf_negative_sampling   graph_recsys_benchmark/datasets/movielens.py:879-997 (BPR branch :920-940, BCE branch :886-917, shuffle :994-997)
                            (Yelp twin: datasets/yelp.py:746-760)
     kg_negative_sampling   graph_recsys_benchmark/datasets/movielens.py:861-877 (the KG quadruples CFKG trains on)
     generate_candidates    graph_recsys_benchmark/solvers.py:21-31
@@ -27,8 +27,10 @@ def cf_negative_sampling(dataset):
     """BPR training triples: every positive (u, i+) repeated `num_negative_samples` times + one sampled negative
     column, then a torch.randperm shuffle.  Sets dataset.train_data / train_data_length like the reference and
     returns the int64 [M*neg, 3] tensor."""
+    if dataset.cf_loss_type == 'BCE':
+        return _cf_negative_sampling_bce(dataset)
     if dataset.cf_loss_type != 'BPR':
-        raise NotImplementedError('only the BPR branch is on the accelerated path')
+        raise NotImplementedError('only the BPR and BCE branches are on the accelerated path')
     pos = dataset.edge_index_nps['user2item'].T
     num_interactions = pos.shape[0]
     k = dataset.num_negative_samples
@@ -53,6 +55,35 @@ def cf_negative_sampling(dataset):
         raise NotImplementedError('entity_aware=True needs dataset.iid_feat_nids / uid_feat_nids / nid2e_dict '
                                   '(built by the reference\'s dataset preprocessing); attach them to the dataset')
     train_data_t = torch.from_numpy(train_data_np).long()
+    shuffle_idx = torch.randperm(train_data_t.shape[0])
+    dataset.train_data = train_data_t[shuffle_idx]
+    dataset.train_data_length = train_data_t.shape[0]
+    return dataset.train_data
+
+
+def _cf_negative_sampling_bce(dataset):
+    """The BCE branch (datasets/movielens.py:886-917), what NFM trains on: every positive (u, i+, 1), then
+    `num_negative_samples` rows (u, sampled item, 0) per positive, then the shared torch.randperm shuffle: int64
+    [M (1 + neg), 3].  'random': ONE np.random.randint over all negatives; 'unseen': one np.random.choice per positive over the
+    user's held-out and never-seen items -- numpy's stream here, where the BPR branch draws with Python's `random`."""
+    pos = dataset.edge_index_nps['user2item'].T
+    num_interactions = pos.shape[0]
+    k = dataset.num_negative_samples
+    pos_samples_np = np.hstack([pos, np.ones((num_interactions, 1))])
+    users = np.repeat(pos_samples_np[:, 0].reshape(-1, 1), repeats=k, axis=0)
+    if dataset.sampling_strategy == 'random':
+        lo = dataset.type_accs['iid']
+        neg = np.random.randint(low=lo, high=lo + dataset.num_iids, size=(num_interactions * k, 1))
+    elif dataset.sampling_strategy == 'unseen':
+        parts = []
+        for u_nid in pos_samples_np[:, 0]:
+            pool = dataset.test_pos_unid_inid_map[u_nid] + dataset.neg_unid_inid_map[u_nid]
+            parts.append(np.random.choice(pool, size=(k, 1)))
+        neg = np.vstack(parts)
+    else:
+        raise NotImplementedError
+    neg_samples_np = np.hstack([users, neg, np.zeros((num_interactions * k, 1))])
+    train_data_t = torch.from_numpy(np.vstack([pos_samples_np, neg_samples_np])).long()
     shuffle_idx = torch.randperm(train_data_t.shape[0])
     dataset.train_data = train_data_t[shuffle_idx]
     dataset.train_data_length = train_data_t.shape[0]
