@@ -1,5 +1,5 @@
 """ctypes binding of libpeahip.so (C ABI: include/peahip.h, include/peahip_kge.h, include/peahip_eval.h,
-include/peahip_sample.h and include/peahip_fm.h).
+include/peahip_sample.h, include/peahip_fm.h and include/peahip_fm_eval.h).
 
 The product path has NO fallback: if the HIP library is missing or no gfx950 device is visible, every
 compute entry point raises.  (CPU parity checking lives in oracle/, which this package never imports.)
@@ -251,6 +251,19 @@ FM_SIGNATURES = {
 }
 NFM_PAIRS, NFM_ROWS, NFM_RANGE, NFM_MAX_BATCH = 0, 1, 2, 8192     # include/peahip_fm.h PEA_NFM_*
 
+# every symbol include/peahip_fm_eval.h declares (the full-catalogue scan over the NFM fold); the fold is the first 11 arguments
+_fold = [_int, _int, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]
+FM_EVAL_SIGNATURES = {
+    'pea_nfm_scan_supported': (_int, [_int, _int, _int]),
+    'pea_nfm_scan_splits': (_int, [_i64, _i64, _int]),
+    'pea_nfm_scan_workspace_bytes': (_sz, [_i64, _i64, _i64, _i64, _int, _int, _int]),
+    'pea_nfm_recommend_topk': (_int, _fold + [_vp, _i64, _int, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'pea_nfm_rank_full': (_int, _fold + [_vp, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'pea_nfm_rank_full_multi': (_int, _fold + [_vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
+                                               _vp]),
+}
+NFM_SCAN_USERS = 8     # include/peahip_fm_eval.h PEA_NFM_SCAN_USERS
+
 KGU_KGAT, KGU_KGCN, KGU_NGCF = 0, 1, 2     # include/peahip.h PEA_KGU_*
 
 _lib = None
@@ -265,7 +278,8 @@ def load():
                               '(or make -C graph_recsys_benchmark_amd/csrc); there is no CPU fallback' % LIB_PATH)
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(KGE_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) +
-                                  list(SAMPLE_SIGNATURES.items()) + list(FM_SIGNATURES.items())):
+                                  list(SAMPLE_SIGNATURES.items()) + list(FM_SIGNATURES.items()) +
+                                  list(FM_EVAL_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

@@ -35,6 +35,7 @@
 #include <algorithm>
 
 #include "../../include/peahip_fm.h"
+#include "nfm_tile.h"
 #include "tile16.h"
 #include "train_common.h"
 
@@ -541,11 +542,8 @@ __device__ __forceinline__ void pair_of(const NsArgs &a, int64_t k, int64_t &u, 
     }
 }
 
-// One workgroup walks tiles of kSP = 64 pairs, four MFMA row blocks: x = e_u (.) e_i in LDS, z = x W'^T as four chains that
-// share each weight value (rows_times_wt<1, 4>; wave w the output tiles w, w + 4, ..), relu(z + b') w2 added per lane over its
-// tiles in tile order, over the lane's four column groups by two xor shuffles, over the waves in wave order; the logit
-// adds (lin[u] + lin[U + i]) + bias first, as the training step does.
-constexpr int kSB = 4, kSP = kSB * kTR;
+// One workgroup walks tiles of kSP = 64 pairs; the tile's arithmetic is nfm_tile.h's (nfm_x4, nfm_tile_dots, nfm_logit), which
+// the catalogue scan of nfm_scan.hip calls too.
 
 __global__ __launch_bounds__(kThreads) void nfm_score_kernel(const NsArgs a) {
     const int LD = a.LD, E = a.E, H = a.H, e4 = E / 4;
@@ -554,9 +552,7 @@ __global__ __launch_bounds__(kThreads) void nfm_score_kernel(const NsArgs a) {
     float *part = Xt + kSP * LD;                                  // [4 waves][64]
     int64_t *ids = reinterpret_cast<int64_t *>(part + kWaves * kSP);
     int *valid = reinterpret_cast<int *>(ids + 2 * kSP);
-    const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave, n = lane & 15, g = lane >> 4;
     const int64_t n_tiles = (a.n_pairs + kSP - 1) / kSP;
-    const int HT = a.HP / 16;
     for (int i = threadIdx.x; i < kSP * LD; i += kThreads) Xt[i] = 0.f;
     stage_weight<4>(a.wf, H, E, 0, Ws, a.HP, a.EP, LD);
     for (int64_t T = blockIdx.x; T < n_tiles; T += gridDim.x) {
@@ -578,40 +574,16 @@ __global__ __launch_bounds__(kThreads) void nfm_score_kernel(const NsArgs a) {
         for (int i = threadIdx.x; i < kSP * e4; i += kThreads) {
             const int rr = i / e4, c = 4 * (i - rr * e4);
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (valid[rr]) {
-                const float4 x = ld4(a.emb + ids[rr] * a.ld_emb + c), y = ld4(a.emb + ids[kSP + rr] * a.ld_emb + c);
-                v = make_float4(x.x * y.x, x.y * y.y, x.z * y.z, x.w * y.w);
-            }
+            if (valid[rr]) v = nfm_x4(ld4(a.emb + ids[rr] * a.ld_emb + c), ld4(a.emb + ids[kSP + rr] * a.ld_emb + c));
             st4(Xt + rr * LD + c, v);
         }
         __syncthreads();
-        float s[kSB] = {0.f, 0.f, 0.f, 0.f};
-        for (int v = wave; v < HT; v += kWaves) {
-            f32x4 z[kSB] = {};
-            rows_times_wt<1, kSB>(Ws, a.HP, LD, Xt, LD, e4, v, n, g, z);
-            const int col = 16 * v + 4 * g;
-            if (col >= H) continue;
-            const float4 b = ld4(a.bf + col), w = ld4(a.w2 + col);
-#pragma unroll
-            for (int c = 0; c < kSB; ++c)
-                s[c] += ((fmaxf(z[c][0] + b.x, 0.f) * w.x + fmaxf(z[c][1] + b.y, 0.f) * w.y) +
-                         (fmaxf(z[c][2] + b.z, 0.f) * w.z + fmaxf(z[c][3] + b.w, 0.f) * w.w));
-        }
-#pragma unroll
-        for (int c = 0; c < kSB; ++c) {
-            s[c] += __shfl_xor(s[c], 16);
-            s[c] += __shfl_xor(s[c], 32);
-            if (g == 0) part[wave * kSP + c * kTR + n] = s[c];
-        }
-        __syncthreads();
+        const float d = nfm_tile_dots(Ws, Xt, part, a.bf, a.w2, H, a.HP, LD, e4);
         if (threadIdx.x < kSP) {
             const int64_t k = T * kSP + threadIdx.x;
             if (k < a.n_pairs) {
                 float y = 0.f;
-                if (valid[threadIdx.x]) {
-                    const float d = (part[threadIdx.x] + part[kSP + threadIdx.x]) + (part[2 * kSP + threadIdx.x] + part[3 * kSP + threadIdx.x]);
-                    y = ((a.lin[ids[threadIdx.x]] + a.lin[ids[kSP + threadIdx.x]]) + a.bias[0]) + d;
-                }
+                if (valid[threadIdx.x]) y = nfm_logit(a.lin[ids[threadIdx.x]], a.lin[ids[kSP + threadIdx.x]], a.bias[0], d);
                 if (a.logit) a.logit[k] = y;
                 if (a.pred) a.pred[k] = 1.0f / (1.0f + expf(-y));
             }

@@ -25,7 +25,8 @@ from .losses import (  # noqa: F401
 from .scoring import (  # noqa: F401
     _catalogue_args, _check_scored, _dot_table, _entity_launch, _EntityReg, _rank_io, bpr_score, dot_predict, dot_rank_eval,
     dot_rank_full, dot_rank_full_multi, dot_recommend_topk, entity_reg, fuse_ablate, predict, rank_eval, rank_eval_multi, rank_full,
-    rank_full_multi, recommend_topk, NfmFolded, nfm_fold, nfm_fold_torch, nfm_predict, nfm_rank_eval, nfm_score_block)
+    rank_full_multi, recommend_topk, NfmFolded, nfm_fold, nfm_fold_torch, nfm_predict, nfm_rank_eval, nfm_score_block,
+    nfm_rank_full, nfm_rank_full_multi, nfm_recommend_topk, nfm_scan_splits, nfm_scan_supported)
 from .sharding import ShardLayout
 from .walk_ops import (  # noqa: F401
     _SkipgramLoss, _walk_rows, _walk_starts, metapath_walks, skipgram_loss, skipgram_supported, skipgram_train_raw, uniform_walks)

@@ -19,8 +19,13 @@ and are the torch composition everywhere.  On the GPU, for a shape engine.nfm_su
     and predict in eval mode, rank_eval, rank_full and recommend run on the MFMA pair scorer (engine.nfm_*).
 On the CPU, or for a shape the kernels refuse, the same fold is built in torch.  rank_eval, rank_full and recommend take NODE
 ids and subtract acc_uids / acc_iids: solvers.metrics, metrics_full and metrics_full_multi accept the model through the hooks
-they look for.  rank_full and recommend are compositions: the scorer's item-range form in user chunks, then a comparison or
-torch.topk-style selection; there is no fused catalogue scan for this scorer."""
+they look for, rank_full_multi among them (one catalogue scan for users with several held-out positives).
+  * fused_scan=True (the default): where the HIP scorer runs and engine.nfm_scan_supported takes the widths and k, recommend,
+    rank_full and rank_full_multi are ONE fused pass over the catalogue each (csrc/nfm_scan.hip, include/peahip_fm_eval.h):
+    the [users, items] logit matrix is never written, and a pair's logit has the bits of the pair scorer, so the lists and
+    integers are the composition's.
+  * otherwise (fused_scan=False, the CPU, a refused shape, k > 128) they are compositions, the yardstick the fused route is
+    tested and measured against: the scorer's item-range form per USER_CHUNK users, then a comparison or a stable sort."""
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -111,6 +116,7 @@ class NFMRecsysModel(MFRecsysModel):
         self.acc_uids, self.acc_iids = int(kwargs.get('acc_uids', 0)), int(kwargs.get('acc_iids', 0))
         self.native = bool(kwargs.get('native', True))
         self.native_train = bool(kwargs.get('native_train', False))
+        self.fused_scan = bool(kwargs.get('fused_scan', True))
         self.emb = _NeuralFactorizationMachineModel([self.num_users, self.num_items], self.emb_dim, (self.hidden_size,),
                                                     [self.dropout, self.dropout])
         self.folded = None            # engine.NfmFolded of the last eval()
@@ -208,6 +214,14 @@ class NFMRecsysModel(MFRecsysModel):
     def _hip_scorer(self):
         return self.folded.device.type == 'cuda' and self._native_ok()
 
+    def _fused(self, k=0):
+        """whether a catalogue call keeping k items per user (0: the rank forms) takes the fused scan"""
+        return self.fused_scan and self._hip_scorer() and _engine.nfm_scan_supported(self.emb_dim, self.hidden_size, k)
+
+    @staticmethod
+    def _on(exclude, dev):
+        return None if exclude is None else tuple(t.to(dev) for t in exclude)
+
     def _logits_torch(self, uid, iid):
         """y of local ids uid [..] x iid [..] (broadcast against each other) over the fold, in torch"""
         f = self.folded
@@ -261,13 +275,16 @@ class NFMRecsysModel(MFRecsysModel):
     def rank_full(self, unids, pos_items, item_range, exclude=None):
         """engine.rank_full's contract for this model, on NODE ids: per user the rank of the held-out positive among the items of
         item_range that are neither excluded nor the positive itself (those whose logit is strictly higher), the share of them
-        strictly lower, and the positive's logit.  A composition: the scorer's range form per USER_CHUNK users, then a
-        comparison.  What solvers.metrics_full calls."""
+        strictly lower, and the positive's logit.  One fused scan (engine.nfm_rank_full) where _fused() holds; else a
+        composition: the scorer's range form per USER_CHUNK users, then a comparison.  What solvers.metrics_full calls."""
         self._require_fold('rank_full()')
         lo, hi = int(item_range[0]), int(item_range[1])
         with torch.no_grad():
             dev = self.folded.device
             unids, pos_items = unids.to(dev).to(torch.int64), pos_items.to(dev).to(torch.int64)
+            if self._fused():
+                return _engine.nfm_rank_full(self.folded, unids - self.acc_uids, pos_items, lo - self.acc_iids, hi - lo,
+                                             item_node0=self.acc_iids, exclude=self._on(exclude, dev))
             ranks, aucs, poss = [], [], []
             for r0 in range(0, unids.numel(), self.USER_CHUNK):
                 r1 = min(r0 + self.USER_CHUNK, unids.numel())
@@ -289,13 +306,16 @@ class NFMRecsysModel(MFRecsysModel):
     def recommend(self, unids, k, item_range, exclude=None):
         """GraphRecsysModel.recommend's contract on NODE ids: the k best items of item_range for every user, ordered by (logit
         descending, node id ascending), exclude = (rowptr, items) left out; (items int64 [U, k], logits [U, k]) with a
-        (-1, -inf) tail where fewer than k items are eligible.  A composition: the scorer's range form per USER_CHUNK users,
-        then a stable sort."""
+        (-1, -inf) tail where fewer than k items are eligible.  One fused scan (engine.nfm_recommend_topk) where _fused(k)
+        holds; else a composition: the scorer's range form per USER_CHUNK users, then a stable sort."""
         self._require_fold('recommend()')
         lo, hi = int(item_range[0]), int(item_range[1])
         with torch.no_grad():
             dev = self.folded.device
             unids = torch.as_tensor(unids, device=dev).to(torch.int64)
+            if 1 <= int(k) <= 128 and self._fused(int(k)):
+                return _engine.nfm_recommend_topk(self.folded, unids - self.acc_uids, int(k), lo - self.acc_iids, hi - lo,
+                                                  item_node0=self.acc_iids, exclude=self._on(exclude, dev))
             items = torch.arange(lo, hi, device=dev)
             out_i, out_s = [], []
             for r0 in range(0, unids.numel(), self.USER_CHUNK):
@@ -312,3 +332,46 @@ class NFMRecsysModel(MFRecsysModel):
                 out_i.append(top_i)
                 out_s.append(top_s)
             return torch.cat(out_i), torch.cat(out_s)
+
+    POS_CHUNK = 1024          # positives compared at once in the composition of rank_full_multi: a [1024, items] block
+
+    def rank_full_multi(self, unids, pos_rowptr, pos_items, item_range, exclude=None):
+        """engine.rank_full_multi's contract for this model, on NODE ids: the positives are a CSR (pos_rowptr [U + 1], pos_items
+        [Q], every row strictly ascending); a user's negatives are the items of item_range in neither its exclusion row nor its
+        positive row.  Returns, in the flat order of pos_items, (above int32 [Q] = negatives whose logit is strictly higher,
+        below int32 [Q] = strictly lower, pos_score [Q]) and n_neg int32 [U].  One fused scan (engine.nfm_rank_full_multi)
+        where _fused() holds; else the scorer's range form per USER_CHUNK users and a comparison per positive.  What
+        solvers.metrics_full_multi calls."""
+        self._require_fold('rank_full_multi()')
+        lo, hi = int(item_range[0]), int(item_range[1])
+        with torch.no_grad():
+            dev = self.folded.device
+            unids = torch.as_tensor(unids, device=dev).to(torch.int64)
+            pos_rowptr, pos_items = pos_rowptr.to(dev).to(torch.int64), pos_items.to(dev).to(torch.int64)
+            if self._fused():
+                return _engine.nfm_rank_full_multi(self.folded, unids - self.acc_uids, pos_rowptr, pos_items, lo - self.acc_iids,
+                                                   hi - lo, item_node0=self.acc_iids, exclude=self._on(exclude, dev))
+            n_users = unids.numel()
+            owner = torch.repeat_interleave(torch.arange(n_users, device=dev), pos_rowptr[1:] - pos_rowptr[:-1])
+            above, below, poss, n_neg = [], [], [], []
+            for r0 in range(0, n_users, self.USER_CHUNK):
+                r1 = min(r0 + self.USER_CHUNK, n_users)
+                uid = unids[r0:r1] - self.acc_uids
+                scores = self._block(uid, lo - self.acc_iids, hi - lo)
+                negative = ~(self._excluded(n_users, lo, hi, exclude, dev, r0, r1) |
+                             self._excluded(n_users, lo, hi, (pos_rowptr, pos_items), dev, r0, r1))
+                n_neg.append(negative.sum(dim=1).to(torch.int32))
+                b, e = int(pos_rowptr[r0]), int(pos_rowptr[r1])
+                for p0 in range(b, e, self.POS_CHUNK):
+                    p1 = min(p0 + self.POS_CHUNK, e)
+                    row = owner[p0:p1] - r0
+                    pos_local = pos_items[p0:p1] - self.acc_iids
+                    if self._hip_scorer():
+                        pos = _engine.nfm_predict(self.folded, uid[row], pos_local, logits=True)[0]
+                    else:
+                        pos = self._logits_torch(uid[row], pos_local)
+                    above.append(((scores[row] > pos.view(-1, 1)) & negative[row]).sum(dim=1).to(torch.int32))
+                    below.append(((scores[row] < pos.view(-1, 1)) & negative[row]).sum(dim=1).to(torch.int32))
+                    poss.append(pos.view(-1))
+            cat = lambda parts, dtype: torch.cat(parts) if parts else torch.zeros(0, dtype=dtype, device=dev)
+            return cat(above, torch.int32), cat(below, torch.int32), cat(poss, torch.float32), cat(n_neg, torch.int32)

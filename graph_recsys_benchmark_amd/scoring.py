@@ -465,3 +465,125 @@ def nfm_score_block(fold, uids, item_lo, n_items):
     if not (0 <= int(item_lo) and int(n_items) >= 1 and int(item_lo) + int(n_items) <= fold.num_items):
         raise ValueError('the item range must lie inside the %d items' % fold.num_items)
     return _nfm_score(fold, _lib.NFM_RANGE, uids, None, uids.numel(), int(n_items), int(item_lo), True, False, False)[0]
+
+
+# ---- the full-catalogue scan over the NFM fold (csrc/nfm_scan.hip, include/peahip_fm_eval.h)
+def nfm_scan_supported(emb_dim, hidden_size, k=0):
+    """Whether the fused catalogue scan takes these widths and k (pea_nfm_scan_supported; k = 0 asks for the rank forms,
+    else k in 1..128).  Needs no device."""
+    return bool(_lib.load().pea_nfm_scan_supported(int(emb_dim), int(hidden_size), int(k)))
+
+
+def nfm_scan_splits(n_users, n_items, k=0):
+    """The item ranges a fused call over n_users users and n_items items uses (pea_nfm_scan_splits)."""
+    return int(_lib.load().pea_nfm_scan_splits(int(n_users), int(n_items), int(k)))
+
+
+def _nfm_scan_args(fold, what, uids, k, item_lo, n_items, exclude):
+    """What the three fused calls share: (lib, the 11 fold arguments, uids, item_lo, n_items, exclusion rowptr, items)"""
+    lib = _lib.require_device()
+    e, h = fold.emb.shape[1], fold.w.shape[0]
+    if not lib.pea_nfm_scan_supported(e, h, int(k)):
+        raise ValueError('%s: widths (%d, %d) with k = %d not supported (engine.nfm_scan_supported)' % (what, e, h, int(k)))
+    uids = uids.to(torch.int64).contiguous()
+    if uids.dim() != 1:
+        raise ValueError('uids must be 1-d')
+    item_lo, n_items = int(item_lo), int(n_items)
+    if not (0 <= item_lo and n_items >= 0 and item_lo + n_items <= fold.num_items):
+        raise ValueError('the item range must lie inside the %d items' % fold.num_items)
+    rowptr = items = None
+    if exclude is not None:
+        rowptr, items = exclude
+        if rowptr.dtype != torch.int64 or items.dtype != torch.int64 or rowptr.numel() != uids.numel() + 1:
+            raise ValueError('exclude is (rowptr int64 [U + 1], items int64) -- see utils.interactions.seen_items_csr')
+        if rowptr.device != fold.device or items.device != fold.device:
+            raise ValueError('the exclusion lists must live on the device of the fold')
+        rowptr, items = rowptr.contiguous(), items.contiguous()
+        if items.numel() == 0:                  # a valid pointer for the C side even when nobody has seen anything
+            items = torch.zeros(1, dtype=torch.int64, device=fold.device)
+    head = (e, h, fold.num_users, fold.num_items, _lib.ptr(fold.emb), fold.emb.stride(0), _lib.ptr(fold.lin), _lib.ptr(fold.w),
+            _lib.ptr(fold.b), _lib.ptr(fold.w2), _lib.ptr(fold.bias))
+    return lib, head, uids, item_lo, n_items, rowptr, items
+
+
+def _nfm_scan_ws(lib, fold, n_users, q, items, n_items, k):
+    """(workspace, its size, the zeroed error flag) of a fused call"""
+    n_excl = int(items.numel()) if items is not None else 0
+    ws_bytes = int(lib.pea_nfm_scan_workspace_bytes(n_users, q, n_excl, n_items, int(k), fold.emb.shape[1], fold.w.shape[0]))
+    return (torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=fold.device), ws_bytes,
+            torch.zeros(1, dtype=torch.int32, device=fold.device))
+
+
+def nfm_recommend_topk(fold, uids, k, item_lo, n_items, item_node0=0, exclude=None):
+    """The k best of the LOCAL items item_lo .. item_lo + n_items - 1 for every LOCAL user of uids over the folded weights, in
+    one pass over the catalogue (include/peahip_fm_eval.h, pea_nfm_recommend_topk): (items int64 [U', k] as NODE ids =
+    item_node0 + local, logits [U', k]) ordered by (logit descending, node id ascending) with a (-1, -inf) tail.  exclude =
+    (rowptr [U' + 1], items) names NODE ids to leave out, every row strictly ascending.  The logits are nfm_score_block's
+    bits.  A user id out of range gets an empty list and raises IndexError at the next check_pending_errors()."""
+    check_pending_errors()
+    lib, head, uids, item_lo, n_items, rowptr, items = _nfm_scan_args(fold, 'nfm_recommend_topk', uids, k, item_lo, n_items, exclude)
+    u, k, dev = uids.numel(), int(k), fold.device
+    out_items = torch.empty((u, k), dtype=torch.int64, device=dev)
+    out_scores = torch.empty((u, k), dtype=torch.float32, device=dev)
+    if u == 0:
+        return out_items, out_scores
+    ws, ws_bytes, flag = _nfm_scan_ws(lib, fold, u, 0, items, n_items, k)
+    _lib.check(lib.pea_nfm_recommend_topk(*head, _lib.ptr(uids), u, k, item_lo, n_items, int(item_node0), _lib.ptr(rowptr),
+                                          _lib.ptr(items), _lib.ptr(out_items), _lib.ptr(out_scores), _lib.ptr(flag), _lib.ptr(ws),
+                                          ws_bytes, _lib.current_stream()))
+    _defer_error(flag, NFM_ID_MESSAGE)
+    return out_items, out_scores
+
+
+def nfm_rank_full(fold, uids, pos_items, item_lo, n_items, item_node0=0, exclude=None):
+    """The all-item rank of one held-out positive (a NODE id) per LOCAL user over the folded weights, in one pass over the
+    catalogue (pea_nfm_rank_full): (rank int32 [U'] = the catalogue items, neither excluded nor the positive, whose logit is
+    strictly higher, auc [U'] = float32(those strictly lower) / float32(their number), pos_score [U'])."""
+    check_pending_errors()
+    lib, head, uids, item_lo, n_items, rowptr, items = _nfm_scan_args(fold, 'nfm_rank_full', uids, 0, item_lo, n_items, exclude)
+    pos_items = pos_items.to(torch.int64).contiguous()
+    if pos_items.shape != uids.shape:
+        raise ValueError('one positive per requested user')
+    u, dev = uids.numel(), fold.device
+    rank = torch.empty(u, dtype=torch.int32, device=dev)
+    auc, pos_score = torch.empty(u, dtype=torch.float32, device=dev), torch.empty(u, dtype=torch.float32, device=dev)
+    if u == 0:
+        return rank, auc, pos_score
+    ws, ws_bytes, flag = _nfm_scan_ws(lib, fold, u, u, items, n_items, 0)
+    _lib.check(lib.pea_nfm_rank_full(*head, _lib.ptr(uids), u, _lib.ptr(pos_items), item_lo, n_items, int(item_node0),
+                                     _lib.ptr(rowptr), _lib.ptr(items), _lib.ptr(rank), _lib.ptr(auc), _lib.ptr(pos_score),
+                                     _lib.ptr(flag), _lib.ptr(ws), ws_bytes, _lib.current_stream()))
+    _defer_error(flag, NFM_ID_MESSAGE)
+    return rank, auc, pos_score
+
+
+def nfm_rank_full_multi(fold, uids, pos_rowptr, pos_items, item_lo, n_items, item_node0=0, exclude=None):
+    """nfm_rank_full for users with any number of held-out positives, in one catalogue scan (pea_nfm_rank_full_multi): the
+    positives are a CSR (pos_rowptr int64 [U' + 1], pos_items int64 [Q] of NODE ids) on the fold's device, every row strictly
+    ascending.  Returns, in the flat order of pos_items, (above int32 [Q], below int32 [Q], pos_score [Q]) and n_neg int32
+    [U']: the contract of rank_full_multi."""
+    check_pending_errors()
+    lib, head, uids, item_lo, n_items, rowptr, items = _nfm_scan_args(fold, 'nfm_rank_full_multi', uids, 0, item_lo, n_items, exclude)
+    u, dev = uids.numel(), fold.device
+    for t in (pos_rowptr, pos_items):
+        if not torch.is_tensor(t) or t.dtype != torch.int64 or t.dim() != 1:
+            raise ValueError('positives are (pos_rowptr int64 [U + 1], pos_items int64 [Q]) -- see utils.interactions.positives_csr')
+        if t.device != dev:
+            raise ValueError('the positives must live on the device of the fold')
+    if pos_rowptr.numel() != u + 1:
+        raise ValueError('pos_rowptr must have one entry per requested user and one more')
+    pos_rowptr, pos_items = pos_rowptr.contiguous(), pos_items.contiguous()
+    q = pos_items.numel()
+    above, below = (torch.empty(q, dtype=torch.int32, device=dev) for _ in range(2))
+    pos_score = torch.empty(q, dtype=torch.float32, device=dev)
+    n_neg = torch.empty(u, dtype=torch.int32, device=dev)
+    if u == 0:
+        return above, below, pos_score, n_neg
+    ws, ws_bytes, flag = _nfm_scan_ws(lib, fold, u, q, items, n_items, 0)
+    spare = torch.zeros(2, dtype=torch.int64, device=dev) if q == 0 else None      # a valid address where there is nothing to read
+    at = _lib.ptr if q else (lambda t: _lib.ptr(spare))
+    _lib.check(lib.pea_nfm_rank_full_multi(*head, _lib.ptr(uids), u, _lib.ptr(pos_rowptr), at(pos_items), q, item_lo, n_items,
+                                           int(item_node0), _lib.ptr(rowptr), _lib.ptr(items), at(above), at(below), at(pos_score),
+                                           _lib.ptr(n_neg), _lib.ptr(flag), _lib.ptr(ws), ws_bytes, _lib.current_stream()))
+    _defer_error(flag, NFM_ID_MESSAGE)
+    return above, below, pos_score, n_neg
