@@ -17,7 +17,7 @@ Differences, all on purpose:
 import torch
 from torch.nn import Parameter
 
-from .. import engine as _engine
+from .. import engine as _engine, evaluators
 from ..autograd import PEALossFunction, PEAStackFunction, StackOptions
 from ..nn.inits import glorot
 
@@ -421,10 +421,7 @@ class MFRecsysModel(torch.nn.Module):
             pred = self.predict(pos_neg_pair_t[:, 0], pos_neg_pair_t[:, 1])
             label = pos_neg_pair_t[:, -1].float()
         else:
-            pos_pred = self.predict(pos_neg_pair_t[:, 0], pos_neg_pair_t[:, 1])[:1]
-            neg_pred = self.predict(pos_neg_pair_t[:, 0], pos_neg_pair_t[:, 2])
-            pred = torch.cat([pos_pred, neg_pred])
-            label = torch.cat([torch.ones_like(pos_pred), torch.zeros_like(neg_pred)]).float()
+            pred, label = evaluators.eval_pairs(self.predict, pos_neg_pair_t)
         return loss_func(pred, label)
 
     def predict(self, unids, inids):

@@ -18,7 +18,7 @@ import torch
 import torch.nn.functional as F
 from torch.nn import Parameter
 
-from .. import engine as _engine
+from .. import engine as _engine, evaluators
 from ..nn.inits import glorot
 from .base import GraphRecsysModel
 
@@ -98,10 +98,7 @@ class CFKGRecsysModel(GraphRecsysModel):
             pred = self.predict(pos_neg_pair_t[:, 0], pos_neg_pair_t[:, 1])
             label = pos_neg_pair_t[:, -1].float()
         else:
-            pos_pred = self.predict(pos_neg_pair_t[:, 0], pos_neg_pair_t[:, 1])[:1]
-            neg_pred = self.predict(pos_neg_pair_t[:, 0], pos_neg_pair_t[:, 2])
-            pred = torch.cat([pos_pred, neg_pred])
-            label = torch.cat([torch.ones_like(pos_pred), torch.zeros_like(neg_pred)]).float()
+            pred, label = evaluators.eval_pairs(self.predict, pos_neg_pair_t)
         return F.binary_cross_entropy_with_logits(pred, label)
 
     def eval(self):
@@ -113,18 +110,10 @@ class CFKGRecsysModel(GraphRecsysModel):
             self.cached_repr = table
         return self
 
-    @staticmethod
-    def _eval_bce(pred):
-        """The reference's evaluation loss of rows (u, pos, neg...) from their predictions [U, C], column 0 the positive
-        (models/base.py:117-122 in eval mode): labels [1, 0, ...], BCEWithLogitsLoss; one value per row."""
-        label = torch.zeros_like(pred)
-        label[:, 0] = 1.0
-        return F.binary_cross_entropy_with_logits(pred, label, reduction='none').mean(dim=1)
-
     def rank_eval(self, unids, cand):
         """engine.dot_rank_eval's contract on the eval-mode table (cand [U, C], column 0 the held-out positive): rank of the
         positive and auc from the kernel's log-scores, exp(scores) as the predictions, and the per-user eval loss recomputed
-        from them in the BCE form above.  What solvers.metrics calls."""
+        from them in the BCE form of the reference's eval mode (models/base.py:117-122).  What solvers.metrics calls."""
         if self.training or self.cached_repr is None:
             raise RuntimeError('rank_eval() reads the eval-mode table: call model.eval() first')
         if self.cached_repr.is_cuda:
@@ -132,11 +121,9 @@ class CFKGRecsysModel(GraphRecsysModel):
         else:
             t = self.cached_repr
             scores = torch.sum(t[unids.long()].unsqueeze(1) * t[cand.long()], dim=-1)
-            pos, neg = scores[:, :1], scores[:, 1:]
-            rank = (neg > pos).sum(dim=1).to(torch.int32)
-            auc = (neg < pos).sum(dim=1).to(torch.float32) / max(neg.shape[1], 1)
+            rank, auc = evaluators.candidate_ranks(scores)
         pred = torch.exp(scores)
-        return pred, rank, auc, self._eval_bce(pred)
+        return pred, rank, auc, evaluators.leave_one_out_loss(pred, 'bce')
 
     def recommend(self, unids, k, item_range, exclude=None):
         """GraphRecsysModel.recommend with exp of the kernel's scores: the predictions; the order is unchanged"""

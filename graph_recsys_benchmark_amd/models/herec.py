@@ -14,7 +14,7 @@ shape the kernels refuse, the same table is built in torch (and loss() stays the
 import torch
 import torch.nn.functional as F
 
-from .. import engine as _engine
+from .. import engine as _engine, evaluators
 from ..nn.inits import glorot
 from .base import GraphRecsysModel
 
@@ -89,14 +89,6 @@ class HeRecRecsysModel(GraphRecsysModel):
             return self.forward(unids, inids)
         return self.scored('predict', unids, inids)
 
-    @staticmethod
-    def _eval_mse(scores):
-        """The reference's evaluation loss of rows (u, pos, neg...) from their scores [U, C], column 0 the positive
-        (experiments/herec_solver_bpr.py:108-121 in eval mode): labels [1, 0, ...], MSELoss; one value per row."""
-        label = torch.zeros_like(scores)
-        label[:, 0] = 1.0
-        return ((scores - label) ** 2).mean(dim=1)
-
     def loss(self, batch):
         if self.training:
             unids, inids, labels = batch[:, 0], batch[:, 1], batch[:, -1].float()
@@ -106,11 +98,7 @@ class HeRecRecsysModel(GraphRecsysModel):
                                               self.user_rk_bias.weight, self.item_rk_bias.weight, self.acc_uids, self.acc_iids,
                                               unids.long(), inids.long(), labels)
             return F.mse_loss(self.forward(unids.long(), inids.long()), labels)
-        pos_pred = self.predict(batch[:, 0], batch[:, 1])[:1]
-        neg_pred = self.predict(batch[:, 0], batch[:, 2])
-        pred = torch.cat([pos_pred, neg_pred])
-        label = torch.cat([torch.ones_like(pos_pred), torch.zeros_like(neg_pred)]).float()
-        return F.mse_loss(pred, label)
+        return F.mse_loss(*evaluators.eval_pairs(self.predict, batch))
 
     def _table_torch(self):
         """cached_repr in torch: what engine.herec_table builds (include/peahip.h, pea_herec_table)"""
@@ -142,8 +130,8 @@ class HeRecRecsysModel(GraphRecsysModel):
 
     def rank_eval(self, unids, cand):
         """engine.dot_rank_eval's contract on the eval-mode table (cand [U, C], column 0 the held-out positive): scores, rank of
-        the positive and auc from the kernel; the per-user eval loss is recomputed from the scores as the MSE form above
-        (dot_rank_eval's own loss is the BPR one).  What solvers.metrics calls."""
+        the positive and auc from the kernel; the per-user eval loss is recomputed from the scores in the MSE form of the driver's eval
+        mode (experiments/herec_solver_bpr.py:108-121; dot_rank_eval's own loss is the BPR one).  What solvers.metrics calls."""
         if self.training or self.cached_repr is None:
             raise RuntimeError('rank_eval() reads the eval-mode table: call model.eval() first')
         if self.cached_repr.is_cuda:
@@ -151,7 +139,5 @@ class HeRecRecsysModel(GraphRecsysModel):
         else:
             t = self.cached_repr
             scores = torch.sum(t[unids.long()].unsqueeze(1) * t[cand.long()], dim=-1)
-            pos, neg = scores[:, :1], scores[:, 1:]
-            rank = (neg > pos).sum(dim=1).to(torch.int32)
-            auc = (neg < pos).sum(dim=1).to(torch.float32) / max(neg.shape[1], 1)
-        return scores, rank, auc, self._eval_mse(scores)
+            rank, auc = evaluators.candidate_ranks(scores)
+        return scores, rank, auc, evaluators.leave_one_out_loss(scores, 'mse')

@@ -24,13 +24,13 @@ they look for, rank_full_multi among them (one catalogue scan for users with sev
     rank_full and rank_full_multi are ONE fused pass over the catalogue each (csrc/nfm_scan.hip, include/peahip_fm_eval.h):
     the [users, items] logit matrix is never written, and a pair's logit has the bits of the pair scorer, so the lists and
     integers are the composition's.
-  * otherwise (fused_scan=False, the CPU, a refused shape, k > 128) they are compositions, the yardstick the fused route is
-    tested and measured against: the scorer's item-range form per USER_CHUNK users, then a comparison or a stable sort."""
+  * otherwise (fused_scan=False, the CPU, a refused shape, k > 128) they are the compositions of evaluators.py, the yardstick
+    the fused route is tested and measured against: the scorer's item-range form per USER_CHUNK users, then a comparison or a
+    stable sort."""
 import numpy as np
 import torch
-import torch.nn.functional as F
 
-from .. import engine as _engine
+from .. import engine as _engine, evaluators
 from .base import MFRecsysModel
 
 
@@ -107,7 +107,8 @@ class _NeuralFactorizationMachineModel(torch.nn.Module):
 
 
 class NFMRecsysModel(MFRecsysModel):
-    USER_CHUNK = 256          # users per launch of the item-range form in rank_full / recommend: a [256, items] logit block
+    USER_CHUNK = 256          # users per launch of the item-range form in the compositions: a [256, items] logit block
+    POS_CHUNK = 1024          # positives compared at once in the composition of rank_full_multi: a [1024, items] block
 
     def _init(self, **kwargs):
         self.num_users, self.num_items = int(kwargs['num_users']), int(kwargs['num_items'])
@@ -182,10 +183,7 @@ class NFMRecsysModel(MFRecsysModel):
             pred = self.predict(batch[:, 0], batch[:, 1])
             label = batch[:, -1].float()
         else:
-            pos_pred = self.predict(batch[:, 0], batch[:, 1])[:1]
-            neg_pred = self.predict(batch[:, 0], batch[:, 2])
-            pred = torch.cat([pos_pred, neg_pred])
-            label = torch.cat([torch.ones_like(pos_pred), torch.zeros_like(neg_pred)]).float()
+            pred, label = evaluators.eval_pairs(self.predict, batch)
         return torch.nn.MSELoss()(pred, label)
 
     # ------------------------------------------------------------------ eval mode: the fold and the scorer
@@ -236,19 +234,24 @@ class NFMRecsysModel(MFRecsysModel):
         items = torch.arange(lo, lo + n, device=uid.device)
         return self._logits_torch(uid.view(-1, 1), items.view(1, -1))
 
-    @staticmethod
-    def _eval_mse(pred):
-        """The reference's evaluation loss of rows (u, pos, neg...) from their predictions [U, C], column 0 the positive
-        (models/nfm.py:27-32): labels [1, 0, ...], MSELoss; one value per row."""
-        label = torch.zeros_like(pred)
-        label[:, 0] = 1.0
-        return ((pred - label) ** 2).mean(dim=1)
+    def _callbacks(self, unids, lo, hi):
+        """what evaluators' compositions ask of this model: (block, pairs) over the requested NODE users unids and the catalogue
+        [lo, hi) -- the scorer's item-range form on a slice of the users, and the logits of (user row, item NODE id) pairs"""
+        def block(r0, r1):
+            return self._block(unids[r0:r1] - self.acc_uids, lo - self.acc_iids, hi - lo)
+
+        def pairs(rows, items):
+            uid, iid = unids[rows] - self.acc_uids, items - self.acc_iids
+            if self._hip_scorer():
+                return _engine.nfm_predict(self.folded, uid, iid, logits=True)[0]
+            return self._logits_torch(uid, iid)
+        return block, pairs
 
     def rank_eval(self, unids, cand):
         """engine.dot_rank_eval's contract for this model, on NODE ids (cand [U, C], column 0 the held-out positive): (pred
         [U, C], rank of the positive int32 [U], auc [U], eval loss [U]).  rank and auc compare the logits (pred orders alike
-        until the sigmoid saturates); the loss is the reference's eval-branch MSE recomputed from pred.  What
-        solvers.metrics calls."""
+        until the sigmoid saturates); the loss is the reference's eval-branch MSE recomputed from pred (models/nfm.py:27-32).
+        What solvers.metrics calls."""
         self._require_fold('rank_eval()')
         with torch.no_grad():
             uid, items = unids.to(torch.int64) - self.acc_uids, cand.to(torch.int64) - self.acc_iids
@@ -257,20 +260,8 @@ class NFMRecsysModel(MFRecsysModel):
             else:
                 y = self._logits_torch(uid.view(-1, 1), items)
                 pred = torch.sigmoid(y)
-                pos, neg = y[:, :1], y[:, 1:]
-                rank = (neg > pos).sum(dim=1).to(torch.int32)
-                auc = (neg < pos).sum(dim=1).to(torch.float32) / max(neg.shape[1], 1)
-            return pred, rank, auc, self._eval_mse(pred)
-
-    def _excluded(self, n_users, lo, hi, exclude, device, r0, r1):
-        """bool [r1 - r0, hi - lo]: the items of the node range [lo, hi) that exclude = (rowptr, items) names for users r0 .. r1"""
-        mask = torch.zeros((r1 - r0, hi - lo), dtype=torch.bool, device=device)
-        if exclude is not None:
-            rowptr, excl = (t.to(device) for t in exclude)
-            rows = torch.repeat_interleave(torch.arange(n_users, device=device), rowptr[1:] - rowptr[:-1])
-            inside = (excl >= lo) & (excl < hi) & (rows >= r0) & (rows < r1)
-            mask[rows[inside] - r0, excl[inside] - lo] = True
-        return mask
+                rank, auc = evaluators.candidate_ranks(y)
+            return pred, rank, auc, evaluators.leave_one_out_loss(pred, 'mse')
 
     def rank_full(self, unids, pos_items, item_range, exclude=None):
         """engine.rank_full's contract for this model, on NODE ids: per user the rank of the held-out positive among the items of
@@ -285,23 +276,7 @@ class NFMRecsysModel(MFRecsysModel):
             if self._fused():
                 return _engine.nfm_rank_full(self.folded, unids - self.acc_uids, pos_items, lo - self.acc_iids, hi - lo,
                                              item_node0=self.acc_iids, exclude=self._on(exclude, dev))
-            ranks, aucs, poss = [], [], []
-            for r0 in range(0, unids.numel(), self.USER_CHUNK):
-                r1 = min(r0 + self.USER_CHUNK, unids.numel())
-                uid = unids[r0:r1] - self.acc_uids
-                scores = self._block(uid, lo - self.acc_iids, hi - lo)
-                pos_local = pos_items[r0:r1] - self.acc_iids
-                if self._hip_scorer():
-                    pos = _engine.nfm_predict(self.folded, uid, pos_local, logits=True)[0].view(-1, 1)
-                else:
-                    pos = self._logits_torch(uid, pos_local).view(-1, 1)
-                items = torch.arange(lo, hi, device=dev)
-                eligible = (items.unsqueeze(0) != pos_items[r0:r1].unsqueeze(1)) & ~self._excluded(unids.numel(), lo, hi, exclude, dev, r0, r1)
-                n = eligible.sum(dim=1)
-                ranks.append(((scores > pos) & eligible).sum(dim=1).to(torch.int32))
-                aucs.append(((scores < pos) & eligible).sum(dim=1).to(torch.float32) / n.clamp(min=1))
-                poss.append(pos.view(-1))
-            return torch.cat(ranks), torch.cat(aucs), torch.cat(poss)
+            return evaluators.rank_full(*self._callbacks(unids, lo, hi), pos_items, (lo, hi), exclude, self.USER_CHUNK)
 
     def recommend(self, unids, k, item_range, exclude=None):
         """GraphRecsysModel.recommend's contract on NODE ids: the k best items of item_range for every user, ordered by (logit
@@ -316,31 +291,15 @@ class NFMRecsysModel(MFRecsysModel):
             if 1 <= int(k) <= 128 and self._fused(int(k)):
                 return _engine.nfm_recommend_topk(self.folded, unids - self.acc_uids, int(k), lo - self.acc_iids, hi - lo,
                                                   item_node0=self.acc_iids, exclude=self._on(exclude, dev))
-            items = torch.arange(lo, hi, device=dev)
-            out_i, out_s = [], []
-            for r0 in range(0, unids.numel(), self.USER_CHUNK):
-                r1 = min(r0 + self.USER_CHUNK, unids.numel())
-                scores = self._block(unids[r0:r1] - self.acc_uids, lo - self.acc_iids, hi - lo).clone()
-                scores[self._excluded(unids.numel(), lo, hi, exclude, dev, r0, r1)] = float('-inf')
-                order = torch.sort(scores, dim=1, descending=True, stable=True).indices[:, :k]
-                top_s = torch.gather(scores, 1, order)
-                top_i = torch.where(torch.isinf(top_s) & (top_s < 0), torch.full_like(order, -1), items[order])
-                if top_s.shape[1] < k:
-                    pad = k - top_s.shape[1]
-                    top_s = F.pad(top_s, (0, pad), value=float('-inf'))
-                    top_i = F.pad(top_i, (0, pad), value=-1)
-                out_i.append(top_i)
-                out_s.append(top_s)
-            return torch.cat(out_i), torch.cat(out_s)
-
-    POS_CHUNK = 1024          # positives compared at once in the composition of rank_full_multi: a [1024, items] block
+            block, _ = self._callbacks(unids, lo, hi)
+            return evaluators.recommend(block, unids.numel(), k, (lo, hi), exclude, self.USER_CHUNK, device=dev)
 
     def rank_full_multi(self, unids, pos_rowptr, pos_items, item_range, exclude=None):
         """engine.rank_full_multi's contract for this model, on NODE ids: the positives are a CSR (pos_rowptr [U + 1], pos_items
         [Q], every row strictly ascending); a user's negatives are the items of item_range in neither its exclusion row nor its
         positive row.  Returns, in the flat order of pos_items, (above int32 [Q] = negatives whose logit is strictly higher,
         below int32 [Q] = strictly lower, pos_score [Q]) and n_neg int32 [U].  One fused scan (engine.nfm_rank_full_multi)
-        where _fused() holds; else the scorer's range form per USER_CHUNK users and a comparison per positive.  What
+        where _fused() holds; else the scorer's range form per USER_CHUNK users and a comparison per POS_CHUNK positives.  What
         solvers.metrics_full_multi calls."""
         self._require_fold('rank_full_multi()')
         lo, hi = int(item_range[0]), int(item_range[1])
@@ -351,27 +310,5 @@ class NFMRecsysModel(MFRecsysModel):
             if self._fused():
                 return _engine.nfm_rank_full_multi(self.folded, unids - self.acc_uids, pos_rowptr, pos_items, lo - self.acc_iids,
                                                    hi - lo, item_node0=self.acc_iids, exclude=self._on(exclude, dev))
-            n_users = unids.numel()
-            owner = torch.repeat_interleave(torch.arange(n_users, device=dev), pos_rowptr[1:] - pos_rowptr[:-1])
-            above, below, poss, n_neg = [], [], [], []
-            for r0 in range(0, n_users, self.USER_CHUNK):
-                r1 = min(r0 + self.USER_CHUNK, n_users)
-                uid = unids[r0:r1] - self.acc_uids
-                scores = self._block(uid, lo - self.acc_iids, hi - lo)
-                negative = ~(self._excluded(n_users, lo, hi, exclude, dev, r0, r1) |
-                             self._excluded(n_users, lo, hi, (pos_rowptr, pos_items), dev, r0, r1))
-                n_neg.append(negative.sum(dim=1).to(torch.int32))
-                b, e = int(pos_rowptr[r0]), int(pos_rowptr[r1])
-                for p0 in range(b, e, self.POS_CHUNK):
-                    p1 = min(p0 + self.POS_CHUNK, e)
-                    row = owner[p0:p1] - r0
-                    pos_local = pos_items[p0:p1] - self.acc_iids
-                    if self._hip_scorer():
-                        pos = _engine.nfm_predict(self.folded, uid[row], pos_local, logits=True)[0]
-                    else:
-                        pos = self._logits_torch(uid[row], pos_local)
-                    above.append(((scores[row] > pos.view(-1, 1)) & negative[row]).sum(dim=1).to(torch.int32))
-                    below.append(((scores[row] < pos.view(-1, 1)) & negative[row]).sum(dim=1).to(torch.int32))
-                    poss.append(pos.view(-1))
-            cat = lambda parts, dtype: torch.cat(parts) if parts else torch.zeros(0, dtype=dtype, device=dev)
-            return cat(above, torch.int32), cat(below, torch.int32), cat(poss, torch.float32), cat(n_neg, torch.int32)
+            return evaluators.rank_full_multi(*self._callbacks(unids, lo, hi), pos_rowptr, pos_items, (lo, hi), exclude,
+                                              self.USER_CHUNK, self.POS_CHUNK)

@@ -184,6 +184,53 @@ def _scorer(op, repr_, fc):
     return table, run, getattr(lib, prefix + query)
 
 
+def _exclusion_csr(exclude, n_users, device, owner):
+    """exclude checked and contiguous, or (None, None); owner ('table' or 'fold') is what must share its device"""
+    if exclude is None:
+        return None, None
+    rowptr, items = exclude
+    if rowptr.dtype != torch.int64 or items.dtype != torch.int64 or rowptr.numel() != n_users + 1:
+        raise ValueError('exclude is (rowptr int64 [U + 1], items int64) -- see utils.interactions.seen_items_csr')
+    if rowptr.device != device or items.device != device:
+        raise ValueError('the exclusion lists must live on the device of the %s' % owner)
+    rowptr, items = rowptr.contiguous(), items.contiguous()
+    if items.numel() == 0:                  # a valid pointer for the C side even when nobody has seen anything
+        items = torch.zeros(1, dtype=torch.int64, device=device)
+    return rowptr, items
+
+
+def _positives_csr(pos_rowptr, pos_items, n_users, device, owner):
+    """the positives CSR (pos_rowptr int64 [n_users + 1], pos_items int64 [Q]) checked and contiguous"""
+    for t in (pos_rowptr, pos_items):
+        if not torch.is_tensor(t) or t.dtype != torch.int64 or t.dim() != 1:
+            raise ValueError('positives are (pos_rowptr int64 [U + 1], pos_items int64 [Q]) -- see utils.interactions.positives_csr')
+        if t.device != device:
+            raise ValueError('the positives must live on the device of the %s' % owner)
+    if pos_rowptr.numel() != n_users + 1:
+        raise ValueError('pos_rowptr must have one entry per requested user and one more')
+    return pos_rowptr.contiguous(), pos_items.contiguous()
+
+
+def _rank_outputs(u, dev):
+    """(rank int32, auc, pos_score) [u] of the all-item rank forms"""
+    return (torch.empty(u, dtype=torch.int32, device=dev), torch.empty(u, dtype=torch.float32, device=dev),
+            torch.empty(u, dtype=torch.float32, device=dev))
+
+
+def _multi_outputs(u, q, dev):
+    """(above int32 [q], below int32 [q], pos_score [q], n_neg int32 [u]) of the multi-positive rank forms"""
+    return (torch.empty(q, dtype=torch.int32, device=dev), torch.empty(q, dtype=torch.int32, device=dev),
+            torch.empty(q, dtype=torch.float32, device=dev), torch.empty(u, dtype=torch.int32, device=dev))
+
+
+def _ptr_or_spare(q, dev):
+    """_lib.ptr for the [Q] arrays of a multi-positive call; with Q == 0 a spare address, valid where there is nothing to read"""
+    if q:
+        return _lib.ptr
+    spare = torch.zeros(2, dtype=torch.int64, device=dev)
+    return lambda t: _lib.ptr(spare)
+
+
 def _catalogue_args(repr_, unids, item_range, exclude):
     unids = unids.to(torch.int64).contiguous()
     if unids.dim() != 1:
@@ -191,16 +238,7 @@ def _catalogue_args(repr_, unids, item_range, exclude):
     item_lo, item_hi = int(item_range[0]), int(item_range[1])
     if item_hi < item_lo:
         raise ValueError('item_range is (first item node id, one past the last)')
-    rowptr = items = None
-    if exclude is not None:
-        rowptr, items = exclude
-        if rowptr.dtype != torch.int64 or items.dtype != torch.int64 or rowptr.numel() != unids.numel() + 1:
-            raise ValueError('exclude is (rowptr int64 [U + 1], items int64) -- see utils.interactions.seen_items_csr')
-        if rowptr.device != repr_.device or items.device != repr_.device:
-            raise ValueError('the exclusion lists must live on the device of the table')
-        rowptr, items = rowptr.contiguous(), items.contiguous()
-        if items.numel() == 0:                  # a valid pointer for the C side even when nobody has seen anything
-            items = torch.zeros(1, dtype=torch.int64, device=repr_.device)
+    rowptr, items = _exclusion_csr(exclude, unids.numel(), repr_.device, 'table')
     return unids, item_lo, item_hi - item_lo, rowptr, items
 
 
@@ -248,8 +286,7 @@ def _rank_full(repr_, unids, pos_items, item_range, exclude, fc):
     if pos_items.shape != unids.shape:
         raise ValueError('one positive per requested user')
     u, r, dev = unids.shape[0], table.shape[1], table.device
-    rank = torch.empty(u, dtype=torch.int32, device=dev)
-    auc, pos_score = torch.empty(u, dtype=torch.float32, device=dev), torch.empty(u, dtype=torch.float32, device=dev)
+    rank, auc, pos_score = _rank_outputs(u, dev)
     ws, ws_bytes = _catalogue_ws(query, u, n_items, 1, r, dev)
     run((u, r, table.shape[0], _lib.ptr(table), _lib.ptr(unids), _lib.ptr(pos_items), item_lo, n_items, _lib.ptr(rowptr),
          _lib.ptr(items)), (_lib.ptr(rank), _lib.ptr(auc), _lib.ptr(pos_score), _lib.ptr(ws), ws_bytes))
@@ -260,25 +297,14 @@ def _rank_full_multi(repr_, unids, pos_rowptr, pos_items, item_range, exclude, f
     table, run, query = _scorer('rank_full_multi', repr_, fc)
     unids, item_lo, n_items, rowptr, items = _catalogue_args(table, unids, item_range, exclude)
     u, r, dev = unids.shape[0], table.shape[1], table.device
-    for t in (pos_rowptr, pos_items):
-        if not torch.is_tensor(t) or t.dtype != torch.int64 or t.dim() != 1:
-            raise ValueError('positives are (pos_rowptr int64 [U + 1], pos_items int64 [Q]) -- see utils.interactions.positives_csr')
-        if t.device != dev:
-            raise ValueError('the positives must live on the device of the table')
-    if pos_rowptr.numel() != u + 1:
-        raise ValueError('pos_rowptr must have one entry per requested user and one more')
-    pos_rowptr, pos_items = pos_rowptr.contiguous(), pos_items.contiguous()
+    pos_rowptr, pos_items = _positives_csr(pos_rowptr, pos_items, u, dev, 'table')
     q = pos_items.numel()
-    above, below = (torch.empty(q, dtype=torch.int32, device=dev) for _ in range(2))
-    pos_score = torch.empty(q, dtype=torch.float32, device=dev)
-    n_neg = torch.empty(u, dtype=torch.int32, device=dev)
+    above, below, pos_score, n_neg = _multi_outputs(u, q, dev)
     if u == 0:                                  # nobody asked: an empty tensor has no address to hand to the C side
         return above, below, pos_score, n_neg
     ws_bytes = int(query(u, q, n_items, r))
     ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-    # a valid address for the C side even where there is nothing to read or write
-    spare = torch.zeros(2, dtype=torch.int64, device=dev) if q == 0 else None
-    at = _lib.ptr if q else (lambda t: _lib.ptr(spare))
+    at = _ptr_or_spare(q, dev)
     run((u, r, table.shape[0], _lib.ptr(table), _lib.ptr(unids), _lib.ptr(pos_rowptr), at(pos_items), q, item_lo, n_items,
          _lib.ptr(rowptr), _lib.ptr(items)),
         (at(above), at(below), at(pos_score), _lib.ptr(n_neg), _lib.ptr(ws), ws_bytes))
@@ -491,16 +517,7 @@ def _nfm_scan_args(fold, what, uids, k, item_lo, n_items, exclude):
     item_lo, n_items = int(item_lo), int(n_items)
     if not (0 <= item_lo and n_items >= 0 and item_lo + n_items <= fold.num_items):
         raise ValueError('the item range must lie inside the %d items' % fold.num_items)
-    rowptr = items = None
-    if exclude is not None:
-        rowptr, items = exclude
-        if rowptr.dtype != torch.int64 or items.dtype != torch.int64 or rowptr.numel() != uids.numel() + 1:
-            raise ValueError('exclude is (rowptr int64 [U + 1], items int64) -- see utils.interactions.seen_items_csr')
-        if rowptr.device != fold.device or items.device != fold.device:
-            raise ValueError('the exclusion lists must live on the device of the fold')
-        rowptr, items = rowptr.contiguous(), items.contiguous()
-        if items.numel() == 0:                  # a valid pointer for the C side even when nobody has seen anything
-            items = torch.zeros(1, dtype=torch.int64, device=fold.device)
+    rowptr, items = _exclusion_csr(exclude, uids.numel(), fold.device, 'fold')
     head = (e, h, fold.num_users, fold.num_items, _lib.ptr(fold.emb), fold.emb.stride(0), _lib.ptr(fold.lin), _lib.ptr(fold.w),
             _lib.ptr(fold.b), _lib.ptr(fold.w2), _lib.ptr(fold.bias))
     return lib, head, uids, item_lo, n_items, rowptr, items
@@ -544,9 +561,8 @@ def nfm_rank_full(fold, uids, pos_items, item_lo, n_items, item_node0=0, exclude
     pos_items = pos_items.to(torch.int64).contiguous()
     if pos_items.shape != uids.shape:
         raise ValueError('one positive per requested user')
-    u, dev = uids.numel(), fold.device
-    rank = torch.empty(u, dtype=torch.int32, device=dev)
-    auc, pos_score = torch.empty(u, dtype=torch.float32, device=dev), torch.empty(u, dtype=torch.float32, device=dev)
+    u = uids.numel()
+    rank, auc, pos_score = _rank_outputs(u, fold.device)
     if u == 0:
         return rank, auc, pos_score
     ws, ws_bytes, flag = _nfm_scan_ws(lib, fold, u, u, items, n_items, 0)
@@ -565,23 +581,13 @@ def nfm_rank_full_multi(fold, uids, pos_rowptr, pos_items, item_lo, n_items, ite
     check_pending_errors()
     lib, head, uids, item_lo, n_items, rowptr, items = _nfm_scan_args(fold, 'nfm_rank_full_multi', uids, 0, item_lo, n_items, exclude)
     u, dev = uids.numel(), fold.device
-    for t in (pos_rowptr, pos_items):
-        if not torch.is_tensor(t) or t.dtype != torch.int64 or t.dim() != 1:
-            raise ValueError('positives are (pos_rowptr int64 [U + 1], pos_items int64 [Q]) -- see utils.interactions.positives_csr')
-        if t.device != dev:
-            raise ValueError('the positives must live on the device of the fold')
-    if pos_rowptr.numel() != u + 1:
-        raise ValueError('pos_rowptr must have one entry per requested user and one more')
-    pos_rowptr, pos_items = pos_rowptr.contiguous(), pos_items.contiguous()
+    pos_rowptr, pos_items = _positives_csr(pos_rowptr, pos_items, u, dev, 'fold')
     q = pos_items.numel()
-    above, below = (torch.empty(q, dtype=torch.int32, device=dev) for _ in range(2))
-    pos_score = torch.empty(q, dtype=torch.float32, device=dev)
-    n_neg = torch.empty(u, dtype=torch.int32, device=dev)
+    above, below, pos_score, n_neg = _multi_outputs(u, q, dev)
     if u == 0:
         return above, below, pos_score, n_neg
     ws, ws_bytes, flag = _nfm_scan_ws(lib, fold, u, q, items, n_items, 0)
-    spare = torch.zeros(2, dtype=torch.int64, device=dev) if q == 0 else None      # a valid address where there is nothing to read
-    at = _lib.ptr if q else (lambda t: _lib.ptr(spare))
+    at = _ptr_or_spare(q, dev)
     _lib.check(lib.pea_nfm_rank_full_multi(*head, _lib.ptr(uids), u, _lib.ptr(pos_rowptr), at(pos_items), q, item_lo, n_items,
                                            int(item_node0), _lib.ptr(rowptr), _lib.ptr(items), at(above), at(below), at(pos_score),
                                            _lib.ptr(n_neg), _lib.ptr(flag), _lib.ptr(ws), ws_bytes, _lib.current_stream()))

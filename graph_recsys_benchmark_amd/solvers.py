@@ -58,34 +58,31 @@ def metrics_from_ranks(rank):
     return hr, ndcg
 
 
+def _hook(model, op):
+    """The model's own method `op` where it has one, else engine.<op> of its scorer on cached_repr (GraphRecsysModel.scored,
+    unbound: it serves whatever model object it is handed)."""
+    own = getattr(model, op, None)
+    return own if own is not None else (lambda *args, **kwargs: GraphRecsysModel.scored(model, op, *args, **kwargs))
+
+
 def metrics(model, dataset, num_neg_candidates=99):
     """Returns (HR[16], NDCG[16], AUC[1], eval_loss[1]) means over the test users, like BaseSolver.metrics.
     `model` must be in eval() mode (cached_repr refreshed; for KGAT / KGCN: model.cf_eval(att_map), as the reference's
     solver does).  A model whose scorer is 'dot' is ranked by engine.dot_rank_eval (GraphRecsysModel.scored)."""
     u_nids = list(dataset.test_pos_unid_inid_map.keys())
-    cand = np.empty((len(u_nids), 1 + num_neg_candidates), dtype=np.int64)
-    for idx, u_nid in enumerate(u_nids):
-        pos_i_nids, neg_i_nids = generate_candidates(dataset, u_nid, num_neg_candidates)
-        if len(pos_i_nids) == 0 or len(neg_i_nids) == 0:
-            raise ValueError("No pos or neg samples found in evaluation!")
-        if len(pos_i_nids) != 1:
-            raise NotImplementedError('the batched evaluator expects the leave-one-out protocol (one positive per user, '
-                                      'datasets/movielens.py:304-308)')
-        cand[idx, 0] = pos_i_nids[0]
-        cand[idx, 1:] = neg_i_nids
+    cand = _draw_candidates(dataset, u_nids, num_neg_candidates)
     dev = model.cached_repr.device
     u_t = torch.as_tensor(np.asarray(u_nids, dtype=np.int64), device=dev)
-    if hasattr(model, 'rank_eval'):                   # a model that picks its own evaluator (models/walk.py: HIP or torch by width)
-        scores, rank, auc, loss = model.rank_eval(u_t, torch.from_numpy(cand).to(dev))
-    else:                                             # by its scorer; KGAT / KGCN: after model.cf_eval(att_map)
-        scores, rank, auc, loss = GraphRecsysModel.scored(model, 'rank_eval', u_t, torch.from_numpy(cand).to(dev))
+    # a model that picks its own evaluator (models/walk.py: HIP or torch by width), else by its scorer; KGAT / KGCN: after
+    # model.cf_eval(att_map)
+    scores, rank, auc, loss = _hook(model, 'rank_eval')(u_t, torch.from_numpy(cand).to(dev))
     hr, ndcg = metrics_from_ranks(rank.cpu().numpy())
     return hr.mean(axis=0), ndcg.mean(axis=0), np.array([auc.double().mean().item()]), np.array([loss.double().mean().item()])
 
 
 def _draw_candidates(dataset, u_nids, num_neg_candidates):
-    """One metrics() worth of draws: [U, 1 + num_neg_candidates], column 0 the held-out positive (same calls, same order,
-    same leave-one-out checks as `metrics`)."""
+    """One metrics() worth of draws: [U, 1 + num_neg_candidates], column 0 the held-out positive, the very np.random.choice
+    call per user of the reference, with its leave-one-out checks."""
     cand = np.empty((len(u_nids), 1 + num_neg_candidates), dtype=np.int64)
     for idx, u_nid in enumerate(u_nids):
         pos_i_nids, neg_i_nids = generate_candidates(dataset, u_nid, num_neg_candidates)
@@ -161,17 +158,23 @@ def metrics_full(model, u_nids, pos_items, item_range, exclude=None):
     dev = model.cached_repr.device
     u_t = torch.as_tensor(np.asarray(u_nids, dtype=np.int64), device=dev)
     pos_t = torch.as_tensor(np.asarray(pos_items, dtype=np.int64), device=dev)
-    if hasattr(model, 'rank_full'):
-        rank, auc, _ = model.rank_full(u_t, pos_t, item_range, exclude=exclude)
-    else:
-        rank, auc, _ = GraphRecsysModel.scored(model, 'rank_full', u_t, pos_t, item_range, exclude=exclude)
+    rank, auc, _ = _hook(model, 'rank_full')(u_t, pos_t, item_range, exclude=exclude)
     return metrics_full_from_ranks(rank.cpu().numpy(), auc.double().cpu().numpy())
+
+
+def _catalogue_of(model, dataset):
+    """(u_nids, item_range, exclude) of a dataset's test users: the keys of test_pos_unid_inid_map, the item block from
+    type_accs / num_iids and the exclusion CSR from edge_index_nps['user2item'], on the model's device"""
+    u_nids = list(dataset.test_pos_unid_inid_map.keys())
+    item_range = (dataset.type_accs['iid'], dataset.type_accs['iid'] + dataset.num_iids)
+    u_t = torch.as_tensor(np.asarray(u_nids, dtype=np.int64), device=model.cached_repr.device)
+    return u_nids, item_range, seen_items_csr(dataset.edge_index_nps['user2item'], u_t, item_range)
 
 
 def metrics_full_from_dataset(model, dataset):
     """metrics_full with users and positives from dataset.test_pos_unid_inid_map (one positive per user, as `metrics`
     insists), the item block from dataset.type_accs / num_iids and the exclusion from dataset.edge_index_nps['user2item']."""
-    u_nids = list(dataset.test_pos_unid_inid_map.keys())
+    u_nids, item_range, exclude = _catalogue_of(model, dataset)
     pos = []
     for u_nid in u_nids:
         p = dataset.test_pos_unid_inid_map[u_nid]
@@ -179,10 +182,6 @@ def metrics_full_from_dataset(model, dataset):
             raise NotImplementedError('the batched evaluator expects the leave-one-out protocol (one positive per user, '
                                       'datasets/movielens.py:304-308)')
         pos.append(p[0])
-    item_range = (dataset.type_accs['iid'], dataset.type_accs['iid'] + dataset.num_iids)
-    dev = model.cached_repr.device
-    u_t = torch.as_tensor(np.asarray(u_nids, dtype=np.int64), device=dev)
-    exclude = seen_items_csr(dataset.edge_index_nps['user2item'], u_t, item_range)
     return metrics_full(model, u_nids, pos, item_range, exclude)
 
 
@@ -259,8 +258,8 @@ def rank_full_multi_flattened(rank_full, u_nids, pos_rowptr, pos_items, item_ran
     de-duplicated union of the user's exclusion row and its positive row (rank_full skips the positive itself).  Then
     above = rank, pos_score as is, n_neg = the catalogue items outside that union, below = round(auc n_neg): auc is the
     float32 quotient below / n_neg, off by at most 2^-24 of itself, so the product is within one half of below for a catalogue
-    of fewer than 2^23 items (a larger one is refused).  Pays the catalogue scan once per positive: the route of a model that has a rank_full of its own only (models/walk.py), and the yardstick the native
-    route is tested and measured against.  Returns numpy (above int64 [Q], below int64 [Q], pos_score float32 [Q], n_neg
+    of fewer than 2^23 items (a larger one is refused).  Pays the catalogue scan once per positive: the route of a model that
+    has a rank_full of its own only, and the yardstick the native route is tested and measured against.  Returns numpy (above int64 [Q], below int64 [Q], pos_score float32 [Q], n_neg
     int64 [U])."""
     u_nids = np.asarray(u_nids, dtype=np.int64).reshape(-1)
     rowptr = np.asarray(pos_rowptr, dtype=np.int64).reshape(-1)
@@ -306,14 +305,11 @@ def metrics_full_multi(model, u_nids, positives, item_range, exclude=None):
     rowptr_np = pos_rowptr.cpu().numpy()
     if u_t.numel() == 0 or np.any(np.diff(rowptr_np) == 0):
         raise ValueError("No pos or neg samples found in evaluation!")
-    if hasattr(model, 'rank_full_multi'):
-        above, below, pos_score, n_neg = model.rank_full_multi(u_t, pos_rowptr, pos_items, item_range, exclude=exclude)
-    elif hasattr(model, 'rank_full'):
+    if hasattr(model, 'rank_full') and not hasattr(model, 'rank_full_multi'):
         above, below, pos_score, n_neg = rank_full_multi_flattened(model.rank_full, u_t.cpu().numpy(), rowptr_np,
                                                                    pos_items.cpu().numpy(), item_range, exclude, device=dev)
     else:
-        above, below, pos_score, n_neg = GraphRecsysModel.scored(model, 'rank_full_multi', u_t, pos_rowptr, pos_items, item_range,
-                                                                 exclude=exclude)
+        above, below, pos_score, n_neg = _hook(model, 'rank_full_multi')(u_t, pos_rowptr, pos_items, item_range, exclude=exclude)
     above, below, pos_score, n_neg = (t.cpu().numpy() if torch.is_tensor(t) else t for t in (above, below, pos_score, n_neg))
     if np.any(np.asarray(n_neg) <= 0):
         raise ValueError("No pos or neg samples found in evaluation!")
@@ -324,10 +320,6 @@ def metrics_full_multi(model, u_nids, positives, item_range, exclude=None):
 def metrics_full_multi_from_dataset(model, dataset):
     """metrics_full_multi with users and positives from dataset.test_pos_unid_inid_map (lists of any length), the item block from
     dataset.type_accs / num_iids and the exclusion from dataset.edge_index_nps['user2item']."""
-    u_nids = list(dataset.test_pos_unid_inid_map.keys())
+    u_nids, item_range, exclude = _catalogue_of(model, dataset)
     positives = [dataset.test_pos_unid_inid_map[u_nid] for u_nid in u_nids]
-    item_range = (dataset.type_accs['iid'], dataset.type_accs['iid'] + dataset.num_iids)
-    dev = model.cached_repr.device
-    u_t = torch.as_tensor(np.asarray(u_nids, dtype=np.int64), device=dev)
-    exclude = seen_items_csr(dataset.edge_index_nps['user2item'], u_t, item_range)
     return metrics_full_multi(model, u_nids, positives, item_range, exclude)

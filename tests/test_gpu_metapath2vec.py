@@ -194,3 +194,64 @@ def test_walk_model_evaluators_at_every_width(dim):
     u_nids = list(data.test_pos_unid_inid_map)
     hr2, ndcg2, auc2 = solvers.metrics_full(model, u_nids, [data.test_pos_unid_inid_map[u][0] for u in u_nids], (40, 70))
     assert hr2.shape == (16,) and 0.0 <= auc2[0] <= 1.0 and (np.diff(hr2) >= 0).all()
+
+
+def _int_recsys(dim):
+    """a Walk model of small integers: table in {-2..2}, fc weights and biases in {-1, 0, 1}.  Every score is an integer below
+    2^24, exact in fp32 whatever the blocking or the summation order: HIP and torch routes agree to the bit"""
+    from graph_recsys_benchmark_amd.models import WalkBasedRecsysModel
+    g = torch.Generator().manual_seed(100 + dim)
+    table = torch.randint(-2, 3, (75, dim), generator=g).float()
+    model = WalkBasedRecsysModel(embedding=table, embedding_dim=dim)
+    with torch.no_grad():
+        for p in model.parameters():
+            p.copy_(torch.randint(-1, 2, p.shape, generator=g).float())
+    return model.cuda().eval()
+
+
+@pytest.mark.parametrize('dim', [64, 72])
+def test_walk_model_ranks_several_positives_in_one_scan(dim):
+    """rank_full_multi, on the HIP scorer (64) or the torch composition (72), against the flattened route over the model's own
+    rank_full: all four outputs, and solvers.metrics_full_multi on top of the hook"""
+    from graph_recsys_benchmark_amd import solvers
+    model = _int_recsys(dim)
+    assert model._hip_scorer() == (dim == 64)
+    rng = np.random.default_rng(dim)
+    u_nids = np.arange(0, 39, 3)
+    assert u_nids.size == 13
+    lists = [np.sort(rng.choice(np.arange(40, 70), size=1 + q % 4, replace=False)) for q in range(13)]
+    pos_rowptr = torch.tensor(np.cumsum([0] + [len(r) for r in lists]), device='cuda')
+    pos_items = torch.tensor(np.concatenate(lists), device='cuda')
+    exclude = (torch.arange(0, 3 * 13 + 1, 3, device='cuda'),
+               torch.tensor(np.concatenate([np.sort(rng.choice(np.arange(40, 70), size=3, replace=False)) for _ in range(13)]), device='cuda'))
+    model.USER_CHUNK, model.POS_CHUNK = 5, 3                 # the torch route: several blocks of users and of positives
+    got = model.rank_full_multi(torch.as_tensor(u_nids, device='cuda'), pos_rowptr, pos_items, (40, 70), exclude=exclude)
+    want = solvers.rank_full_multi_flattened(model.rank_full, u_nids, pos_rowptr.cpu().numpy(), pos_items.cpu().numpy(), (40, 70),
+                                             exclude, device='cuda')
+    assert [t.dtype for t in got] == [torch.int32, torch.int32, torch.float32, torch.int32]
+    for g, w, what in zip(got, want, ('above', 'below', 'pos_score', 'n_neg')):
+        assert np.array_equal(g.cpu().numpy(), w), what
+    assert got[0].sum() > 0 and got[1].sum() > 0
+    # metrics_full_multi takes the hook, once, and no longer flattens
+    calls, hook = [], model.rank_full_multi
+    model.rank_full_multi = lambda *a, **kw: calls.append(1) or hook(*a, **kw)
+    try:
+        metrics = solvers.metrics_full_multi(model, u_nids, (pos_rowptr, pos_items), (40, 70), exclude=exclude)
+    finally:
+        del model.rank_full_multi
+    assert calls == [1]
+    per_user = solvers.multi_metrics_from_counts(want[0], want[2], want[1], pos_rowptr.cpu().numpy(), want[3])
+    assert sorted(metrics) == sorted(solvers.MULTI_METRICS)
+    for name, v in per_user.items():
+        np.testing.assert_array_equal(metrics[name], v.mean(axis=0), err_msg=name)
+    if dim == 72:                                            # the torch recommend: all but 2 items excluded, k = 7
+        left = [47, 62]
+        rows = (torch.tensor([0, 28], device='cuda'), torch.tensor([i for i in range(40, 70) if i not in left], device='cuda'))
+        user = torch.tensor([6], device='cuda')
+        items, scores = model.recommend(user, 7, (40, 70), exclude=rows)
+        with torch.no_grad():
+            s = model.predict(user.repeat(2), torch.tensor(left, device='cuda')).view(-1).tolist()
+        assert items.shape == scores.shape == (1, 7)
+        assert items[0, :2].tolist() == sorted(left, key=lambda i: (-s[left.index(i)], i))
+        assert scores[0, :2].tolist() == sorted(s, reverse=True)
+        assert (items[0, 2:] == -1).all() and (scores[0, 2:] == float('-inf')).all()

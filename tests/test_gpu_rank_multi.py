@@ -380,7 +380,15 @@ def test_end_to_end_dot_model():
     check_end_to_end(model, ds)
 
 
-def test_walk_model_goes_through_the_flattened_route():
+class _RankFullAlone:
+    """what solvers.metrics_full_multi reads of a model with a rank_full of its own and no rank_full_multi: here the Walk model's
+    rank_full without its other hooks"""
+
+    def __init__(self, model):
+        self.cached_repr, self.rank_full = model.cached_repr, model.rank_full
+
+
+def test_a_model_with_rank_full_alone_goes_through_the_flattened_route():
     from graph_recsys_benchmark_amd.models import WalkBasedRecsysModel
     g = torch.Generator().manual_seed(64)
     table = torch.randn((75, 64), generator=g) * 0.4
@@ -389,6 +397,7 @@ def test_walk_model_goes_through_the_flattened_route():
         for p in model.parameters():
             p.copy_(torch.randn(p.shape, generator=g) * 0.3)
     model = model.cuda().eval()
+    walk, model = model, _RankFullAlone(model)
     assert hasattr(model, 'rank_full') and not hasattr(model, 'rank_full_multi')
     rng = np.random.default_rng(2)
     u_nids = list(range(0, 40, 3))
@@ -402,9 +411,16 @@ def test_walk_model_goes_through_the_flattened_route():
     assert calls == [1]
     # the same table through the native route of an 'mlp' model: the very same counts
     rowptr, items = positives_csr(lists, u_t)
-    nat = engine.rank_full_multi(model.cached_repr, u_t, rowptr, items, (40, 70), model.fc1.weight, model.fc1.bias,
-                                 model.fc2.weight, model.fc2.bias, exclude=exclude)
+    nat = engine.rank_full_multi(walk.cached_repr, u_t, rowptr, items, (40, 70), walk.fc1.weight, walk.fc1.bias,
+                                 walk.fc2.weight, walk.fc2.bias, exclude=exclude)
     a, b, ps, nn = (t.cpu().numpy() for t in nat)
     per_user = solvers.multi_metrics_from_counts(a, ps, b, rowptr.cpu().numpy(), nn)
     for name in solvers.MULTI_METRICS:
         assert np.array_equal(got[name], per_user[name].mean(axis=0)), name
+    # the Walk model itself has the hook: one scan, no call of its rank_full, the same numbers
+    del calls[:]
+    walk.rank_full = model.rank_full
+    own = solvers.metrics_full_multi(walk, u_nids, lists, (40, 70), exclude)
+    assert hasattr(walk, 'rank_full_multi') and calls == []
+    for name in solvers.MULTI_METRICS:
+        assert np.array_equal(own[name], got[name]), name
