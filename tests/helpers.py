@@ -1200,20 +1200,249 @@ def es_sliced_bins(ei, n, chunk=512, short_deg=32, slices=ES_SLICES):
     """The same for a source-sliced plan of `slices` = 8 slices (one phase): a row of more than `chunk` and at least 8 x 32 edges is
     cut into its per-slice segments (slice of an edge = (src - min src) * S // span), each segment into equalised chunks; the
     chunks are laid out four per workgroup and slice, padded with `slot == -2` items to whole rounds of 8 x 4, ahead of every
-    other item.  Also returns `sliced_degrees`, the degrees of the rows that were cut."""
+    other item.  Also returns `sliced_degrees`, the degrees of the rows that were cut.  The one-phase call of
+    sliced_plan_bins."""
+    assert slices == ES_SLICES
+    return sliced_plan_bins(ei, n, chunk, short_deg, slices)
+
+
+# ------------------------------------------------------------------------------------------------------------
+# the conv gathers on source-sliced plans (csrc/plan.hip: build_relation's XCD-affine layout; csrc/agg.hip, csrc/agg_bwd.hip):
+# tests/test_gpu_agg_sliced_matrix.py runs the shapes below on the GPU, tests/test_agg_sliced_cpu.py checks the table, the
+# layouts and the float32 headroom without one
+# ------------------------------------------------------------------------------------------------------------
+def edge_slices(src, slices):
+    """slice of every edge: (src - min src) * S // span over the source-id range of the given (kept) edges (plan.hip: keys_with_slice)"""
+    smin, span = int(src.min()), int(src.max()) - int(src.min()) + 1
+    return (src.astype(np.int64) - smin) * slices // span
+
+
+def sliced_plan_items(ei, n, chunk=512, short_deg=32, slices=8):
+    """The hub rows of the plan csrc/plan.hip makes of the KEPT edges `ei` [2, E] under `slices` source slices, by hand:
+    (cut, records) with cut = the rows cut per slice (a row of more than `chunk` and at least slices x 32 edges, slices > 1) and
+    records = {hub row: [(slice or -1, first CSR position inside the row, length) per chunk record, in record order]}.  A cut
+    row's segment of each slice is split into ceil(len / chunk) equalised chunks; any other hub row is split as a whole."""
     src, dst = ei
     deg = np.bincount(dst, minlength=n)
-    smin, span = int(src.min()), int(src.max()) - int(src.min()) + 1
-    sl = (src - smin) * slices // span
-    cut = (deg > short_deg) & (deg > chunk) & (deg >= slices * ES_SLICE_MIN_SEGMENT)
-    hub = (deg > short_deg) & (deg > chunk) & ~cut
-    plain = es_plan_bins(np.where(cut, 0, deg), chunk, short_deg)
-    per_slice, slots = np.zeros(slices, np.int64), 0
-    for row in np.flatnonzero(cut):
+    sl = edge_slices(src, slices) if slices > 1 and src.size else np.zeros(src.size, np.int64)
+    hub = (deg > short_deg) & (deg > chunk)
+    cut = hub & (deg >= slices * ES_SLICE_MIN_SEGMENT) & (slices > 1)
+
+    def split(first, length, tag):
+        nch = -(-length // chunk)
+        ln = -(-length // nch)
+        return [(tag, first + c * ln, min(ln, length - c * ln)) for c in range(nch)]
+
+    records = {}
+    for row in np.flatnonzero(hub):
+        if not cut[row]:
+            records[int(row)] = split(0, int(deg[row]), -1)
+            continue
         seg = np.bincount(sl[dst == row], minlength=slices)
-        per_slice += -(-seg // chunk)
-        slots += int((-(-seg // chunk)).sum())
-    rounds = int((-(-per_slice // 4)).max()) if cut.any() else 0
+        first = np.concatenate([[0], np.cumsum(seg)])
+        records[int(row)] = [rec for s in range(slices) if seg[s] for rec in split(int(first[s]), int(seg[s]), s)]
+    return cut, records
+
+
+def sliced_plan_bins(ei, n, chunk=512, short_deg=32, slices=8):
+    """es_plan_bins for a source-sliced plan of any number of phases (slices = 8 x phases; 1: no slices), from the KEPT edges:
+    the six leading fields of pea_plan_relation_info (hub_slots is the info's `hub_chunks`), and
+        sliced_degrees   degrees of the rows cut per slice
+        pad_items        `slot == -2` items: plan.hip pads per phase, rounds_ph = max over the phase's 8 slices of ceil(items / 4),
+                         and the head of the item list holds 32 x sum(rounds_ph) items
+        hub_records      chunk records of the busiest hub row (0 without hub rows)"""
+    src, dst = ei
+    deg = np.bincount(dst, minlength=n)
+    cut, records = sliced_plan_items(ei, n, chunk, short_deg, slices)
+    per_slice = np.zeros(max(slices, 8), np.int64)
+    for row in np.flatnonzero(cut):
+        for s, _, _ in records[int(row)]:
+            per_slice[s] += 1
+    rounds = int(sum((-(-per_slice[ph * 8:ph * 8 + 8] // 4)).max() for ph in range(slices // 8))) if cut.any() else 0
+    slots = sum(len(r) for r in records.values())
+    cut_slots = int(per_slice.sum())
+    direct = int(((deg > short_deg) & (deg <= chunk)).sum())
     return dict(edges=int(deg.sum()), max_degree=int(deg.max()), short_rows=int((deg <= short_deg).sum()),
-                long_items=plain['long_items'] + rounds * slices * 4, hub_rows=int(hub.sum() + cut.sum()),
-                hub_slots=plain['hub_slots'] + slots, sliced_degrees=sorted(int(d) for d in deg[cut]), pad_items=rounds * slices * 4 - slots)
+                long_items=direct + (slots - cut_slots) + 32 * rounds, hub_rows=len(records), hub_slots=slots,
+                sliced_degrees=sorted(int(d) for d in deg[cut]), pad_items=32 * rounds - cut_slots,
+                hub_records=max([len(r) for r in records.values()] or [0]))
+
+
+def sliced_csr(ei, n, slices):
+    """(rowptr int32 [n + 1], col int32 [E], order) of the KEPT edges: numpy's stable sort by (destination, slice of the source)"""
+    src, dst = ei
+    sl = edge_slices(src, slices) if slices > 1 and src.size else np.zeros(src.size, np.int64)
+    order = np.argsort(dst.astype(np.int64) * slices + sl, kind='stable')
+    rowptr = np.concatenate([[0], np.cumsum(np.bincount(dst, minlength=n))]).astype(np.int32)
+    return rowptr, src[order].astype(np.int32), order
+
+
+SLICE_MIN_EDGES = 2000000        # common.h: kSliceMinEdges
+SLICE_BYTES = 6.0e6              # common.h: kSliceBytes
+
+
+def slice_count(span, row_bytes, n_edges, min_edges=SLICE_MIN_EDGES, slice_bytes=SLICE_BYTES):
+    """The slice decision of csrc/plan.hip (build_relation) by hand: no slices unless the plan names the gathered rows' size, the
+    relation has `min_edges` edges and the gather table (span of the kept edges' source ids x row bytes) exceeds 1.5 slices'
+    worth; then 8 slices per phase, ceil(table / (8 slice_bytes)) phases, 8 at the most."""
+    table = float(span) * row_bytes
+    if not (row_bytes > 0 and n_edges >= min_edges and table > 1.5 * slice_bytes):
+        return 1
+    return 8 * int(min(8, -(-table // (8.0 * slice_bytes))))
+
+
+CONV_ROW_BYTES = 256             # engine.py: GraphPlan's default gather_row_bytes, what the nn.conv plans pass
+AGG_BIG_DEGREES = AGG_DEGREES + (2047, 2048, 2049, 4200)
+AGG_BIG_FILL = 6400              # filler nodes of the `s64_big` graph: a 4200-edge star needs that many distinct neighbours
+
+
+def agg_big_graph():
+    return degree_graph(n_fill=AGG_BIG_FILL, degrees=AGG_BIG_DEGREES)
+
+
+def kept_edges(ei, drop_loops, reverse=False):
+    """the [2, E] edges a plan keeps of the relation `ei` (reverse: of the flipped relation), in input order"""
+    if drop_loops:
+        ei = ei[:, ei[0] != ei[1]]
+    return np.ascontiguousarray(ei[::-1] if reverse else ei)
+
+
+def relation_spans(ei):
+    """source-id range of the kept edges of the relation and of its reverse, with the self loops dropped and kept"""
+    return [int(k[0].max()) - int(k[0].min()) + 1 for drop in (True, False) for rev in (False, True) for k in [kept_edges(ei, drop, rev)]]
+
+
+def slice_bytes_for(ei, row_bytes, slices):
+    """The PEA_SLICE_BYTES (with PEA_SLICE_MIN_EDGES=1) under which slice_count gives `slices` for the relation `ei` AND for its
+    reverse, self loops dropped or kept: the largest gather table / slices, rounded up, so that ceil(table / (8 bytes)) is the
+    wanted number of phases.  Checked, not assumed: every span must give `slices`."""
+    spans = relation_spans(ei)
+    value = -(-max(spans) * row_bytes // slices)
+    assert all(slice_count(sp, row_bytes, 1, 1, value) == slices for sp in spans), (spans, row_bytes, slices, value)
+    return value
+
+
+def _sliced_shapes():
+    small, big = degree_graph()['edge_index'], agg_big_graph()['edge_index']
+    knobs = lambda ei, slices, **more: dict({'PEA_SLICE_MIN_EDGES': '1', 'PEA_SLICE_BYTES': str(slice_bytes_for(ei, CONV_ROW_BYTES, slices))},
+                                            **more)
+    # cut: the degrees of the rows cut per slice (each on two rows of either side); hub: the other hub rows' degrees
+    return {
+        's8': dict(big=False, slices=8, chunk=512, env=knobs(small, 8), cut=(513, 1100), hub=()),
+        's16': dict(big=False, slices=16, chunk=512, env=knobs(small, 16), cut=(513, 1100), hub=()),
+        's32': dict(big=False, slices=32, chunk=512, env=knobs(small, 32), cut=(1100,), hub=(513,)),
+        's8_chunk64': dict(big=False, slices=8, chunk=64, env=knobs(small, 8, PEA_CHUNK='64'), cut=(511, 512, 513, 1100),
+                           hub=(65, 127, 128, 129, 200)),
+        # beyond the four shapes above: chunks of 8 edges put 144 records on the 1100-edge row, more than the 8 x 64 / G = 128 a
+        # 4-lane forward merge folds per trip (chunks of 64 give that row 24 records: a second trip at G = 32 and 64 only)
+        's8_chunk8': dict(big=False, slices=8, chunk=8, env=knobs(small, 8, PEA_CHUNK='8'), cut=(511, 512, 513, 1100),
+                          hub=(33, 63, 64, 65, 127, 128, 129, 200)),
+        's64_big': dict(big=True, slices=64, chunk=512, env=knobs(big, 64), cut=(2048, 2049, 4200), hub=(513, 1100, 2047)),
+    }
+
+
+AGG_SLICED_SHAPES = _sliced_shapes()
+AGG_SLICED_KNOBS = ('PEA_CHUNK', 'PEA_SHORT_DEG', 'PEA_SLICE_MIN_EDGES', 'PEA_SLICE_BYTES')
+
+
+def agg_sliced_graph(shape):
+    return agg_big_graph() if AGG_SLICED_SHAPES[shape]['big'] else degree_graph()
+
+
+# the single-conv cases run with PEA_CHUNK=64 (tests/test_gpu_agg_bwd_matrix.py): one GAT width per G (the slope widths, slope 0.2), GCN
+# and SAGE at the narrowest, a middle and the widest G
+AGG_CHUNK64_CASES = [c for c in AGG_CONV_CASES
+                     if (c['kind'] == 'gat' and c['slope'] == 0.2 and AGG_GAT_SLOPE_WIDTHS[agg_lanes(c['heads'] * c['out'])] == (c['heads'], c['out']))
+                     or (c['kind'] == 'gcn' and (c['out'], c['deg']) in ((12, 'row'), (32, 'col'), (256, 'row')))
+                     or (c['kind'] == 'sage' and c['in_ch'] in (4, 96))]
+# the sliced matrix adds a `four` and a `generic` head class at G = 16 (4 heads of 16; one head of 40 columns, idle lanes): their
+# row-end code (the head sum over 4 lanes / over a width that is no power of two) then meets per-slice chunk records too
+AGG_SLICED_EXTRA = ((4, 16), (1, 40))
+# ... and the (kind, G) cells that selection leaves empty: GCN at G = 16 and 32, SAGE at G = 8, 16 and 64
+AGG_SLICED_CASES = AGG_CHUNK64_CASES + [c for c in AGG_CONV_CASES
+                                        if (c['kind'] == 'gat' and c['slope'] == 0.2 and (c['heads'], c['out']) in AGG_SLICED_EXTRA)
+                                        or (c['kind'] == 'gcn' and (c['out'], c['deg']) in ((64, 'row'), (96, 'col')))
+                                        or (c['kind'] == 'sage' and c['in_ch'] in (32, 64, 256))]
+
+
+def agg_case_lanes(case):
+    """the lane width a single-conv case aggregates at: GAT and GCN their output rows, SAGE its input rows"""
+    return agg_lanes(case['in_ch'] if case['kind'] == 'sage' else case['heads'] * case['out'])
+
+
+def slice_ordered_graph(graph, slices, drop_loops):
+    """the graph with its kept edges in the order a plan of `slices` source slices visits them -- (destination, slice of the
+    source), input order inside -- and the dropped self loops behind them: torch's CPU scatter adds in edge order, so the
+    float32 restatement on this graph sums every row the way the sliced CSR lists it"""
+    ei = graph['edge_index']
+    kept = kept_edges(ei, drop_loops)
+    rest = ei[:, ei[0] == ei[1]] if drop_loops else ei[:, :0]
+    order = sliced_csr(kept, graph['n'], slices)[2]
+    return dict(graph, edge_index=np.ascontiguousarray(np.concatenate([kept[:, order], rest], axis=1)))
+
+
+# --- SAGE on integers: the edge bookkeeping without a tolerance ---
+def pow2_rows(deg):
+    """rows whose degree is 0 or a power of two: the only rows whose 1 / degree is exact in float32"""
+    return (deg & (deg - 1)) == 0
+
+
+def sage_integer_tensors(case, graph):
+    """float32 CPU tensors of a SAGE case on which both aggregations of the conv are EXACT in float32, whatever order the edges are
+    summed in: x integer in [-8, 8] and weights integer in [-2, 2], so a row's neighbour sum is an integer below 2^24 that is
+    divided once by its degree; the output gradient integer in [-4, 4] on the rows whose in-degree (self loops kept) is 0 or a
+    power of two and zero elsewhere -- the backward sums (lin_rel^T gout_i) / deg_i over a source's out-edges, per edge, and a
+    reciprocal that is not a power of two would leave every term a rounded fraction whose sum depends on the order."""
+    import torch
+    g = torch.Generator().manual_seed(case['seed'] + 7000)
+    ints = lambda lo, hi, *shape: torch.randint(lo, hi + 1, shape, generator=g).float()
+    n, i, f = graph['n'], case['in_ch'], case['out']
+    deg_in = kept_degrees(graph['edge_index'], n, False)[0]
+    params = {'lin_rel.weight': ints(-2, 2, f, i), 'lin_rel.bias': ints(-2, 2, f), 'lin_root.weight': ints(-2, 2, f, i)}
+    gout = ints(-4, 4, n, f) * torch.from_numpy(pow2_rows(deg_in)).float()[:, None]
+    return ints(-8, 8, n, i), params, gout
+
+
+def sage_by_edges(x, params, gout, src, dst, deg, dtype):
+    """(out, grads) of L = sum(SAGEConv(x) * gout) with the mean taken over the listed edges in the listed order and divided by
+    `deg` (so a wrong edge list keeps the right divisor): lin_rel(sum_{j -> i} x_j / deg_i) + lin_root(x_i).  numpy in, numpy out."""
+    import torch
+    x = x.detach().clone().to(dtype).requires_grad_(True)
+    p = {k: v.detach().clone().to(dtype).requires_grad_(True) for k, v in params.items()}
+    src, dst = torch.from_numpy(np.ascontiguousarray(src)), torch.from_numpy(np.ascontiguousarray(dst))
+    mean = torch.zeros_like(x).index_add(0, dst, x[src]) / torch.from_numpy(np.maximum(deg, 1)).to(dtype)[:, None]
+    out = mean @ p['lin_rel.weight'].t() + p['lin_rel.bias'] + x @ p['lin_root.weight'].t()
+    (out * gout.to(dtype)).sum().backward()
+    grads = {'x': x.grad.numpy().astype(np.float64)}
+    grads.update({k: v.grad.numpy().astype(np.float64) for k, v in p.items()})
+    return out.detach().numpy(), grads
+
+
+def sliced_edge_list(graph, shape, wrong=None, reverse=False):
+    """(src, dst, deg) of a SAGE plan (self loops kept) of the shape (reverse: of its reversed relation, which the backward walks),
+    edges in CSR order.  wrong='drop_last_chunk': without the edges of the last chunk record of the first 1100-edge row;
+    wrong='neighbour_row': the edges of that row's first slice segment are added to the next hub row instead.  `deg` is the
+    true degree either way."""
+    sh = AGG_SLICED_SHAPES[shape]
+    n = graph['n']
+    kept = kept_edges(graph['edge_index'], False, reverse)
+    rowptr, col, order = sliced_csr(kept, n, sh['slices'])
+    src, dst = kept[0][order].copy(), kept[1][order].copy()
+    deg = np.bincount(kept[1], minlength=n)
+    if wrong is not None:
+        cut, records = sliced_plan_items(kept, n, sh['chunk'], 32, sh['slices'])
+        hubs = sorted(records)                                  # plan.hip lists the cut rows in row order
+        row = next(r for r in hubs if cut[r] and deg[r] == deg[cut].max())      # the 1100-edge row (`s64_big`: the 4200-edge row)
+        if wrong == 'drop_last_chunk':
+            _, first, length = records[row][-1]
+            keep = np.ones(src.size, bool)
+            keep[rowptr[row] + first:rowptr[row] + first + length] = False
+            src, dst = src[keep], dst[keep]
+        else:
+            assert wrong == 'neighbour_row'
+            s0 = records[row][0][0]
+            length = sum(ln for s, _, ln in records[row] if s == s0)
+            other = hubs[(hubs.index(row) + 1) % len(hubs)]
+            assert other != row and length > 0
+            dst[rowptr[row] + records[row][0][1]:rowptr[row] + records[row][0][1] + length] = other
+    return src, dst, deg

@@ -124,19 +124,22 @@ def _conv_module(case):
     return nn.SAGEConv(case['in_ch'], case['out'])
 
 
-def _conv_reference(case):
-    g = H.degree_graph()
-    return _cached(('conv', case['id']), lambda: (H.conv_reference(case, g, torch.float32)[0],) + H.conv_reference(case, g, torch.float64))
+def _conv_reference(case, g=None, tag=None):
+    g = g or H.degree_graph()
+    key = ('conv', case['id']) if tag is None else ('conv', case['id'], tag)
+    return _cached(key, lambda: (H.conv_reference(case, g, torch.float32)[0],) + H.conv_reference(case, g, torch.float64))
 
 
-def _check_single_conv(case, chunk):
-    g = H.degree_graph()
+def _check_single_conv(case, chunk, graph=None, ei=None):
+    """graph, ei: another graph (a dict of helpers.degree_graph) and a device copy of its edges whose plans the caller has shaped
+    (tests/test_gpu_agg_sliced_matrix.py); default: the degree graph and the edge tensor of `chunk`"""
+    g = graph or H.degree_graph()
     x, params, gout = H.conv_case_tensors(case, g['n'])
     conv = _conv_module(case)
     conv.load_state_dict(params, strict=True)
     conv = conv.cuda().train()
     xg = x.cuda().requires_grad_(True)
-    ei = _edge_tensor(chunk)
+    ei = _edge_tensor(chunk) if ei is None else ei
 
     out = conv(xg, ei)
     _, names = _kernel_names(lambda: (out * gout.cuda()).sum().backward())       # the launches of the backward alone
@@ -147,7 +150,7 @@ def _check_single_conv(case, chunk):
     else:       # a linear aggregation's backward is the weighted sum over the reversed relation: GCN at the output width,
         G = H.agg_lanes(case['out'] if case['kind'] == 'gcn' else case['in_ch'])           # SAGE at the input width
         assert {'agg_rows_g%d_gcn' % G, 'agg_merge_g%d_gcn' % G, 'colsum'} <= names, sorted(names)
-    out32, out64, want = _conv_reference(case)
+    out32, out64, want = _conv_reference(case, g, None if graph is None else g['n'])      # the graphs in use differ in size
     got = {'x': xg.grad.cpu().numpy()}
     for name, p in conv.named_parameters():
         assert p.grad is not None, name
@@ -155,6 +158,7 @@ def _check_single_conv(case, chunk):
     assert set(got) == set(want) == {'x'} | set(H.CONV_PARAM_NAMES[case['kind']])
     frac, worst = H.grad_rule_fraction(got, want)
     print('%s chunk %d: gradients use %.3f of the rule (%s)' % (case['id'], chunk, frac, worst))
+    assert bool(torch.isfinite(out).all()), case['id']         # (a NaN compares false with every bound; the rule has its own check)
     H.assert_fp32_close(out.detach().cpu().numpy(), out32, out64, what=case['id'] + ' out')
     assert frac <= 1.0, '%s: gradient of %s is off by %.2f times the rule' % (case['id'], worst, frac)
 
@@ -164,10 +168,7 @@ def test_single_conv_matches_float64(case):
     _check_single_conv(case, 512)
 
 
-_CHUNK64_CASES = [c for c in H.AGG_CONV_CASES
-                  if (c['kind'] == 'gat' and c['slope'] == 0.2 and H.AGG_GAT_SLOPE_WIDTHS[H.agg_lanes(c['heads'] * c['out'])] == (c['heads'], c['out']))
-                  or (c['kind'] == 'gcn' and (c['out'], c['deg']) in ((12, 'row'), (32, 'col'), (256, 'row')))
-                  or (c['kind'] == 'sage' and c['in_ch'] in (4, 96))]
+_CHUNK64_CASES = H.AGG_CHUNK64_CASES
 
 
 @pytest.mark.parametrize('case', _CHUNK64_CASES, ids=[c['id'] for c in _CHUNK64_CASES])
