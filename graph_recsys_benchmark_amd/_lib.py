@@ -264,6 +264,13 @@ FM_EVAL_SIGNATURES = {
 }
 NFM_SCAN_USERS = 8     # include/peahip_fm_eval.h PEA_NFM_SCAN_USERS
 
+# every symbol include/peahip_cf_sample.h declares (the on-device CF epoch sampler)
+CF_SAMPLE_SIGNATURES = {
+    'pea_cf_sample': (_int, [_i64, _int, _int, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _int, _vp,
+                             _vp, C.c_uint64, C.c_uint32, _int, _vp, _i64, _vp, _vp, _vp]),
+}
+CF_MAX_BLOCKS, CF_BPR, CF_BCE = 64, 0, 1     # include/peahip_cf_sample.h PEA_CF_MAX_BLOCKS, PEA_CF_BPR, PEA_CF_BCE
+
 KGU_KGAT, KGU_KGCN, KGU_NGCF = 0, 1, 2     # include/peahip.h PEA_KGU_*
 
 _lib = None
@@ -279,7 +286,7 @@ def load():
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(KGE_SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) +
                                   list(SAMPLE_SIGNATURES.items()) + list(FM_SIGNATURES.items()) +
-                                  list(FM_EVAL_SIGNATURES.items())):
+                                  list(FM_EVAL_SIGNATURES.items()) + list(CF_SAMPLE_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

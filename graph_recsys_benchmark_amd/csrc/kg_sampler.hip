@@ -12,50 +12,13 @@
 // per output row and stores in order, measured no faster and was not kept: DESIGN.md section 20).  Integers only; no scratch.
 #include "common.h"
 #include "philox.h"
+#include "sample_common.h"
 #include "../../include/peahip_sample.h"
 
 namespace pea {
 namespace {
 
 constexpr int kBlock = 256;
-constexpr int kMaxAttempts = 64;
-constexpr unsigned kTagDraw = 1u << 8, kTagShuffle = 2u << 8;
-
-struct Stream {
-    unsigned k0, k1, offset;
-};
-
-// the same search as contains() of sampler.hip
-__device__ __forceinline__ bool contains(const long long *__restrict__ keys, long long n, long long key) {
-    long long lo = 0, hi = n;
-    while (lo < hi) {
-        const long long mid = (lo + hi) >> 1;
-        if (keys[mid] < key) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo < n && keys[lo] == key;
-}
-
-__device__ __forceinline__ unsigned round_fn(unsigned r, unsigned j, const Stream &st) {
-    return philox4x32_10(U4{r, j, kTagShuffle, st.offset}, st.k0, st.k1).x;
-}
-
-// perm(x) for x < n: the pass (L, R) -> (R, L ^ F_j(R)), j = 0..3, repeated while the result is >= n
-__device__ __forceinline__ unsigned long long perm_of(unsigned long long x, unsigned long long n, int hb, const Stream &st) {
-    const unsigned long long m = (1ull << hb) - 1;
-    do {
-        unsigned long long L = x >> hb, R = x & m;
-#pragma unroll 1
-        for (unsigned j = 0; j < 4; ++j) {
-            const unsigned long long t = L ^ ((unsigned long long)round_fn((unsigned)R, j, st) & m);
-            L = R;
-            R = t;
-        }
-        x = (L << hb) | R;
-    } while (x >= n);
-    return x;
-}
-
 // thread e: store row e, written at output row perm(e) (shuffle) or e
 __global__ __launch_bounds__(kBlock) void kg_sample_kernel(long long n, const long long *__restrict__ heads,
                                                            const long long *__restrict__ tails, int n_seg,
@@ -129,14 +92,6 @@ __global__ __launch_bounds__(kBlock) void permute_rows_kernel(long long n, int w
     const long long *src = in + i * ld_in;
     long long *o = out + dst * ld_out;
     for (int c = 0; c < width; ++c) o[c] = src[c];
-}
-
-// hb of the header: half the bit length of n - 1, rounded up, at least 1
-int half_bits(long long n) {
-    int b = 0;
-    for (unsigned long long v = (unsigned long long)(n - 1); v; v >>= 1) ++b;
-    if (b < 1) b = 1;
-    return (b + 1) / 2;
 }
 
 }  // namespace

@@ -9,22 +9,10 @@
 // 32-bit output word w maps to an item as floor(w * num_items / 2^32).  oracle/philox.py restates it in numpy.
 #include "common.h"
 #include "philox.h"
+#include "sample_common.h"
 
 namespace pea {
 namespace {
-
-// first index with keys[idx] >= key
-__device__ __forceinline__ bool contains(const long long *__restrict__ keys, long long n, long long key) {
-    long long lo = 0, hi = n;
-    while (lo < hi) {
-        const long long mid = (lo + hi) >> 1;
-        if (keys[mid] < key) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo < n && keys[lo] == key;
-}
-
-constexpr int kMaxAttempts = 64;  // a user who has seen almost every item: the last draw is kept and flagged
 
 __global__ __launch_bounds__(256) void sample_kernel(long long n_pos, int k, const long long *__restrict__ pos_u,
                                                      const long long *__restrict__ pos_i, long long item_lo,

@@ -8,6 +8,7 @@ reference's 30-epoch BaseSolver.run() (out of scope: training driver, checkpoint
 sequence on the synthetic preset of the dataset the flags name:
 
     model.train(); loss(batch) [+ backward + optimizer step with --train_step true]   solvers.py:211-218
+        (--entity_aware true: the batch is the head of the device CF table, nine columns; utils.device_cf_negative_sampling)
     model.eval()                                                                      solvers.py:227 / models/base.py:88-96
     metrics(model, dataset)                                                           solvers.py:33-104
     [--metapath_test true, the default] metrics per metapath p with p zeroed          solvers.py:229-241
@@ -113,7 +114,7 @@ def main(argv=None, dataset=None):
     """Runs the sequence and returns the result dict (also printed as one JSON line when run as a script).
     `dataset`: an already built SyntheticHIN (tests share one); by default the preset the flags name."""
     from . import models, solvers
-    from .utils import SyntheticHIN, update_pea_graph_input
+    from .utils import SyntheticHIN, device_cf_negative_sampling, update_pea_graph_input
 
     args = build_parser().parse_args(argv)
     if args.device == 'cpu' or not torch.cuda.is_available():
@@ -125,7 +126,10 @@ def main(argv=None, dataset=None):
     if dataset is None:
         dataset = SyntheticHIN(PRESET_OF[key], seed=2019)
     if dataset_args['entity_aware']:
-        raise NotImplementedError('entity_aware batches need the entity lists of the processed dataset (absent)')
+        # the entity lists the reference's preprocessing builds, from the preset's own relations, and what the sampler dispatches on
+        dataset.entity_lists()
+        dataset.cf_loss_type, dataset.entity_aware = dataset_args['cf_loss_type'], True
+        dataset.sampling_strategy, dataset.num_negative_samples = dataset_args['sampling_strategy'], dataset_args['num_negative_samples']
     steps = model_args['meta_path_steps']
     train_args['num_metapaths'] = len(steps)            # the first n metapaths of the dataset's table
     torch.cuda.set_device(int(args.gpu_idx))
@@ -149,7 +153,11 @@ def main(argv=None, dataset=None):
     model = PEARecsysModel(**model_args).to(train_args['device'])
     opt = torch.optim.Adam(model.parameters(), lr=train_args['lr'], weight_decay=train_args['weight_decay'])
 
-    batch = torch.from_numpy(dataset.bpr_batch(batch_size=train_args['batch_size'])).to(train_args['device'])
+    if dataset_args['entity_aware']:
+        # nine-column rows (u, i+, i-, six entity columns): the head of the epoch table sampled on the device
+        batch = device_cf_negative_sampling(dataset, seed=2020, device=train_args['device'])[:train_args['batch_size']]
+    else:
+        batch = torch.from_numpy(dataset.bpr_batch(batch_size=train_args['batch_size'])).to(train_args['device'])
     model.train()                                        # solvers.py:211-218
     if args.train_step.lower() == 'true':
         opt.zero_grad()

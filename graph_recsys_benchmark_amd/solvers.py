@@ -6,7 +6,8 @@ candidate ids are drawn on the host with the very same np.random.choice call per
 position afterwards), then ALL users are scored by one launch of pea_rank_eval; HR@5..20 / NDCG@5..20 / AUC / eval
 loss follow graph_recsys_benchmark/utils/rec_utils.py:7-30 (hit :7, ndcg :18, auc :28) and solvers.py:72,93-96.
 
-kg_epoch is the KG-phase training loop of the KGAT / KGCN / CFKG drivers over a table that already lives on the device.
+kg_epoch is the KG-phase training loop of the KGAT / KGCN / CFKG drivers over a table that already lives on the device; cf_epoch is
+its CF twin (model.loss per step), the loop every model here trains with.
 """
 import numpy as np
 import torch
@@ -26,9 +27,23 @@ def kg_epoch(model, optimizer, train_data, batch_size, max_steps=None):
     per-batch losses stay in one device tensor and are read ONCE: the return value is their float64 mean, the reference's
     np.mean(kg_loss_per_batch), where its loop reads every step's loss with .item().  max_steps caps the number of steps.
     Pending id errors of the epoch's launches raise here (engine.check_pending_errors)."""
+    return _epoch('kg_epoch', model.kg_loss, optimizer, train_data, batch_size, max_steps)
+
+
+def cf_epoch(model, optimizer, train_data, batch_size, max_steps=None):
+    """The CF twin of kg_epoch: the training loop of the reference's BaseSolver.run (solvers.py:211-218) over a table that is
+    already on the model's device (utils.device_cf_negative_sampling; three columns, or nine for an entity-aware model).  Every
+    step runs zero_grad, model.loss(batch), backward, step on a view of consecutive rows, the last short batch included;
+    the losses stay on the device and are read ONCE, the return value is their float64 mean.  max_steps caps the number of
+    steps.  Pending id errors of the epoch's launches raise here (engine.check_pending_errors)."""
+    return _epoch('cf_epoch', model.loss, optimizer, train_data, batch_size, max_steps)
+
+
+def _epoch(who, loss_of, optimizer, train_data, batch_size, max_steps):
+    """the loop of kg_epoch and cf_epoch over loss_of(batch)"""
     n, batch_size = int(train_data.shape[0]), int(batch_size)
     if batch_size < 1:
-        raise ValueError('kg_epoch: batch_size %d' % batch_size)
+        raise ValueError('%s: batch_size %d' % (who, batch_size))
     steps = (n + batch_size - 1) // batch_size
     if max_steps is not None:
         steps = min(steps, int(max_steps))
@@ -38,7 +53,7 @@ def kg_epoch(model, optimizer, train_data, batch_size, max_steps=None):
     for k in range(steps):
         batch = train_data[k * batch_size:(k + 1) * batch_size]
         optimizer.zero_grad()
-        loss = model.kg_loss(batch)
+        loss = loss_of(batch)
         loss.backward()
         optimizer.step()
         losses[k] = loss.detach()

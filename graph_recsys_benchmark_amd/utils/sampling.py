@@ -16,6 +16,9 @@ device-side Philox stream would not reproduce the reference's ids (SURVEY.md 5.8
     device_kg_negative_sampling   its KG twin (csrc/kg_sampler.hip): the (h, t+, t-, rel) table of kg_negative_sampling from
                                one launch over a kg_triple_store, the epoch shuffle a keyed bijection inside that launch;
                                device_shuffle_rows applies the same bijection to any int64 table.
+    device_cf_negative_sampling   the CF epoch table from one launch (csrc/cf_sampler.hip): the BPR rows of device_negative_sampling,
+                               the BCE rows NFM trains on, or the nine-column entity-aware rows over an entity_store, the epoch
+                               shuffle inside the launch.
 """
 import random as rd
 
@@ -346,4 +349,134 @@ def device_shuffle_rows(rows, seed, epoch=0):
     out = torch.empty_like(rows)
     _lib.check(lib.pea_permute_rows(rows.shape[0], rows.shape[1], _lib.ptr(rows), rows.stride(0), _lib.ptr(out), out.stride(0),
                                     int(seed) & (2 ** 64 - 1), int(epoch) & 0xFFFFFFFF, _lib.current_stream()))
+    return out
+
+
+# ---- the CF epoch table from one launch (csrc/cf_sampler.hip, include/peahip_cf_sample.h): BPR, BCE and entity-aware rows.  An
+# ---- addition next to cf_negative_sampling / entity_aware_row / device_negative_sampling above, never their replacement.
+_NO_ENTITY_LISTS = ('entity_aware=True needs dataset.iid_feat_nids / uid_feat_nids / nid2e_dict '
+                    '(built by the reference\'s dataset preprocessing); attach them to the dataset')
+
+
+class EntityStore:
+    """The entity lists of a dataset laid out for pea_cf_sample: CSR (item_ptr [num_iids + 1], item_ent) and (user_ptr
+    [num_uids + 1], user_ent) of the entity node ids of every item and user, and the node-type blocks (block_lo ascending,
+    block_n) an entity's negative is drawn from.  `host` holds the numpy copies of the six tables."""
+
+    def __init__(self, item_ptr, item_ent, user_ptr, user_ent, block_lo, block_n, block_types, device):
+        self.host = {'item_ptr': item_ptr, 'item_ent': item_ent, 'user_ptr': user_ptr, 'user_ent': user_ent,
+                     'block_lo': block_lo, 'block_n': block_n}
+        self.block_types = list(block_types)
+        self.nnz_i, self.nnz_u = int(item_ent.size), int(user_ent.size)
+        # an empty list table still gets a word, so that its pointer is not null (all four tables are given, or none)
+        to = lambda a: torch.as_tensor(np.ascontiguousarray(a if a.size else np.zeros(1), dtype=np.int64)).to(device)
+        self.item_ptr, self.item_ent, self.user_ptr, self.user_ent = to(item_ptr), to(item_ent), to(user_ptr), to(user_ent)
+        self.block_lo, self.block_n = to(block_lo), to(block_n)
+        self.device = self.item_ptr.device
+
+    @property
+    def num_blocks(self):
+        return int(self.host['block_lo'].size)
+
+
+def _csr_of_lists(lists, n, what):
+    if len(lists) != n:
+        raise ValueError('entity_store: %s has %d lists for %d owners' % (what, len(lists), n))
+    ptr = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum([len(l) for l in lists], out=ptr[1:])
+    ids = np.fromiter((v for l in lists for v in l), dtype=np.int64, count=int(ptr[-1]))
+    return ptr, ids
+
+
+def entity_store(dataset, device='cuda'):
+    """The EntityStore of a dataset, built once and kept at dataset.entity_store, from the reference's attributes
+    (datasets/movielens.py:941-991): iid_feat_nids / uid_feat_nids (one list of entity node ids per item / user), nid2e_dict
+    (node id -> (type, ...)), type_accs and num_<type>s.  Checks on the host what the launch cannot: every listed id lies in
+    the block [type_accs[t], type_accs[t] + num_<t>s) of its nid2e_dict type, the blocks are disjoint (kept ascending) and at
+    most 64.  ValueError otherwise; NotImplementedError when the lists are absent."""
+    from .. import _lib
+    want = torch.empty(0, device=device).device
+    store = getattr(dataset, 'entity_store', None)
+    if isinstance(store, EntityStore) and store.device == want:
+        return store
+    if not all(hasattr(dataset, a) for a in ('iid_feat_nids', 'uid_feat_nids', 'nid2e_dict')):
+        raise NotImplementedError(_NO_ENTITY_LISTS)
+    item_ptr, item_ent = _csr_of_lists(dataset.iid_feat_nids, int(dataset.num_iids), 'iid_feat_nids')
+    user_ptr, user_ent = _csr_of_lists(dataset.uid_feat_nids, int(dataset.num_uids), 'uid_feat_nids')
+    if max(item_ent.size, user_ent.size) >= 2 ** 32:
+        raise ValueError('entity_store: 2^32 or more list entries')
+    # the blocks of every node type the dataset sizes (num_<type>s), ascending
+    blocks = sorted((int(lo), int(getattr(dataset, 'num_%ss' % t)), t) for t, lo in dataset.type_accs.items()
+                    if hasattr(dataset, 'num_%ss' % t))
+    if not 1 <= len(blocks) <= _lib.CF_MAX_BLOCKS:
+        raise ValueError('entity_store: %d node-type blocks (1..%d)' % (len(blocks), _lib.CF_MAX_BLOCKS))
+    for k, (lo, cnt, t) in enumerate(blocks):
+        if lo < 0 or not 1 <= cnt < 2 ** 32:
+            raise ValueError('entity_store: block (%d, %d) of %r' % (lo, cnt, t))
+        if k and lo < blocks[k - 1][0] + blocks[k - 1][1]:
+            raise ValueError('entity_store: the blocks of %r and %r overlap' % (blocks[k - 1][2], t))
+    span = {t: (lo, lo + cnt) for lo, cnt, t in blocks}
+    for e in np.unique(np.concatenate([item_ent, user_ent])).tolist():
+        entry = dataset.nid2e_dict.get(e)
+        if entry is None or entry[0] not in span:
+            raise ValueError('entity_store: entity %d has no sized node type in nid2e_dict' % e)
+        lo, hi = span[entry[0]]
+        if not lo <= e < hi:
+            raise ValueError('entity_store: entity %d lies outside the block [%d, %d) of its type %r' % (e, lo, hi, entry[0]))
+    store = EntityStore(item_ptr, item_ent, user_ptr, user_ent, np.asarray([b[0] for b in blocks], dtype=np.int64),
+                        np.asarray([b[1] for b in blocks], dtype=np.int64), [b[2] for b in blocks], device)
+    dataset.entity_store = store
+    return store
+
+
+def device_cf_negative_sampling(dataset, seed, epoch=0, device='cuda', shuffle=True):
+    """The CF training table of an epoch sampled ON THE GPU by one launch of csrc/cf_sampler.hip, the epoch shuffle included (a
+    keyed bijection of the row index: no randperm, no second table); int64 CUDA tensor.
+        cf_loss_type 'BPR'                 [M k, 3]        (u, i+, i-): unshuffled, bitwise device_negative_sampling(shuffle=False)
+        'BPR' with dataset.entity_aware    [M k, 9]        + (e+, e-, mask_i, f+, f-, mask_u), the columns entity_aware_row appends,
+                                                           over entity_store(dataset)
+        'BCE'                              [M (1 + k), 3]  (u, i+, 1) for every positive, then (u, i-, 0) k per positive
+    sampling_strategy 'random': uniform items; 'unseen': uniform over the items the user has no training interaction with (64
+    rejection attempts; a row they do not suffice for keeps a seen item, is counted in negatives_exhausted and warned about).
+    `epoch` is the Philox counter's fourth word: an independent draw and shuffle per epoch.  Sets train_data,
+    train_data_length and negatives_exhausted; a user or item id outside its block raises ValueError."""
+    from .. import _lib
+    mode = {'BPR': _lib.CF_BPR, 'BCE': _lib.CF_BCE}.get(dataset.cf_loss_type)
+    if mode is None:
+        raise NotImplementedError('only the BPR and BCE branches are on the accelerated path')
+    if dataset.sampling_strategy not in ('random', 'unseen'):
+        raise NotImplementedError('sampling_strategy %r (random or unseen)' % (dataset.sampling_strategy,))
+    ent = bool(getattr(dataset, 'entity_aware', False))
+    if ent and mode == _lib.CF_BCE:
+        raise NotImplementedError('entity-aware rows exist in the BPR branch only (datasets/movielens.py:941-991)')
+    store = entity_store(dataset, device) if ent else None
+    lib = _lib.require_device()
+    pos = torch.as_tensor(dataset.edge_index_nps['user2item']).to(device=device, dtype=torch.int64)
+    pos_u, pos_i = pos[0].contiguous(), pos[1].contiguous()
+    k = int(dataset.num_negative_samples)
+    lo, n_items = int(dataset.type_accs['iid']), int(dataset.num_iids)
+    u_lo, n_users = int(dataset.type_accs['uid']), int(dataset.num_uids)
+    keys = torch.unique(pos_u * n_items + (pos_i - lo)) if dataset.sampling_strategy == 'unseen' else None       # ascending
+    n_pos = pos_u.numel()
+    out = torch.empty((n_pos * (k + 1 if mode == _lib.CF_BCE else k), 9 if ent else 3), dtype=torch.int64, device=device)
+    counts = torch.zeros(2, dtype=torch.int32, device=device)              # exhausted, bad rows: one host read for both
+    tables = [None, None, 0, None, None, 0, 0, None, None] if store is None else [
+        _lib.ptr(store.item_ptr), _lib.ptr(store.item_ent), store.nnz_i, _lib.ptr(store.user_ptr), _lib.ptr(store.user_ent),
+        store.nnz_u, store.num_blocks, _lib.ptr(store.block_lo), _lib.ptr(store.block_n)]
+    _lib.check(lib.pea_cf_sample(n_pos, k, mode, _lib.ptr(pos_u), _lib.ptr(pos_i), lo, n_items, u_lo, n_users, _lib.ptr(keys),
+                                 0 if keys is None else keys.numel(), *tables, int(seed) & (2 ** 64 - 1),
+                                 int(epoch) & 0xFFFFFFFF, int(bool(shuffle)), _lib.ptr(out), out.stride(0), _lib.ptr(counts),
+                                 _lib.ptr(counts[1:]), _lib.current_stream()))
+    n_exhausted, n_bad = (int(v) for v in counts.tolist())
+    if n_bad:
+        raise ValueError('device_cf_negative_sampling: %d of %d rows carry a user or item id outside its block (or an entity '
+                         'list outside its table)' % (n_bad, out.shape[0]))
+    if n_exhausted:
+        # 'unseen': 64 rejection attempts all hit seen items (a user who has rated nearly every item); the row keeps
+        # a seen item as its negative.  Loud, because such a row is a false negative.
+        import warnings
+        warnings.warn('device_cf_negative_sampling: %d of %d negatives are seen items (rejection sampling exhausted)'
+                      % (n_exhausted, out.shape[0]), RuntimeWarning)
+    dataset.negatives_exhausted = n_exhausted
+    dataset.train_data, dataset.train_data_length = out, out.shape[0]
     return out

@@ -165,6 +165,44 @@ class SyntheticHIN:
         neg = rs.randint(low=self.type_accs['iid'], high=self.type_accs['iid'] + self.num_iids, size=(b, 1))
         return np.hstack([u2i[:, pick].T.astype(np.int64), neg.astype(np.int64)])
 
+    def entity_lists(self):
+        """The entity lists the reference's preprocessing builds for entity-aware training (datasets/movielens.py:949-991), from
+        the preset's own relations: iid_feat_nids[i] = the sources of every *2item relation other than user2item that point at
+        item i (relation by relation, each in edge order), uid_feat_nids[u] the same over the *2user relations, nid2e_dict
+        {entity node id: (type, index in its block)} and num_<type>s for every node type.  One stable sort per relation.
+        Sets the attributes once (a second call changes nothing) and returns (iid_feat_nids, uid_feat_nids)."""
+        if not hasattr(self, 'iid_feat_nids'):
+            for t, n in self.type_sizes.items():
+                setattr(self, 'num_%ss' % t, n)
+            self.nid2e_dict = {self.type_accs[t] + j: (t, j) for t, n in self.type_sizes.items() if t not in ('uid', 'iid')
+                               for j in range(n)}
+            self.iid_feat_nids = self._lists_into('iid')
+            self.uid_feat_nids = self._lists_into('uid')
+        return self.iid_feat_nids, self.uid_feat_nids
+
+    def _lists_into(self, dst_t):
+        """per node of type dst_t, the sources of the attribute relations that end in it"""
+        n, lo = self.type_sizes[dst_t], self.type_accs[dst_t]
+        parts, total = [], np.zeros(n, dtype=np.int64)
+        for name, (src_t, to_t, _) in self.spec['relations'].items():
+            if to_t != dst_t or src_t in ('uid', 'iid'):
+                continue
+            ei = self.edge_index_nps[name].astype(np.int64)
+            dst = ei[1] - lo
+            order = np.argsort(dst, kind='stable')
+            cnt = np.bincount(dst, minlength=n)
+            parts.append((ei[0][order], cnt))
+            total += cnt
+        ptr = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(total, out=ptr[1:])
+        ids = np.zeros(int(ptr[-1]), dtype=np.int64)
+        base = ptr[:-1].copy()
+        for src, cnt in parts:                                 # relation q's entries follow those of the relations before it
+            within = np.arange(src.size) - np.repeat(np.cumsum(cnt) - cnt, cnt)
+            ids[np.repeat(base, cnt) + within] = src
+            base += cnt
+        return [ids[ptr[k]:ptr[k + 1]].tolist() for k in range(n)]
+
     def eval_split(self, num_users=None, seed=2021):
         """Leave-one-out evaluation maps in the reference's layout (datasets/movielens.py:304-308, read by
         solvers.py:21-31,50-54): test_pos_unid_inid_map[u] = [one item u has not rated], neg_unid_inid_map[u] = every
