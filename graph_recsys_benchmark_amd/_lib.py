@@ -229,6 +229,7 @@ EVAL_SIGNATURES = {
                                        _sz, _vp]),
 }
 RANK_MULTI_CHUNK = 8     # csrc/topk_select.h kPC: thresholds of one (user, chunk) row
+RANK_THREAD_FINISH_USERS = 1 << 19     # csrc/topk_select.h kThreadFinishUsers: from here a single-positive rank finishes by threads
 
 # every symbol include/peahip_sample.h declares (the on-device KG triple sampler and row shuffle)
 SAMPLE_SIGNATURES = {

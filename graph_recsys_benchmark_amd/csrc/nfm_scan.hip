@@ -104,16 +104,6 @@ struct ScArgs {
 
 extern __shared__ __attribute__((aligned(16))) float sc_smem[];
 
-// user q's positives [b, e): multi_span, or the q-th alone for a call without a row pointer (pea_nfm_rank_full)
-__device__ __forceinline__ void pos_span(const ScArgs &a, int64_t q, int64_t &b, int64_t &e) {
-    if (a.pos_rowptr) {
-        multi_span(a.pos_rowptr, q, a.Q, b, e);
-    } else {
-        b = q;
-        e = q + 1;
-    }
-}
-
 // the first position of the ascending row[b, e) whose entry is >= node
 __device__ __forceinline__ int64_t lower_bound(const int64_t *__restrict__ row, int64_t b, int64_t e, int64_t node) {
     while (b < e) {
@@ -214,7 +204,7 @@ __global__ __launch_bounds__(kThreads) void nfm_scan_kernel(const ScArgs a) {
             if (ee < eb) ee = eb;
         }
         if (RANK && ok) {
-            pos_span(a, q, pb, pe);
+            pos_span(a.pos_rowptr, q, a.Q, pb, pe);
             pbase[tid] = pb;
             np[tid] = pe - pb < 0x7fffffff ? (int)(pe - pb) : 0x7fffffff;
             eb = lower_bound(a.excl_items, eb, ee, cat_node0 + i0);
@@ -431,7 +421,7 @@ __global__ __launch_bounds__(256) void nfm_rank_finish_kernel(const ScArgs a, in
     const int64_t u = a.uid[q];
     const bool ok = u >= 0 && u < a.U;
     int64_t b, e;
-    pos_span(a, q, b, e);
+    pos_span(a.pos_rowptr, q, a.Q, b, e);
     int64_t taken = 0;
     for (int c = 0; c < S; ++c) taken += ok ? a.gone[(int64_t)c * a.n_users + q] : 0;
     const int64_t others = ok ? a.n_items - taken : 0;

@@ -6,6 +6,9 @@
 //   s(u, i) = (fma chain over k of max(A[u,k] + B[i,k], 0) * fc2_w[k], from 0) + fc2_b            (pair_score)
 // Every score of this file goes through pair_score on rows written by topk_prep, so a pair has the same bits wherever
 // it is computed (top-K scan, rank scan, the exclusion walk of rank_full, any U / K / item split).  No float atomics.
+// pea_rank_full keeps a scan of its own, the RANK form of topk_scan_kernel: over 1.7 M users the T = 1 scan of the
+// several-positives rank was measured 3.7 % slower (profiles/r18/rank_one_scan.md); the inner product's pea_dot_rank_full
+// IS its several-positives call.
 #include <algorithm>
 
 #include "score_common.h"
@@ -21,32 +24,46 @@ constexpr int kTileFloats = 2048;   // LDS tile of item rows: 8 KB = 128 rows at
 // fma(max(0 + 0, 0), 0, o) = o, so the padding changes no bit of the score
 int padded_r(int R) { return R <= 16 ? 16 : (R <= 32 ? 32 : 64); }
 
+// what topk_prep writes, at the head of every workspace of this file: fc2_w padded, the user halves A [U, RP], the
+// positives' item halves P [Q, RP] and the catalogue's item halves B [n_items, RP]
+struct Prep {
+    int RP = 16;
+    size_t off_w2 = 0, off_a = 0, off_p = 0, off_b = 0, end = 0;
+};
+
+Prep make_prep(int64_t U, int64_t Q, int64_t n_items, int R) {
+    Prep p;
+    p.RP = padded_r(R);
+    size_t o = 256;                                                           // error flag
+    p.off_w2 = o; o = align256(o + (size_t)p.RP * 4);
+    p.off_a = o;  o = align256(o + (size_t)std::max<int64_t>(U, 1) * p.RP * 4);
+    p.off_p = o;  o = align256(o + (size_t)std::max<int64_t>(Q, 1) * p.RP * 4);
+    p.off_b = o;  o = align256(o + (size_t)std::max<int64_t>(n_items, 1) * p.RP * 4);
+    p.end = o;
+    return p;
+}
+
 struct Layout {
-    int RP = 16, NT = 128, S = 1;
+    Prep prep;
+    int NT = 128, S = 1;
     int64_t span = 0;
-    size_t off_w2 = 0, off_a = 0, off_p = 0, off_b = 0, off_part = 0, bytes = 0;
+    size_t off_part = 0, bytes = 0;
 };
 
 // How a call is cut: NT users per workgroup (one per lane), the catalogue in S item ranges of `span` items so that few
 // users still fill the machine.  Depends on (U, n_items, K, R) only, so the workspace query and the call agree.
 Layout make_layout(int64_t U, int64_t n_items, int K, int R) {
     Layout L;
-    L.RP = padded_r(R);
+    L.prep = make_prep(U, U, n_items, R);      // P: the positives of pea_rank_full
     L.NT = K <= 32 ? 128 : 64;      // a lane's K-entry list is an LDS column of 8 K bytes
-    catalogue_split(std::max<int64_t>((U + L.NT - 1) / L.NT, 1), n_items, std::max(K, 1), kTileFloats / L.RP, &L.S, &L.span);
-    size_t o = 256;                                                           // error flag
-    L.off_w2 = o; o = align256(o + (size_t)L.RP * 4);
-    L.off_a = o;  o = align256(o + (size_t)std::max<int64_t>(U, 1) * L.RP * 4);
-    L.off_p = o;  o = align256(o + (size_t)std::max<int64_t>(U, 1) * L.RP * 4);
-    L.off_b = o;  o = align256(o + (size_t)std::max<int64_t>(n_items, 1) * L.RP * 4);
-    L.off_part = o;
-    o = align256(o + (size_t)L.S * std::max(K, 1) * std::max<int64_t>(U, 1) * 8);
-    L.bytes = o;
+    catalogue_split(std::max<int64_t>((U + L.NT - 1) / L.NT, 1), n_items, std::max(K, 1), kTileFloats / L.prep.RP, &L.S, &L.span);
+    L.off_part = L.prep.end;
+    L.bytes = align256(L.off_part + (size_t)L.S * std::max(K, 1) * std::max<int64_t>(U, 1) * 8);
     return L;
 }
 
 // ---------------------------------------------------------------------------------------------- prep
-// One thread per (row, column): rows [0, U) the user halves A, [U, U + U_pos) the positives' item halves (rank_full),
+// One thread per (row, column): rows [0, U) the user halves A, [U, U + U_pos) the positives' item halves (the rank forms),
 // the rest the catalogue's item halves B.  Fixed summation order: c ascending, bias last.
 __global__ __launch_bounds__(256) void topk_prep_kernel(int64_t U, int64_t U_pos, int64_t n_items, int R, int RP, int64_t N,
                                                         const float *__restrict__ repr, const int64_t *__restrict__ unids,
@@ -259,12 +276,12 @@ int launch_scan_nt(const Layout &L, const ScanArgs &g, hipStream_t stream) {
 template <bool RANK>
 int launch_scan(const Layout &L, const ScanArgs &g, hipStream_t stream) {
     if (RANK || L.NT == 128) {
-        if (L.RP == 16) return launch_scan_nt<16, RANK, 128>(L, g, stream);
-        if (L.RP == 32) return launch_scan_nt<32, RANK, 128>(L, g, stream);
+        if (L.prep.RP == 16) return launch_scan_nt<16, RANK, 128>(L, g, stream);
+        if (L.prep.RP == 32) return launch_scan_nt<32, RANK, 128>(L, g, stream);
         return launch_scan_nt<64, RANK, 128>(L, g, stream);
     }
-    if (L.RP == 16) return launch_scan_nt<16, false, 64>(L, g, stream);
-    if (L.RP == 32) return launch_scan_nt<32, false, 64>(L, g, stream);
+    if (L.prep.RP == 16) return launch_scan_nt<16, false, 64>(L, g, stream);
+    if (L.prep.RP == 32) return launch_scan_nt<32, false, 64>(L, g, stream);
     return launch_scan_nt<64, false, 64>(L, g, stream);
 }
 
@@ -273,14 +290,14 @@ int check_r(const char *what, int R) {
     return PEA_OK;
 }
 
-int launch_prep(const Layout &L, int64_t U, int64_t U_pos, int64_t n_items, int R, int64_t N, const float *repr,
+int launch_prep(const Prep &p, int64_t U, int64_t U_pos, int64_t n_items, int R, int64_t N, const float *repr,
                 const int64_t *unids, const int64_t *pos_items, int64_t item_lo, const float *fc1_w, const float *fc1_b,
                 const float *fc2_w, char *ws, hipStream_t stream) {
-    ProfScope ps("topk_prep", stream, 4.0 * (double)(U + U_pos + n_items) * (R + L.RP));
-    const int64_t threads = std::max<int64_t>((U + U_pos + n_items) * L.RP, L.RP);
-    PEA_LAUNCH(topk_prep_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, U, U_pos, n_items, R, L.RP, N,
-               repr, unids, pos_items, item_lo, fc1_w, fc1_b, fc2_w, (float *)(ws + L.off_a), (float *)(ws + L.off_p),
-               (float *)(ws + L.off_b), (float *)(ws + L.off_w2), (int *)ws);
+    ProfScope ps("topk_prep", stream, 4.0 * (double)(U + U_pos + n_items) * (R + p.RP));
+    const int64_t threads = std::max<int64_t>((U + U_pos + n_items) * p.RP, p.RP);
+    PEA_LAUNCH(topk_prep_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, U, U_pos, n_items, R, p.RP, N,
+               repr, unids, pos_items, item_lo, fc1_w, fc1_b, fc2_w, (float *)(ws + p.off_a), (float *)(ws + p.off_p),
+               (float *)(ws + p.off_b), (float *)(ws + p.off_w2), (int *)ws);
     PEA_HIP(hipGetLastError());
     return PEA_OK;
 }
@@ -288,9 +305,10 @@ int launch_prep(const Layout &L, int64_t U, int64_t U_pos, int64_t n_items, int 
 // ---------------------------------------------------------------------------------------------- several positives per user
 // pea_rank_full_multi (include/peahip_eval.h): the rows, counters and finish of topk_select.h with pair_score.
 struct MultiLayout {
-    int RP = 16, S = 1;
+    Prep prep;
+    int S = 1;
     int64_t span = 0, rows = 0;
-    size_t off_w2 = 0, off_a = 0, off_p = 0, off_b = 0, off_thr = 0, off_part = 0, bytes = 0;
+    size_t off_thr = 0, off_part = 0, bytes = 0;
 };
 
 constexpr int kMultiNT = 128;       // rows of one workgroup of the scan, one per lane
@@ -298,14 +316,10 @@ constexpr int kMultiNT = 128;       // rows of one workgroup of the scan, one pe
 // Depends on (U, Q, n_items, R) only: the rows are the bound multi_rows, not the rows in use.
 MultiLayout make_multi_layout(int64_t U, int64_t Q, int64_t n_items, int R) {
     MultiLayout L;
-    L.RP = padded_r(R);
-    L.rows = multi_rows(U, Q);
-    catalogue_split(std::max<int64_t>((L.rows + kMultiNT - 1) / kMultiNT, 1), n_items, 1, kTileFloats / L.RP, &L.S, &L.span);
-    size_t o = 256;                                                           // error flag
-    L.off_w2 = o;   o = align256(o + (size_t)L.RP * 4);
-    L.off_a = o;    o = align256(o + (size_t)std::max<int64_t>(U, 1) * L.RP * 4);
-    L.off_p = o;    o = align256(o + (size_t)std::max<int64_t>(Q, 1) * L.RP * 4);
-    L.off_b = o;    o = align256(o + (size_t)std::max<int64_t>(n_items, 1) * L.RP * 4);
+    L.prep = make_prep(U, Q, n_items, R);
+    L.rows = multi_rows(U, Q, true);
+    catalogue_split(std::max<int64_t>((L.rows + kMultiNT - 1) / kMultiNT, 1), n_items, 1, kTileFloats / L.prep.RP, &L.S, &L.span);
+    size_t o = L.prep.end;
     L.off_thr = o;  o = align256(o + (size_t)std::max<int64_t>(Q, 1) * 4);
     L.off_part = o; o = align256(o + (size_t)L.S * 2 * kPC * std::max<int64_t>(L.rows, 1) * 4);
     L.bytes = o;
@@ -330,7 +344,7 @@ __global__ __launch_bounds__(256) void rank_multi_pos_kernel(const MultiArgs g) 
     float a[RP];
     load_half<RP>(g.A + q * RP, a);
     const float b2 = g.fc2_b[0];
-    multi_thresholds(q, g.Q, g.pos_rowptr, lane, [&](int64_t j) { return pair_score<RP>(a, g.P + j * RP, g.w2, b2); }, g.thr);
+    multi_thresholds(q, g.Q, g.pos_rowptr, lane, kWave, [&](int64_t j) { return pair_score<RP>(a, g.P + j * RP, g.w2, b2); }, g.thr);
 }
 
 // topk_scan_kernel's RANK loop with a (user, chunk) row per lane and multi_count over T thresholds in place of the two
@@ -377,27 +391,25 @@ __global__ __launch_bounds__(kMultiNT) void rank_multi_scan_kernel(const MultiAr
             }
         }
     }
-    if (n > 0) multi_store(g.part, blockIdx.y, g.rows, r, n, hi, lo);
+    if (n > 0) multi_store(g.part, blockIdx.y, kPC, g.rows, r, n, hi, lo);
 }
 
 // one wave per user: rank_multi_finish of topk_select.h with pair_score on the rows the scan compared (the same bits)
 template <int RP>
-__global__ __launch_bounds__(256) void rank_multi_finish_kernel(const MultiArgs g, int32_t *above, int32_t *below,
-                                                                float *pos_score, int32_t *n_neg) {
+__global__ __launch_bounds__(256) void rank_multi_finish_kernel(const MultiArgs g, const RankOut out) {
     const int lane = threadIdx.x % kWave;
     const int64_t q = (int64_t)blockIdx.x * (256 / kWave) + threadIdx.x / kWave;
     if (q >= g.U) return;
     float a[RP];
     load_half<RP>(g.A + q * RP, a);
     const float b2 = g.fc2_b[0];
-    rank_multi_finish(q, g.U, g.Q, g.rows, g.S, g.n_items, g.item_lo, g.pos_rowptr, g.pos_items, g.thr, g.excl_rowptr,
+    rank_multi_finish(q, g.U, g.Q, g.rows, kPC, g.S, g.n_items, g.item_lo, g.pos_rowptr, g.pos_items, g.thr, g.excl_rowptr,
                       g.excl_items, g.part,
-                      [&](int64_t node) { return pair_score<RP>(a, g.B + (node - g.item_lo) * RP, g.w2, b2); }, lane, above,
-                      below, pos_score, n_neg);
+                      [&](int64_t node) { return pair_score<RP>(a, g.B + (node - g.item_lo) * RP, g.w2, b2); }, lane, out);
 }
 
 template <int RP>
-int launch_multi(const MultiArgs &g, int R, int32_t *above, int32_t *below, float *pos_score, int32_t *n_neg, hipStream_t stream) {
+int launch_multi(const MultiArgs &g, int R, const RankOut &out, hipStream_t stream) {
     const dim3 waves((unsigned)((g.U + 3) / 4));
     if (g.Q > 0) {
         {
@@ -413,7 +425,7 @@ int launch_multi(const MultiArgs &g, int R, int32_t *above, int32_t *below, floa
         PEA_HIP(hipGetLastError());
     }
     ProfScope ps("rank_multi_finish", stream, 8.0 * (double)g.Q * g.S);
-    PEA_LAUNCH(rank_multi_finish_kernel<RP>, waves, dim3(256), 0, stream, g, above, below, pos_score, n_neg);
+    PEA_LAUNCH(rank_multi_finish_kernel<RP>, waves, dim3(256), 0, stream, g, out);
     PEA_HIP(hipGetLastError());
     return PEA_OK;
 }
@@ -446,11 +458,11 @@ extern "C" int pea_recommend_topk(int64_t U, int K, int R, int64_t num_nodes, co
     if (U == 0) return PEA_OK;
     char *ws = (char *)workspace;
     PEA_MEMSET_ASYNC((int *)ws, 0, sizeof(int), stream);
-    PEA_TRY(launch_prep(L, U, 0, n_items, R, num_nodes, repr, unids, nullptr, item_lo, fc1_w, fc1_b, fc2_w, ws, stream));
+    PEA_TRY(launch_prep(L.prep, U, 0, n_items, R, num_nodes, repr, unids, nullptr, item_lo, fc1_w, fc1_b, fc2_w, ws, stream));
     ScanArgs g;
     g.U = U; g.n_items = n_items; g.item_lo = item_lo; g.span = L.span; g.K = K;
-    g.A = (const float *)(ws + L.off_a); g.B = (const float *)(ws + L.off_b); g.P = nullptr;
-    g.w2 = (const float *)(ws + L.off_w2); g.fc2_b = fc2_b;
+    g.A = (const float *)(ws + L.prep.off_a); g.B = (const float *)(ws + L.prep.off_b); g.P = nullptr;
+    g.w2 = (const float *)(ws + L.prep.off_w2); g.fc2_b = fc2_b;
     g.excl_rowptr = excl_rowptr; g.excl_items = excl_items;
     g.part_s = (float *)(ws + L.off_part);
     g.part_i = (int *)(ws + L.off_part + (size_t)L.S * K * U * 4);
@@ -486,11 +498,11 @@ extern "C" int pea_rank_full(int64_t U, int R, int64_t num_nodes, const float *r
     if (U == 0) return PEA_OK;
     char *ws = (char *)workspace;
     PEA_MEMSET_ASYNC((int *)ws, 0, sizeof(int), stream);
-    PEA_TRY(launch_prep(L, U, U, n_items, R, num_nodes, repr, unids, pos_items, item_lo, fc1_w, fc1_b, fc2_w, ws, stream));
+    PEA_TRY(launch_prep(L.prep, U, U, n_items, R, num_nodes, repr, unids, pos_items, item_lo, fc1_w, fc1_b, fc2_w, ws, stream));
     ScanArgs g;
     g.U = U; g.n_items = n_items; g.item_lo = item_lo; g.span = L.span; g.K = 0;
-    g.A = (const float *)(ws + L.off_a); g.B = (const float *)(ws + L.off_b); g.P = (const float *)(ws + L.off_p);
-    g.w2 = (const float *)(ws + L.off_w2); g.fc2_b = fc2_b;
+    g.A = (const float *)(ws + L.prep.off_a); g.B = (const float *)(ws + L.prep.off_b); g.P = (const float *)(ws + L.prep.off_p);
+    g.w2 = (const float *)(ws + L.prep.off_w2); g.fc2_b = fc2_b;
     g.excl_rowptr = nullptr; g.excl_items = nullptr;
     g.part_s = nullptr;
     g.part_i = (int *)(ws + L.off_part);
@@ -500,8 +512,8 @@ extern "C" int pea_rank_full(int64_t U, int R, int64_t num_nodes, const float *r
 #define PEA_RANK_FINISH(rp)                                                                                              \
     PEA_LAUNCH(rank_full_kernel<rp>, dim3((unsigned)((U + 63) / 64)), dim3(64), 0, stream, U, L.S, n_items, item_lo, g.A, \
                g.B, g.P, g.w2, fc2_b, pos_items, excl_rowptr, excl_items, (const int *)g.part_i, rank, auc, pos_score)
-        if (L.RP == 16) PEA_RANK_FINISH(16);
-        else if (L.RP == 32) PEA_RANK_FINISH(32);
+        if (L.prep.RP == 16) PEA_RANK_FINISH(16);
+        else if (L.prep.RP == 32) PEA_RANK_FINISH(32);
         else PEA_RANK_FINISH(64);
 #undef PEA_RANK_FINISH
         PEA_HIP(hipGetLastError());
@@ -535,18 +547,17 @@ extern "C" int pea_rank_full_multi(int64_t U, int R, int64_t num_nodes, const fl
     if (U == 0) return PEA_OK;
     char *ws = (char *)workspace;
     PEA_MEMSET_ASYNC((int *)ws, 0, sizeof(int), stream);
-    Layout prep;
-    prep.RP = L.RP; prep.off_w2 = L.off_w2; prep.off_a = L.off_a; prep.off_p = L.off_p; prep.off_b = L.off_b;
-    PEA_TRY(launch_prep(prep, U, Q, n_items, R, num_nodes, repr, unids, pos_items, item_lo, fc1_w, fc1_b, fc2_w, ws, stream));
+    PEA_TRY(launch_prep(L.prep, U, Q, n_items, R, num_nodes, repr, unids, pos_items, item_lo, fc1_w, fc1_b, fc2_w, ws, stream));
     MultiArgs g;
     g.U = U; g.Q = Q; g.rows = L.rows; g.n_items = n_items; g.item_lo = item_lo; g.span = L.span; g.S = L.S;
-    g.A = (const float *)(ws + L.off_a); g.B = (const float *)(ws + L.off_b); g.P = (const float *)(ws + L.off_p);
-    g.w2 = (const float *)(ws + L.off_w2); g.fc2_b = fc2_b;
+    g.A = (const float *)(ws + L.prep.off_a); g.B = (const float *)(ws + L.prep.off_b); g.P = (const float *)(ws + L.prep.off_p);
+    g.w2 = (const float *)(ws + L.prep.off_w2); g.fc2_b = fc2_b;
     g.pos_rowptr = pos_rowptr; g.pos_items = pos_items; g.excl_rowptr = excl_rowptr; g.excl_items = excl_items;
     g.thr = (float *)(ws + L.off_thr);
     g.part = (int *)(ws + L.off_part);
-    if (L.RP == 16) PEA_TRY(launch_multi<16>(g, R, above, below, pos_score, n_neg, stream));
-    else if (L.RP == 32) PEA_TRY(launch_multi<32>(g, R, above, below, pos_score, n_neg, stream));
-    else PEA_TRY(launch_multi<64>(g, R, above, below, pos_score, n_neg, stream));
+    const RankOut out = {above, below, pos_score, n_neg, nullptr};
+    if (L.prep.RP == 16) PEA_TRY(launch_multi<16>(g, R, out, stream));
+    else if (L.prep.RP == 32) PEA_TRY(launch_multi<32>(g, R, out, stream));
+    else PEA_TRY(launch_multi<64>(g, R, out, stream));
     return read_err_flag((int *)ws, stream, "rank_full_multi");
 }

@@ -279,36 +279,41 @@ def _recommend_topk(repr_, unids, k, item_range, exclude, fc):
     return out_items, out_scores
 
 
+def _rank_call(run, query, query_args, table, unids, pos_ptrs, catalogue, out_ptrs):
+    """What the two all-item rank forms share once their arguments are checked: the workspace of query(*query_args) bytes and the
+    call itself (one set of kernels on the C side too: include/peahip_eval.h).  catalogue: what _catalogue_args returns after unids."""
+    item_lo, n_items, rowptr, items = catalogue
+    ws_bytes = int(query(*query_args))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=table.device)
+    run((unids.shape[0], table.shape[1], table.shape[0], _lib.ptr(table), _lib.ptr(unids), *pos_ptrs, item_lo, n_items, _lib.ptr(rowptr),
+         _lib.ptr(items)), (*out_ptrs, _lib.ptr(ws), ws_bytes))
+
+
 def _rank_full(repr_, unids, pos_items, item_range, exclude, fc):
     table, run, query = _scorer('rank_full', repr_, fc)
-    unids, item_lo, n_items, rowptr, items = _catalogue_args(table, unids, item_range, exclude)
+    unids, *catalogue = _catalogue_args(table, unids, item_range, exclude)
     pos_items = pos_items.to(torch.int64).contiguous()
     if pos_items.shape != unids.shape:
         raise ValueError('one positive per requested user')
-    u, r, dev = unids.shape[0], table.shape[1], table.device
-    rank, auc, pos_score = _rank_outputs(u, dev)
-    ws, ws_bytes = _catalogue_ws(query, u, n_items, 1, r, dev)
-    run((u, r, table.shape[0], _lib.ptr(table), _lib.ptr(unids), _lib.ptr(pos_items), item_lo, n_items, _lib.ptr(rowptr),
-         _lib.ptr(items)), (_lib.ptr(rank), _lib.ptr(auc), _lib.ptr(pos_score), _lib.ptr(ws), ws_bytes))
-    return rank, auc, pos_score
+    u, r = unids.shape[0], table.shape[1]
+    outs = _rank_outputs(u, table.device)
+    _rank_call(run, query, (u, catalogue[1], 1, r), table, unids, (_lib.ptr(pos_items),), catalogue, [_lib.ptr(t) for t in outs])
+    return outs
 
 
 def _rank_full_multi(repr_, unids, pos_rowptr, pos_items, item_range, exclude, fc):
     table, run, query = _scorer('rank_full_multi', repr_, fc)
-    unids, item_lo, n_items, rowptr, items = _catalogue_args(table, unids, item_range, exclude)
+    unids, *catalogue = _catalogue_args(table, unids, item_range, exclude)
     u, r, dev = unids.shape[0], table.shape[1], table.device
     pos_rowptr, pos_items = _positives_csr(pos_rowptr, pos_items, u, dev, 'table')
     q = pos_items.numel()
-    above, below, pos_score, n_neg = _multi_outputs(u, q, dev)
+    above, below, pos_score, n_neg = outs = _multi_outputs(u, q, dev)
     if u == 0:                                  # nobody asked: an empty tensor has no address to hand to the C side
-        return above, below, pos_score, n_neg
-    ws_bytes = int(query(u, q, n_items, r))
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+        return outs
     at = _ptr_or_spare(q, dev)
-    run((u, r, table.shape[0], _lib.ptr(table), _lib.ptr(unids), _lib.ptr(pos_rowptr), at(pos_items), q, item_lo, n_items,
-         _lib.ptr(rowptr), _lib.ptr(items)),
-        (at(above), at(below), at(pos_score), _lib.ptr(n_neg), _lib.ptr(ws), ws_bytes))
-    return above, below, pos_score, n_neg
+    _rank_call(run, query, (u, q, catalogue[1], r), table, unids, (_lib.ptr(pos_rowptr), at(pos_items), q), catalogue,
+               (at(above), at(below), at(pos_score), _lib.ptr(n_neg)))
+    return outs
 
 
 def predict(repr_, unids, inids, fc1_w, fc1_b, fc2_w, fc2_b):

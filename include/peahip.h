@@ -590,7 +590,8 @@ int pea_rank_full(int64_t U, int R, int64_t num_nodes, const float *repr, const 
  *   (catalogue block, ascending exclusion lists with entries outside the catalogue ignored, (score descending, node id
  *   ascending) order also inside a tie group at the K-th place, (-1, -inf) tail, NaN and -inf never returned, K in
  *   1..128, the positive scored wherever it is and never counted among the others, the same error codes at the same
- *   times) without the four fc pointers.  workspace: pea_dot_topk_workspace_bytes(U, n_items, K, D) bytes
+ *   times) without the four fc pointers.  pea_dot_rank_full is pea_dot_rank_full_multi (peahip_eval.h) with one positive per
+ *   user and no row pointer: the same launches on rows of one threshold, so the two cannot disagree.  workspace: pea_dot_topk_workspace_bytes(U, n_items, K, D) bytes
  *   (pea_dot_rank_full: K = 1); 0 = bad arguments.
  * pea_dot_predict and pea_dot_rank_eval synchronise the stream once to report ids outside [0, num_nodes) as
  * PEA_ERR_RANGE, as pea_predict does.

@@ -29,8 +29,10 @@ extern "C" {
  *   These are the integers of the single-positive entry point: pea_rank_full([u_q], [pos_items[j]], exclusion = the sorted
  *   union of q's exclusion row and q's positive row) gives rank == above[j], auc == (float)below[j] / (float)n_neg[q] and the
  *   same pos_score, because a pair's score has the same bits in every entry point of its scorer.
+ *   (pea_dot_rank_full IS pea_dot_rank_full_multi with one positive per user: it runs the same launches without a row
+ *   pointer.  pea_rank_full keeps a scan of its own.)
  * How: a user's positives are cut into chunks of 8 thresholds; one (user, chunk) row rides in the scan where one user rides
- *   in the single-positive scan, and every catalogue score is compared against the row's thresholds; a user with P positives
+ *   in a top-K scan, and every catalogue score is compared against the row's thresholds; a user with P positives
  *   costs ceil(P / 8) passes of scoring work.  The rows of a call are bounded by U + Q / 8 from the arguments alone, which
  *   sizes the launch and the workspace; per item range partial counts are added in range order (no atomics on counts, no
  *   float atomics: bitwise reproducible).  The finish scores every excluded item and every in-catalogue positive of a user

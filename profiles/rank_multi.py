@@ -1,5 +1,5 @@
 """Measurement of the multi-positive all-item evaluation (include/peahip_eval.h: engine.rank_full_multi, engine.dot_rank_full_multi)
-against the flattened route on the single-positive kernels, at the catalogue of the headline preset.
+against the flattened route on the single-positive entry points, at the catalogue of the headline preset.
 
     timeout -k 10 900 python profiles/rank_multi.py [--users 162541] [--items 59047] [--r 16] [--d 112] [--max-pos 20]
                                                     [--repeats 10] [--warmup 2] [--out profiles/r13/rank_multi_r13.json]
@@ -10,9 +10,12 @@ Shape: every user against every item, the users' seen items excluded (log-normal
 as profiles/recommend_dot.py), both scorers: the fc1 / fc2 scorer on an [N, --r] table, the inner product on an [N, --d] table.
   leg 'multi'  positives per user drawn uniformly from 1 .. --max-pos (distinct catalogue items, ascending)
   leg 'one'    exactly one positive per user
-Yardstick: the flattened route, i.e. engine.rank_full / engine.dot_rank_full unchanged -- one (user, positive) pair per flat
-positive, the pair's exclusion row the sorted union of the user's seen items and the user's positives (built once, outside the
-timed region: only the kernel time of the route is charged).
+Yardstick: the flattened route, i.e. engine.rank_full / engine.dot_rank_full -- one (user, positive) pair per flat positive,
+the pair's exclusion row the sorted union of the user's seen items and the user's positives (built once, outside the timed
+region: only the kernel time of the route is charged).  On the inner product both sides run the same kernels (dot_rank_full
+is dot_rank_full_multi without a row pointer): the yardstick is another ROW LAYOUT of them, one scan row of one threshold per
+flat pair against chunked rows of up to 8 thresholds per user, so its 'one' leg compares a call with itself but for the row
+pointer.  On the fc scorer rank_full has a scan of its own.
 Timing: HIP events around each call, warm-up, the two sides alternated call by call in one process, median.  The per-launch
 split of the library's own events (pea_profile_*) comes from one extra call per side; the per-kernel split of rocprofv3
 from a run of its own (--trace-only: one warm call and one traced call per form, leg and side).  One JSON line (also --out).

@@ -55,7 +55,7 @@ def alternated(fused, composed, warmup, repeats, torch_repeats):
             t.append(event_ms(composed))
     f.sort()
     t.sort()
-    return f[len(f) // 2], (t[len(t) // 2] if t else None)
+    return f[len(f) // 2], (t[len(t) // 2] if t else None), (f[0], f[-1])
 
 
 def exclusion_lists(n_users, lo, n_items, total, seed):
@@ -144,11 +144,12 @@ def main():
         'b_topk_serving': (lambda: engine.dot_recommend_topk(table, users_srv, K, (lo, lo + ni), exclude=(srv_ptr, srv_seen)),
                            lambda: composed(users_srv, srv_ptr, srv_seen), int(users_srv.numel()), 'dot_topk_scan'),
         'c_rank_all': (lambda: engine.dot_rank_full(table, users_all, pos, (lo, lo + ni), exclude=(rowptr, seen)),
-                       lambda: composed(users_all, rowptr, seen, rank_of=pos), nu, 'dot_rank_scan'),
+                       lambda: composed(users_all, rowptr, seen, rank_of=pos), nu, 'dot_rank_multi_scan'),
     }
     for name, (fused, comp, n_u, scope) in work.items():
-        f_ms, t_ms = alternated(fused, None if a.hip_only else comp, a.warmup, a.repeats, a.torch_repeats)
+        f_ms, t_ms, f_min_max = alternated(fused, None if a.hip_only else comp, a.warmup, a.repeats, a.torch_repeats)
         res[name + '_hip_ms'] = round(f_ms, 4)
+        res[name + '_hip_min_max_ms'] = [round(v, 4) for v in f_min_max]
         if t_ms is not None:
             res[name + '_torch_ms'] = round(t_ms, 3)
             res[name + '_speedup'] = round(t_ms / f_ms, 2)
@@ -156,7 +157,8 @@ def main():
         res[name + '_launch_ms'] = scopes
         floor_ms = 2.0 * n_u * ni * D / MFMA_F32_FLOPS * 1e3
         res[name + '_scan_floor_ms'] = round(floor_ms, 4)
-        res[name + '_scan_share_of_mfma_floor'] = round(floor_ms / scopes[scope], 3)
+        if scope in scopes:                     # (a PEA_LIB build may name its launches otherwise)
+            res[name + '_scan_share_of_mfma_floor'] = round(floor_ms / scopes[scope], 3)
         torch.cuda.empty_cache()
     line = json.dumps(res)
     print(line)

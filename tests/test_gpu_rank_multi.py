@@ -3,8 +3,12 @@ scorer, engine.dot_rank_full_multi on the inner product), on the smallest shapes
 
   integer inputs   every score is exact in float32 and ties are plentiful: above / below / n_neg equal a float64 brute force
                    over the definition, pos_score is exact
-  random floats    above / pos_score / n_neg equal the flattened route on the single-positive kernels (one rank_full call per
-                   positive, the user's other positives excluded too), below through the bits of its auc
+  random floats    above / pos_score / n_neg equal the flattened route (one rank_full call per positive, the user's other
+                   positives excluded too: for the inner product the same kernels with one row per flat pair), below through
+                   the bits of its auc; and above / below lie inside the intervals the float64 scores leave them
+  one positive     engine.rank_full (a scan of its own) and engine.dot_rank_full (the several-positives body without a row
+                   pointer): exact on integer inputs against the same brute force, each of their three outputs may be NULL in
+                   the C call, and the inner product's thread-per-user finish for very many users equals its wave-per-user one
 Rows of one call mix 0, 1, PC - 1, PC, PC + 1, 2 PC + 1 and 40 positives per user (PC = the thresholds of one scan row), positives
 outside the catalogue and inside the exclusion row, exclusion entries outside the catalogue, a user without negatives, an empty
 exclusion row and repeated users."""
@@ -118,6 +122,30 @@ def brute_force(s64, pos_rows, excl_rows, item_range):
             torch.tensor(n_neg, dtype=torch.int32))
 
 
+def tol(s):
+    """tests/test_gpu_recommend.py: what a float32 score may be away from the float64 one"""
+    return 1e-5 * np.abs(s) + 1e-6
+
+
+def f64_intervals(s64, pos_rows, excl_rows, item_range):
+    """per (user, positive) in flat order, from float64 scores [U, N] alone: (r_lo, r_hi, b_lo, b_hi), the bounds of above and
+    below once every negative within 2 tol of the positive's score may fall on either side (test_rank_full_real_tables)"""
+    lo, hi = item_range
+    s64 = s64.cpu().numpy()
+    out = []
+    for q, (pos, ex) in enumerate(zip(pos_rows, excl_rows)):
+        neg = np.ones(hi - lo, dtype=bool)
+        for ids in (pos, ex):
+            ids = np.asarray(ids, dtype=np.int64)
+            neg[ids[(ids >= lo) & (ids < hi)] - lo] = False
+        sn = s64[q, lo:hi][neg]
+        for p in pos:
+            p64 = s64[q, p]
+            t = 2.0 * tol(p64)
+            out.append((int((sn > p64 + t).sum()), int((sn >= p64 - t).sum()), int((sn < p64 - t).sum()), int((sn <= p64 + t).sum())))
+    return np.asarray(out, dtype=np.int64).reshape(-1, 4).T
+
+
 def flattened(sc, unids, pos_rows, excl_rows, item_range):
     """the identity of include/peahip_eval.h, spelled out on the single-positive entry point: (rank, auc, pos_score) of one call
     over the Q (user, positive) pairs, each with the union of the user's exclusion row and positive row excluded"""
@@ -192,6 +220,11 @@ def test_random_floats_equal_the_flattened_route(form, U, n, width):
     above, below, pos_score, n_neg = (t.cpu() for t in sc.multi(u_t, rowptr, items, item_range, exclude=exclude))
     rank, auc, ps = flattened(sc, unids, pos_rows, excl_rows, item_range)
     assert torch.equal(above, rank) and torch.equal(pos_score, ps)
+    # a yardstick that is none of the kernels: the float64 scores hold most pairs to one rank and every pair to an interval
+    r_lo, r_hi, b_lo, b_hi = f64_intervals(sc.f64_scores(u_t), pos_rows, excl_rows, item_range)
+    assert r_lo.size == 0 or (r_lo == r_hi).mean() >= 0.9, 'the float64 intervals are too wide for this case to test anything'
+    assert np.all((above.numpy() >= r_lo) & (above.numpy() <= r_hi)), 'above outside its float64 interval'
+    assert np.all((below.numpy() >= b_lo) & (below.numpy() <= b_hi)), 'below outside its float64 interval'
     flat_q = torch.repeat_interleave(torch.arange(U), rowptr.cpu()[1:] - rowptr.cpu()[:-1])
     others = n_neg[flat_q]
     want_auc = torch.where(others > 0, below.float() / others.float(), torch.zeros(()))
@@ -209,6 +242,115 @@ def test_random_floats_equal_the_flattened_route(form, U, n, width):
     again = sc.multi(u_t, rowptr, items, item_range, exclude=exclude)
     for a, b in zip((above, below, pos_score, n_neg), again):
         assert torch.equal(a, b.cpu())
+
+
+def one_positive_per_user(seed, pos_rows, item_range):
+    """the first positive of every row of make_rows; a user whose row is empty gets an arbitrary node"""
+    rng = np.random.default_rng(seed)
+    return np.asarray([p[0] if len(p) else rng.integers(0, item_range[1] + TAIL) for p in pos_rows], dtype=np.int64)
+
+
+def single_positive_rows(pos_rows, excl_rows):
+    """the exclusion rows of make_rows for a call that keeps one positive per user: the user make_rows leaves without negatives
+    (q % 7 == 3: everything excluded or positive) has its other positives excluded too, so that it still has none"""
+    return [np.union1d(ex, pos[1:]).astype(np.int64) if q % 7 == 3 else ex for q, (pos, ex) in enumerate(zip(pos_rows, excl_rows))]
+
+
+@pytest.mark.parametrize('form,U,n,width', CASES)
+def test_single_positive_entry_points_are_exact(form, U, n, width):
+    sc, unids, u_t, pos_rows, excl_rows, item_range, _, _ = case(form, U, n, width, integer=True)
+    pos = one_positive_per_user(U + n, pos_rows, item_range)
+    excl_rows = single_positive_rows(pos_rows, excl_rows)
+    lo, hi = item_range
+    if U >= 17:
+        assert ((pos < lo) | (pos >= hi)).any() and any(p in e for p, e in zip(pos, excl_rows))
+    s64 = sc.f64_scores(u_t)
+    for rows in (excl_rows, None):
+        above, below, ps, n_neg = brute_force(s64, [[p] for p in pos], rows if rows is not None else [[]] * U, item_range)
+        rank, auc, pos_score = sc.single(u_t, torch.from_numpy(pos).to(DEV), item_range, exclude=to_csr(rows) if rows is not None else None)
+        assert [t.dtype for t in (rank, auc, pos_score)] == [torch.int32, torch.float32, torch.float32]
+        what = 'with exclusion' if rows is not None else 'without exclusion'
+        assert torch.equal(rank.cpu(), above), what
+        want_auc = torch.where(n_neg > 0, below.float() / n_neg.float(), torch.zeros(()))   # the bits of (float)below / (float)n_neg
+        assert torch.equal(auc.cpu(), want_auc), what
+        assert torch.equal(pos_score.cpu().double(), ps), what
+        if rows is not None and U > 3:
+            assert int((n_neg == 0).sum()) > 0 and bool((auc.cpu()[n_neg == 0] == 0).all()), 'no user without negatives in this case'
+
+
+def test_single_positive_finish_by_threads_equals_the_finish_by_waves(form='dot', width=20):
+    """engine.dot_rank_full over at least _lib.RANK_THREAD_FINISH_USERS users scores its positives and finishes by one thread per
+    user, a smaller call by one wave per user: the call at the threshold has the bytes of its two halves, which are below it, and
+    on integer inputs its first users have the counts of the float64 brute force"""
+    U, n = _lib.RANK_THREAD_FINISH_USERS, 33
+    lo, n_nodes = N_USER_NODES, N_USER_NODES + n + TAIL
+    sc = Scorer(form, 11, n_nodes, width, integer=False)
+    g = torch.Generator(device=DEV).manual_seed(11)
+    u_t = torch.randint(0, lo, (U,), device=DEV, generator=g)
+    pos = torch.randint(0, n_nodes, (U,), device=DEV, generator=g)            # inside and outside the catalogue
+    mask = torch.rand((U, n + 1), device=DEV, generator=g) < 0.3             # column 0: node 0, an entry outside the catalogue
+    mask[torch.arange(0, U, 5, device=DEV)] = False                           # empty rows
+    mask[torch.arange(3, U, 7, device=DEV), 1:] = True                        # nothing left but (perhaps) the positive
+    rowptr = torch.zeros(U + 1, dtype=torch.int64, device=DEV)
+    rowptr[1:] = torch.cumsum(mask.sum(1), 0)
+    col = mask.nonzero()[:, 1]                                                # row-major: every row ascends
+    items = torch.where(col == 0, torch.zeros_like(col), lo + col - 1)
+    whole = sc.single(u_t, pos, (lo, lo + n), exclude=(rowptr, items))
+    assert int((whole[1] == 0).sum()) > 0 and int((whole[0] > 0).sum()) > 0
+    h = U // 2
+    for part, cut in ((slice(0, h), (0, h)), (slice(h, U), (h, U))):
+        e0 = int(rowptr[cut[0]])
+        ex = ((rowptr[cut[0]:cut[1] + 1] - e0).contiguous(), items[e0:int(rowptr[cut[1]])].contiguous())
+        half = sc.single(u_t[part].contiguous(), pos[part].contiguous(), (lo, lo + n), exclude=ex)
+        for w, got in zip(whole, half):
+            assert torch.equal(w[part], got)
+    for w, got in zip(sc.single(u_t, pos, (lo, lo + n)), (torch.cat(t) for t in zip(sc.single(u_t[:h].contiguous(), pos[:h].contiguous(), (lo, lo + n)),
+                                                                                   sc.single(u_t[h:].contiguous(), pos[h:].contiguous(), (lo, lo + n))))):
+        assert torch.equal(w, got)
+    # a yardstick that is neither finish: integer tables, the first 70 users (empty rows, rows that leave nothing, positives
+    # outside the catalogue among them) against the definition
+    sci = Scorer(form, 12, n_nodes, width, integer=True)
+    rank, auc, pos_score = (t[:70].cpu() for t in sci.single(u_t, pos, (lo, lo + n), exclude=(rowptr, items)))
+    ptr, flat = rowptr[:71].cpu().numpy(), items[:int(rowptr[70])].cpu().numpy()
+    rows = [flat[ptr[q]:ptr[q + 1]] for q in range(70)]
+    above, below, ps, n_neg = brute_force(sci.f64_scores(u_t[:70]), [[int(p)] for p in pos[:70].cpu()], rows, (lo, lo + n))
+    assert int((n_neg == 0).sum()) > 0 and int((above > 0).sum()) > 0
+    assert torch.equal(rank, above) and torch.equal(pos_score.double(), ps)
+    assert torch.equal(auc, torch.where(n_neg > 0, below.float() / n_neg.float(), torch.zeros(())))
+
+
+@pytest.mark.parametrize('form,width', [('dot', 20), ('mlp', 16)])
+def test_single_positive_outputs_may_be_null(form, width):
+    """the raw C entry points at (U, n) = (33, 129): each of rank, auc and pos_score NULL in turn leaves the other two as the
+    all-three call writes them"""
+    sc, unids, u_t, pos_rows, excl_rows, item_range, _, _ = case(form, 33, 129, width, integer=False)
+    pos = torch.from_numpy(one_positive_per_user(33 + 129, pos_rows, item_range)).to(DEV)
+    exclude = to_csr(excl_rows)
+    lib, p = _lib.load(), _lib.ptr
+    (lo, hi), (n_nodes, w) = item_range, sc.repr.shape
+    query = lib.pea_topk_workspace_bytes if form == 'mlp' else lib.pea_dot_topk_workspace_bytes
+    need = int(query(33, hi - lo, 1, w))
+    ws = torch.empty(need, dtype=torch.uint8, device=DEV)
+    fn = lib.pea_rank_full if form == 'mlp' else lib.pea_dot_rank_full
+
+    def call(skip):
+        outs = [torch.full((33,), -7, dtype=torch.int32, device=DEV), torch.full((33,), -7.0, device=DEV), torch.full((33,), -7.0, device=DEV)]
+        rc = fn(33, w, n_nodes, p(sc.repr), p(u_t), p(pos), lo, hi - lo, p(exclude[0]), p(exclude[1]), *[p(t) for t in sc.fc],
+                *[None if i == skip else p(t) for i, t in enumerate(outs)], p(ws), need, _lib.current_stream())
+        torch.cuda.synchronize()
+        assert rc == 0
+        return [t.cpu() for t in outs]
+
+    full = call(None)
+    for g, e in zip(full, sc.single(u_t, pos, item_range, exclude=exclude)):
+        assert torch.equal(g, e.cpu())
+    for skip in range(3):
+        got = call(skip)
+        for i in range(3):
+            if i == skip:
+                assert bool((got[i] == -7).all()), 'an output that was not asked for was written'
+            else:
+                assert got[i].numpy().tobytes() == full[i].numpy().tobytes()
 
 
 @pytest.mark.parametrize('form,width', [('dot', 20), ('mlp', 16)])
