@@ -325,13 +325,6 @@ __device__ __forceinline__ void long_item(const AggGroup &P, const LongItem it, 
     end_item<G>(P, it, R, st, sum, sub == 0 && active);
 }
 
-// Long item `item` of a group.  slot == -2 means no work: the padding of the XCD-affine item layout (plan.hip), and here
-// also an index past the group's items.  Wave-uniform.
-__device__ __forceinline__ LongItem item_at(const AggGroup &P, int item) {
-    if (item >= P.n_long) return LongItem{0, 0, 0, -2};
-    return P.long_items[item];
-}
-
 // This wave's item number in group gi, the group of its workgroup (find_group): 4 items per workgroup.
 __device__ __forceinline__ int wave_index(const AggLaunch &L, int gi) {
     return ((int)blockIdx.x - L.blk_start[gi]) * (kBlock / kWave) + (int)threadIdx.x / kWave;
@@ -568,19 +561,6 @@ template <int MODE>
 MsgBytes msg_bytes(const AggGroup &g) {
     return {4.0 * g.W + 4.0 * g.idx_share + (MODE == AGG_GAT ? 4.0 * (g.W / g.F) : MODE == AGG_GCN ? 4.0 * g.idx_share : 0.0),
             4.0 * g.W + 4.0 + (MODE == AGG_GCN ? 4.0 : 0.0)};
-}
-// the gather footprint of a group (a launch reports the largest among its groups)
-double table_bytes(const AggGroup &g) { return g.table_rows * 4.0 * g.W; }
-
-// Appends g to L with n_long of its long items (4 per workgroup): a group starts on a multiple of 8 workgroups, so that
-// item -> workgroup -> XCD (round-robin) is the plan's placement in the thin and in the fat kernel alike.
-AggGroup &add_group(AggLaunch &L, const AggGroup &g, int n_long, int &blocks) {
-    L.blk_start[L.n_groups] = blocks;
-    AggGroup &c = L.g[L.n_groups++];
-    c = g;
-    c.n_long = n_long;
-    blocks += ((n_long + 3) / 4 + 7) / 8 * 8;
-    return c;
 }
 
 template <int G, int MODE, int F4T>

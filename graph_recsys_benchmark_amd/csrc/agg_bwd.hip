@@ -13,6 +13,10 @@
 // recomputed from the rows exactly as in agg.hip (natural units; the weight is 2^(e log2(e) - m_i), agg_common.h: Soft).
 // Same work decomposition as the forward: short rows per lane subgroup, long rows / hub chunks per wave, hub chunks
 // folded in chunk order by a merge kernel -> bitwise reproducible gradients.
+//
+// Each pass (D, S, and the linear AGG_SUM_BWD_S) is one Pass<MODE, F4T>: what a lane keeps of its row, the 4-edge step, the
+// hub chunk's record and the row's end.  bwd_short_rows, bwd_long_item and bwd_merge_kernel walk edges and records and know
+// no mode.
 #include <algorithm>
 
 #include "agg_common.h"
@@ -20,37 +24,40 @@
 namespace pea {
 namespace {
 
-struct RowD {  // row-local state of the D pass
-    float4 att_s, g, hself;
-    float a_d, m, inv_s, c;
+// ------------------------------------------------------------------------------------------------ the lane, the flags
+// What a lane is in a gather body: lane sl of the sub-th G-lane subgroup of its wave; it owns columns c4 .. c4 + 3, which
+// belong to head k of nk, as lane pos of that head's F4 lanes.  Lanes past the group's width (and those of a subgroup
+// without a row) are not `active`: they run along on column 0, because the head sums are cross-lane, and store nothing.
+// wave_row: the wave's subgroups share one row (a long item, a hub row), so a test on the row is wave-uniform.
+struct LaneView {
+    int lane, sub, sl, c4, F4, pos, k, nk;
+    bool active, pow2, wave_row, head_first;
+    __device__ __forceinline__ LaneView(const AggGroup &P, int G, bool valid, bool wave_row_) : wave_row(wave_row_) {
+        lane = (int)threadIdx.x % kWave;
+        sub = lane / G;
+        sl = lane % G;
+        active = valid && sl * 4 < P.W;
+        c4 = active ? sl * 4 : 0;
+        F4 = P.F / 4;
+        pos = sl % F4;
+        pow2 = (F4 & (F4 - 1)) == 0;
+        k = c4 / P.F;
+        head_first = c4 - k * P.F == 0;   // the lane that reads and writes its head's scalars (one division for both)
+        nk = P.W / P.F;
+    }
+    template <int F4T>
+    __device__ __forceinline__ float head_sum(float v) const { return pea::head_sum<F4T>(v, lane, pos, F4, pow2); }
 };
 
-template <int F4T>
-__device__ __forceinline__ RowD load_row_d(const AggGroup &P, int row, int c4, int lane, int pos, int F4, bool pow2) {
-    RowD r;
-    r.att_s = ld4(P.att_src + c4);
-    r.hself = ld4(row_at(P.feat_self + c4, row, P.ld_self));
-    r.a_d = head_sum<F4T>(dot4(r.hself, ld4(P.att_dst + c4)), lane, pos, F4, pow2);
-    r.g = ld4(row_at(P.g_self + c4, row, P.ld_g));
-    float4 o = ld4(row_at(P.o_self + c4, row, P.ld_g));
-    if (P.bias) {
-        const float4 b = ld4(P.bias + c4);
-        o = make_float4(o.x - b.x, o.y - b.y, o.z - b.z, o.w - b.w);
-    }
-    r.c = head_sum<F4T>(dot4(r.g, o), lane, pos, F4, pow2);
-    const float *sp = P.stats + (size_t)row * P.ld_stats + 2 * (c4 / P.F);
-    r.m = sp[0];
-    r.inv_s = 1.0f / (sp[1] + 1e-16f);
-    return r;
-}
-
-// d z of one edge as seen from the destination row (h = gathered T_j)
-template <int F4T>
-__device__ __forceinline__ float dz_edge_d(const AggGroup &P, const RowD &r, float4 h, int lane, int pos, int F4, bool pow2) {
-    const float zl = head_sum<F4T>(dot4(h, r.att_s), lane, pos, F4, pow2) + r.a_d;
-    const float alpha = __builtin_amdgcn_exp2f(fmaf(leaky(zl, P.neg_slope), kLog2e, -r.m)) * r.inv_s;
-    const float dal = head_sum<F4T>(dot4(h, r.g), lane, pos, F4, pow2);
-    return alpha * (dal - r.c) * (zl > 0.f ? 1.f : P.neg_slope);
+// row_active (optional): rows whose output gradient is exactly zero (every row outside the BPR batch, for the last
+// layer) contribute nothing: the D pass writes d a_dst = 0 for them without gathering, the S pass skips their edges.
+// SP: the launch has groups with row flags (the last layer of a training step).  The dense launches (SP = false: the first
+// layer's x-space passes, 1.9 of the step's 5.6 ms) are compiled without the flag tests and the survivor queue: as run-time
+// branches on a null pointer they cost the S pass 127 M scalar instructions per launch against 38 M of the D pass
+// (SQ_INSTS_SALU, profiles/collect_sq_kind.sh gat train).
+template <bool SP>
+__device__ __forceinline__ bool row_flagged(const AggGroup &P, int row) {
+    return !SP || !P.row_active || P.row_active[row] != 0;
 }
 
 // is the gathered row i live?  (bitmap when the host built one, else the byte flags)
@@ -59,312 +66,344 @@ __device__ __forceinline__ bool row_live(const AggGroup &P, int i) {
     return P.row_active[i] != 0;
 }
 
-__device__ __forceinline__ void finish_d(const AggGroup &P, const RowD &r, int row, int c4, float dsum) {
-    if (c4 % P.F != 0) return;
-    const int k = c4 / P.F;
-    P.ksum[(size_t)row * P.ld_k + k] = dsum;
-    st4(P.side_out + (size_t)row * P.ld_side + 4 * k, make_float4(r.a_d, r.m, r.inv_s, r.c));
+// The id at CSR slot e of a row that ends at `end`; -1 past the end and (FILTER: a pass over out-edges, in an SP launch) for a
+// gathered row that is not flagged: rows known to be zero are not fetched.
+template <bool FILTER>
+__device__ __forceinline__ int live_id(const AggGroup &P, int e, int end) {
+    int id = e < end ? P.col[e] : -1;
+    if (FILTER && P.row_active && id >= 0 && !row_live(P, id)) id = -1;
+    return id;
 }
 
-struct RowS {  // row-local state of the S pass
-    float4 att_s, t;
-    float a_s;
+// ------------------------------------------------------------------------------------------------ the passes
+// What a pass sums over the edges of a row (ACC: a row of W columns; DZ: one scalar per head), and how the sums travel:
+// across the subgroups of a wave, into a hub chunk's partial record [acc (W) | per head: unused, dsum], out of the records.
+template <bool ACC, bool DZ>
+struct RowSums {
+    const AggGroup &P;
+    const LaneView &V;
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    float dsum = 0.f;
+    __device__ __forceinline__ RowSums(const AggGroup &P_, const LaneView &V_) : P(P_), V(V_) {}
+
+    template <int G>
+    __device__ __forceinline__ void fold() {
+#pragma unroll
+        for (int off = G; off < kWave; off <<= 1) {
+            if (DZ) dsum += __shfl_xor(dsum, off);
+            if (ACC) acc = add4(acc, shfl_xor4(acc, off));
+        }
+    }
+    __device__ __forceinline__ float *record(int slot) const { return P.partial + (size_t)slot * (size_t)(P.W + 2 * V.nk); }
+    __device__ __forceinline__ void partial(int slot) const {
+        float *rec = record(slot);
+        if (ACC) st4(rec + V.c4, acc);
+        if (DZ && V.head_first) rec[P.W + 2 * V.k + 1] = dsum;
+    }
+    // chunk order, every subgroup the same value; 8 records in flight per step (one dependent load per record made this
+    // kernel 0.13 ms for a hub row of ~300 chunks): slots past the end re-read the last record and add zero, so the adds
+    // stay unconditional and the compiler keeps the loads ahead of them
+    __device__ __forceinline__ void merge(int first, int count) {
+        constexpr int UM = 8;
+        for (int c0 = 0; c0 < count; c0 += UM) {
+            float4 a[UM];
+            float dd[UM];
+#pragma unroll
+            for (int u = 0; u < UM; ++u) {
+                const float *rec = record(first + (c0 + u < count ? c0 + u : count - 1));
+                a[u] = ACC ? ld4(rec + V.c4) : make_float4(0.f, 0.f, 0.f, 0.f);
+                dd[u] = DZ ? rec[P.W + 2 * V.k + 1] : 0.f;
+            }
+#pragma unroll
+            for (int u = 0; u < UM; ++u) {
+                const float f = c0 + u < count ? 1.f : 0.f;
+                if (ACC) acc = fma4(f, a[u], acc);
+                if (DZ) dsum = fmaf(f, dd[u], dsum);
+            }
+        }
+    }
+};
+
+// A pass: load(row), step4(ids, ok) per 4 edges (ids of slots that are not ok are 0; every load of the step goes ahead of
+// its arithmetic), fold / partial / merge from RowSums, close(row, row_on, store) at the row's end.  close<true> is the
+// late-load form of the merge kernel: no load() went before.  kFiltered: the pass walks a source row's out-edges and drops
+// those to unflagged rows; kSkipsDead: an unflagged row of its own gathers nothing and ends in dead().
+template <int MODE, int F4T>
+struct Pass;
+
+template <int F4T>
+struct Pass<AGG_GAT_BWD_D, F4T> : RowSums<false, true> {
+    static constexpr bool kFiltered = false, kSkipsDead = true;
+    float4 att_s, g, hself;
+    float a_d, m, inv_s, c;
+    using RowSums::RowSums;
+
+    __device__ __forceinline__ void load(int row) {
+        att_s = ld4(P.att_src + V.c4);
+        hself = ld4(row_at(P.feat_self + V.c4, row, P.ld_self));
+        a_d = V.head_sum<F4T>(dot4(hself, ld4(P.att_dst + V.c4)));
+        g = ld4(row_at(P.g_self + V.c4, row, P.ld_g));
+        float4 o = ld4(row_at(P.o_self + V.c4, row, P.ld_g));
+        if (P.bias) {
+            const float4 b = ld4(P.bias + V.c4);
+            o = make_float4(o.x - b.x, o.y - b.y, o.z - b.z, o.w - b.w);
+        }
+        c = V.head_sum<F4T>(dot4(g, o));
+        const float *sp = P.stats + (size_t)row * P.ld_stats + 2 * (V.c4 / P.F);
+        m = sp[0];
+        inv_s = 1.0f / (sp[1] + 1e-16f);
+    }
+    // d z of one edge as seen from the destination row (h = gathered T_j)
+    __device__ __forceinline__ float dz_edge(float4 h) const {
+        const float zl = V.head_sum<F4T>(dot4(h, att_s)) + a_d;
+        const float alpha = __builtin_amdgcn_exp2f(fmaf(leaky(zl, P.neg_slope), kLog2e, -m)) * inv_s;
+        const float dal = V.head_sum<F4T>(dot4(h, g));
+        return alpha * (dal - c) * (zl > 0.f ? 1.f : P.neg_slope);
+    }
+    __device__ __forceinline__ void step4(const int (&ids)[4], const bool (&ok)[4]) {
+        float4 h[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) h[u] = ld4(row_at(P.feat + V.c4, ids[u], P.ld_feat));
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const float dz = dz_edge(h[u]);
+            dsum = ok[u] ? dsum + dz : dsum;   // a select: as a branch the compiler sinks each edge's arithmetic into it
+        }
+    }
+    // d a_dst of an unflagged row (its side record is never read: the S pass does not fetch the row)
+    __device__ __forceinline__ void dead(int row, bool store) const {
+        if (store && V.head_first) P.ksum[(size_t)row * P.ld_k + V.k] = 0.f;
+    }
+    // row_on is lane-local (short rows: one row per subgroup), the head sum of the self loop is not: every lane runs it
+    template <bool LATE = false>
+    __device__ __forceinline__ void close(int row, bool row_on, bool store) {
+        if (LATE) load(row);
+        if (P.self_loop) {
+            const float dz = dz_edge(hself);
+            if (row_on) dsum += dz;
+        }
+        if (!row_on) return dead(row, store);
+        if (!store || !V.head_first) return;
+        P.ksum[(size_t)row * P.ld_k + V.k] = dsum;
+        st4(P.side_out + (size_t)row * P.ld_side + 4 * V.k, make_float4(a_d, m, inv_s, c));
+    }
 };
 
 template <int F4T>
-__device__ __forceinline__ RowS load_row_s(const AggGroup &P, int row, int c4, int lane, int pos, int F4, bool pow2) {
-    RowS r;
-    r.att_s = ld4(P.att_src + c4);
-    r.t = ld4(row_at(P.feat_self + c4, row, P.ld_self));
-    r.a_s = head_sum<F4T>(dot4(r.t, r.att_s), lane, pos, F4, pow2);
-    return r;
-}
+struct Pass<AGG_GAT_BWD_S, F4T> : RowSums<true, true> {
+    static constexpr bool kFiltered = true, kSkipsDead = false;
+    float4 att_s, t;
+    float a_s;
+    using RowSums::RowSums;
 
-// one out-edge as seen from the source row: g = gathered output-gradient row of the destination, sd = its side record
-template <int F4T>
-__device__ __forceinline__ void edge_s(const AggGroup &P, const RowS &r, float4 g, float4 sd, bool ok, int lane, int pos,
-                                       int F4, bool pow2, float4 &acc, float &dzs) {
-    const float zl = r.a_s + sd.x;
-    const float alpha = __builtin_amdgcn_exp2f(fmaf(leaky(zl, P.neg_slope), kLog2e, -sd.y)) * sd.z;
-    const float dal = head_sum<F4T>(dot4(g, r.t), lane, pos, F4, pow2);
-    const float dz = alpha * (dal - sd.w) * (zl > 0.f ? 1.f : P.neg_slope);
-    if (ok) {
-        acc = fma4(alpha, g, acc);
-        dzs += dz;
+    __device__ __forceinline__ void load(int row) {
+        att_s = ld4(P.att_src + V.c4);
+        t = ld4(row_at(P.feat_self + V.c4, row, P.ld_self));
+        a_s = V.head_sum<F4T>(dot4(t, att_s));
     }
-}
+    // one out-edge as seen from the source row: g = gathered output-gradient row of the destination, sd = its side record
+    __device__ __forceinline__ void edge(float4 g, float4 sd, bool ok) {
+        const float zl = a_s + sd.x;
+        const float alpha = __builtin_amdgcn_exp2f(fmaf(leaky(zl, P.neg_slope), kLog2e, -sd.y)) * sd.z;
+        const float dal = V.head_sum<F4T>(dot4(g, t));
+        const float dz = alpha * (dal - sd.w) * (zl > 0.f ? 1.f : P.neg_slope);
+        if (ok) {
+            acc = fma4(alpha, g, acc);
+            dsum += dz;
+        }
+    }
+    __device__ __forceinline__ void step4(const int (&ids)[4], const bool (&ok)[4]) {
+        float4 g[4], sd[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            g[u] = ld4(row_at(P.feat + V.c4, ids[u], P.ld_feat));
+            sd[u] = ld4(row_at(P.side + 4 * V.k, ids[u], P.ld_side));
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) edge(g[u], sd[u], ok[u]);
+    }
+    // The self loop is an edge to the row's own side record, unless the row is `lone` (deg0_self: its forward softmax had
+    // the self loop alone, alpha = 1 exactly and d z = 0; it has no side record).  Two forms, the same values.  One row per
+    // wave (long items, hub rows): a branch on `lone`, the form these bodies have always had.  Short rows: lone and row_on
+    // differ between the subgroups of a wave and the head sum inside edge() is cross-lane, so every lane runs edge() and
+    // the flags only decide what is kept.
+    template <bool LATE = false>
+    __device__ __forceinline__ void close(int row, bool row_on, bool store) {
+        if (LATE) load(row);
+        if (P.self_loop) {
+            const bool lone = P.deg0_self && P.deg0_self[row] != 0;
+            if (V.wave_row) {
+                if (!lone) edge(ld4(row_at(P.feat + V.c4, row, P.ld_feat)), ld4(row_at(P.side + 4 * V.k, row, P.ld_side)), row_on);
+                else if (row_on) acc = add4(acc, ld4(row_at(P.feat + V.c4, row, P.ld_feat)));
+            } else {
+                const float4 gs = ld4(row_at(P.feat + V.c4, row, P.ld_feat));
+                float4 sd = make_float4(0.f, 0.f, 1.f, 0.f);
+                if (!lone) sd = ld4(row_at(P.side + 4 * V.k, row, P.ld_side));
+                edge(gs, sd, row_on && !lone);
+                if (row_on && lone) acc = add4(acc, gs);
+            }
+        }
+        if (!store) return;
+        const float dad = P.da_dst[(size_t)row * P.ld_k + V.k];
+        const float4 at_d = ld4(P.att_dst + V.c4);
+        const float ws = dsum, wd = dad;   // natural-unit logits and attention vectors: d z / d T_j = att_j
+        float4 o;
+        o.x = acc.x + ws * att_s.x + wd * at_d.x;
+        o.y = acc.y + ws * att_s.y + wd * at_d.y;
+        o.z = acc.z + ws * att_s.z + wd * at_d.z;
+        o.w = acc.w + ws * att_s.w + wd * at_d.w;
+        st4(P.out + (size_t)row * P.ld_out + V.c4, o);
+        if (V.head_first) P.ksum[(size_t)row * P.ld_k + V.k] = dsum;
+    }
+};
 
-__device__ __forceinline__ void finish_s(const AggGroup &P, const RowS &r, int row, int c4, float4 acc, float dzs) {
-    const int k = c4 / P.F;
-    const float dad = P.da_dst[(size_t)row * P.ld_k + k];
-    const float4 at_d = ld4(P.att_dst + c4);
-    const float ws = dzs, wd = dad;   // natural-unit logits and attention vectors: d z / d T_j = att_j
-    float4 o;
-    o.x = acc.x + ws * r.att_s.x + wd * at_d.x;
-    o.y = acc.y + ws * r.att_s.y + wd * at_d.y;
-    o.z = acc.z + ws * r.att_s.z + wd * at_d.z;
-    o.w = acc.w + ws * r.att_s.w + wd * at_d.w;
-    st4(P.out + (size_t)row * P.ld_out + c4, o);
-    if (c4 % P.F == 0) P.ksum[(size_t)row * P.ld_k + k] = dzs;
-}
+template <int F4T>
+struct Pass<AGG_SUM_BWD_S, F4T> : RowSums<true, false> {
+    static constexpr bool kFiltered = true, kSkipsDead = false;
+    float di;
+    using RowSums::RowSums;
+
+    __device__ __forceinline__ void load(int row) { di = P.dinv_self[row]; }
+    __device__ __forceinline__ void step4(const int (&ids)[4], const bool (&ok)[4]) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (!ok[u]) continue;                       // rows known to be zero are not fetched
+            acc = fma4(P.dinv[ids[u]], ld4(row_at(P.feat + V.c4, ids[u], P.ld_feat)), acc);
+        }
+    }
+    template <bool LATE = false>
+    __device__ __forceinline__ void close(int row, bool row_on, bool store) {
+        if (LATE) load(row);
+        if (P.self_loop && row_on) acc = fma4(di, ld4(row_at(P.feat_self + V.c4, row, P.ld_self)), acc);
+        if (store) st4(P.out + (size_t)row * P.ld_out + V.c4, scale4(acc, di));
+    }
+};
 
 // ------------------------------------------------------------------------------------------------ short rows
-// SP (here and in bwd_long_item): the launch has groups with row flags (the last layer of a training step).  The dense
-// launches (SP = false: the first layer's x-space passes, 1.9 of the step's 5.6 ms) are compiled without the flag tests and
-// the survivor queue: as run-time branches on a null pointer they cost the S pass 127 M scalar instructions per launch
-// against 38 M of the D pass (SQ_INSTS_SALU, profiles/collect_sq_kind.sh gat train).
+// One G-lane subgroup per row, 4 edges in flight (ids, then rows, then the arithmetic), as in the forward's short_rows.
 template <int G, int MODE, int F4T, bool SP>
 __device__ __forceinline__ void bwd_short_rows(const AggGroup &P, const int blk) {
+    using PassT = Pass<MODE, F4T>;
     const int item = blk * (kBlock / G) + (int)threadIdx.x / G;
-    const int sl = (int)threadIdx.x % G, lane = (int)threadIdx.x % kWave;
     const bool valid = item < P.n_short;
     const int row = valid ? P.short_rows[item] : 0;
-    const bool active = valid && sl * 4 < P.W;
-    const int c4 = active ? sl * 4 : 0;
-    // row_active (optional): rows whose output gradient is exactly zero (every row outside the BPR batch, for the last
-    // layer) contribute nothing: the D pass writes d a_dst = 0 for them without gathering, the S pass skips their edges
-    const bool row_on = !SP || !P.row_active || P.row_active[row] != 0;
+    const LaneView V(P, G, valid, false);
+    const bool row_on = row_flagged<SP>(P, row);
     const int beg = P.rowptr[row];
-    const int end = (valid && (MODE != AGG_GAT_BWD_D || row_on)) ? P.rowptr[row + 1] : beg;
-    const int F4 = P.F / 4, pos = sl % F4;
-    const bool pow2 = (F4 & (F4 - 1)) == 0;
-    const int k = c4 / P.F;
+    const int end = (valid && !(PassT::kSkipsDead && !row_on)) ? P.rowptr[row + 1] : beg;
     int len = end - beg;
     for (int off = G; off < kWave; off <<= 1) len = max(len, __shfl_xor(len, off));  // head sums are cross-lane
-    if (MODE == AGG_SUM_BWD_S) {
-        const float di = P.dinv_self[row];
-        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-        constexpr int U = 4;
-        for (int t = 0; t < len; t += U) {
-            bool ok[U];
-            int ii[U];
+    PassT pass(P, V);
+    pass.load(row);
+    for (int t = 0; t < len; t += 4) {
+        int ids[4];
+        bool ok[4];
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
-                ok[u] = beg + t + u < end;
-                ii[u] = ok[u] ? P.col[beg + t + u] : 0;
-                if (SP && P.row_active && ok[u] && !row_live(P, ii[u])) ok[u] = false, ii[u] = 0;
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                if (!ok[u]) continue;                       // rows known to be zero are not fetched
-                acc = fma4(P.dinv[ii[u]], ld4(row_at(P.feat + c4, ii[u], P.ld_feat)), acc);
-            }
+        for (int u = 0; u < 4; ++u) {
+            const int id = live_id<SP && PassT::kFiltered>(P, beg + t + u, end);
+            ok[u] = id >= 0;
+            ids[u] = ok[u] ? id : 0;
         }
-        if (P.self_loop && row_on) acc = fma4(di, ld4(row_at(P.feat_self + c4, row, P.ld_self)), acc);
-        if (active) st4(P.out + (size_t)row * P.ld_out + c4, scale4(acc, di));
-        return;
+        pass.step4(ids, ok);
     }
-    if (MODE == AGG_GAT_BWD_D) {
-        const RowD r = load_row_d<F4T>(P, row, c4, lane, pos, F4, pow2);
-        float dsum = 0.f;
-        constexpr int U = 4;  // edges in flight per subgroup (ids, then rows, then the arithmetic), as in agg_short_kernel
-        for (int t = 0; t < len; t += U) {
-            bool ok[U];
-            float4 h[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                ok[u] = beg + t + u < end;
-                const int j = ok[u] ? P.col[beg + t + u] : 0;
-                h[u] = ld4(row_at(P.feat + c4, j, P.ld_feat));
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const float dz = dz_edge_d<F4T>(P, r, h[u], lane, pos, F4, pow2);
-                if (ok[u]) dsum += dz;
-            }
-        }
-        if (P.self_loop) {
-            const float dz = dz_edge_d<F4T>(P, r, r.hself, lane, pos, F4, pow2);
-            if (row_on) dsum += dz;
-        }
-        if (active) {
-            if (row_on) finish_d(P, r, row, c4, dsum);
-            else if (c4 % P.F == 0) P.ksum[(size_t)row * P.ld_k + k] = 0.f;
-        }
-    } else {
-        const RowS r = load_row_s<F4T>(P, row, c4, lane, pos, F4, pow2);
-        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-        float dzs = 0.f;
-        constexpr int U = 4;
-        for (int t = 0; t < len; t += U) {
-            bool ok[U];
-            float4 g[U], sd[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                ok[u] = beg + t + u < end;
-                int i = ok[u] ? P.col[beg + t + u] : 0;
-                if (SP && P.row_active && ok[u] && !row_live(P, i)) ok[u] = false, i = 0;
-                g[u] = ld4(row_at(P.feat + c4, i, P.ld_feat));
-                sd[u] = ld4(row_at(P.side + 4 * k, i, P.ld_side));
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) edge_s<F4T>(P, r, g[u], sd[u], ok[u], lane, pos, F4, pow2, acc, dzs);
-        }
-        if (P.self_loop) {
-            const bool lone = P.deg0_self && P.deg0_self[row] != 0;   // wave-divergent per subgroup: both forms are lane-local
-            const float4 gs = ld4(row_at(P.feat + c4, row, P.ld_feat));
-            float4 sd = make_float4(0.f, 0.f, 1.f, 0.f);
-            if (!lone) sd = ld4(row_at(P.side + 4 * k, row, P.ld_side));
-            float4 acc2 = acc;
-            float dz2 = dzs;
-            edge_s<F4T>(P, r, gs, sd, row_on, lane, pos, F4, pow2, acc2, dz2);   // head sums are cross-lane: every lane runs it
-            if (lone) {
-                if (row_on) acc = add4(acc, gs);        // alpha = 1 exactly, d z = 0
-            } else {
-                acc = acc2;
-                dzs = dz2;
-            }
-        }
-        if (active) finish_s(P, r, row, c4, acc, dzs);
-    }
+    pass.close(row, row_on, V.active);
 }
 
 // ------------------------------------------------------------------------------------------------ long rows / hub chunks
+// 64 ids, one per lane (< 0: none), of which the first cnt slots count: 4 per subgroup and step, in slot order.
+template <int G, class PassT>
+__device__ __forceinline__ void walk_ids(PassT &pass, const LaneView &V, int id, int cnt) {
+    constexpr int NSG = kWave / G;
+    for (int t = 0; t < cnt; t += NSG * 4) {
+        int ids[4];
+        bool ok[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int idx = t + u * NSG + V.sub;
+            const int j = __shfl(id, idx & (kWave - 1));
+            ok[u] = idx < cnt && j >= 0;
+            ids[u] = ok[u] ? j : 0;
+        }
+        pass.step4(ids, ok);
+    }
+}
+
+// Batch-sparse S pass (the last layer: 2.5 % of the gathered rows carry a gradient): the surviving edges of SEVERAL batches
+// of 64 are queued (edge order kept) and processed together.  Packing each batch on its own (round 2) still paid one
+// whole 4-edges-per-subgroup iteration for the 1-2 survivors of nearly every batch: 0.32 ms to find and process the
+// 0.6 M live edges among 24.8 M.
+// The queue is the wave's row of LDS: up to 64 ids, oldest first.
+struct LiveQueue {
+    int *slot;
+    int n = 0;
+    __device__ __forceinline__ explicit LiveQueue(int *wave_row) : slot(wave_row) {}
+    // `live`: the ballot of the lanes whose id of the batch survived
+    __device__ __forceinline__ bool fits(unsigned long long live) const { return n + __popcll(live) <= kWave; }
+    // appends the batch's survivors in lane (= edge) order
+    __device__ __forceinline__ void offer(int id, unsigned long long live) {
+        const int before = __builtin_amdgcn_mbcnt_hi((unsigned)(live >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)live, 0));
+        if (id >= 0) slot[n + before] = id;
+        n += __popcll(live);
+    }
+    // hands the queue over, one id per lane, and empties it
+    __device__ __forceinline__ int take(int lane, int &cnt) {
+        const int id = lane < n ? slot[lane] : -1;
+        cnt = n;
+        n = 0;
+        return id;
+    }
+};
+
 template <int G, int MODE, int F4T, bool SP>
 __device__ __forceinline__ void bwd_long_item(const AggGroup &P, const int blk) {
-    constexpr int NSG = kWave / G, U = 4;
-    const int lane = (int)threadIdx.x % kWave;
-    const int item = blk * (kBlock / kWave) + (int)threadIdx.x / kWave;
-    if (item >= P.n_long) return;
-    const LongItem it = P.long_items[item];
+    using PassT = Pass<MODE, F4T>;
+    constexpr bool kFilter = SP && PassT::kFiltered;
+    const LongItem it = item_at(P, blk * (kBlock / kWave) + (int)threadIdx.x / kWave);
     if (it.slot == -2) return;
-    const int sub = lane / G, sl = lane % G;
-    const bool active = sl * 4 < P.W;
-    const int c4 = active ? sl * 4 : 0;
-    const int row = it.row;
-    const int F4 = P.F / 4, pos = sl % F4;
-    const bool pow2 = (F4 & (F4 - 1)) == 0;
-    const int k = c4 / P.F, nk = P.W / P.F;
-    const bool row_on = !SP || !P.row_active || P.row_active[row] != 0;  // see bwd_short_kernel
-    if (MODE == AGG_GAT_BWD_D && !row_on) {
-        if (it.slot < 0 && sub == 0 && active && c4 % P.F == 0) P.ksum[(size_t)row * P.ld_k + k] = 0.f;
-        return;  // hub chunks of such a row leave their partial records alone: the merge kernel does not read them
+    const LaneView V(P, G, true, true);
+    const bool store = V.sub == 0 && V.active;
+    const bool row_on = row_flagged<SP>(P, it.row);
+    PassT pass(P, V);
+    if constexpr (PassT::kSkipsDead) {
+        if (!row_on) {   // hub chunks of such a row leave their partial records alone: the merge kernel does not read them
+            if (it.slot < 0) pass.dead(it.row, store);
+            return;
+        }
     }
-    constexpr bool kSrc = MODE == AGG_GAT_BWD_S || MODE == AGG_SUM_BWD_S;   // walks a source row's out-edges, filtered
-    RowD rd;
-    RowS rs;
-    if (MODE == AGG_GAT_BWD_D) rd = load_row_d<F4T>(P, row, c4, lane, pos, F4, pow2);
-    else if (MODE == AGG_GAT_BWD_S) rs = load_row_s<F4T>(P, row, c4, lane, pos, F4, pow2);
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    float dsum = 0.f;
-    int src = it.beg + lane < it.end ? P.col[it.beg + lane] : -1;
-    if (SP && kSrc && P.row_active && src >= 0 && !row_live(P, src)) src = -1;
-    // Batch-sparse S pass (the last layer: 2.5 % of the gathered rows carry a gradient): the surviving edges of SEVERAL batches
-    // of 64 are queued (edge order kept) and processed together.  Packing each batch on its own (round 2) still paid one
-    // whole 4-edges-per-subgroup iteration for the 1-2 survivors of nearly every batch: 0.32 ms to find and process the
-    // 0.6 M live edges among 24.8 M.
-    __shared__ int live_q[kBlock / kWave][kWave];
-    const int wq = (int)threadIdx.x / kWave;
-    const bool queued = SP && kSrc && P.row_active != nullptr;
-    int q_n = 0;
+    pass.load(it.row);
+    __shared__ int live_rows[kBlock / kWave][kWave];
+    LiveQueue queue(live_rows[(int)threadIdx.x / kWave]);
+    const bool queued = kFilter && P.row_active != nullptr;
+    // Unqueued, a batch of 64 ids is walked as it is.  Queued, its survivors join the queue and nothing is walked (collect and
+    // continue) unless they no longer fit: then the queue is walked first and the batch starts the next one (a flush, mid-row
+    // or on the last batch).  What is queued when the row ends is walked behind the loop: the whole row's survivors, the
+    // second walk after a flush on the last batch, or nothing.  One walk_ids serves the batch and the flush: as two inlined
+    // copies they cost eleven flagged S instantiations 5 to 13 VGPRs and a wave of occupancy.
+    int id = live_id<kFilter>(P, it.beg + V.lane, it.end), cnt;
     for (int base = it.beg; base < it.end; base += kWave) {
-        const int nxt = base + kWave + lane;
-        int src_next = nxt < it.end ? P.col[nxt] : -1;
-        if (SP && kSrc && P.row_active && src_next >= 0 && !row_live(P, src_next)) src_next = -1;
-        int cnt = min(kWave, it.end - base);
+        const int id_next = live_id<kFilter>(P, base + kWave + V.lane, it.end);
+        int now = id;
+        bool walk = true;
+        cnt = min(kWave, it.end - base);
         if (queued) {
-            const unsigned long long live = __ballot(src >= 0);
-            const int n_live = __popcll(live);
-            const int before = __builtin_amdgcn_mbcnt_hi((unsigned)(live >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)live, 0));
-            const bool last_batch = base + kWave >= it.end;
-            bool flush = false;
-            if (q_n + n_live > kWave) {            // (wave-uniform) the queue cannot take this batch: process it first
-                flush = true;
-            }
-            if (flush) {
-                const int mine = lane < q_n ? live_q[wq][lane] : -1;
-                // process the queue, then start a new one with this batch
-                const int take = q_n;
-                q_n = 0;
-                if (src >= 0) live_q[wq][before] = src;
-                q_n = n_live;
-                src = mine;
-                cnt = take;
-            } else {
-                if (src >= 0) live_q[wq][q_n + before] = src;
-                q_n += n_live;
-                if (!last_batch) {                  // keep collecting
-                    src = src_next;
-                    continue;
-                }
-                src = lane < q_n ? live_q[wq][lane] : -1;
-                cnt = q_n;
-                q_n = 0;
-            }
+            const unsigned long long live = __ballot(id >= 0);
+            walk = !queue.fits(live);                // (wave-uniform)
+            if (walk) now = queue.take(V.lane, cnt);
+            queue.offer(id, live);
         }
-        for (int pass = 0; pass < 2; ++pass) {     // (queued, after a flush on the last batch: the new queue is processed too)
-        for (int t = 0; t < cnt; t += NSG * U) {
-            int jj[U];
-            bool ok[U];
-            float4 h[U], sd[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int idx = t + u * NSG + sub;
-                const int j = __shfl(src, idx & (kWave - 1));
-                ok[u] = idx < cnt && j >= 0;
-                jj[u] = ok[u] ? j : 0;
-            }
-            if (MODE == AGG_SUM_BWD_S) {
-#pragma unroll
-                for (int u = 0; u < U; ++u)
-                    if (ok[u]) acc = fma4(P.dinv[jj[u]], ld4(row_at(P.feat + c4, jj[u], P.ld_feat)), acc);
-                continue;
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                h[u] = ld4(row_at(P.feat + c4, jj[u], P.ld_feat));
-                if (MODE == AGG_GAT_BWD_S) sd[u] = ld4(row_at(P.side + 4 * k, jj[u], P.ld_side));
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                if (MODE == AGG_GAT_BWD_D) {
-                    const float dz = dz_edge_d<F4T>(P, rd, h[u], lane, pos, F4, pow2);
-                    if (ok[u]) dsum += dz;
-                } else {
-                    edge_s<F4T>(P, rs, h[u], sd[u], ok[u], lane, pos, F4, pow2, acc, dsum);
-                }
-            }
-        }
-        if (!(queued && q_n > 0 && base + kWave >= it.end)) break;
-        src = lane < q_n ? live_q[wq][lane] : -1;   // the last batch overflowed the queue: what it left behind
-        cnt = q_n;
-        q_n = 0;
-        }
-        src = src_next;
+        if (walk) walk_ids<G>(pass, V, now, cnt);
+        id = id_next;
     }
-#pragma unroll
-    for (int off = G; off < kWave; off <<= 1) {
-        dsum += __shfl_xor(dsum, off);
-        if (kSrc) acc = add4(acc, shfl_xor4(acc, off));
+    if (queued) {
+        id = queue.take(V.lane, cnt);
+        walk_ids<G>(pass, V, id, cnt);
     }
-    if (it.slot >= 0) {  // hub chunk: partial record [acc (W) | per head: unused, dsum]
-        if (sub == 0 && active) {
-            float *rec = P.partial + (size_t)it.slot * (size_t)(P.W + 2 * nk);
-            if (kSrc) st4(rec + c4, acc);
-            if (MODE != AGG_SUM_BWD_S && c4 % P.F == 0) rec[P.W + 2 * k + 1] = dsum;
-        }
+    pass.template fold<G>();
+    if (it.slot >= 0) {
+        if (store) pass.partial(it.slot);
         return;
     }
-    if (MODE == AGG_SUM_BWD_S) {
-        const float di = P.dinv_self[row];
-        if (P.self_loop && row_on) acc = fma4(di, ld4(row_at(P.feat_self + c4, row, P.ld_self)), acc);
-        if (sub == 0 && active) st4(P.out + (size_t)row * P.ld_out + c4, scale4(acc, di));
-        return;
-    }
-    if (P.self_loop) {
-        if (MODE == AGG_GAT_BWD_D) {
-            dsum += dz_edge_d<F4T>(P, rd, rd.hself, lane, pos, F4, pow2);
-        } else if (P.deg0_self && P.deg0_self[row] != 0) {   // wave-uniform: one row per wave
-            if (row_on) acc = add4(acc, ld4(row_at(P.feat + c4, row, P.ld_feat)));
-        } else {
-            edge_s<F4T>(P, rs, ld4(row_at(P.feat + c4, row, P.ld_feat)), ld4(row_at(P.side + 4 * k, row, P.ld_side)), row_on, lane,
-                        pos, F4, pow2, acc, dsum);
-        }
-    }
-    if (sub == 0 && active) {
-        if (MODE == AGG_GAT_BWD_D) finish_d(P, rd, row, c4, dsum);
-        else finish_s(P, rs, row, c4, acc, dsum);
-    }
+    pass.close(it.row, row_on, store);
 }
 
 // One launch per pass and lane width, like the forward's agg_rows_kernel: workgroups [0, n_long_blocks) take the long rows
@@ -383,136 +422,108 @@ __global__ __launch_bounds__(kBlock) void bwd_rows_kernel(const AggLaunch L) {
 }
 
 // ------------------------------------------------------------------------------------------------ hub rows
+// One wave per hub row: its chunks' records in chunk order, then the row's end.
 template <int G, int MODE, int F4T>
 __global__ __launch_bounds__(kBlock) void bwd_merge_kernel(const AggLaunch L) {
+    using PassT = Pass<MODE, F4T>;
     const int gi = find_group(L);
     const AggGroup &P = L.g[gi];
-    const int lane = (int)threadIdx.x % kWave;
     const int item = ((int)blockIdx.x - L.blk_start[gi]) * (kBlock / kWave) + (int)threadIdx.x / kWave;
     if (item >= P.n_hub) return;
-    const int row = P.hub_rows[item];
-    const int first = P.hub_first[item], count = P.hub_count[item];
-    const int sub = lane / G, sl = lane % G;
-    const bool active = sl * 4 < P.W;
-    const int c4 = active ? sl * 4 : 0;
-    const int F4 = P.F / 4, pos = sl % F4;
-    const bool pow2 = (F4 & (F4 - 1)) == 0;
-    const int k = c4 / P.F, nk = P.W / P.F;
-    const size_t rec_sz = (size_t)(P.W + 2 * nk);
-    const bool row_on = !P.row_active || P.row_active[row] != 0;  // see bwd_short_kernel
-    if (MODE == AGG_GAT_BWD_D && !row_on) {
-        if (sub == 0 && active && c4 % P.F == 0) P.ksum[(size_t)row * P.ld_k + k] = 0.f;
-        return;
+    // All three loads before anything that needs the row: read where they are used, or with hub_rows first (the compiler then
+    // waits for the row before it issues the third), each late load cost the hub row a dependent round trip (+ 0.2 ... 1 us).
+    const int first = P.hub_first[item], count = P.hub_count[item], row = P.hub_rows[item];
+    const LaneView V(P, G, true, true);
+    const bool store = V.sub == 0 && V.active;
+    const bool row_on = row_flagged<true>(P, row);
+    PassT pass(P, V);
+    if constexpr (PassT::kSkipsDead) {
+        if (!row_on) return pass.dead(row, store);
     }
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    float dsum = 0.f;
-    // chunk order, every subgroup the same value; 8 records in flight per step (one dependent load per record made this
-    // kernel 0.13 ms for a hub row of ~300 chunks): slots past the end re-read the last record and add zero, so the adds
-    // stay unconditional and the compiler keeps the loads ahead of them
-    constexpr int UM = 8;
-    for (int c0 = 0; c0 < count; c0 += UM) {
-        float4 a[UM];
-        float dd[UM];
-#pragma unroll
-        for (int u = 0; u < UM; ++u) {
-            const int c = c0 + u < count ? c0 + u : count - 1;
-            const float *rec = P.partial + (size_t)(first + c) * rec_sz;
-            a[u] = MODE != AGG_GAT_BWD_D ? ld4(rec + c4) : make_float4(0.f, 0.f, 0.f, 0.f);
-            dd[u] = MODE != AGG_SUM_BWD_S ? rec[P.W + 2 * k + 1] : 0.f;
+    pass.merge(first, count);
+    pass.template close<true>(row, row_on, store);
+}
+
+// ------------------------------------------------------------------------------------------------ host
+// profile names as profiles/summarize.py derives them from rocprofv3's kernel names (bwd_rows_kernel<G, MODE, F4T>).
+// Launches whose rows / gathered rows are filtered by row_active (the last layer: only the BPR batch's rows carry a
+// gradient) get their own name, *_batch.  A function-local static table, as the forward's launch_name.
+template <int MODE>
+constexpr const char *bwd_pass_name() {
+    return MODE == AGG_GAT_BWD_D ? "gat_bwd_dst" : MODE == AGG_SUM_BWD_S ? "sum_bwd_src" : "gat_bwd_src";
+}
+template <int MODE>
+constexpr const char *bwd_merge_name() {
+    return MODE == AGG_GAT_BWD_D ? "gat_bwd_dst_merge" : MODE == AGG_SUM_BWD_S ? "sum_bwd_src_merge" : "gat_bwd_src_merge";
+}
+template <int G, int MODE>
+const char *bwd_rows_name(bool batch) {
+    struct Names {
+        char s[2][32];
+        Names() {
+            snprintf(s[0], sizeof(s[0]), "%s_g%d", bwd_pass_name<MODE>(), G);
+            snprintf(s[1], sizeof(s[1]), "%s_g%d_batch", bwd_pass_name<MODE>(), G);
         }
-#pragma unroll
-        for (int u = 0; u < UM; ++u) {
-            const float f = c0 + u < count ? 1.f : 0.f;
-            if (MODE != AGG_GAT_BWD_D) acc = fma4(f, a[u], acc);
-            dsum = fmaf(f, dd[u], dsum);
-        }
-    }
-    if (MODE == AGG_SUM_BWD_S) {
-        const float di = P.dinv_self[row];
-        if (P.self_loop && row_on) acc = fma4(di, ld4(row_at(P.feat_self + c4, row, P.ld_self)), acc);
-        if (sub == 0 && active) st4(P.out + (size_t)row * P.ld_out + c4, scale4(acc, di));
-        return;
-    }
-    if (MODE == AGG_GAT_BWD_D) {
-        const RowD r = load_row_d<F4T>(P, row, c4, lane, pos, F4, pow2);
-        if (P.self_loop) dsum += dz_edge_d<F4T>(P, r, r.hself, lane, pos, F4, pow2);
-        if (sub == 0 && active) finish_d(P, r, row, c4, dsum);
-    } else {
-        const RowS r = load_row_s<F4T>(P, row, c4, lane, pos, F4, pow2);
-        if (P.self_loop) {
-            if (P.deg0_self && P.deg0_self[row] != 0) {   // wave-uniform (one hub row per wave): see bwd_short_kernel
-                if (row_on) acc = add4(acc, ld4(row_at(P.feat + c4, row, P.ld_feat)));
-            } else {
-                edge_s<F4T>(P, r, ld4(row_at(P.feat + c4, row, P.ld_feat)), ld4(row_at(P.side + 4 * k, row, P.ld_side)), row_on,
-                            lane, pos, F4, pow2, acc, dsum);
-            }
-        }
-        if (sub == 0 && active) finish_s(P, r, row, c4, acc, dsum);
-    }
+    };
+    static const Names names;
+    return names.s[batch];
+}
+
+// bytes a dense launch pulls through the memory system per message, each once (bench.py's live roofline): the gathered
+// row chunk (D: T_j; S: the output-gradient row g_i) + the 4-byte index (+ S: the 16-byte side record per head)
+template <int MODE>
+double bwd_msg_bytes(const AggGroup &g) {
+    return 4.0 * g.W + 4.0 + (MODE == AGG_GAT_BWD_S ? 16.0 * (g.W / g.F) : 0.0);
 }
 
 template <int G, int MODE, int F4T>
 int launch_bwd_g(const AggLaunch &base, const int *sel, int n_sel, hipStream_t stream) {
-    // launches whose rows / gathered rows are filtered by row_active (the last layer: only the BPR batch's rows carry a
-    // gradient) get their own name: the live messages are not known on the host, so no byte count is attributed to them
+    // the live messages of a filtered launch are not known on the host, so no byte count is attributed to it
     bool sparse = false;
     for (int i = 0; i < n_sel; ++i) sparse = sparse || base.g[sel[i]].row_active != nullptr;
-    // names as profiles/summarize.py derives them from rocprofv3's kernel names (bwd_rows_kernel<G, MODE, F4T>)
-    static char names[2][32];
-    if (!names[0][0]) {
-        const char *fam = MODE == AGG_SUM_BWD_S ? "sum_bwd" : "gat_bwd";
-        snprintf(names[0], sizeof(names[0]), "%s_%s_g%d", fam, MODE == AGG_GAT_BWD_D ? "dst" : "src", G);
-        snprintf(names[1], sizeof(names[1]), "%s_%s_g%d_batch", fam, MODE == AGG_GAT_BWD_D ? "dst" : "src", G);
-    }
-    const char *nm = names[sparse ? 1 : 0];
     AggLaunch L;
-    {   // long rows + hub chunks first, short rows behind them, one launch
-        L.n_groups = 0;
-        int blocks = 0, sblocks = 0;
-        // bytes the launch pulls through the memory system, each once per message (bench.py's live roofline): the gathered
-        // row chunk (D: T_j; S: the output-gradient row g_i) + the 4-byte index (+ S: the 16-byte side record per head)
-        double pulled = 0.0, table = 0.0;
-        for (int i = 0; i < n_sel; ++i) {
-            const AggGroup &g = base.g[sel[i]];
-            if (g.n_short <= 0 && g.n_long <= 0) continue;
-            if (!sparse) {
-                const double per = 4.0 * g.W + 4.0 + (MODE == AGG_GAT_BWD_S ? 16.0 * (g.W / g.F) : 0.0);
-                pulled += per * (g.msgs_short + g.msgs_long);
-                table = std::max(table, g.table_rows * 4.0 * g.W);
-            }
-            L.blk_start[L.n_groups] = blocks;
-            L.blk_short[L.n_groups] = sblocks;
-            L.g[L.n_groups++] = g;
-            if (g.n_long > 0) blocks += ((g.n_long + 3) / 4 + 7) / 8 * 8;
-            if (g.n_short > 0) sblocks += (g.n_short + (kBlock / G) - 1) / (kBlock / G);
+    // long rows + hub chunks first, short rows behind them, one launch
+    L.n_groups = 0;
+    int blocks = 0, sblocks = 0;
+    double pulled = 0.0, table = 0.0;
+    for (int i = 0; i < n_sel; ++i) {
+        const AggGroup &g = base.g[sel[i]];
+        if (g.n_short <= 0 && g.n_long <= 0) continue;
+        if (!sparse) {
+            pulled += bwd_msg_bytes<MODE>(g) * (g.msgs_short + g.msgs_long);
+            table = std::max(table, table_bytes(g));
         }
-        L.blk_start[L.n_groups] = blocks;
         L.blk_short[L.n_groups] = sblocks;
-        L.n_long_blocks = blocks;
-        if (blocks + sblocks > 0) {
-            ProfScope ps(nm, stream, pulled, pulled, table);
-            if (sparse) PEA_LAUNCH((bwd_rows_kernel<G, MODE, F4T, true>), dim3(blocks + sblocks), dim3(kBlock), 0, stream, L);
-            else PEA_LAUNCH((bwd_rows_kernel<G, MODE, F4T, false>), dim3(blocks + sblocks), dim3(kBlock), 0, stream, L);
-            PEA_HIP(hipGetLastError());
-        }
+        add_group(L, g, g.n_long, blocks);
+        if (g.n_short > 0) sblocks += (g.n_short + (kBlock / G) - 1) / (kBlock / G);
     }
-    {   // hub merge
-        L.n_groups = 0;
-        int blocks = 0;
-        for (int i = 0; i < n_sel; ++i) {
-            const AggGroup &g = base.g[sel[i]];
-            if (g.n_hub <= 0) continue;
-            L.blk_start[L.n_groups] = blocks;
-            L.g[L.n_groups++] = g;
-            blocks += (g.n_hub + 3) / 4;
-        }
+    L.blk_start[L.n_groups] = blocks;
+    L.blk_short[L.n_groups] = sblocks;
+    L.n_long_blocks = blocks;
+    if (blocks + sblocks > 0) {
+        ProfScope ps(bwd_rows_name<G, MODE>(sparse), stream, pulled, pulled, table);
+        if (sparse) PEA_LAUNCH((bwd_rows_kernel<G, MODE, F4T, true>), dim3(blocks + sblocks), dim3(kBlock), 0, stream, L);
+        else if constexpr (MODE != AGG_SUM_BWD_S)
+            PEA_LAUNCH((bwd_rows_kernel<G, MODE, F4T, false>), dim3(blocks + sblocks), dim3(kBlock), 0, stream, L);
+        else   // the linear pass exists for the flags and has no dense kernel (launch_gat_backward says so first)
+            PEA_REQUIRE(false, PEA_ERR_ARG, "AGG_SUM_BWD_S: no row_active flags (AGG_GCN is the dense form of this sum)");
+        PEA_HIP(hipGetLastError());
+    }
+    // hub merge
+    L.n_groups = 0;
+    blocks = 0;
+    for (int i = 0; i < n_sel; ++i) {
+        const AggGroup &g = base.g[sel[i]];
+        if (g.n_hub <= 0) continue;
         L.blk_start[L.n_groups] = blocks;
-        if (blocks > 0) {
-            ProfScope ps(MODE == AGG_GAT_BWD_D ? "gat_bwd_dst_merge" : MODE == AGG_SUM_BWD_S ? "sum_bwd_src_merge" : "gat_bwd_src_merge",
-                         stream, 0.0);
-            PEA_LAUNCH((bwd_merge_kernel<G, MODE, F4T>), dim3(blocks), dim3(kBlock), 0, stream, L);
-            PEA_HIP(hipGetLastError());
-        }
+        L.g[L.n_groups++] = g;
+        blocks += (g.n_hub + 3) / 4;
+    }
+    L.blk_start[L.n_groups] = blocks;
+    if (blocks > 0) {
+        ProfScope ps(bwd_merge_name<MODE>(), stream, 0.0);
+        PEA_LAUNCH((bwd_merge_kernel<G, MODE, F4T>), dim3(blocks), dim3(kBlock), 0, stream, L);
+        PEA_HIP(hipGetLastError());
     }
     return PEA_OK;
 }
@@ -685,7 +696,12 @@ int launch_gat_backward(AggMode mode, const AggGroup *groups, int n_groups, hipS
     AggLaunch base;
     base.n_groups = n_groups;
     for (int i = 0; i < n_groups; ++i) base.g[i] = groups[i];
-    if (mode == AGG_SUM_BWD_S) return launch_bwd_mode<AGG_SUM_BWD_S>(base, stream);
+    if (mode == AGG_SUM_BWD_S) {
+        for (int i = 0; i < n_groups; ++i)
+            PEA_REQUIRE(groups[i].row_active != nullptr, PEA_ERR_ARG,
+                        "AGG_SUM_BWD_S: group %d has no row_active flags (AGG_GCN is the dense form of this sum)", i);
+        return launch_bwd_mode<AGG_SUM_BWD_S>(base, stream);
+    }
     return mode == AGG_GAT_BWD_D ? launch_bwd_mode<AGG_GAT_BWD_D>(base, stream) : launch_bwd_mode<AGG_GAT_BWD_S>(base, stream);
 }
 

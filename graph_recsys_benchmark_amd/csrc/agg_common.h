@@ -160,11 +160,32 @@ __device__ __forceinline__ int find_group(const AggLaunch &L) {
     return g;
 }
 
+// Long item `item` of a group.  slot == -2 means no work: the padding of the XCD-affine item layout (plan.hip), and here
+// also an index past the group's items.  Wave-uniform.  By value: the four fields arrive in one 16-byte load.
+__device__ __forceinline__ LongItem item_at(const AggGroup &P, int item) {
+    if (item >= P.n_long) return LongItem{0, 0, 0, -2};
+    return P.long_items[item];
+}
 
+// ------------------------------------------------------------------------------------------------ host: launch planning
 inline int lanes_for(int W) {
     int g = 4;
     while (g * 4 < W) g <<= 1;
     return g;
+}
+
+// the gather footprint of a group (a launch reports the largest among its groups)
+inline double table_bytes(const AggGroup &g) { return g.table_rows * 4.0 * g.W; }
+
+// Appends g to L with n_long of its long items (4 per workgroup): a group starts on a multiple of 8 workgroups, so that
+// item -> workgroup -> XCD (round-robin) is the plan's placement in the thin and in the fat kernel alike, forward and backward.
+inline AggGroup &add_group(AggLaunch &L, const AggGroup &g, int n_long, int &blocks) {
+    L.blk_start[L.n_groups] = blocks;
+    AggGroup &c = L.g[L.n_groups++];
+    c = g;
+    c.n_long = n_long;
+    blocks += ((n_long + 3) / 4 + 7) / 8 * 8;
+    return c;
 }
 
 }  // namespace

@@ -101,7 +101,7 @@ int sage_two_step_1(const Bwd &b) {
     const pea_model *m = b.m;
     const Level &L = b.L;
     PEA_TRY(b.bias_gradient(b.own, L.n_cols, b.dX, m->ld_x, L.bias_off));
-    const unsigned *active_bits = nullptr;   // only the batch's rows of dX are non-zero: the others are not fetched (csrc/agg.hip)
+    const unsigned *active_bits = nullptr;   // only the batch's rows of dX are non-zero: the others are not fetched (csrc/agg_bwd.hip)
     if (m->active_rows) PEA_TRY(build_active_bits(b, &active_bits));
     std::vector<AggGroup> gs;
     for (const GroupPlan &g : L.groups) {
@@ -320,7 +320,7 @@ int level_wise(const Bwd &b, bool part_a, bool part_b, bool premasked) {
     }
     if (part_a && !premasked) PEA_TRY(mask_continuing(b));
     // only the final outputs' gradient is known to be batch-sparse
-    // (GCN: the reverse aggregation skips the gathered rows known to be zero, csrc/agg.hip)
+    // (GCN: the reverse aggregation skips the gathered rows known to be zero, csrc/agg_bwd.hip: AGG_SUM_BWD_S)
     const unsigned *active_bits = nullptr;
     if (m->active_rows && part_b && std::any_of(L.groups.begin(), L.groups.end(), [](const GroupPlan &g) { return g.last; }))
         PEA_TRY(build_active_bits(b, &active_bits));

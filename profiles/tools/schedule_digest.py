@@ -7,8 +7,10 @@ Per case it prints the schedule's sizes and statistics (doubles as hex floats), 
 every output of the forward-family entry points and of one backward_conv_stack (dense and batch-sparse), and the launch
 log of each call: name, algorithmic bytes, gathered bytes and table bytes per launch, in order.  Sharded cases (world 3,
 rank 0, collectives skipped: ShardLayout.dry) print launch logs only; their values are pinned by tests/test_gpu_sharded.py.
-The last cases (gather_paths) are there for csrc/agg.hip: the fat-lane kernels (PEA_FAT=1), lane width 64, heads of 16 columns
-and the per-edge weighted sum; each fails if the launch log does not show the kernel it is there for.
+The last cases are there for the gathers: gather_paths for csrc/agg.hip (the fat-lane kernels (PEA_FAT=1), lane width 64, heads
+of 16 columns and the per-edge weighted sum), backward_paths for csrc/agg_bwd.hip (hub rows and their merges at PEA_CHUNK=64, row
+flags on every node, flagged last layers of lane width 4, 16 and 64, the flagged linear pass of a two-step SAGE); each fails if
+the launch log does not show the kernel it is there for.
 """
 import ctypes as C
 import hashlib
@@ -105,14 +107,15 @@ def batch_ids():
     return torch.from_numpy(ids.astype(np.int64)).cuda()
 
 
-def backward_digest(tag, eng, lp, x, sparse):
-    """One backward_conv_stack after a training forward: dense d_stack, or the batch's rows only with their flags set."""
+def backward_digest(tag, eng, lp, x, sparse, ids=None):
+    """One backward_conv_stack after a training forward: dense d_stack, or the rows `ids` only (default: a batch's) with their
+    flags set."""
     lib = _lib.load()
     g = torch.Generator().manual_seed(5)
     d_stack = (torch.randn((N, eng.P, eng.repr_dim), generator=g) * 0.1).cuda()
-    ids = mask = None
+    mask = None
     if sparse:
-        ids = batch_ids()
+        ids = batch_ids() if ids is None else ids
         keep = torch.zeros(N, dtype=torch.bool, device='cuda').index_fill_(0, ids, True)
         d_stack = d_stack * keep.view(-1, 1, 1)
         mask = keep.to(torch.uint8)
@@ -141,7 +144,7 @@ def inference(tag, args):
     print('%s ablate %s %s' % (tag, sha(tables), sha(weights)))
 
 
-def training(tag, args, fused2_train):
+def training(tag, args, fused2_train, every_node=False):
     os.environ['PEA_FUSED2_TRAIN'] = str(fused2_train)
     try:
         model, lp, x, att = make(*args)
@@ -155,6 +158,11 @@ def training(tag, args, fused2_train):
         out, stack = logged(t + ' forward', lambda: eng.forward(lp, x, att, want_stack=True, train=True))
         print('%s forward %s %s' % (t, sha(out), sha(stack)))
         backward_digest(t + ' backward', eng, lp, x, sparse)
+    if every_node:      # flags on every row: the survivor queue of the S pass fills with every batch of 64 edges
+        t = tag + ' allrows'
+        out, stack = logged(t + ' forward', lambda: eng.forward(lp, x, att, want_stack=True, train=True))
+        print('%s forward %s %s' % (t, sha(out), sha(stack)))
+        backward_digest(t + ' backward', eng, lp, x, True, ids=torch.arange(N, device='cuda'))
 
 
 def sharded(tag, args):
@@ -225,6 +233,72 @@ def gather_paths():
         reached(tag, since, '_wsum')
 
 
+def backward_paths():
+    """The backward gathers' remaining paths (csrc/agg_bwd.hip)."""
+    level_wise = lambda kind, rep: (kind, MIXED[0], MIXED[1], 32, 24, rep, 1, 'att', 'row')
+    os.environ['PEA_CHUNK'] = '64'      # read when a plan is made: hub rows of many chunks, dense and flagged
+    try:
+        for kind, parts in (('gat', ('gat_bwd_dst_merge', 'gat_bwd_src_merge', 'gat_bwd_src_g4_batch')),
+                            ('gcn', ('sum_bwd_src_merge', 'sum_bwd_src_g4_batch'))):
+            tag, since = '%s chunk64 levelwise' % kind, len(SEEN)
+            training(tag, level_wise(kind, 16), 1, every_node=True)
+            for part in parts:
+                reached(tag, since, part)
+    finally:
+        os.environ.pop('PEA_CHUNK')
+    tag, since = 'gat allrows levelwise', len(SEEN)
+    training(tag, level_wise('gat', 16), 1, every_node=True)
+    reached(tag, since, 'gat_bwd_src_g4_batch')
+    for rep, G in ((64, 16), (256, 64)):        # (16 columns, lane width 4: the cases above)
+        for kind, part in (('gat', 'gat_bwd_src_g%d_batch'), ('gcn', 'sum_bwd_src_g%d_batch')):
+            tag, since = '%s last%d levelwise' % (kind, rep), len(SEEN)
+            training(tag, level_wise(kind, rep), 1, every_node=True)
+            reached(tag, since, part % G)
+            if kind == 'gat':
+                reached(tag, since, 'gat_bwd_dst_g%d_batch' % G)
+    tag, since = 'sage flags twostep64', len(SEEN)
+    training(tag, ('sage', TWO[0], TWO[1], 64, 64, 16, 1, 'att', 'row'), 1, every_node=True)
+    reached(tag, since, 'sum_bwd_src_g')
+    if not any(n.startswith('sum_bwd_src_g') and n.endswith('_batch') for n in SEEN[since:]):
+        raise RuntimeError('%s: no launch named sum_bwd_src_g*_batch' % tag)
+
+
+def flagged_heads():
+    """Row flags on a layer of several heads: the one-channel, one-step engine of nn.conv (its last layer is heads * out wide),
+    backward_conv_stack called with the flags directly.  (heads, out): lane width and head class of the flagged kernels."""
+    from graph_recsys_benchmark_amd.engine import PEAEngine
+    from graph_recsys_benchmark_amd.nn import conv
+    ei = torch.from_numpy(U2I).cuda()
+    for chunk in (512, 64):
+        os.environ['PEA_CHUNK'] = str(chunk)
+        try:
+            plan = conv._train_plan_for(ei.clone(), N, True)
+        finally:
+            os.environ.pop('PEA_CHUNK')
+        for heads, out in ((2, 8), (2, 16), (4, 16), (2, 32), (3, 12)):
+            width = heads * out
+            G = next(g for g in (4, 8, 16, 32, 64) if 4 * g >= width)
+            eng = PEAEngine(plan, 'gat', [1], 32, out, out, heads=heads, channel_aggr='mean', enable_backward=True)
+            g = torch.Generator().manual_seed(100 * heads + out)
+            rand = lambda *shape: (torch.randn(shape, generator=g) * 0.2).cuda()
+            x, lp = rand(N, 32), [(rand(width, 32), rand(1, heads, out), rand(1, heads, out), rand(width))]
+            scratch = torch.empty((N, out), dtype=torch.float32, device='cuda')
+            for name, ids in (('batch', batch_ids()), ('allrows', torch.arange(N, device='cuda'))):
+                tag, since = 'flagged heads%dx%d chunk%d %s' % (heads, out, chunk, name), len(SEEN)
+                logged(tag + ' forward', lambda: eng.forward(lp, x, att=None, train=True, out=scratch))
+                keep = torch.zeros(N, dtype=torch.bool, device='cuda').index_fill_(0, ids, True)
+                d_out = rand(N, 1, width) * keep.view(-1, 1, 1)
+                mask = keep.to(torch.uint8)
+                _lib.check(_lib.load().pea_model_set_active_rows(eng._h, _lib.ptr(mask)))
+                try:
+                    dx, grads = logged(tag, lambda: backward_conv_stack(eng, d_out, x, lp, active_ids=ids, batch_flags=mask))
+                finally:
+                    _lib.check(_lib.load().pea_model_set_active_rows(eng._h, None))
+                print('%s dx %s %s' % (tag, sha(dx), ' '.join(sha(t) for t in grads[0])))
+                for part in ('gat_bwd_dst_g%d_batch' % G, 'gat_bwd_src_g%d_batch' % G):
+                    reached(tag, since, part)
+
+
 def main():
     torch.cuda.set_device(0)
     print('library %s' % _lib.load().pea_version().decode())
@@ -262,6 +336,8 @@ def main():
             sharded('gat sharded heads2', (kind, MIXED_HEADS[0], MIXED_HEADS[1], 32, 24, 16, 2, 'att', 'row'))
     single_convs()
     gather_paths()
+    backward_paths()
+    flagged_heads()
     print('done')
 
 
