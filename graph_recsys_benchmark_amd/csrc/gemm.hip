@@ -6,14 +6,23 @@
 // k-major blocks  B[k][col]  so one GEMM job can serve several channels that share the same input
 // (all P first-layer channels read the same x, models/base.py:192-193).
 //
-// f32-input MFMA (exact fp32 products, fp32 accumulation).  Three kernels:
-//   gemm_persist_kernel  (k <= 128): persistent workgroups keep the whole k-major B (+ bias row) in LDS; one wave owns a
-//                        32-row tile, its A fragment in registers (lane (r, h) holds float4 chunks 2q + h of row r -- the k
-//                        order is permuted identically on the B side, which a sum over k does not care about), and walks
-//                        32-column tiles: 16 LDS reads ahead, 32 v_mfma_f32_32x32x2_f32, 16 stores with no memory wait
-//                        anywhere in the column loop.
-//   gemm_skinny_kernel   (<= 16 output columns): 64 rows per wave, 4 independent v_mfma_f32_16x16x4_f32 chains, float4 stores.
-//   gemm_mfma_kernel     (k > 128): B tiles staged through a double-buffered LDS image.
+// f32-input MFMA (exact fp32 products, fp32 accumulation).  Five kernels; a body reads: row tile, load A, walk B, store.
+// The k order of one MFMA step is what makes two kernels round differently (host side: plan_gemm_launches picks the kernel).
+//   gemm_persist_kernel        (k <= 128): persistent workgroups keep the whole k-major B (+ bias row) in LDS; one wave owns
+//                              a 32-row tile, its A fragment in registers, and walks 32-column tiles: 16 LDS reads ahead, 32
+//                              v_mfma_f32_32x32x2_f32, 16 stores with no memory wait anywhere in the column loop.
+//                              k order: a step takes k and k + 4 (lane (r, h) holds float4 chunks 2q + h of row r).
+//   gemm_skinny_kernel         (<= 16 output columns): 64 rows per wave, 4 independent v_mfma_f32_16x16x4_f32 chains, float4
+//                              stores.  k order: a step takes k, k + 4, k + 8, k + 12 (lane (j, q): float4 chunks 4i + q).
+//   gemm_mfma_kernel           (k > 128, staged fallback): (column tile, 128-deep k chunk) stages through a double-buffered
+//                              LDS image.  k order: chunks in order, a step takes k and k + 64.
+//   gemm_deep_kernel           (k > 128): one stage per 128-deep k chunk for all column tiles.  k order: as gemm_mfma_kernel.
+//   gemm_deep_resident_kernel  (k > 128, B fits the LDS): no barrier after the copy.  k order: 64-deep chunks in order, a
+//                              step takes k and k + 4.
+// Shared: job_rows / source_row / RowTile (which rows a wave owns), a_row / a_src / a_bias / a_fix (one input row with the
+// edge-less-row substitution; every kernel loads A through them), find_out (where a column goes; every kernel), store_tile
+// (the 16 stores of a 32x32 tile).  gemm_persist_kernel shares load_a, find_out and load_orow only: its row preamble, segment
+// preload, gate chain and store epilogue stay written out in its body (see the comment on it).
 // Measured (profiles/tools/gemm_bench.cpp, mfma_peak.cpp, mfma_lds.cpp): the fp32 matrix pipe sustains 154 TFLOP/s on this
 // part; the [N,64]x[64,576] first-layer transform runs at 66-75 TFLOP/s because fp32 MFMA chains and an HBM store stream
 // are additive here (profiles/tools/overlap_probe.cpp: two kernels on two streams, or specialised waves of one kernel,
@@ -35,13 +44,72 @@ struct GemmBatch {
     GemmJob j[kMaxBatch];
 };
 
-// Branch-free A fragment load: every lane issues all its float4 loads back to back (invalid rows / k-ranges are
-// clamped to a valid address and zeroed afterwards), then the edge-less-row transform is applied with selects.
-template <int KH, bool IL = false>
-__device__ __forceinline__ void load_a(const GemmJob &J, int64_t srow, bool rv, int kbase, float (&a)[KH]) {
-    // IL: the two k-halves of a row interleave by float4 (kbase = 4h): one load instruction then reads 32 contiguous
-    // bytes per row instead of two 16-byte pieces 128 bytes apart
-    const int K = J.K1 + J.K2;
+// ---------------------------------------------------------------------------------------------- row tile
+// The rows a job covers: its own row list where it has one, else the launch's (null list = rows 0 .. n - 1).  LISTED =
+// false: the launch has no list anywhere, known at compile time.
+struct RowSet {
+    const int *rows;
+    int64_t n;
+};
+template <bool LISTED = true>
+__device__ __forceinline__ RowSet job_rows(const GemmJob &J, const int *rows, int64_t n_rows) {
+    if (!LISTED) return RowSet{nullptr, n_rows};
+    return J.rows ? RowSet{J.rows, J.n_rows} : RowSet{rows, n_rows};
+}
+// row g of the set: whether it exists, and the table row it names (0 when it does not, so that every address stays valid)
+__device__ __forceinline__ int64_t source_row(const RowSet &R, int64_t g, bool &rv) {
+    rv = g < R.n;
+    return rv ? (R.rows ? (int64_t)R.rows[g] : g) : 0;
+}
+
+// A wave's 32-row tile.  Lane (r, h) reads input row row0 + r (rv, srow) and stores accumulator rows (reg & 3) + 8 *
+// (reg >> 2) + 4 * h: orow holds their ids (row-list jobs; loaded once per tile), valid the bit mask of those inside the
+// job.  The constructor resolves the input row; load_ids, a step of its own so that a kernel can issue its A loads first,
+// fills orow and valid.  (gemm_persist_kernel keeps its own preamble, see the comment on it; it calls load_orow directly
+// and, unlisted, skips it for a full tile.)
+struct RowTile {
+    RowSet R;
+    int64_t row0, srow;
+    bool rv, listed;
+    int orow[16];
+    unsigned valid;
+    __device__ __forceinline__ RowTile(const RowSet &R_, int64_t row0_, int lane)
+        : R(R_), row0(row0_), listed(R_.rows != nullptr), valid(0xffffu) {
+        srow = source_row(R, row0 + (lane & 31), rv);
+    }
+    // Row ids of the lane's 16 accumulator rows and the bit mask of those inside the job; consuming the loads here keeps
+    // memory waits out of the epilogue.  (A function of its own that returns the mask: written into `valid` in place, the
+    // same statements cost the persistent kernel two more spilled registers.)
+    static __device__ __forceinline__ unsigned load_orow(const int *rows, int64_t row0, int h, int64_t n_rows, int (&orow)[16]) {
+        unsigned valid = 0;
+#pragma unroll
+        for (int reg = 0; reg < 16; ++reg) {
+            const int64_t g = row0 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
+            orow[reg] = g < n_rows ? (rows ? rows[g] : (int)g) : 0;
+            valid |= (g < n_rows ? 1u : 0u) << reg;
+        }
+        if (rows) {
+            int probe = 0;
+#pragma unroll
+            for (int reg = 0; reg < 16; ++reg) probe |= orow[reg];
+            if (probe < 0) valid = 0;  // never true (ids are non-negative): makes the loads complete here
+        }
+        return valid;
+    }
+    __device__ __forceinline__ void load_ids(int h) { valid = load_orow(R.rows, row0, h, R.n, orow); }
+};
+
+// ---------------------------------------------------------------------------------------------- A operand
+// One input row as a lane reads it: block pointers, and the edge-less-row substitution where the row is flagged.
+// PLAIN (the backward's products): one input block, no substitution -- nothing but p1 and rv is formed.
+struct ARow {
+    const float *p1, *p2;
+    bool rv, alt;
+    float sc;
+};
+template <bool PLAIN = false>
+__device__ __forceinline__ ARow a_row(const GemmJob &J, int64_t srow, bool rv) {
+    if (PLAIN) return ARow{J.A1 + srow * J.lda1, nullptr, rv, false, 1.f};
     const bool alt = J.a1_mask != nullptr && rv && J.a1_mask[srow] != 0;
     float sc = 1.f;
     if (J.a1_scale) {
@@ -50,55 +118,105 @@ __device__ __forceinline__ void load_a(const GemmJob &J, int64_t srow, bool rv, 
     }
     const float *p1 = alt ? J.a1_alt + srow * J.lda_alt : J.A1 + srow * J.lda1;
     const float *p2 = J.K2 > 0 ? J.A2 + srow * J.lda2 : p1;
+    return ARow{p1, p2, rv, alt, sc};
+}
+// address of float4 chunk k of the row: first block, second block, or (k past the end) a valid address to be zeroed later
+template <bool PLAIN = false>
+__device__ __forceinline__ const float *a_src(const GemmJob &J, const ARow &R, int k) {
+    if (PLAIN) return R.p1 + (k < J.K1 ? k : 0);
+    const bool ok = k < J.K1 + J.K2;
+    return (k < J.K1 || !ok) ? R.p1 + (ok ? k : 0) : R.p2 + (k - J.K1);
+}
+// chunk k of the substitution's bias (the same for every row)
+__device__ __forceinline__ float4 a_bias(const GemmJob &J, int k) {
+    return (J.a1_mask != nullptr && J.a1_bias != nullptr && k < J.K1) ? ld4(J.a1_bias + k) : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+// a loaded chunk as the MFMA takes it: substituted (sub: the row is flagged and k lies in the first block), zero unless keep
+// (the row exists and k < K).  The callers form the two predicates: with the job and the row passed in and `k < K1 + K2`
+// formed here, gemm_persist_kernel came out as another instruction stream, and a slower one.
+__device__ __forceinline__ float4 a_fix(bool sub, float sc, bool keep, float4 t, float4 bv) {
+    if (sub) {  // same roundings as the aggregation kernel's finish_row: product, + bias, relu
+        t = make_float4(fmaxf(sc * t.x + bv.x, 0.f), fmaxf(sc * t.y + bv.y, 0.f), fmaxf(sc * t.z + bv.z, 0.f),
+                        fmaxf(sc * t.w + bv.w, 0.f));
+    }
+    return make_float4(keep ? t.x : 0.f, keep ? t.y : 0.f, keep ? t.z : 0.f, keep ? t.w : 0.f);
+}
+
+// Branch-free A fragment load: every lane issues all its float4 loads back to back (invalid rows / k-ranges are
+// clamped to a valid address and zeroed afterwards), then the edge-less-row transform is applied with selects.
+template <int KH, bool IL = false>
+__device__ __forceinline__ void load_a(const GemmJob &J, int64_t srow, bool rv, int kbase, float (&a)[KH]) {
+    // IL: the two k-halves of a row interleave by float4 (kbase = chunk start + 4h, chunks 8 floats apart): one load
+    // instruction then reads 32 contiguous bytes per row instead of two 16-byte pieces 128+ bytes apart
+    const int K = J.K1 + J.K2;
+    const ARow R = a_row(J, srow, rv);
     float4 v[KH / 4], bv[KH / 4];
 #pragma unroll
     for (int q = 0; q < KH / 4; ++q) {
         const int k = IL ? kbase + q * 8 : kbase + q * 4;
-        const bool ok = k < K;
-        const float *p = (k < J.K1 || !ok) ? p1 + (ok ? k : 0) : p2 + (k - J.K1);
-        v[q] = ld4(p);
-        bv[q] = (J.a1_mask != nullptr && J.a1_bias != nullptr && k < J.K1) ? ld4(J.a1_bias + k) : make_float4(0.f, 0.f, 0.f, 0.f);
+        v[q] = ld4(a_src(J, R, k));
+        bv[q] = a_bias(J, k);
     }
 #pragma unroll
     for (int q = 0; q < KH / 4; ++q) {
         const int k = IL ? kbase + q * 8 : kbase + q * 4;
-        float4 t = v[q];
-        if (alt && k < J.K1) {  // same roundings as the aggregation kernel's finish_row: product, + bias, relu
-            t = make_float4(fmaxf(sc * t.x + bv[q].x, 0.f), fmaxf(sc * t.y + bv[q].y, 0.f), fmaxf(sc * t.z + bv[q].z, 0.f),
-                            fmaxf(sc * t.w + bv[q].w, 0.f));
-        }
-        const bool keep = rv && k < K;
-        a[q * 4 + 0] = keep ? t.x : 0.f;
-        a[q * 4 + 1] = keep ? t.y : 0.f;
-        a[q * 4 + 2] = keep ? t.z : 0.f;
-        a[q * 4 + 3] = keep ? t.w : 0.f;
+        const float4 t = a_fix(R.alt && k < J.K1, R.sc, rv && k < K, v[q], bv[q]);
+        a[q * 4 + 0] = t.x;
+        a[q * 4 + 1] = t.y;
+        a[q * 4 + 2] = t.z;
+        a[q * 4 + 3] = t.w;
+    }
+}
+// The plain, interleaved form for the resident kernel, whose 128-register budget has no room for the loaded chunks
+// beside the fragment: each chunk is fixed up as it is loaded (the loads still go out together; the compiler moves them).
+template <int KH>
+__device__ __forceinline__ void load_a_plain(const GemmJob &J, int64_t srow, bool rv, int kbase, float (&a)[KH]) {
+    const ARow R = a_row<true>(J, srow, rv);
+#pragma unroll
+    for (int q = 0; q < KH / 4; ++q) {
+        const int k = kbase + q * 8;
+        const float4 t = a_fix(false, 1.f, rv && k < J.K1, ld4(a_src<true>(J, R, k)), make_float4(0.f, 0.f, 0.f, 0.f));
+        a[q * 4 + 0] = t.x;
+        a[q * 4 + 1] = t.y;
+        a[q * 4 + 2] = t.z;
+        a[q * 4 + 3] = t.w;
     }
 }
 
-// Where column c of a job's output goes.  The job is wave-uniform, so the segment table is read with scalar loads and
-// the per-lane answer is a chain of selects (no memory wait in the epilogue).
+// ---------------------------------------------------------------------------------------------- epilogue
+// Segments of a job in registers, the unused entries emptied: a loop that reads them has no scalar-memory wait.
+__device__ __forceinline__ void load_segments(const GemmJob &J, GemmSegment (&S)[kMaxSegments]) {
+    const int n_seg = J.n_seg;
+#pragma unroll
+    for (int sg = 0; sg < kMaxSegments; ++sg) {
+        S[sg] = J.seg[sg < n_seg ? sg : 0];
+        if (sg >= n_seg) S[sg].c1 = S[sg].c0;
+    }
+}
+
+// Where column c of a job's output goes.  The job is wave-uniform, so the segment table is read with scalar loads (or
+// sits in registers: load_segments) and the per-lane answer is a chain of selects (no memory wait in the epilogue).
 struct OutCol {
     float *dst;
     int ld, relu;
 };
-__device__ __forceinline__ OutCol find_out(const GemmJob &J, int c) {
+__device__ __forceinline__ OutCol find_out(const GemmSegment *seg, int n_seg, int n_out, int c) {
     OutCol o{nullptr, 0, 0};
-    for (int sg = 0; sg < J.n_seg; ++sg) {
-        const bool in = c >= J.seg[sg].c0 && c < J.seg[sg].c1;
-        o.dst = in ? J.seg[sg].dst + (c - J.seg[sg].c0) : o.dst;
-        o.ld = in ? J.seg[sg].ld : o.ld;
-        o.relu = in ? J.seg[sg].relu : o.relu;
+    for (int sg = 0; sg < n_seg; ++sg) {
+        const bool in = c >= seg[sg].c0 && c < seg[sg].c1;
+        o.dst = in ? seg[sg].dst + (c - seg[sg].c0) : o.dst;
+        o.ld = in ? seg[sg].ld : o.ld;
+        o.relu = in ? seg[sg].relu : o.relu;
     }
-    if (c >= J.n_out) o.dst = nullptr;
+    if (c >= n_out) o.dst = nullptr;
     return o;
 }
 
 // Accumulator rows of a lane: (reg & 3) + 8 * (reg >> 2) + 4 * h.  All 16 stores are issued back to back: nothing in
 // here may wait on memory (a wait between two stores serialises them on the store acknowledgements, which is what
-// bounded the first version of this epilogue).  orow: row ids of a row-list job, loaded once per tile (-1 = past the
-// end); null-list jobs address arithmetically.
-__device__ __forceinline__ void store_tile(const f32x16 &acc, const OutCol o, float bias, bool listed, const int (&orow)[16],
-                                           unsigned valid, int64_t row0, int h) {
+// bounded the first version of this epilogue).  T.orow: row ids of a row-list job, loaded once per tile; null-list jobs
+// address arithmetically.
+__device__ __forceinline__ void store_tile(const f32x16 &acc, const OutCol o, float bias, const RowTile &T, int h) {
     if (!o.dst) return;
     float v[16];  // every value first, in straight-line code: the predicated stores below then touch no loaded register
 #pragma unroll
@@ -106,40 +224,43 @@ __device__ __forceinline__ void store_tile(const f32x16 &acc, const OutCol o, fl
         const float t = acc[reg] + bias;
         v[reg] = o.relu ? fmaxf(t, 0.f) : t;
     }
-    if (listed) {
+    if (T.listed) {
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg)
-            if ((valid >> reg) & 1u) o.dst[(int64_t)orow[reg] * o.ld] = v[reg];
+            if ((T.valid >> reg) & 1u) o.dst[(int64_t)T.orow[reg] * o.ld] = v[reg];
         return;
     }
-    float *p = o.dst + (row0 + 4 * h) * o.ld;
-    if (valid == 0xffffu) {
+    float *p = o.dst + (T.row0 + 4 * h) * o.ld;
+    if (T.valid == 0xffffu) {
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg) p[(int64_t)((reg & 3) + 8 * (reg >> 2)) * o.ld] = v[reg];
     } else {
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg)
-            if ((valid >> reg) & 1u) p[(int64_t)((reg & 3) + 8 * (reg >> 2)) * o.ld] = v[reg];
+            if ((T.valid >> reg) & 1u) p[(int64_t)((reg & 3) + 8 * (reg >> 2)) * o.ld] = v[reg];
     }
 }
 
-// Row ids of the lane's 16 accumulator rows (row-list jobs) and the bit mask of those inside the job; consuming the
-// loads here keeps memory waits out of the epilogue.
-__device__ __forceinline__ unsigned load_orow(const int *rows, int64_t row0, int h, int64_t n_rows, int (&orow)[16]) {
-    unsigned valid = 0;
+// ---------------------------------------------------------------------------------------------- staged B
+// One stage of a double-buffered B image, 256 threads: rows [k0, k0 + 256 * NLD / (W / 4)) x columns [col0, col0 + W) of
+// the job's k-major B, fetched into registers while the previous stage's MFMAs run, stashed after them.
+template <int W, int NLD>
+__device__ __forceinline__ void fetch_b(const GemmJob &J, int k0, int col0, int tid, float4 (&pre)[NLD]) {
+    const int K = J.K1 + J.K2;
 #pragma unroll
-    for (int reg = 0; reg < 16; ++reg) {
-        const int64_t g = row0 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
-        orow[reg] = g < n_rows ? (rows ? rows[g] : (int)g) : 0;
-        valid |= (g < n_rows ? 1u : 0u) << reg;
+    for (int i = 0; i < NLD; ++i) {
+        const int idx = tid + i * 256;
+        const int k = k0 + idx / (W / 4), c = col0 + (idx % (W / 4)) * 4;
+        pre[i] = (k < K && c < J.b_cols) ? ld4(J.B + (size_t)k * J.ldb + c) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    if (rows) {
-        int probe = 0;
+}
+template <int W, int NLD>
+__device__ __forceinline__ void stash_b(float *img, int tid, const float4 (&pre)[NLD]) {
 #pragma unroll
-        for (int reg = 0; reg < 16; ++reg) probe |= orow[reg];
-        if (probe < 0) valid = 0;  // never true (ids are non-negative): makes the loads complete here
+    for (int i = 0; i < NLD; ++i) {
+        const int idx = tid + i * 256;
+        *reinterpret_cast<float4 *>(img + (idx / (W / 4)) * W + (idx % (W / 4)) * 4) = pre[i];
     }
-    return valid;
 }
 
 // 4 waves = 4 row tiles per block share each 32-column B tile through a double-buffered LDS image
@@ -149,42 +270,19 @@ __global__ __launch_bounds__(256) void gemm_mfma_kernel(const GemmBatch Bt, cons
     __shared__ float Bs[2][2 * KH][32];
     constexpr int NLD = (2 * KH * 32 / 4) / 256;  // float4 loads per thread per B tile
     const GemmJob &J = Bt.j[blockIdx.y];
-    if (J.rows) {
-        rows = J.rows;
-        n_rows = J.n_rows;
-    }
     const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5;
-    const int64_t row0 = ((int64_t)blockIdx.x * 4 + (tid >> 6)) * 32;
-    const int64_t grow = row0 + r;
-    const bool rv = grow < n_rows;
-    const int64_t srow = rv ? (rows ? (int64_t)rows[grow] : grow) : 0;
+    RowTile T(job_rows(J, rows, n_rows), ((int64_t)blockIdx.x * 4 + (tid >> 6)) * 32, lane);
     const int K = J.K1 + J.K2;
     const int nkc = (K + 2 * KH - 1) / (2 * KH), nct = (J.n_out + 31) / 32;
     const int n_stage = nkc * nct;
     float a[KH];
-    if (nkc == 1) load_a<KH>(J, srow, rv, h * KH, a);
-    int orow[16];
-    const unsigned valid = load_orow(rows, row0, h, n_rows, orow);
+    if (nkc == 1) load_a<KH>(J, T.srow, T.rv, h * KH, a);
+    T.load_ids(h);
 
     float4 pre[NLD];
-    auto fetch = [&](int stage) {
-        const int col0 = (stage / nkc) * 32, kc = (stage % nkc) * 2 * KH;
-#pragma unroll
-        for (int i = 0; i < NLD; ++i) {
-            const int idx = tid + i * 256;
-            const int k = kc + idx / 8, c = col0 + (idx & 7) * 4;
-            pre[i] = (k < K && c < J.b_cols) ? ld4(J.B + (size_t)k * J.ldb + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    };
-    auto stash = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < NLD; ++i) {
-            const int idx = tid + i * 256;
-            *reinterpret_cast<float4 *>(&Bs[buf][idx / 8][(idx & 7) * 4]) = pre[i];
-        }
-    };
+    auto fetch = [&](int stage) { fetch_b<32>(J, (stage % nkc) * 2 * KH, (stage / nkc) * 32, tid, pre); };
     fetch(0);
-    stash(0);
+    stash_b<32>(&Bs[0][0][0], tid, pre);
     f32x16 acc;
     for (int s = 0; s < n_stage; ++s) {
         __syncthreads();
@@ -194,18 +292,18 @@ __global__ __launch_bounds__(256) void gemm_mfma_kernel(const GemmBatch Bt, cons
 #pragma unroll
             for (int i = 0; i < 16; ++i) acc[i] = 0.f;
         }
-        if (nkc > 1) load_a<KH>(J, srow, rv, kci * 2 * KH + h * KH, a);
+        if (nkc > 1) load_a<KH>(J, T.srow, T.rv, kci * 2 * KH + h * KH, a);
         const float *bs = &Bs[s & 1][h * KH][r];
 #pragma unroll
         for (int kk = 0; kk < KH; ++kk) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[kk], bs[kk * 32], acc, 0, 0, 0);
         if (kci == nkc - 1) {
             // epilogue: this lane owns column c of rows (reg&3) + 8*(reg>>2) + 4*h
             const int c = col0 + r;
-            const OutCol o = find_out(J, c);
+            const OutCol o = find_out(J.seg, J.n_seg, J.n_out, c);
             const float bias = (J.bias && c < J.n_out) ? J.bias[c] : 0.f;
-            store_tile(acc, o, bias, rows != nullptr, orow, valid, row0, h);
+            store_tile(acc, o, bias, T, h);
         }
-        if (s + 1 < n_stage) stash((s + 1) & 1);
+        if (s + 1 < n_stage) stash_b<32>(&Bs[(s + 1) & 1][0][0], tid, pre);
     }
 }
 
@@ -221,50 +319,27 @@ template <int NCT>
 __global__ __launch_bounds__(256) void gemm_deep_kernel(const GemmBatch Bt, const int *__restrict__ rows, int64_t n_rows) {
     constexpr int KH = 64, W = 32 * NCT, NLD = 32 * W / 256;   // float4 loads per thread per B stage (128 x W floats)
     const GemmJob &J = Bt.j[blockIdx.y];
-    if (J.rows) {
-        rows = J.rows;
-        n_rows = J.n_rows;
-    }
     const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5;
-    const int64_t row0 = ((int64_t)blockIdx.x * 4 + (tid >> 6)) * 32;
-    const int64_t grow = row0 + r;
-    const bool rv = grow < n_rows;
-    const int64_t srow = rv ? (rows ? (int64_t)rows[grow] : grow) : 0;
+    RowTile T(job_rows(J, rows, n_rows), ((int64_t)blockIdx.x * 4 + (tid >> 6)) * 32, lane);
+    T.load_ids(h);
     const int K = J.K1 + J.K2;
     const int nkc = (K + 2 * KH - 1) / (2 * KH);
-    int orow[16];
-    const unsigned valid = load_orow(rows, row0, h, n_rows, orow);
     float4 pre[NLD];
-    auto fetch = [&](int kc) {
-#pragma unroll
-        for (int i = 0; i < NLD; ++i) {
-            const int idx = tid + i * 256;
-            const int k = kc * 2 * KH + idx / (W / 4), c = (idx % (W / 4)) * 4;
-            pre[i] = (k < K && c < J.b_cols) ? ld4(J.B + (size_t)k * J.ldb + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    };
-    auto stash = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < NLD; ++i) {
-            const int idx = tid + i * 256;
-            *reinterpret_cast<float4 *>(g_lds + ((size_t)buf * 2 * KH + idx / (W / 4)) * W + (idx % (W / 4)) * 4) = pre[i];
-        }
-    };
     float a[KH], a2[KH];
     f32x16 acc[NCT];
 #pragma unroll
     for (int ct = 0; ct < NCT; ++ct)
 #pragma unroll
         for (int i = 0; i < 16; ++i) acc[ct][i] = 0.f;
-    fetch(0);
-    stash(0);
-    load_a<KH>(J, srow, rv, h * KH, a);
+    fetch_b<W>(J, 0, 0, tid, pre);
+    stash_b<W>(g_lds, tid, pre);
+    load_a<KH>(J, T.srow, T.rv, h * KH, a);
     for (int kc = 0; kc < nkc; ++kc) {
         __syncthreads();
         const bool more = kc + 1 < nkc;
         if (more) {
-            fetch(kc + 1);
-            load_a<KH>(J, srow, rv, (kc + 1) * 2 * KH + h * KH, a2);
+            fetch_b<W>(J, (kc + 1) * 2 * KH, 0, tid, pre);
+            load_a<KH>(J, T.srow, T.rv, (kc + 1) * 2 * KH + h * KH, a2);
         }
         const float *bs = g_lds + ((size_t)(kc & 1) * 2 * KH + h * KH) * W + r;
 #pragma unroll
@@ -272,7 +347,7 @@ __global__ __launch_bounds__(256) void gemm_deep_kernel(const GemmBatch Bt, cons
 #pragma unroll
             for (int kk = 0; kk < KH; ++kk) acc[ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[kk], bs[kk * W + 32 * ct], acc[ct], 0, 0, 0);
         if (more) {
-            stash((kc + 1) & 1);
+            stash_b<W>(g_lds + (size_t)((kc + 1) & 1) * 2 * KH * W, tid, pre);
 #pragma unroll
             for (int kk = 0; kk < KH; ++kk) a[kk] = a2[kk];
         }
@@ -280,9 +355,9 @@ __global__ __launch_bounds__(256) void gemm_deep_kernel(const GemmBatch Bt, cons
 #pragma unroll
     for (int ct = 0; ct < NCT; ++ct) {
         const int c = 32 * ct + r;
-        const OutCol o = find_out(J, c);
+        const OutCol o = find_out(J.seg, J.n_seg, J.n_out, c);
         const float bias = (J.bias && c < J.n_out) ? J.bias[c] : 0.f;
-        store_tile(acc[ct], o, bias, rows != nullptr, orow, valid, row0, h);
+        store_tile(acc[ct], o, bias, T, h);
     }
 }
 
@@ -291,33 +366,12 @@ __global__ __launch_bounds__(256) void gemm_deep_kernel(const GemmBatch Bt, cons
 // below, but over k chunks of 64.  NOT the k order of gemm_deep_kernel: one MFMA step here takes k and k + 4 (the lane
 // halves interleave by float4, as in the persistent kernel), there k and k + 64, so the two round differently and a
 // product is bit-identical only against the same kernel (which one runs follows from the batch's largest k and n_out).
-// lean A fragment load for jobs with one input block and no edge-less-row substitution (the backward's products): no
-// temporaries beyond the fragment itself
-template <int KH>
-__device__ __forceinline__ void load_a_plain(const GemmJob &J, int64_t srow, bool rv, int kbase, float (&a)[KH]) {
-    // the two k-halves of a row interleave by float4 (kbase = chunk start + 4h, chunks 8 floats apart): one load
-    // instruction reads 32 contiguous bytes per row instead of two 16-byte pieces 128+ bytes apart
-    const float *p = J.A1 + srow * J.lda1;
-#pragma unroll
-    for (int q = 0; q < KH / 4; ++q) {
-        const int k = kbase + q * 8;
-        const bool keep = rv && k < J.K1;
-        const float4 t = ld4(p + (k < J.K1 ? k : 0));
-        a[q * 4 + 0] = keep ? t.x : 0.f;
-        a[q * 4 + 1] = keep ? t.y : 0.f;
-        a[q * 4 + 2] = keep ? t.z : 0.f;
-        a[q * 4 + 3] = keep ? t.w : 0.f;
-    }
-}
-
+// Its jobs have one input block and no edge-less-row substitution (the backward's products): load_a_plain.
 template <int NCT>
 __global__ __launch_bounds__(1024) void gemm_deep_resident_kernel(const GemmBatch Bt, const int *__restrict__ rows, int64_t n_rows) {
     constexpr int KH = 32, W = 32 * NCT, NW = 16;   // 64-deep k chunks: 112 registers per lane, 16 waves per CU
     const GemmJob &J = Bt.j[blockIdx.y];
-    if (J.rows) {
-        rows = J.rows;
-        n_rows = J.n_rows;
-    }
+    const RowSet R = job_rows(J, rows, n_rows);
     const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5, wave = tid >> 6;
     const int K = J.K1 + J.K2;
     const int nkc = (K + 2 * KH - 1) / (2 * KH);
@@ -326,13 +380,10 @@ __global__ __launch_bounds__(1024) void gemm_deep_resident_kernel(const GemmBatc
         *reinterpret_cast<float4 *>(g_lds + (size_t)k * W + c) = c < J.b_cols ? ld4(J.B + (size_t)k * J.ldb + c) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
     __syncthreads();
-    const int64_t n_tiles = (n_rows + 31) / 32;
+    const int64_t n_tiles = (R.n + 31) / 32;
     for (int64_t tile = (int64_t)blockIdx.x * NW + wave; tile < n_tiles; tile += (int64_t)gridDim.x * NW) {
-        const int64_t row0 = tile * 32, grow = row0 + r;
-        const bool rv = grow < n_rows;
-        const int64_t srow = rv ? (rows ? (int64_t)rows[grow] : grow) : 0;
-        int orow[16];
-        const unsigned valid = load_orow(rows, row0, h, n_rows, orow);
+        RowTile T(R, tile * 32, lane);
+        T.load_ids(h);
         float a[KH];   // no second fragment buffer: 16 waves per CU cover the load latency, a 128-register budget does not fit one
         f32x16 acc[NCT];
 #pragma unroll
@@ -340,7 +391,7 @@ __global__ __launch_bounds__(1024) void gemm_deep_resident_kernel(const GemmBatc
 #pragma unroll
             for (int i = 0; i < 16; ++i) acc[ct][i] = 0.f;
         for (int kc = 0; kc < nkc; ++kc) {
-            load_a_plain<KH>(J, srow, rv, kc * 2 * KH + 4 * h, a);   // a[4q + e] = k  kc * 64 + 4 (2q + h) + e
+            load_a_plain<KH>(J, T.srow, T.rv, kc * 2 * KH + 4 * h, a);   // a[4q + e] = k  kc * 64 + 4 (2q + h) + e
             const float *bs = g_lds + ((size_t)kc * 2 * KH + 4 * h) * W + r;   // image row of a[kl]: + 8 (kl / 4) + kl % 4
             const bool last_partial = (kc + 1) * 2 * KH > K;            // wave-uniform
             const int kbase = kc * 2 * KH + 4 * h;                      // image row of a[0] of this lane half
@@ -368,9 +419,9 @@ __global__ __launch_bounds__(1024) void gemm_deep_resident_kernel(const GemmBatc
 #pragma unroll
         for (int ct = 0; ct < NCT; ++ct) {
             const int c = 32 * ct + r;
-            const OutCol o = find_out(J, c);
+            const OutCol o = find_out(J.seg, J.n_seg, J.n_out, c);
             const float bias = (J.bias && c < J.n_out) ? J.bias[c] : 0.f;
-            store_tile(acc[ct], o, bias, rows != nullptr, orow, valid, row0, h);
+            store_tile(acc[ct], o, bias, T, h);
         }
     }
 }
@@ -379,7 +430,11 @@ __global__ __launch_bounds__(1024) void gemm_deep_resident_kernel(const GemmBatc
 // (the 9 first-layer transforms of the MovieLens model are one 64 x 596 block = 149 KiB of the CU's 160 KiB), then its
 // 16 waves walk (job, 32-row tile, column group) items with no barrier at all: A fragment from global, B fragment
 // from LDS, 32 MFMAs per 32x32 output tile, stores straight from the accumulators.
-constexpr int kColGroup = 5;       // 32-column tiles per item
+// Its body shares load_a, find_out and RowTile::load_orow with the other kernels and keeps the rest written out: built on
+// RowTile, load_segments and store_tile (the gate an operand of it) its listed launches measured 5 - 7 % slower, and its
+// instruction stream follows every statement of the body (profiles/gemm_kernels_refactor.md, sections 1 and 3).  So the row
+// override, the segment preload, a gate-only select chain and the relu / gate / store triple exist here a second time.
+constexpr int kColGroup = 5;      // 32-column tiles per item
 struct PersistArgs {
     int n_items;                   // all jobs
     int col_group;                 // 32-column tiles per item
@@ -447,7 +502,7 @@ __global__ __launch_bounds__(KH > 32 ? 512 : 1024) void gemm_persist_kernel(cons
         load_a<KH, true>(J, srow, rv, 4 * h, a);
         int orow[16];
         unsigned valid = 0xffffu;
-        if (LISTED || row0 + 32 > jn) valid = load_orow(jrows, row0, h, jn, orow);
+        if (LISTED || row0 + 32 > jn) valid = RowTile::load_orow(jrows, row0, h, jn, orow);
         const int ld = Pa.lds_ld[j];
         // k order of a lane: float4 chunks 2q + h of the row (the two halves of a row interleave by 16 bytes, so one
         // load instruction reads 32 contiguous bytes per row); the B image is read with the same permutation
@@ -503,16 +558,10 @@ __global__ __launch_bounds__(KH > 32 ? 512 : 1024) void gemm_persist_kernel(cons
             }
             // epilogue: lane (r, h) owns column c of rows (reg & 3) + 8 * (reg >> 2) + 4h.  Nothing in here waits on
             // memory, so the 16 stores go out back to back.
-            float *dst = nullptr;
-            int ldo = 0, relu = 0;
-#pragma unroll
-            for (int sg = 0; sg < kMaxSegments; ++sg) {
-                const bool in = c >= S[sg].c0 && c < S[sg].c1;
-                dst = in ? S[sg].dst + (c - S[sg].c0) : dst;
-                ldo = in ? S[sg].ld : ldo;
-                relu = in ? S[sg].relu : relu;
-            }
-            if (c >= n_out || !dst) continue;
+            const OutCol o = find_out(S, kMaxSegments, n_out, c);
+            if (!o.dst) continue;
+            float *dst = o.dst;
+            const int ldo = o.ld, relu = o.relu;
             float v[16];
 #pragma unroll
             for (int reg = 0; reg < 16; ++reg) {
@@ -590,54 +639,27 @@ __global__ __launch_bounds__(512) void gemm_skinny_kernel(const GemmBatch Bt, co
             tile = item - Sa.item_start[j];
         }
         const GemmJob &J = Bt.j[j];
-        const int *jrows = LISTED ? (J.rows ? J.rows : rows) : nullptr;
-        const int64_t jn = (LISTED && J.rows) ? J.n_rows : n_rows;
+        const RowSet R = job_rows<LISTED>(J, rows, n_rows);
         const int64_t row0 = (int64_t)tile * (16 * G);
-        const int K = J.K1 + J.K2, K1 = J.K1, n_out = J.n_out, n_seg = J.n_seg;
+        const int K = J.K1 + J.K2, K1 = J.K1, n_out = J.n_out;
         GemmSegment S[kMaxSegments];
-#pragma unroll
-        for (int sg = 0; sg < kMaxSegments; ++sg) {
-            S[sg] = J.seg[sg < n_seg ? sg : 0];
-            if (sg >= n_seg) S[sg].c1 = S[sg].c0;
-        }
+        load_segments(J, S);
         // ---- input rows: all G * KQ float4 loads of the lane go out before the first use
         int64_t srow[G];
-        bool rv[G], alt[G];
-        float sc[G];
+        bool rv[G];
 #pragma unroll
-        for (int g = 0; g < G; ++g) {
-            const int64_t grow = row0 + 16 * g + jr;
-            rv[g] = grow < jn;
-            srow[g] = rv[g] ? ((LISTED && jrows) ? (int64_t)jrows[grow] : grow) : 0;
-        }
+        for (int g = 0; g < G; ++g) srow[g] = source_row(R, row0 + 16 * g + jr, rv[g]);
+        ARow ar[G];
 #pragma unroll
-        for (int g = 0; g < G; ++g) {
-            alt[g] = J.a1_mask != nullptr && rv[g] && J.a1_mask[srow[g]] != 0;
-            sc[g] = 1.f;
-            if (J.a1_scale) {
-                const float di = J.a1_scale[srow[g]];
-                sc[g] = alt[g] ? di * di : 1.f;
-            }
-        }
+        for (int g = 0; g < G; ++g) ar[g] = a_row(J, srow[g], rv[g]);
         float4 xa[G][KQ];
 #pragma unroll
-        for (int g = 0; g < G; ++g) {
-            const float *p1 = alt[g] ? J.a1_alt + srow[g] * J.lda_alt : J.A1 + srow[g] * J.lda1;
-            const float *p2 = J.K2 > 0 ? J.A2 + srow[g] * J.lda2 : p1;
+        for (int g = 0; g < G; ++g)
 #pragma unroll
-            for (int i = 0; i < KQ; ++i) {
-                const int k = 16 * i + 4 * q;
-                const bool ok = k < K;
-                const float *p = (k < K1 || !ok) ? p1 + (ok ? k : 0) : p2 + (k - K1);
-                xa[g][i] = ld4(p);
-            }
-        }
+            for (int i = 0; i < KQ; ++i) xa[g][i] = ld4(a_src(J, ar[g], 16 * i + 4 * q));
         float4 ab[KQ];  // bias of the edge-less-row transform (same for every row)
 #pragma unroll
-        for (int i = 0; i < KQ; ++i) {
-            const int k = 16 * i + 4 * q;
-            ab[i] = (J.a1_mask != nullptr && J.a1_bias != nullptr && k < K1) ? ld4(J.a1_bias + k) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
+        for (int i = 0; i < KQ; ++i) ab[i] = a_bias(J, 16 * i + 4 * q);
         // ---- weights of this job: lane (col = jr, q) holds W[16i + 4q + e][jr]
         const float *img = g_lds + Sa.lds_off[j];
         float w[KQ][4];
@@ -651,13 +673,7 @@ __global__ __launch_bounds__(512) void gemm_skinny_kernel(const GemmBatch Bt, co
 #pragma unroll
             for (int i = 0; i < KQ; ++i) {
                 const int k = 16 * i + 4 * q;
-                float4 t = xa[g][i];
-                if (alt[g] && k < K1) {  // same roundings as the aggregation kernel's finish_row: product, + bias, relu
-                    t = make_float4(fmaxf(sc[g] * t.x + ab[i].x, 0.f), fmaxf(sc[g] * t.y + ab[i].y, 0.f),
-                                    fmaxf(sc[g] * t.z + ab[i].z, 0.f), fmaxf(sc[g] * t.w + ab[i].w, 0.f));
-                }
-                const bool keep = rv[g] && k < K;
-                xa[g][i] = keep ? t : make_float4(0.f, 0.f, 0.f, 0.f);
+                xa[g][i] = a_fix(ar[g].alt && k < K1, ar[g].sc, rv[g] && k < K, xa[g][i], ab[i]);
             }
         f32x4 acc[G];
 #pragma unroll
@@ -674,30 +690,22 @@ __global__ __launch_bounds__(512) void gemm_skinny_kernel(const GemmBatch Bt, co
             for (int g = 0; g < G; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[i][3], xa[g][i].w, acc[g], 0, 0, 0);
         }
         // ---- epilogue: columns c .. c+3 of row srow[g]
-        const int c = 4 * q;
-        float *dst = nullptr;
-        int ldo = 0, relu = 0;
-#pragma unroll
-        for (int sg = 0; sg < kMaxSegments; ++sg) {
-            const bool in = c >= S[sg].c0 && c < S[sg].c1;
-            dst = in ? S[sg].dst + (c - S[sg].c0) : dst;
-            ldo = in ? S[sg].ld : ldo;
-            relu = in ? S[sg].relu : relu;
-        }
-        if (c >= n_out || !dst) continue;
+        const OutCol o = find_out(S, kMaxSegments, n_out, 4 * q);
+        if (!o.dst) continue;
 #pragma unroll
         for (int g = 0; g < G; ++g) {
             float4 v = make_float4(acc[g][0] + bias.x, acc[g][1] + bias.y, acc[g][2] + bias.z, acc[g][3] + bias.w);
-            if (relu) v = make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f));
-            if (rv[g]) *reinterpret_cast<float4 *>(dst + srow[g] * ldo) = v;
+            if (o.relu) v = make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f));
+            if (rv[g]) *reinterpret_cast<float4 *>(o.dst + srow[g] * o.ld) = v;
         }
     }
 }
 
 
+constexpr int kMaxPack = 24;   // layers per pack launch (the launch record travels as a kernel argument)
 struct PackLaunch {
     int n;
-    PackJob j[24];
+    PackJob j[kMaxPack];
 };
 
 // one block per layer: writes the k-major weight block (and the folded attention columns)
@@ -1079,9 +1087,9 @@ int gemm_route(const GemmJob *jobs, int n_jobs, bool rows_given, int64_t n_rows,
 }
 
 int launch_pack(const PackJob *jobs, int n_jobs, hipStream_t stream) {
-    for (int base = 0; base < n_jobs; base += 24) {
+    for (int base = 0; base < n_jobs; base += kMaxPack) {
         PackLaunch L;
-        L.n = n_jobs - base < 24 ? n_jobs - base : 24;
+        L.n = n_jobs - base < kMaxPack ? n_jobs - base : kMaxPack;
         for (int i = 0; i < L.n; ++i) L.j[i] = jobs[base + i];
         ProfScope ps("pack_weights", stream);
         PEA_LAUNCH(pack_kernel, dim3(L.n), dim3(256), 0, stream, L);
